@@ -12,11 +12,22 @@ backward (+ bucketed RCCL all-reduce when N>1) -> fused Adam -> no-grad SSIM met
 synthetic U[0,1) tensors resident in HBM; weights are the reference's Kaiming init.  The per-step
 `.item()` host syncs of the reference are not reproduced (nothing is read back inside the timed region).
 
-Prints ONE JSON line on rank 0 (see the repo prompt for the schema) with extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and
+prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...), nothing more.
+
+--full adds the measurements that take runs of their own, after the timed steps, as extra objects of the same line:
 `roofline` for the dominant MFMA kernel (largest total time among the live-timed convolution kernels),
 `roofline_hbm` for the dominant bandwidth-bound kernel (largest total time among the live-timed element-wise / reduction
 launches, achieved = algorithmic bytes / time against the 8 TB/s HBM peak), `conv_ms_per_step` / `elementwise_ms_per_step`
-(sums of the same instrumented pass) and `cpu_baseline` (the oracle port timed on this box's host cores, rank 0 at N=1 only).
+(sums of the same instrumented pass), `forward` (eval forward of the same model / batch), the step time without the
+gradient exchange in `collective` (N > 1 or MRISR_FORCE_DP=1) and `cpu_baseline` (the oracle port timed on this box's host
+cores, rank 0 at N=1 only).  --no-kernel-timer / --no-forward-metric / --no-cpu-baseline drop single parts of --full.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0) as DIR/<name>.npy, float32, after the
+timed region: `output` (the network output), `loss` and `ssim` (the no-grad metric); --forward-only writes `output` only.
+Inputs and weights are seeded, and with this option the last timed step restarts from the seeded weights with a fresh Adam
+state (float-atomic gradient sums make earlier steps drift from run to run), so every run computes the same last step and
+two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import hashlib
@@ -66,6 +77,10 @@ def parse():
                                                                     "the per-step kernel / traffic totals free of its launches)")
     ap.add_argument("--forward-only", action="store_true", help="eval forward only (inference metric; not the headline)")
     ap.add_argument("--graph", action="store_true", help="with --forward-only: replay the forward as one HIP graph")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the instrumented kernel pass, the "
+                                                        "eval-forward metric, the no-exchange step time and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32, <= 64 MB in all)")
     return ap.parse_args()
 
 
@@ -138,6 +153,24 @@ def pmc_traffic():
     return j, f"rocprofv3 PMC passes at csrc {have} ({j.get('command', 'bench.py')})"
 
 
+DUMP_BUDGET = {"output": 48 << 20}       # bytes per array (float32); any other array gets 1 MiB
+
+
+def dump_outputs(d, arrays):
+    """Writes each tensor of ``arrays`` as d/<name>.npy in float32.  An array larger than its DUMP_BUDGET is replaced by a
+    fixed sample of its flattened elements: sorted indices drawn by numpy's PCG64 seeded with 0, the same for every run of
+    the same shapes."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        cap = DUMP_BUDGET.get(name, 1 << 20) // 4
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, cap))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` typed directly (no WORLD_SIZE in the environment): this parent makes NO GPU call (it
     never imports torch); it starts `python -m torch.distributed.run` with N fresh rank processes as a child, relays its
@@ -193,6 +226,10 @@ def main():
     torch.manual_seed(0)
     model = UNetSuperRes(1, 1, args.base_filters, depth=args.depth).to(dev).set_compute_dtype(dtype).train()
     opt = FusedAdam(model, lr=1e-4, weight_decay=1e-5)
+    # --dump-outputs: the seeded initial weights, restored (with a fresh Adam state) in front of the last timed step.  The
+    # gradient sums use float atomics, and Adam turns their run-to-run rounding differences into visible weight changes
+    # within a few steps; restarting the last step from this state makes its outputs the same in every run.
+    init_params = model.flat_params.detach().clone() if args.dump_outputs and not args.forward_only else None
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")            # random-init VGG19 announcement (stated in `data` below)
@@ -212,7 +249,9 @@ def main():
     low = torch.rand(B, 1, S, S, generator=g).to(dev)
     high = torch.rand(B, 1, 2 * S, 2 * S, generator=g).to(dev)
 
-    def train_step():
+    kept = {}         # --dump-outputs: what the LAST timed step returned to its caller (references only, no copy)
+
+    def train_step(keep=False):
         opt.zero_grad(set_to_none=True)
         out = model(low)
         loss = crit(out, high)
@@ -228,12 +267,17 @@ def main():
                 dp.finish_gradients()
             opt.step()
         with torch.no_grad():
-            metric(out, high)
+            ssim_value = metric(out, high)
+        if keep:
+            kept.update(output=out, loss=loss, ssim=ssim_value)
         return loss
 
-    def fwd_step():
+    def fwd_step(keep=False):
         with torch.no_grad():
-            return model(low)
+            out = model(low)
+        if keep:
+            kept["output"] = out
+        return out
 
     if args.forward_only:
         model.eval()
@@ -243,9 +287,20 @@ def main():
         graphed = model.graphed_forward(low)
         args.no_kernel_timer = True           # events cannot be recorded inside a replayed graph
 
-        def fwd_step():                       # noqa: F811
-            return graphed(low)
+        def fwd_step(keep=False):             # noqa: F811
+            out = graphed(low)
+            if keep:
+                kept["output"] = out
+            return out
     step = fwd_step if args.forward_only else train_step
+
+    @torch.no_grad()
+    def restart_from_initial_state():
+        model.flat_params.copy_(init_params)
+        opt.exp_avg.zero_()
+        opt.exp_avg_sq.zero_()
+        opt.set_step_count(0)
+        model.mark_weights_changed()
 
     def sync():
         torch.cuda.synchronize()
@@ -258,21 +313,27 @@ def main():
     sync()
     # ---- headline region: EXACTLY K steps, nothing instrumented, nothing read back
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        last = step()
+    for i in range(args.steps):
+        if init_params is not None and i == args.steps - 1:
+            restart_from_initial_state()
+        last = step(keep=i == args.steps - 1)
     host_elapsed = time.perf_counter() - t0          # the host has enqueued everything (the GPU is still running)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # before anything else steps the model again
+        dump_outputs(args.dump_outputs, kept)
+    kept.clear()
     if world > 1 or force_dp:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    # ---- everything below the headline figure runs with --full only (each part can be dropped by its --no-* switch)
     # ---- roofline pass: the same step again with a HIP-event pair around every convolution launch on the launch
     # stream.  Kept out of the headline region because each event record is a barrier packet on the queue: with
     # ~110 timed launches per step it stretches the step by 6-10 % (measured), which would understate `value`.
     timer = None
     timed_steps = 0
-    if not args.no_kernel_timer:            # every rank steps (the step holds collectives); rank 0 reports
+    if args.full and not args.no_kernel_timer:      # every rank steps (the step holds collectives); rank 0 reports
         timer = model._engine.timer = mrisr_lib.timer = KernelTimer()     # convolutions by variant, L.call(nbytes=) launches by entry
         if vgg_eng is not None:
             vgg_eng.timer = timer
@@ -287,7 +348,7 @@ def main():
             vgg_eng.timer = None
     # ---- step time WITHOUT the gradient exchange (same steps, all-reduce skipped: ranks diverge, timing only)
     noex_elapsed = None
-    if dp is not None and not args.forward_only:
+    if args.full and dp is not None and not args.forward_only:
         sync()
         t2 = time.perf_counter()
         with dp.no_sync():
@@ -300,7 +361,7 @@ def main():
         noex_elapsed = float(tt.item())
     # ---- forward-only metric (scripts/infer.py:268-276: eval forward, no_grad) in the same run, same batch
     fwd_elapsed, fwd_steps = None, 20
-    if not args.forward_only and not args.no_forward_metric:
+    if args.full and not args.forward_only and not args.no_forward_metric:
         model.eval()
         for _ in range(3):
             fwd_step()
@@ -409,7 +470,7 @@ def main():
                 rec["kernels"] = {k: {"launches": v["launches"], "us_per_launch": round(v["ms_per_launch"] * 1e3, 2),
                                       "tflops": round(v["tflops"], 2), "share_of_step": round(v["total_ms"] / (timed_elapsed * 1e3), 4)}
                                   for k, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])}
-        if world == 1 and not args.no_cpu_baseline and not args.forward_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.forward_only:
             rec["cpu_baseline"] = cpu_baseline(args.base_filters, S, args.ssim_weight)
         rec["loss"] = float(last.detach()) if not args.forward_only else None
         print(json.dumps(rec))

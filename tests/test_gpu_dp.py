@@ -106,8 +106,8 @@ def test_bench_rccl_rehearsal_through_the_launcher():
     import json
     sys.path.insert(0, REPO)
     import bench
-    cmd = bench.rank_launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-timer",
-                                        "--no-forward-metric"], bench.free_port())
+    cmd = bench.rank_launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                                        "--no-kernel-timer", "--no-forward-metric"], bench.free_port())
     env = dict(os.environ, MRISR_FORCE_DP="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]

@@ -308,6 +308,24 @@ def test_bench_self_launch_command():
     assert len(bench.csrc_sha16()) == 16
 
 
+def test_bench_dump_outputs_float32_within_budget_and_seeded(tmp_path):
+    """bench.py --dump-outputs: every array lands as float32 <name>.npy, an array above its budget is cut to the same
+    seeded sample on every call, and the budgets stay under 64 MB in all."""
+    sys.path.insert(0, REPO)
+    import bench
+    assert sum(bench.DUMP_BUDGET.values()) + 2 * (1 << 20) <= 64 << 20       # + loss and ssim at the default budget
+    big = torch.arange((1 << 20) // 4 + 1000, dtype=torch.float64)
+    arrays = {"output": torch.rand(2, 1, 8, 8).to(torch.bfloat16), "loss": torch.tensor(0.25), "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    for name in arrays:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    assert np.array_equal(np.load(tmp_path / "a" / "output.npy"), arrays["output"].float().numpy())
+    g = np.load(tmp_path / "a" / "big.npy")
+    assert g.size * 4 == 1 << 20 and np.all(np.diff(g) >= 0) and g.max() < big.numel()
+
+
 def test_evaluation_metrics_and_interpolation_baselines():
     """scripts/evaluate.py host logic (reference test_comparison.py:92-134,164-202): PSNR guard, the cv2-style
     half-pixel bilinear / bicubic (a = -0.75) resampling and the 3x3 sharpening."""

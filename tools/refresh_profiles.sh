@@ -8,5 +8,7 @@ bash $R/tools/profile_step.sh $tag > $R/gpurun_out/${tag}_profile.log 2>&1 || ex
 cp $R/gpurun_out/${tag}_pmc_traffic.json $R/profiles/pmc_traffic.json
 bash $R/tools/profile_single_stream.sh $tag > /dev/null 2>&1
 bash $R/tools/step_timeline.sh ${tag}two > /dev/null 2>&1
-cd $R && python bench.py > gpurun_out/${tag}_bench_c2.log 2>&1
-tail -1 gpurun_out/${tag}_bench_c2.log | python tools/bench_summary.py /dev/stdin | head -1
+log=${BENCH_LOG:-$R/build/${tag}_bench_c2.log}      # the bench line with roofline / per-kernel tables (--full)
+mkdir -p "$(dirname "$log")"
+cd $R && python bench.py --full > "$log" 2>&1
+tail -1 "$log" | python tools/bench_summary.py /dev/stdin | head -1
