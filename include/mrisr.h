@@ -114,6 +114,9 @@ size_t mrisr_packed_weight_bytes(int dtype, int Cout, int Cin, int ksize);
  * (packed buffer of mrisr_packed_weight_bytes_ring() bytes; Cout / Cin there are the OPERAND's, i.e. already
  * exchanged for the dgrad operand).                                                        */
 #define MRISR_PACK_RING 256
+/* | MRISR_PACK_UPADJ: the W^T image [Cin][row] of mrisr_conv_upadj (row = k = tap * Cout + co, padded; packed buffer of
+ * mrisr_packed_weight_bytes_upadj() bytes; Cout / Cin are the forward conv's, bit 0 is ignored)                        */
+#define MRISR_PACK_UPADJ 512
 /* output-channel block of the ring layout for an operand with these dims, 0 = the ring kernel does not take it */
 int mrisr_conv_ring_bn(int dtype, int Cout, int Cin, int ksize);
 size_t mrisr_packed_weight_bytes_ring(int dtype, int Cout, int Cin, int ksize);
@@ -128,8 +131,8 @@ typedef struct {
 } mrisr_pack_job;
 int mrisr_pack_weights_batched(int dtype, const mrisr_pack_job* jobs_device, int njobs, void* stream);
 int mrisr_conv_forward(const mrisr_conv_desc* d, void* stream);
-/* writes the name of the kernel instantiation mrisr_conv_forward (wgrad=0) / mrisr_conv_wgrad (wgrad=1) will
- * launch for this descriptor, template arguments as in the mangled symbol rocprofv3 reports               */
+/* writes the name of the kernel instantiation mrisr_conv_forward (wgrad=0) / mrisr_conv_wgrad (wgrad=1) /
+ * mrisr_conv_upadj (wgrad=2) will launch for this descriptor, template arguments as in the mangled symbol rocprofv3 reports */
 int mrisr_conv_variant(const mrisr_conv_desc* d, int wgrad, char* out, size_t n);
 /* weight gradient: dw[Cout][k][k][Cin] (fp32, ACCUMULATED) = sum_pix dy[pix][co] * in[pix+tap][ci];
  * the input is described exactly as in the forward desc (d->out, d->wpacked, d->bias ignored). */
@@ -139,6 +142,14 @@ int mrisr_conv_wgrad(const mrisr_conv_desc* d, const void* dy, float* dw, float*
  * sums go through it and a second kernel adds them into dw; with NULL (or a smaller buffer) they are added with
  * float atomics directly (same result up to summation order, slower).                                            */
 size_t mrisr_conv_wgrad_workspace_floats(const mrisr_conv_desc* d);
+
+/* input gradient of bilinear x2 (align_corners=True) followed by this 3x3 conv (final_up_bilinear, unet_model.py:151-152),
+ * formed at low resolution: d_low [N][H/2][W/2][Cin] = U^T (conv-dgrad(g)), g [N][H][W][Cout] = dL/d(conv output).
+ * d describes the FORWARD conv (N, H, W even, Cin, Cout, ksize 3, dtype, cu_limit); d->wpacked = the MRISR_PACK_UPADJ
+ * image; src / out / bias are ignored.  Computed as sum_t W_t^T h_t with h_t = U^T applied to g shifted by tap t
+ * (csrc/conv_upadj.hip).  16-bit dtypes, (Cout, Cin) = (8, 16), (16, 32) or (32, 64).                                  */
+size_t mrisr_packed_weight_bytes_upadj(int dtype, int Cout, int Cin, int ksize);   /* 0 = not supported */
+int mrisr_conv_upadj(const mrisr_conv_desc* d, const void* g, void* d_low, void* stream);
 
 /* stem conv Cin==1 (unet_model.py:29 for "inc"): x fp32 [N][H][W], w fp32 [Cout][9]          */
 int mrisr_stem_forward(int dtype, const float* x, const float* w, void* out, double* stats,

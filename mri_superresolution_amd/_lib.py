@@ -16,6 +16,7 @@ SP_NONE, SP_POOL2, SP_UP2, SP_HEAD = 0, 1, 2, 3
 COMBINE_CONCAT, COMBINE_BLEND = 0, 1
 OUT_PLAIN, OUT_PIXEL_SHUFFLE2 = 0, 1
 PACK_RING = 256      # MRISR_PACK_RING: OR into transpose_flip for the ring weight layout (csrc/conv_ring.hip)
+PACK_UPADJ = 512     # MRISR_PACK_UPADJ: the W^T image of mrisr_conv_upadj (csrc/conv_upadj.hip)
 STAT_SLOTS = 16      # = MRISR_STAT_SLOTS of include/mrisr.h; load() replaces it with the library's compiled value
 
 _vp, _fp, _dp, _i, _f, _d, _sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -74,6 +75,8 @@ SIGNATURES = {
     "mrisr_pack_weights": (_i, [_i, _fp, _i, _i, _i, _i, _vp, _vp]),
     "mrisr_pack_weights_batched": (_i, [_i, _vp, _i, _vp]),
     "mrisr_conv_forward": (_i, [C.POINTER(ConvDesc), _vp]),
+    "mrisr_packed_weight_bytes_upadj": (_sz, [_i, _i, _i, _i]),
+    "mrisr_conv_upadj": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp]),
     "mrisr_conv_variant": (_i, [C.POINTER(ConvDesc), _i, C.c_char_p, _sz]),
     "mrisr_conv_wgrad": (_i, [C.POINTER(ConvDesc), _vp, _fp, _fp, _sz, _vp]),
     "mrisr_conv_wgrad_workspace_floats": (_sz, [C.POINTER(ConvDesc)]),
@@ -128,7 +131,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 304      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 305      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

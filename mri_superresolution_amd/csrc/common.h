@@ -155,6 +155,26 @@ __device__ __forceinline__ void up2_coord(int dst, int in_size, int& i0, int& i1
     w1 = src - (float)i0;
 }
 
+// candidate high-res rows of a bilinear x2 (align_corners) adjoint and their weights for low-res index y:
+// src(Y) = Y (n-1)/(2n-1) touches row y only for Y in [2y-1, 2y+2] (checked exhaustively for n <= 512)
+constexpr int kUpAdj = 4;
+__device__ __forceinline__ void up2_adjoint_weights(int y, int in_size, int* idx, float* w) {
+#pragma unroll
+    for (int k = 0; k < kUpAdj; ++k) {
+        const int Y = 2 * y - 1 + k;
+        float wt = 0.f;
+        if (Y >= 0 && Y < 2 * in_size) {
+            int i0, i1;
+            float w1;
+            up2_coord(Y, in_size, i0, i1, w1);
+            if (i0 == y) wt += 1.f - w1;
+            if (i1 == y) wt += w1;
+        }
+        idx[k] = Y;
+        w[k] = wt;
+    }
+}
+
 // slot of a statistics buffer for this workgroup (spreads same-address fp64 atomics)
 __device__ __forceinline__ size_t stat_slot_off(int N, int groups) {
     return (size_t)((blockIdx.x + blockIdx.y) & (MRISR_STAT_SLOTS - 1)) * N * groups * 2;

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "conv_common.h"
+#include "conv_upadj.h"
 
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
@@ -1186,6 +1187,7 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, T* __restrict__
 // one output-channel row apart (mirrored input-gradient operand), the chunk is stored with one 16-byte store.
 // (one thread per ELEMENT with five integer divisions each ran at 1 TB/s: 62 us per training step.)
 struct PackJobDev { const float* w; void* packed; int Cout, Cin, ksize, flip; };
+int conv_upadj_variant(const mrisr_conv_desc* d, char* out, size_t n);
 template <typename T>
 __global__ void pack_weights_batched_kernel(const PackJobDev* __restrict__ jobs) {
     constexpr int BK = kRowBytes / (int)sizeof(T);
@@ -1204,6 +1206,24 @@ __global__ void pack_weights_batched_kernel(const PackJobDev* __restrict__ jobs)
             v.set(e, x);
         }
     };
+    if (j.flip & MRISR_PACK_UPADJ) {
+        // W^T image of the low-resolution input gradient of bilinear x2 + conv (conv_upadj.hip): [Cin][RS] rows of
+        // k = tap * Cout + co, element W[co][tap][ci]; zero past k = 9 Cout (the GEMM's K padding and the row padding)
+        if (!conv_upadj_image_bytes(TypeTraits<T>::kDtype, Cout, Cin, KS)) return;
+        const int RS = upadj_rs(Cout), K9 = ntaps * Cout;
+        const size_t nchunk = (size_t)Cin * RS / EPC;
+        for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < nchunk; idx += (size_t)gridDim.x * blockDim.x) {
+            const int ci = (int)(idx * EPC / RS), k0 = (int)(idx * EPC % RS);
+            Vec16<T> v;
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) {
+                const int k = k0 + e;
+                v.set(e, k < K9 ? w[((size_t)(k % Cout) * ntaps + k / Cout) * Cin + ci] : 0.f);
+            }
+            store_vec16((T*)j.packed + idx * EPC, v);
+        }
+        return;
+    }
     if (j.flip & MRISR_PACK_RING) {
         // ring layout (conv_ring.hip): [cout block][cin chunk of 16][tap][BN rows][32 B]; the 16-B slot s of row r sits at
         // position s ^ ((r >> 3) & 1), so that a row fragment reads conflict-free and a DMA piece is a linear copy
@@ -1269,9 +1289,11 @@ extern "C" int mrisr_pack_weights(int dtype, const float* w, int Cout, int Cin, 
                                   void* packed, void* stream) {
     if (!w || !packed) MRISR_FAIL(MRISR_E_ARG, "pack_weights: null pointer");
     if (ksize != 1 && ksize != 3) MRISR_FAIL(MRISR_E_UNSUPPORTED, "pack_weights: ksize %d", ksize);
-    if (transpose_flip & MRISR_PACK_RING) {
+    if (transpose_flip & (MRISR_PACK_RING | MRISR_PACK_UPADJ)) {
         const int flip = transpose_flip & 1;
-        if (!mrisr_conv_ring_bn(dtype, flip ? Cin : Cout, flip ? Cout : Cin, ksize))
+        if ((transpose_flip & MRISR_PACK_UPADJ) && !conv_upadj_image_bytes(dtype, Cout, Cin, ksize))
+            MRISR_FAIL(MRISR_E_UNSUPPORTED, "pack_weights: no upadj layout for %d -> %d k%d dtype %d", Cin, Cout, ksize, dtype);
+        if (!(transpose_flip & MRISR_PACK_UPADJ) && !mrisr_conv_ring_bn(dtype, flip ? Cin : Cout, flip ? Cout : Cin, ksize))
             MRISR_FAIL(MRISR_E_UNSUPPORTED, "pack_weights: no ring layout for %d -> %d k%d dtype %d", Cin, Cout, ksize, dtype);
         const PackJobDev job{w, packed, Cout, Cin, ksize, transpose_flip};
         PackJobDev* dj = nullptr;      // (stand-alone packing is a test / tool path: the training step uses the batched entry)
@@ -1477,6 +1499,10 @@ static int dispatch_conv_sp(ConvParams& p, int spatial, int ks, hipStream_t s) {
 
 // Name of the template instantiation the dispatcher picks for a descriptor (the grouping rocprofv3 reports).
 extern "C" int mrisr_conv_variant(const mrisr_conv_desc* d, int wgrad, char* out, size_t n) {
+    if (d && wgrad == 2) {
+        if (!out || n < 8) MRISR_FAIL(MRISR_E_ARG, "conv_variant: bad buffer");
+        return conv_upadj_variant(d, out, n);
+    }
     ConvParams p;
     int rc = conv_fill_params(d, p, "conv_variant");
     if (rc) return rc;

@@ -148,26 +148,6 @@ __device__ __forceinline__ void act_of(const T* p, const float* sc, const float*
     for (int e = 0; e < Vec16<T>::N; ++e) o[e] = lrelu(v.get(e) * sc[e] + sh[e]);
 }
 
-// candidate high-res rows of a bilinear x2 (align_corners) adjoint and their weights for low-res index y:
-// src(Y) = Y (n-1)/(2n-1) touches row y only for Y in [2y-1, 2y+2] (checked exhaustively for n <= 512)
-constexpr int kUpAdj = 4;
-__device__ __forceinline__ void up2_adjoint_weights(int y, int in_size, int* idx, float* w) {
-#pragma unroll
-    for (int k = 0; k < kUpAdj; ++k) {
-        const int Y = 2 * y - 1 + k;
-        float wt = 0.f;
-        if (Y >= 0 && Y < 2 * in_size) {
-            int i0, i1;
-            float w1;
-            up2_coord(Y, in_size, i0, i1, w1);
-            if (i0 == y) wt += 1.f - w1;
-            if (i1 == y) wt += w1;
-        }
-        idx[k] = Y;
-        w[k] = wt;
-    }
-}
-
 // PLAIN: every consumer is MRISR_SP_NONE (17 of the 20 nodes of the U-Net) - compiled without the pool / bilinear
 // adjoint code, whose 32-float windows cost the generic kernel 155 VGPRs = 3 waves per SIMD, too few loads in
 // flight for an HBM-bound pass (measured 3.0 TB/s).

@@ -205,17 +205,22 @@ class UNetEngine:
         if self.timer is None:
             return fn()
         flops = 2.0 * desc.N * desc.H * desc.W * desc.Cin * desc.Cout * desc.ksize * desc.ksize
+        if kind == "upadj":
+            flops /= 4              # the GEMM runs at the low resolution
         buf = C.create_string_buffer(96)
-        L.call("mrisr_conv_variant", C.byref(desc), 1 if kind == "wgrad" else 0, buf, 96)
+        L.call("mrisr_conv_variant", C.byref(desc), {"wgrad": 1, "upadj": 2}.get(kind, 0), buf, 96)
         self.timer.launch(buf.value.decode(), flops, fn)
 
     # ------------------------------------------------------------------ weights
-    def _packed_buf(self, layer: Layer, w, dt: int, flip: int, ring: bool = False):
-        key = (layer.name, dt, flip, "ring") if ring else (layer.name, dt, flip)
+    def _packed_buf(self, layer: Layer, w, dt: int, flip: int, ring: bool = False, upadj: bool = False):
+        key = (layer.name, dt, "upadj") if upadj else (layer.name, dt, flip, "ring") if ring else (layer.name, dt, flip)
         buf = self._packed.get(key)
         if buf is None or buf.device != w.device:
-            size = L.load().mrisr_packed_weight_bytes_ring if ring else L.load().mrisr_packed_weight_bytes
-            nbytes = size(dt, layer.cin if flip else layer.cout, layer.cout if flip else layer.cin, layer.ks)
+            if upadj:
+                nbytes = L.load().mrisr_packed_weight_bytes_upadj(dt, layer.cout, layer.cin, layer.ks)
+            else:
+                size = L.load().mrisr_packed_weight_bytes_ring if ring else L.load().mrisr_packed_weight_bytes
+                nbytes = size(dt, layer.cin if flip else layer.cout, layer.cout if flip else layer.cin, layer.ks)
             buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
             self._packed[key] = buf
         return buf
@@ -235,7 +240,7 @@ class UNetEngine:
         dev = params[self.layers[0].name + ".weight"].device
         key = (dt, str(dev), tuple(params[l.name + ".weight"].data_ptr() for l in self.layers))
         if getattr(self, "_jobs_key", None) != key:
-            jobs = (L.PackJob * (4 * len(self.layers)))()
+            jobs = (L.PackJob * (4 * len(self.layers) + 1))()
             i = 0
             for layer in self.layers:
                 w = params[layer.name + ".weight"]
@@ -252,6 +257,14 @@ class UNetEngine:
                         j.w, j.packed, j.Cout, j.Cin, j.ksize, j.transpose_flip = (w.data_ptr(), buf.data_ptr(), layer.cout, layer.cin,
                                                                                    layer.ks, flip | L.PACK_RING)
                         i += 1
+                # final_up_bilinear: the W^T image of its low-resolution input gradient (csrc/conv_upadj.hip)
+                if layer.up_src and not TUNING.no_upadj and L.load().mrisr_packed_weight_bytes_upadj(dt, layer.cout, layer.cin,
+                                                                                                       layer.ks) > 0:
+                    buf = self._packed_buf(layer, w, dt, 0, upadj=True)
+                    j = jobs[i]
+                    j.w, j.packed, j.Cout, j.Cin, j.ksize, j.transpose_flip = (w.data_ptr(), buf.data_ptr(), layer.cout, layer.cin,
+                                                                               layer.ks, L.PACK_UPADJ)
+                    i += 1
             # algorithmic traffic of the launch: every fp32 master once per image built from it + every image written once
             self._jobs_bytes = sum(4 * params[l.name + ".weight"].numel() for l in self.layers) * 2 + \
                 sum(b.numel() for k, b in self._packed.items() if k[1] == dt)
@@ -640,6 +653,27 @@ class UNetEngine:
             if layer.bias and not fuse_bias:
                 L.call("mrisr_channel_sum", dt, dy.data_ptr(), grads[layer.name + ".bias"].data_ptr(),
                        N * layer.H * layer.W, layer.cout, st, nbytes=N * layer.H * layer.W * layer.cout * es)
+            upk = self._packed.get((layer.name, dt, "upadj")) if layer.up_src else None
+            if upk is not None:
+                # bilinear x2 + 3x3 conv: the input gradient of the low-resolution source in ONE launch, sum_t W_t^T h_t
+                # with h_t = the x2 adjoint of dy shifted by tap t (csrc/conv_upadj.hip); neither the high-resolution
+                # input gradient nor its adjoint pass is materialised
+                sn = layer.srcs[0].node
+                ud = L.ConvDesc()
+                ud.dtype, ud.N, ud.H, ud.W = dt, N, layer.H, layer.W
+                ud.Cin, ud.Cout, ud.ksize, ud.nsrc = layer.cin, layer.cout, layer.ks, 1
+                ud.wpacked = upk.data_ptr()
+                ud.cu_limit = _CU_LIMIT
+                if side is not None and side_cus > 0:
+                    ud.cu_limit = max(8, L.num_cus() - side_cus)
+                dlow = torch.empty((N, sn.H, sn.W, layer.cin), dtype=dtype, device=dev)
+                self._launch("upadj", ud, lambda: L.call("mrisr_conv_upadj", C.byref(ud), dy.data_ptr(), dlow.data_ptr(), st))
+                if wgrad_last:
+                    launch_wgrad()
+                sn.consumers.append((dlow, layer.cin, 0, sn.H, sn.W, L.SP_NONE, 0, 0, 0))
+                if bucket_hook:
+                    bucket_hook(layer.name)
+                continue
             # input gradient: the same implicit-GEMM kernel on dy with mirrored, transposed weights
             dd = L.ConvDesc()
             dd.dtype, dd.N, dd.H, dd.W = dt, N, layer.H, layer.W

@@ -19,6 +19,9 @@ that `tools/` can A/B schedules on one box without editing the package.  libmris
                        forward does, instead of forming it in the staging waves of conv_pc_kernel
   MRISR_NO_ONEPASS     1: every GroupNorm backward runs as two launches (reduce + apply) instead of the one-pass kernel with the
                        in-kernel image barrier (csrc/norm.hip: act_bwd_onepass_kernel)
+  MRISR_NO_UPADJ       1: the input gradient of final_up_bilinear's 3x3 conv runs as the conv-dgrad at high resolution plus the
+                       x2 adjoint (mrisr_conv_forward + mrisr_upsample2_adjoint) instead of the one low-resolution launch
+                       (mrisr_conv_upadj, csrc/conv_upadj.hip)
   MRISR_FORCE_DP       1: bench.py / scripts wrap the model in DataParallel even at world size 1 (rehearses the RCCL path)
 """
 from __future__ import annotations
@@ -50,6 +53,7 @@ class Tuning:
     up_fused: bool
     no_onepass: bool
     no_fused_blend: bool
+    no_upadj: bool
 
 
 def _read() -> Tuning:
@@ -65,6 +69,7 @@ def _read() -> Tuning:
         up_fused=_int("MRISR_UP_FUSED", 0) == 1,
         no_onepass=_int("MRISR_NO_ONEPASS", 0) == 1,
         no_fused_blend=_int("MRISR_NO_FUSED_BLEND", 0) == 1,
+        no_upadj=_int("MRISR_NO_UPADJ", 0) == 1,
     )
 
 
