@@ -329,6 +329,16 @@ int mrisr_ssim_l1_backward_win(const float* a, const float* b, const float* coef
 int mrisr_loss_finalize(const double* sums, int N, int H, int W, float l1_w, float ssim_w, float* out,
                         void* stream);
 
+/* ---- image metrics of the evaluation harness (scripts/test_comparison.py:164-202) ---------- */
+/* mrisr_ssim_l1_forward_win's tile pass (same window rule, same error codes, no coefficient planes) with the squared error
+ * as a third sum.  a, b: [N][H][W] fp32.  sums[N][3] (double, accumulated; zero it first):
+ * sums[n][0] += sum|a-b|, sums[n][1] += sum ssim_map, sums[n][2] += sum (a-b)^2.                                        */
+int mrisr_image_metrics(const float* a, const float* b, double* sums, int N, int H, int W, float val_range, float sigma,
+                        int window_size, void* stream);
+/* sums[N][3] of mrisr_image_metrics -> out[N][5] doubles per image: ssim, mse, rmse, mae, psnr with
+ * psnr = mse < 1e-10 ? 100 : 10 log10(val_range^2 / mse) (test_comparison.py:189-194).  No host read-back.              */
+int mrisr_metrics_finalize(const double* sums, int N, int H, int W, float val_range, double* out, void* stream);
+
 /* ---- perceptual loss: glue of the frozen VGG19 feature stack (utils/losses.py:83-151).  The 3x3 convolutions are
  *      mrisr_conv_forward calls (bias + relu_out forward; relu_mask for the input gradient). ------------------- */
 /* channels of the normalised VGG input tensor (3 real + zero padding to one 16-byte bf16 vector) */
@@ -377,6 +387,18 @@ int mrisr_u8_percentile_normalise(const uint8_t* img, const unsigned* hist, size
                                   double q_lo, double q_hi, float* out, float* lohi, void* stream);
 /* out[i] = (uint8)(clamp(x[i], 0, 1) * 255), truncating like ndarray.astype(np.uint8) (infer.py:276, 331).          */
 int mrisr_f32_to_u8(const float* x, uint8_t* out, size_t n, void* stream);
+
+/* ---- x2 interpolation baselines of the evaluation harness on 8-bit images (scripts/test_comparison.py:92-134) ------ */
+#define MRISR_UP2_BILINEAR 0        /* cv2.resize INTER_LINEAR                                                          */
+#define MRISR_UP2_BICUBIC 1         /* cv2.resize INTER_CUBIC (Keys a = -0.75)                                          */
+#define MRISR_UP2_SHARP_BILINEAR 2  /* INTER_LINEAR, then filter2D [[-1,-1,-1],[-1,9,-1],[-1,-1,-1]], BORDER_REFLECT_101 */
+/* in: [batch][h][w] uint8 -> [batch][2h][2w]; cv2's rules as scripts/evaluate.py:upscale_array restates them (half-pixel
+ * centres, border replication, result rounded half to even and saturated to uint8), exact integer arithmetic.
+ * out_u8 (optional) receives the uint8 image, out_f32 (optional) the same values / 255 in float32; at least one of the two.
+ * Any h, w >= 1; batch 1 .. 65535.                                                                                      */
+int mrisr_u8_upscale2(const uint8_t* in, uint8_t* out_u8, float* out_f32, int batch, int h, int w, int method, void* stream);
+/* out[i] = img[i] / 255 in float32 (ToTensor of an 8-bit image; evaluate.py's HR side: normalise -> uint8 -> / 255).    */
+int mrisr_u8_to_unit_f32(const uint8_t* img, float* out, size_t n, void* stream);
 
 /* ---- paired augmentation on the device (utils/dataset.py:138-175) ------------------------- */
 typedef struct {

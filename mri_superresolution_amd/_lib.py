@@ -15,6 +15,7 @@ SRC_RAW, SRC_NORM, SRC_RELU = 0, 1, 2
 SP_NONE, SP_POOL2, SP_UP2, SP_HEAD = 0, 1, 2, 3
 COMBINE_CONCAT, COMBINE_BLEND = 0, 1
 OUT_PLAIN, OUT_PIXEL_SHUFFLE2 = 0, 1
+UP2_BILINEAR, UP2_BICUBIC, UP2_SHARP_BILINEAR = 0, 1, 2      # MRISR_UP2_*: method of mrisr_u8_upscale2
 PACK_RING = 256      # MRISR_PACK_RING: OR into transpose_flip for the ring weight layout (csrc/conv_ring.hip)
 PACK_UPADJ = 512     # MRISR_PACK_UPADJ: the W^T image of mrisr_conv_upadj (csrc/conv_upadj.hip)
 STAT_SLOTS = 16      # = MRISR_STAT_SLOTS of include/mrisr.h; load() replaces it with the library's compiled value
@@ -114,6 +115,8 @@ SIGNATURES = {
     "mrisr_ssim_l1_forward_win": (_i, [_fp, _fp, _dp, _fp, _i, _i, _i, _f, _f, _i, _vp]),
     "mrisr_ssim_l1_backward_win": (_i, [_fp, _fp, _fp, _dp, _fp, _f, _f, _fp, _i, _i, _i, _f, _i, _vp]),
     "mrisr_loss_finalize": (_i, [_dp, _i, _i, _i, _f, _f, _fp, _vp]),
+    "mrisr_image_metrics": (_i, [_fp, _fp, _dp, _i, _i, _i, _f, _f, _i, _vp]),
+    "mrisr_metrics_finalize": (_i, [_dp, _i, _i, _i, _f, _dp, _vp]),
     "mrisr_vgg_input_channels": (_i, []),
     "mrisr_vgg_input_forward": (_i, [_i, _fp, _vp, _sz, _vp]),
     "mrisr_vgg_input_backward": (_i, [_i, _vp, _fp, _f, _fp, _sz, _vp]),
@@ -125,6 +128,8 @@ SIGNATURES = {
     "mrisr_u8_histogram": (_i, [_vp, _sz, _i, _vp, _vp]),
     "mrisr_u8_percentile_normalise": (_i, [_vp, _vp, _sz, _i, _d, _d, _fp, _fp, _vp]),
     "mrisr_f32_to_u8": (_i, [_fp, _vp, _sz, _vp]),
+    "mrisr_u8_upscale2": (_i, [_vp, _vp, _fp, _i, _i, _i, _i, _vp]),
+    "mrisr_u8_to_unit_f32": (_i, [_vp, _fp, _sz, _vp]),
     "mrisr_augment_geo_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _dp, _vp]),
     "mrisr_augment_finish_u8": (_i, [_vp, _fp, _i, _sz, _vp, _dp, _vp]),
     "mrisr_cast": (_i, [_i, _vp, _i, _vp, _sz, _vp]),

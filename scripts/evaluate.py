@@ -11,6 +11,13 @@ host-side numpy restatements of the cv2 resampling rules (half-pixel centres, bo
 results rounded to uint8 as cv2 does on uint8 images).  cv2 / skimage are absent offline: the baselines are **parity
 unpinned** against cv2 itself (structural restatement of its documented kernels).
 
+Extensions: ``--batch_size N`` (default 0 = the per-image path above) evaluates the test set in chunks of N pairs of equal
+size with everything between the decoded PNG bytes and the metric values on the device: the three baselines as one HIP
+launch each per chunk (``utils/evalops.upscale2_u8``, bit-equal to ``upscale_array``), the U-Net as one batched forward
+(replayed as a HIP graph for full chunks unless ``--no_graph``), all five metrics from one pass per method
+(``utils/evalops.image_metrics``) and one read-back per chunk.  Same rows, CSV columns and summary; ``time`` is then the
+chunk's wall time for the method divided by the chunk length.
+
     python scripts/evaluate.py --full_res_dir HR --low_res_dir LR --checkpoint_dir ./checkpoints --output_dir ./evaluation
 """
 from __future__ import annotations
@@ -143,6 +150,70 @@ def run_benchmarks(test_pairs, model, device, use_amp: bool = False):
     return rows
 
 
+def run_benchmarks_batched(test_pairs, model, device, use_amp: bool = False, batch_size: int = 16, use_graph: bool = True,
+                           workers: int = 8, timings: dict | None = None):
+    """The rows of ``run_benchmarks``, computed in chunks of ``batch_size`` pairs of equal size on the device (extension).
+    PNGs are decoded on ``workers`` threads; a chunk is uploaded once (pinned), every method is one batched launch
+    sequence followed by one device synchronisation (its ``time`` = that wall time / chunk length), the four metric
+    tensors are read back together.  ``timings`` (optional) receives the seconds spent in ``decode`` and ``device``."""
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from mri_superresolution_amd.utils import evalops, imageops
+    from scripts.infer import enhance_batch
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    model.set_compute_dtype(torch.float16 if use_amp else torch.float32)   # reference: torch.amp.autocast("cuda") = fp16
+    t_start = time.time()
+    with ThreadPoolExecutor(max_workers=max(1, workers)) as pool:
+        def decode(p):
+            return np.asarray(Image.open(p).convert("L"), dtype=np.uint8)
+        lr_imgs = list(pool.map(decode, [p for p, _ in test_pairs]))
+        hr_imgs = list(pool.map(decode, [p for _, p in test_pairs]))
+    t_decoded = time.time()
+    groups = {}
+    for i, (lr, hr) in enumerate(zip(lr_imgs, hr_imgs)):
+        up_shape = (2 * lr.shape[0], 2 * lr.shape[1])
+        if up_shape != hr.shape:
+            raise ValueError(f"{os.path.basename(test_pairs[i][0])}: bicubic output {up_shape} vs HR {hr.shape}")
+        groups.setdefault(lr.shape, []).append(i)
+    per_image = [None] * len(test_pairs)
+    graphs = {}
+    for idx in groups.values():
+        for i0 in range(0, len(idx), batch_size):
+            chunk = idx[i0:i0 + batch_size]
+            lr_host = torch.from_numpy(np.stack([lr_imgs[i] for i in chunk])).pin_memory()
+            hr_host = torch.from_numpy(np.stack([hr_imgs[i] for i in chunk])).pin_memory()
+            lr_u8 = lr_host.to(device, non_blocking=True)
+            hr_u8 = hr_host.to(device, non_blocking=True)
+            outputs, times = [], []
+            for method in METHODS:
+                t0 = time.time()
+                if method == "unet":
+                    x = imageops.normalise_percentile_u8(lr_u8)
+                    if use_graph and len(chunk) == batch_size:
+                        key = (tuple(x.shape), use_amp)
+                        if key not in graphs:
+                            graphs[key] = model.graphed_forward(x)
+                        out = graphs[key](x).clamp(0.0, 1.0)
+                    else:
+                        out = enhance_batch(model, x, use_amp)
+                else:
+                    out = evalops.upscale2_u8(lr_u8, method)
+                torch.cuda.synchronize()
+                times.append((time.time() - t0) / len(chunk))
+                outputs.append(out)
+            # HR side as _load01: percentile-normalise, through uint8, / 255
+            hr01 = evalops.unit_from_u8(imageops.to_uint8(imageops.normalise_percentile_u8(hr_u8)))
+            vals = torch.cat([evalops.image_metrics(out, hr01, 11, 1.5, 1.0) for out in outputs]).cpu().numpy()
+            for j, i in enumerate(chunk):
+                name = os.path.basename(test_pairs[i][0])
+                per_image[i] = [dict(zip(evalops.METRIC_COLUMNS, (float(v) for v in vals[k * len(chunk) + j])),
+                                     method=method, time=times[k], image=name) for k, method in enumerate(METHODS)]
+    if timings is not None:
+        timings.update(decode=t_decoded - t_start, device=time.time() - t_decoded)
+    return [row for rows in per_image for row in rows]
+
+
 def summarise(rows):
     out = {}
     for method in METHODS:
@@ -169,7 +240,10 @@ def main(args) -> int:
             pairs = pairs[: args.max_images]
         if not pairs:
             raise FileNotFoundError("no LR/HR PNG pairs with matching names")
-        rows = run_benchmarks(pairs, model, device, args.use_amp)
+        if args.batch_size > 0:
+            rows = run_benchmarks_batched(pairs, model, device, args.use_amp, args.batch_size, not args.no_graph)
+        else:
+            rows = run_benchmarks(pairs, model, device, args.use_amp)
         os.makedirs(args.output_dir, exist_ok=True)
         csv_path = os.path.join(args.output_dir, "benchmark_results.csv")
         cols = ["image", "method", "ssim", "psnr", "mse", "rmse", "mae", "time"]
@@ -204,6 +278,8 @@ def parse_args(argv=None):
     p.add_argument("--max_images", type=int, default=0)
     p.add_argument("--use_amp", action="store_true")
     p.add_argument("--cpu", action="store_true")
+    p.add_argument("--batch_size", type=int, default=0, help="(extension) pairs per chunk of the device-side path; 0 = one image at a time, as the reference")
+    p.add_argument("--no_graph", action="store_true", help="(extension) with --batch_size: do not replay the forward as a HIP graph")
     return p.parse_args(argv)
 
 
