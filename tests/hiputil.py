@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 import torch.nn.functional as F
@@ -163,6 +164,154 @@ def conv_wgrad(dt, srcs, dy_nchw, cout, cin, H, W, ks, combine=L.COMBINE_CONCAT,
     L.call("mrisr_conv_wgrad", C.byref(d), dyd.data_ptr(), dw.data_ptr(), L.ptr(ws), ws.numel() if ws is not None else 0, stream())
     torch.cuda.synchronize()
     return dw.cpu().permute(0, 3, 1, 2).contiguous()
+
+
+# ------------------------------------------------------------------------------------------- exact arithmetic
+def dyadic(shape, seed, density, values=(-1, 1)) -> torch.Tensor:
+    """Seeded fp32 CPU tensor on a small dyadic grid: each element is non-zero with probability ``density`` and then
+    drawn uniformly from ``values`` (small integers or powers of two)."""
+    g = torch.Generator().manual_seed(seed)
+    shape = tuple(shape)
+    nz = torch.rand(shape, generator=g) < density
+    pick = torch.randint(len(values), shape, generator=g)
+    v = torch.tensor(values, dtype=torch.float32)[pick]
+    return torch.where(nz, v, torch.zeros((), dtype=torch.float32))
+
+
+def exact_dtype(dt):
+    """torch dtype a result is stored in: a compute dtype code of the library, or "f64" for the statistics."""
+    return torch.float64 if dt == "f64" else tdt(dt)
+
+
+def assert_exact(got: torch.Tensor, ref64: torch.Tensor, dt, tier="A", what=""):
+    """``got`` must equal the float64 reference bit for bit.  Tier A: the reference must itself be representable in the
+    storage type ``dt`` (checked first, so that a test cannot pass vacuously) and is the expected value.  Tier B: the
+    expected value is the reference rounded ONCE (round-to-nearest-even) to the storage type."""
+    assert ref64.dtype == torch.float64 and tier in ("A", "B")
+    assert got.shape == ref64.shape, f"{what}: shape {tuple(got.shape)} != {tuple(ref64.shape)}"
+    assert torch.isfinite(ref64).all(), f"{what}: the reference is not finite"
+    onto = ref64.to(exact_dtype(dt)).double()
+    if tier == "A":
+        off = onto != ref64
+        assert not off.any(), (f"{what}: the float64 reference is not on the {exact_dtype(dt)} grid at {int(off.sum())} elements, "
+                               f"first {_first_indices(off)}")
+    g = got.double()
+    if not torch.equal(g, onto):
+        bad = (g != onto) | torch.isnan(g)
+        first = _first_indices(bad)
+        vals = [(float(g[i]), float(onto[i])) for i in first]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ (tier {tier}); first indices {first}, "
+                             f"(got, expected) {vals}")
+
+
+def _first_indices(mask: torch.Tensor, k=6):
+    return [tuple(int(v) for v in i) for i in mask.nonzero()[:k]]
+
+
+GUARD_BYTES = 4096
+
+
+class Guarded:
+    """A device tensor inside a larger allocation, with GUARD_BYTES of a sentinel byte pattern on both sides; ``check()``
+    asserts that a launch left both bands as they were (a kernel with unpredicated tile stores that overruns its output
+    would otherwise write silently into a neighbouring allocation)."""
+
+    def __init__(self, init: torch.Tensor):
+        """``init``: CPU tensor with the interior's shape, dtype and initial contents."""
+        init = init.contiguous()
+        nbytes = init.numel() * init.element_size()
+        self._n = nbytes
+        self._raw = torch.empty(nbytes + 2 * GUARD_BYTES, dtype=torch.uint8, device=DEV)
+        self._pattern = ((torch.arange(GUARD_BYTES, dtype=torch.int32) * 37 + 11) % 251 + 1).to(torch.uint8).to(DEV)
+        self._raw[:GUARD_BYTES] = self._pattern
+        self._raw[GUARD_BYTES + nbytes:] = self._pattern
+        self.t = self._raw[GUARD_BYTES:GUARD_BYTES + nbytes].view(init.dtype).view(init.shape)
+        self.t.copy_(init)
+        assert self.t.data_ptr() == self._raw.data_ptr() + GUARD_BYTES
+
+    def data_ptr(self):
+        return self.t.data_ptr()
+
+    def check(self, what=""):
+        lo = self._raw[:GUARD_BYTES] != self._pattern
+        hi = self._raw[GUARD_BYTES + self._n:] != self._pattern
+        assert not bool(lo.any()) and not bool(hi.any()), (
+            f"{what}: guard band overwritten: {int(lo.sum())} bytes below (last at -{GUARD_BYTES - int(lo.nonzero().max()) if lo.any() else 0}), "
+            f"{int(hi.sum())} bytes above (first at +{int(hi.nonzero().min()) if hi.any() else 0})")
+
+
+def int_pattern(shape, dtype, mod=7):
+    """Non-zero small-integer start value for the buffers the library ACCUMULATES into (dw, statistics)."""
+    n = math.prod(shape)
+    return ((torch.arange(n, dtype=torch.int64) * 5 + 3) % mod - mod // 2).to(dtype).view(shape)
+
+
+def variant_name(d, wgrad=0) -> str:
+    name = C.create_string_buffer(96)
+    L.call("mrisr_conv_variant", C.byref(d), wgrad, name, 96)
+    return name.value.decode()
+
+
+def conv_forward_guarded(dt, srcs, w, H, W, ks, bias=None, combine=L.COMBINE_CONCAT, out_mode=L.OUT_PLAIN, alpha=None,
+                         stats0=None, use_ring=True, cu_limit=0, relu_out=0, relu_mask=None, flip=0):
+    """mrisr_conv_forward with the output and the statistics inside guard bands.  ``w``: the (Cout,Cin,k,k) master;
+    ``flip`` = 1: the conv runs on its input-gradient operand (sources carry Cout channels, the output Cin).  ``stats0``
+    ([STAT_SLOTS][N][8][2] float64, or None for no statistics epilogue): start value of the statistics buffer.
+    Returns (out NCHW fp32 CPU, statistics buffer summed over the slots or None, name of the kernel that ran)."""
+    keep = []
+    cout, cin = (w.shape[1], w.shape[0]) if flip else (w.shape[0], w.shape[1])
+    d = make_desc(dt, srcs, H, W, cin, cout, ks, combine, out_mode, alpha, keep)
+    d.cu_limit, d.relu_out = cu_limit, relu_out
+    N = d.N
+    wp = pack(w, dt, flip)
+    d.wpacked = wp.data_ptr()
+    wr = pack(w, dt, flip, ring=True) if use_ring else None
+    d.wpacked_ring = L.ptr(wr)
+    if bias is not None:
+        bd = bias.to(DEV)
+        keep.append(bd)
+        d.bias = bd.data_ptr()
+    if relu_mask is not None:
+        md = nhwc(relu_mask, dt)
+        keep.append(md)
+        d.relu_mask = md.data_ptr()
+    shape = (N, 2 * H, 2 * W, cout // 4) if out_mode == L.OUT_PIXEL_SHUFFLE2 else (N, H, W, cout)
+    out = Guarded(torch.full(shape, float("nan"), dtype=tdt(dt)))
+    d.out = out.data_ptr()
+    stats = None
+    if stats0 is not None:
+        assert tuple(stats0.shape) == (L.STAT_SLOTS, N, 8, 2) and stats0.dtype == torch.float64
+        stats = Guarded(stats0)
+        d.stats = stats.data_ptr()
+    ran = variant_name(d, 0)
+    L.call("mrisr_conv_forward", C.byref(d), stream())
+    torch.cuda.synchronize()
+    out.check(f"{ran}: out")
+    if stats is not None:
+        stats.check(f"{ran}: stats")
+    return nchw(out.t), (stats.t.cpu().sum(0) if stats is not None else None), ran
+
+
+def conv_wgrad_guarded(dt, srcs, dy_nchw, cout, cin, H, W, ks, dw0, combine=L.COMBINE_CONCAT, alpha=None, use_ws=False,
+                       cu_limit=0):
+    """mrisr_conv_wgrad accumulating into ``dw0`` ((Cout,Cin,k,k) fp32 CPU start value), with dw and the split-K workspace
+    inside guard bands.  Returns (dw (Cout,Cin,k,k) fp32 CPU, name of the kernel that ran)."""
+    keep = []
+    d = make_desc(dt, srcs, H, W, cin, cout, ks, combine, L.OUT_PLAIN, alpha, keep)
+    d.cu_limit = cu_limit
+    ran = variant_name(d, 1)
+    dyd = nhwc(dy_nchw, dt)
+    dw = Guarded(dw0.permute(0, 2, 3, 1).contiguous().float())
+    ws, nws = None, 0
+    if use_ws:
+        nws = max(int(L.load().mrisr_conv_wgrad_workspace_floats(C.byref(d))), 1)
+        ws = Guarded(torch.full((nws,), float("nan"), dtype=torch.float32))
+    L.call("mrisr_conv_wgrad", C.byref(d), dyd.data_ptr(), dw.data_ptr(), L.ptr(ws), nws, stream())
+    torch.cuda.synchronize()
+    dw.check(f"{ran}: dw")
+    if ws is not None:
+        ws.check(f"{ran}: workspace")
+    return dw.t.cpu().permute(0, 3, 1, 2).contiguous(), ran
 
 
 def relerr(a: torch.Tensor, b: torch.Tensor) -> float:
