@@ -423,6 +423,32 @@ int mrisr_augment_geo_u8(const uint8_t* in, uint8_t* out, int batch, int H, int 
 int mrisr_augment_finish_u8(const uint8_t* in, float* out, int batch, size_t pixels_per_image,
                             const mrisr_aug_photo* params_device, const double* mean_device, void* stream);
 
+/* ---- low-field MRI simulation on the device (extension; reference utils/preprocessing.py:225-293 simulate_low_field_mri,
+ *      utils/extraction_utils.py:136-163): FFT -> keep the centre of k-space -> complex Gaussian noise -> IFFT -> magnitude
+ *      -> min/max renormalisation -> clip -> 2x2 mean -> uint8, as a separable circular convolution with the complex
+ *      Dirichlet rows of the (asymmetric) kept frequency set: any even size, no FFT library (csrc/lowfield.hip). ---------- */
+/* HOST helper: re[d], im[d], d = 0..n-1, of p[d] = (1/n) sum_{k=-a}^{a-1} exp(2 pi i k d / n), a = int(n * crop_factor) / 2;
+ * computed in double, stored as float.  MRISR_E_SHAPE: n odd or below 4; MRISR_E_ARG: null pointer, crop_factor outside
+ * (0, 1], a == 0.                                                                                                       */
+int mrisr_lowfield_dirichlet(int n, double crop_factor, float* re, float* im);
+/* bytes of device workspace the simulation of batch images of H x W needs: the fp32 magnitude plane [batch][H][W], then
+ * four 32-bit words per image (bit patterns of min / max magnitude, min / max 8-bit input value).  0 for a bad shape.     */
+size_t mrisr_lowfield_workspace_bytes(int batch, int H, int W);
+/* high: [batch][H][W] uint8 (x = high / 255) -> out_u8 [batch][H/2][W/2] uint8 and / or out_f32, the unquantised
+ * low-resolution plane in [0,1] (at least one of the two).  Enqueues both passes on stream.
+ * row_re/im [H], col_re/im [W]: DEVICE copies of the Dirichlet tables of (H, crop_factor) and (W, crop_factor).
+ * Noise, white complex Gaussian in image space with per-component standard deviation sigma (= noise_std / 2550 for the
+ * reference's noise_std): explicit device planes noise_re / noise_im [batch][H][W] (added as they are; sigma is not
+ * applied to them), else per-image 64-bit seeds_device [batch] with Box-Muller on hashed (seed, pixel) draws when sigma > 0,
+ * else none.  Bitwise reproducible.  DEVIATION: an image whose magnitude is constant (max == min; the reference divides
+ * 0 by 0) comes out as its own minimum everywhere.
+ * MRISR_E_SHAPE: odd H or W, H or W below 4, batch outside 1..65535, tables past 160 KiB of LDS; MRISR_E_ARG: null
+ * pointer, one noise plane without the other, crop_factor outside (0, 1], int(n * crop_factor) / 2 == 0, sigma < 0.     */
+int mrisr_lowfield_simulate(const uint8_t* high, int batch, int H, int W, double crop_factor, const float* row_re,
+                            const float* row_im, const float* col_re, const float* col_im, float sigma,
+                            const float* noise_re, const float* noise_im, const unsigned long long* seeds_device,
+                            void* workspace, uint8_t* out_u8, float* out_f32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

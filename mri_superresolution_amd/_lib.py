@@ -133,10 +133,13 @@ SIGNATURES = {
     "mrisr_augment_geo_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _dp, _vp]),
     "mrisr_augment_finish_u8": (_i, [_vp, _fp, _i, _sz, _vp, _dp, _vp]),
     "mrisr_cast": (_i, [_i, _vp, _i, _vp, _sz, _vp]),
+    "mrisr_lowfield_dirichlet": (_i, [_i, _d, _fp, _fp]),
+    "mrisr_lowfield_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mrisr_lowfield_simulate": (_i, [_vp, _i, _i, _i, _d, _fp, _fp, _fp, _fp, _f, _fp, _fp, _vp, _vp, _vp, _fp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 305      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 306      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -185,4 +185,20 @@ __device__ __forceinline__ size_t stat_slot_off_id(int id, int N, int groups) {
     return (size_t)(id & (MRISR_STAT_SLOTS - 1)) * N * groups * 2;
 }
 
+// ---------------------------------------------------------------- counter-based noise generator
+__device__ __forceinline__ unsigned mix32(unsigned x) {      // lowbias32 finaliser
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+// two uniform draws of (seed, counter i): u1 in (0, 1], u2 in [0, 1), 24 bits each (Box-Muller operands)
+__device__ __forceinline__ void hashed_uniform_pair(unsigned seed, unsigned i, float& u1, float& u2) {
+    const unsigned h1 = mix32(seed ^ mix32(i * 2u + 1u)), h2 = mix32(seed + 0x9e3779b9u + mix32(i * 2u));
+    u1 = ((float)(h1 >> 8) + 1.f) * (1.f / 16777216.f);
+    u2 = (float)(h2 >> 8) * (1.f / 16777216.f);
+}
+// 32-bit generator key of a 64-bit seed
+__device__ __forceinline__ unsigned noise_key(unsigned long long seed) {
+    return mix32((unsigned)seed ^ mix32((unsigned)(seed >> 32) + 0x9e3779b9u));
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }

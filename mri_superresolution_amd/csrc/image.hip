@@ -166,11 +166,6 @@ __global__ __launch_bounds__(256) void augment_geo_u8_kernel(const uint8_t* __re
     }
 }
 
-__device__ __forceinline__ unsigned mix32(unsigned x) {      // lowbias32 finaliser
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
 __global__ __launch_bounds__(256) void augment_finish_u8_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, size_t n,
                                                                 const mrisr_aug_photo* __restrict__ params, const double* __restrict__ mean) {
     mrisr_aug_photo q = params[blockIdx.y];
@@ -181,9 +176,9 @@ __global__ __launch_bounds__(256) void augment_finish_u8_kernel(const uint8_t* _
         float v = (float)src[i];
         if (q.contrast != 1.f) v = pil_blend_u8((float)q.mean, v, q.contrast);
         if (q.noise_sigma > 0.f) {
-            // Box-Muller on two hashed 32-bit draws of (seed, pixel): np.clip(a + N(0, sigma), 0, 255).astype(uint8)
-            const unsigned h1 = mix32(q.seed ^ mix32((unsigned)i * 2u + 1u)), h2 = mix32(q.seed + 0x9e3779b9u + mix32((unsigned)i * 2u));
-            const float u1 = ((float)(h1 >> 8) + 1.f) * (1.f / 16777216.f), u2 = (float)(h2 >> 8) * (1.f / 16777216.f);
+            // Box-Muller on the two hashed draws of (seed, pixel): np.clip(a + N(0, sigma), 0, 255).astype(uint8)
+            float u1, u2;
+            hashed_uniform_pair(q.seed, (unsigned)i, u1, u2);       // common.h
             const float g = sqrtf(-2.f * __logf(u1)) * __cosf(6.28318530718f * u2);
             v = (float)(int)fminf(fmaxf(v + q.noise_sigma * g, 0.f), 255.f);
         }

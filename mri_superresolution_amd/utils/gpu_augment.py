@@ -103,8 +103,15 @@ class DevicePairLoader:
 
     def __init__(self, dataset, batch_size: int, indices: Optional[Sequence[int]] = None, shuffle: bool = True,
                  augmentation: Optional[bool] = None, seed: int = 0, device="cuda", io_workers: int = 8,
-                 max_resident_bytes: int = 64 << 30, drop_last: bool = False):
+                 max_resident_bytes: int = 64 << 30, drop_last: bool = False, simulate_lr: Optional[dict] = None):
         from PIL import Image
+        # simulate_lr = {"kspace_crop_factor": f, "noise_std": s} (extension): the low-resolution batch is drawn from the
+        # gathered high-resolution one on the device (utils/lowfield.simulate_low_field_u8) with a fresh noise realisation
+        # per sample and epoch; the stored low-resolution files are not read
+        self.simulate_lr = None
+        if simulate_lr is not None:
+            self.simulate_lr = {"kspace_crop_factor": float(simulate_lr.get("kspace_crop_factor", 0.5)),
+                                "noise_std": float(simulate_lr.get("noise_std", 5.0))}
         self.batch_size, self.shuffle, self.seed, self.drop_last = int(batch_size), shuffle, int(seed), drop_last
         self.device = torch.device(device)
         self.params = dict(DEFAULT_AUG)
@@ -116,8 +123,10 @@ class DevicePairLoader:
         names = [dataset.valid_pairs[i] for i in idx]
 
         def load(name):
-            lo = np.asarray(Image.open(dataset.low_res_dir / name).convert("L"), dtype=np.uint8)
             hi = np.asarray(Image.open(dataset.full_res_dir / name).convert("L"), dtype=np.uint8)
+            if self.simulate_lr is not None:
+                return np.zeros((1, 1), dtype=np.uint8), hi      # placeholder: never yielded
+            lo = np.asarray(Image.open(dataset.low_res_dir / name).convert("L"), dtype=np.uint8)
             return lo, hi
 
         with ThreadPoolExecutor(max_workers=max(1, io_workers)) as pool:
@@ -167,6 +176,9 @@ class DevicePairLoader:
         if self.drop_last and chunks and len(chunks[-1]) < self.batch_size:
             chunks.pop()
         nxt = self._fetch(chunks[0]) if chunks else None
+        # seeds of the simulated low-resolution images: (seed, epoch, sample index); a loader that neither shuffles nor
+        # augments (validation) leaves the epoch out and sees the same images every epoch
+        sim_epoch = self.epoch if (self.shuffle or self.augmentation) else None
         for k in range(len(chunks)):
             lo, hi, ev = nxt
             nxt = self._fetch(chunks[k + 1]) if k + 1 < len(chunks) else None     # next batch's copy overlaps this one's step
@@ -174,5 +186,8 @@ class DevicePairLoader:
                 torch.cuda.current_stream().wait_event(ev)
                 lo.record_stream(torch.cuda.current_stream())
                 hi.record_stream(torch.cuda.current_stream())
+            if self.simulate_lr is not None:
+                from .lowfield import derive_seeds, simulate_low_field_u8
+                lo = simulate_low_field_u8(hi, seeds=derive_seeds(self.seed, sim_epoch, chunks[k]), **self.simulate_lr)
             yield augment_pair_u8(lo, hi, self.params, rng, self.augmentation)
         self.epoch += 1

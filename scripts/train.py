@@ -153,11 +153,16 @@ def train(args):
     train_idx, val_idx = perm[:n_train], perm[n_train:]
     val_ids = val_idx[rank::world] if world > 1 else val_idx
     train_dev_loader = None
+    simulate_lr = {"kspace_crop_factor": args.kspace_crop_factor, "noise_std": args.noise_std} if args.simulate_lr else None
     if args.gpu_data:
         from mri_superresolution_amd.utils.gpu_augment import DevicePairLoader
         log_message("Data pipeline: uint8 pairs resident in HBM, batches gathered and augmented on the device.")
+        if simulate_lr:
+            log_message(f"Low-resolution images simulated on the device from the high-resolution ones (k-space crop "
+                        f"{args.kspace_crop_factor}, noise_std {args.noise_std}); the files of --low_res_dir only name the pairs.")
         val_loader = DevicePairLoader(dataset, args.batch_size, val_ids, shuffle=False, augmentation=False, seed=args.seed,
-                                      device=device, io_workers=max(1, args.num_workers)) if val_ids else None
+                                      device=device, io_workers=max(1, args.num_workers),
+                                      simulate_lr=simulate_lr) if val_ids else None
     else:
         val_loader = make_loader(dataset, val_ids, args.batch_size, args.num_workers, False, args.seed) if n_val > 0 else None
 
@@ -193,7 +198,8 @@ def train(args):
             if train_dev_loader is None or world > 1:      # (data parallel: the rank's shard changes with the epoch)
                 train_dev_loader = DevicePairLoader(dataset, args.batch_size, idx, shuffle=True,
                                                     augmentation=args.augmentation, seed=args.seed + rank,
-                                                    device=device, io_workers=max(1, args.num_workers))
+                                                    device=device, io_workers=max(1, args.num_workers),
+                                                    simulate_lr=simulate_lr)
             train_dev_loader.set_epoch(epoch)
             loader = train_dev_loader
         else:
@@ -317,13 +323,24 @@ def parse_args(argv=None):
     p.add_argument("--gpu_data", action="store_true",
                    help="(extension) keep the uint8 slice pairs resident in HBM and assemble / augment every batch on the "
                         "device (utils/gpu_augment.DevicePairLoader) instead of DataLoader workers + PIL")
+    p.add_argument("--simulate_lr", action="store_true",
+                   help="(extension) needs --gpu_data: draw every low-resolution batch from the high-resolution one on the device "
+                        "(low-field simulation: k-space crop + complex Gaussian noise, a fresh noise draw per sample and epoch) "
+                        "instead of using the stored low-resolution images")
+    p.add_argument("--kspace_crop_factor", type=float, default=0.5,
+                   help="(extension) --simulate_lr: share of k-space kept per axis (reference simulate_low_field_mri default)")
+    p.add_argument("--noise_std", type=float, default=5.0,
+                   help="(extension) --simulate_lr: noise standard deviation in 8-bit grey levels of the reference's convention")
     p.add_argument("--amp_dtype", type=str, default="fp16", choices=["fp16", "bf16"],
                    help="(extension) autocast dtype of --use_amp: fp16 as the reference, or bf16 without loss scaling")
     p.add_argument("--cpu", action="store_true", help="REFUSED: accepted only so that the reference's command lines parse; this build runs on an MI355X through "
                         "libmrisr.so only and exits with an error when --cpu is given (there is no CPU fallback)")
     p.add_argument("--checkpoint_dir", type=str, default="./checkpoints")
     p.add_argument("--log_dir", type=str, default="./logs")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.simulate_lr and not args.gpu_data:
+        p.error("--simulate_lr draws the low-resolution images on the device and needs --gpu_data")
+    return args
 
 
 if __name__ == "__main__":
