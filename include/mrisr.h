@@ -449,6 +449,31 @@ int mrisr_lowfield_simulate(const uint8_t* high, int batch, int H, int W, double
                             const float* noise_re, const float* noise_im, const unsigned long long* seeds_device,
                             void* workspace, uint8_t* out_u8, float* out_f32, void* stream);
 
+/* ---- float windowing of whole-volume inference (extension; reference utils/extraction_utils.py:118-131 and
+ *      utils/preprocessing.py:126-158 robust_normalize: every float32 slice windowed at its own percentiles;
+ *      csrc/percentile.hip) -------------------------------------------------------------------------------------------- */
+#define MRISR_WINDOW_F32 0          /* out_dtype of the restore: float32                                                  */
+#define MRISR_WINDOW_I16 1          /* int16: np.rint (half to even), saturated to [-32768, 32767]                        */
+/* bytes of device workspace the percentile selection of batch images needs (any image size); 0 for a batch outside
+ * 1..65535.  The contents need no initialisation and one workspace may serve call after call on one stream.              */
+size_t mrisr_f32_percentile_workspace_bytes(int batch);
+/* lohi[b] = (np.percentile(x[b], q_lo), np.percentile(x[b], q_hi)) for batch contiguous float32 images, method 'linear',
+ * numpy's float32 arithmetic: an exact radix select of the order statistics either side of each quantile, then numpy's
+ * two-branch interpolation.  Enqueues 9 launches on stream, clears what it needs of the workspace itself, never
+ * synchronises with the host (HIP-graph capturable).  The input must be finite (not checked: that would cost a
+ * synchronisation); -0.0 and +0.0 are equal values and either may be returned.
+ * MRISR_E_SHAPE: batch outside 1..65535, no pixels or more than 2^32 - 1; MRISR_E_ARG: null pointer, percentiles not
+ * 0 <= q_lo <= q_hi <= 100.                                                                                              */
+int mrisr_f32_percentile_bounds(const float* x, size_t pixels_per_image, int batch, double q_lo, double q_hi, float* lohi,
+                                void* workspace, void* stream);
+/* out[b][i] = (clip(x[b][i], lo_b, hi_b) - lo_b) / (hi_b - lo_b) in float32, one operation at a time, with
+ * (lo_b, hi_b) = lohi[b]; 0 everywhere where hi_b == lo_b (robust_normalize's rule for constant slices).                 */
+int mrisr_f32_window_normalise(const float* x, const float* lohi, size_t pixels_per_image, int batch, float* out, void* stream);
+/* the way back to scanner intensities: out[b][i] = clamp(y[b][i], 0, 1) * (hi_b - lo_b) + lo_b in float32 (a rounded
+ * product, then a rounded sum), stored as out_dtype (MRISR_WINDOW_*).  MRISR_E_ARG: another out_dtype, null pointer.      */
+int mrisr_f32_window_restore(const float* y, const float* lohi, size_t pixels_per_image, int batch, int out_dtype, void* out,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
