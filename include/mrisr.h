@@ -449,6 +449,18 @@ int mrisr_lowfield_simulate(const uint8_t* high, int batch, int H, int W, double
                             const float* noise_re, const float* noise_im, const unsigned long long* seeds_device,
                             void* workspace, uint8_t* out_u8, float* out_f32, void* stream);
 
+/* any n >= 2 (odd sizes too: the kept frequency set is k in [-a, a) whatever the parity).  MRISR_E_SHAPE: n below 2;
+ * MRISR_E_ARG as above.                                                                                                  */
+int mrisr_lowfield_dirichlet_any(int n, double crop_factor, float* re, float* im);
+/* The float form of the simulation, any size >= 2 x 2: high [batch][H][W] float32 in [0,1] (non-negative: not checked)
+ * -> out_f32 [batch][H][W], the renormalised, clipped plane at FULL size (no 2x2 mean, no uint8).  Tables from
+ * mrisr_lowfield_dirichlet_any; noise, workspace (mrisr_lowfield_workspace_bytes), deviation and errors as above, without
+ * the parity rule.                                                                                                       */
+int mrisr_lowfield_simulate_f32(const float* high, int batch, int H, int W, double crop_factor, const float* row_re,
+                                const float* row_im, const float* col_re, const float* col_im, float sigma,
+                                const float* noise_re, const float* noise_im, const unsigned long long* seeds_device,
+                                void* workspace, float* out_f32, void* stream);
+
 /* ---- float windowing of whole-volume inference (extension; reference utils/extraction_utils.py:118-131 and
  *      utils/preprocessing.py:126-158 robust_normalize: every float32 slice windowed at its own percentiles;
  *      csrc/percentile.hip) -------------------------------------------------------------------------------------------- */
@@ -473,6 +485,33 @@ int mrisr_f32_window_normalise(const float* x, const float* lohi, size_t pixels_
  * product, then a rounded sum), stored as out_dtype (MRISR_WINDOW_*).  MRISR_E_ARG: another out_dtype, null pointer.      */
 int mrisr_f32_window_restore(const float* y, const float* lohi, size_t pixels_per_image, int batch, int out_dtype, void* out,
                              void* stream);
+
+/* ---- table-driven separable resampler with a letter-box epilogue (extension; the resize of the reference's slice
+ *      extraction, utils/preprocessing.py:23-57; csrc/resample.hip).  Parity with cv2.resize is not claimed. ------------- */
+#define MRISR_RESAMPLE_LINEAR 1     /* 2 taps                                                                             */
+#define MRISR_RESAMPLE_CUBIC 2      /* 4 taps, Keys kernel with A = -0.75                                                 */
+#define MRISR_RESAMPLE_AREA 3       /* dst <= src: box overlap weights; dst > src: the LINEAR taps (deviation)            */
+#define MRISR_RESAMPLE_LANCZOS4 4   /* 8 taps, sinc(x) sinc(x / 4), normalised to sum 1                                   */
+/* HOST helper, computed in double: for output sample d of a src -> dst resize, with scale = src / dst and
+ * s = (d + 0.5) scale - 0.5, the *ntaps consecutive source samples around floor(s) (LANCZOS4: floor(s) - 3 .. floor(s) + 4)
+ * clamped to [0, src - 1] (replicated border) and their weights; AREA: sample i weighs
+ * |[i, i + 1] n [d scale, (d + 1) scale]| / min(scale, src - d scale).  index / weight: [dst][max_taps]; slots past *ntaps
+ * get weight 0 and a valid index.  MRISR_E_UNSUPPORTED: more than 16 taps per sample; MRISR_E_SHAPE: src or dst outside
+ * 1..32767, max_taps below the tap count; MRISR_E_ARG: null pointer, unknown method.                                     */
+int mrisr_resample_taps(int method, int src, int dst, int max_taps, int* ntaps, short* index, float* weight);
+/* in [batch][H][W] float32 -> a canvas [batch][out_h][out_w] per image: the (new_h, new_w) resampled block at
+ * (y_off, x_off), pad_value (exactly) everywhere else.  y_index / y_weight [new_h][y_taps] and x_index / x_weight
+ * [new_w][x_taps]: DEVICE tables as mrisr_resample_taps fills them (consecutive indices that do not decrease with the
+ * output sample).  The entry cannot inspect device tables without a synchronisation: for a table that breaks that rule
+ * every access stays inside the image and the staged window, but the RESULT IS UNDEFINED and no error is reported.  Both sums take their taps in ascending slot order with fmaf, rows after columns: bitwise reproducible.
+ * clip != 0 clamps the block to [0,1]; out_f32 and / or out_u8 = (uint8)(int)clamp(v * 255, 0, 255) (at least one).
+ * One launch on stream, no host synchronisation (HIP-graph capturable).
+ * MRISR_E_ARG: null pointer; MRISR_E_SHAPE: batch outside 1..65535, a size below 1 or above 32767, a block that does not
+ * fit the canvas; MRISR_E_UNSUPPORTED: tap counts outside 1..16, a reduction whose tile window exceeds 160 KiB of LDS.   */
+int mrisr_f32_resample_letterbox(const float* in, int batch, int H, int W, const short* y_index, const float* y_weight,
+                                 int y_taps, int new_h, const short* x_index, const float* x_weight, int x_taps, int new_w,
+                                 int out_h, int out_w, int y_off, int x_off, float pad_value, int clip, float* out_f32,
+                                 uint8_t* out_u8, void* stream);
 
 #ifdef __cplusplus
 }

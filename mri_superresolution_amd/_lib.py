@@ -17,6 +17,7 @@ COMBINE_CONCAT, COMBINE_BLEND = 0, 1
 OUT_PLAIN, OUT_PIXEL_SHUFFLE2 = 0, 1
 UP2_BILINEAR, UP2_BICUBIC, UP2_SHARP_BILINEAR = 0, 1, 2      # MRISR_UP2_*: method of mrisr_u8_upscale2
 WINDOW_F32, WINDOW_I16 = 0, 1      # MRISR_WINDOW_*: out_dtype of mrisr_f32_window_restore
+RESAMPLE_LINEAR, RESAMPLE_CUBIC, RESAMPLE_AREA, RESAMPLE_LANCZOS4 = 1, 2, 3, 4      # MRISR_RESAMPLE_*: method of mrisr_resample_taps
 PACK_RING = 256      # MRISR_PACK_RING: OR into transpose_flip for the ring weight layout (csrc/conv_ring.hip)
 PACK_UPADJ = 512     # MRISR_PACK_UPADJ: the W^T image of mrisr_conv_upadj (csrc/conv_upadj.hip)
 STAT_SLOTS = 16      # = MRISR_STAT_SLOTS of include/mrisr.h; load() replaces it with the library's compiled value
@@ -137,6 +138,10 @@ SIGNATURES = {
     "mrisr_lowfield_dirichlet": (_i, [_i, _d, _fp, _fp]),
     "mrisr_lowfield_workspace_bytes": (_sz, [_i, _i, _i]),
     "mrisr_lowfield_simulate": (_i, [_vp, _i, _i, _i, _d, _fp, _fp, _fp, _fp, _f, _fp, _fp, _vp, _vp, _vp, _fp, _vp]),
+    "mrisr_lowfield_dirichlet_any": (_i, [_i, _d, _fp, _fp]),
+    "mrisr_lowfield_simulate_f32": (_i, [_fp, _i, _i, _i, _d, _fp, _fp, _fp, _fp, _f, _fp, _fp, _vp, _vp, _fp, _vp]),
+    "mrisr_resample_taps": (_i, [_i, _i, _i, _i, _vp, _vp, _fp]),
+    "mrisr_f32_resample_letterbox": (_i, [_fp, _i, _i, _i, _vp, _fp, _i, _i, _vp, _fp, _i, _i, _i, _i, _i, _i, _f, _i, _fp, _vp, _vp]),
     "mrisr_f32_percentile_workspace_bytes": (_sz, [_i]),
     "mrisr_f32_percentile_bounds": (_i, [_fp, _sz, _i, _d, _d, _fp, _vp, _vp]),
     "mrisr_f32_window_normalise": (_i, [_fp, _fp, _sz, _i, _fp, _vp]),
@@ -144,7 +149,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 307      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 308      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -24,6 +24,10 @@
 // Pass 2: s = (m - min m) / (max m - min m) * (max x - min x) + min x, clip to [0,1], 2x2 mean (INTER_AREA at exactly
 // half scale), truncation to uint8.  DEVIATION: when max m == min m the reference divides 0 by 0; here s = min x.
 //
+// Float pipeline (mrisr_lowfield_simulate_f32: the slice extraction simulates the percentile-normalised float slice at the
+// scan's own size, often odd): pass 1 templated on the input type, the input's extrema by the same integer atomics on the
+// bit patterns of the non-negative floats, and a pass 2 that stops after the clip - float32 at full size.
+//
 // Compiled with -ffp-contract=off (build.py): pass 2 restates host arithmetic operation by operation; the FMAs of pass 1
 // are written as fmaf().
 #include <math.h>
@@ -33,18 +37,27 @@
 constexpr int kTR = 8;        // output rows per workgroup
 constexpr int kWin = kTR + 7; // table entries that eight consecutive source rows touch
 
+// float2 entries of the two tables in LDS, rounded up to an even count so that U behind them starts on 16 bytes (odd H + W)
+__host__ __device__ constexpr int lf_table_entries(int H, int W) { return (H + 16 + W + 1) & ~1; }
+
 struct LfExt {                // per-image extrema, filled by pass 1
     unsigned m_min, m_max;    // bit patterns of non-negative floats
-    unsigned x_min, x_max;    // 8-bit values
+    unsigned x_min, x_max;    // 8-bit values; float input: bit patterns of non-negative floats
 };
 
-__global__ void lowfield_init_kernel(LfExt* __restrict__ ext, int batch) {
+// input sample as the float the column pass multiplies, and as the unsigned key its extrema are taken on
+__device__ __forceinline__ float lf_value(uint8_t v) { return (float)v; }
+__device__ __forceinline__ float lf_value(float v) { return v; }
+__device__ __forceinline__ unsigned lf_key(uint8_t v) { return v; }
+__device__ __forceinline__ unsigned lf_key(float v) { return __float_as_uint(v + 0.f); }     // -0.0 -> +0.0
+
+__global__ void lowfield_init_kernel(LfExt* __restrict__ ext, int batch, unsigned x_top) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < batch) ext[b] = LfExt{0x7f800000u, 0u, 255u, 0u};
+    if (b < batch) ext[b] = LfExt{0x7f800000u, 0u, x_top, 0u};
 }
 
-template <int kK, int kLT>      // columns per thread, threads per workgroup
-__global__ __launch_bounds__(kLT) void lowfield_pass1_kernel(const uint8_t* __restrict__ img, const float* __restrict__ pr_re,
+template <int kK, int kLT, typename TIn>      // columns per thread, threads per workgroup, input type (uint8_t: x = img / 255)
+__global__ __launch_bounds__(kLT) void lowfield_pass1_kernel(const TIn* __restrict__ img, const float* __restrict__ pr_re,
                                                              const float* __restrict__ pr_im, const float* __restrict__ pc_re,
                                                              const float* __restrict__ pc_im, const float* __restrict__ n_re,
                                                              const float* __restrict__ n_im, const unsigned long long* __restrict__ seeds,
@@ -52,16 +65,19 @@ __global__ __launch_bounds__(kLT) void lowfield_pass1_kernel(const uint8_t* __re
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* tr = reinterpret_cast<float2*>(smem);               // [H + 16]: p_r, periodically extended
     float2* tc = tr + H + 16;                                   // [W]: p_c
-    float* U = reinterpret_cast<float*>(tc + W);                // [W][2 kTR]: re of the kTR rows, then im (16-byte aligned: H, W even)
+    float* U = reinterpret_cast<float*>(tr + lf_table_entries(H, W));   // [W][2 kTR]: re of the kTR rows, then im (16-byte aligned)
     const int t = threadIdx.x, b = blockIdx.y, r0 = blockIdx.x * kTR;
-    const uint8_t* x = img + (size_t)b * H * W;
+    const TIn* x = img + (size_t)b * H * W;
+    constexpr bool kU8 = sizeof(TIn) == 1;
+    constexpr float kInScale = kU8 ? 1.f / 255.f : 1.f;
+    constexpr unsigned kTop = kU8 ? 255u : 0x7f800000u;
 
     for (int i = t; i < H + 16; i += kLT) { const int d = i % H; tr[i] = make_float2(pr_re[d], pr_im[d]); }
     for (int i = t; i < W; i += kLT) tc[i] = make_float2(pc_re[i], pc_im[i]);
     __syncthreads();
 
     // ---- A: column pass over all source rows, eight at a time
-    unsigned xmn = 255u, xmx = 0u;
+    unsigned xmn = kTop, xmx = 0u;
     for (int c0 = 0; c0 < W; c0 += kLT * kK) {
         float are[kK][kTR], aim[kK][kTR];
 #pragma unroll
@@ -82,12 +98,13 @@ __global__ __launch_bounds__(kLT) void lowfield_pass1_kernel(const uint8_t* __re
 #pragma unroll
                 for (int j = 0; j < kK; ++j) {
                     const int n = c0 + t + j * kLT;
-                    unsigned v = 0u;
+                    float v = 0.f;
                     if (m < H && n < W) {
-                        v = x[(size_t)m * W + n];
-                        if (m >= r0 && m < r0 + kTR) { xmn = min(xmn, v); xmx = max(xmx, v); }
+                        const TIn s = x[(size_t)m * W + n];
+                        v = lf_value(s);
+                        if (m >= r0 && m < r0 + kTR) { xmn = min(xmn, lf_key(s)); xmx = max(xmx, lf_key(s)); }
                     }
-                    xv[j] = (float)v;
+                    xv[j] = v;
                 }
 #pragma unroll
                 for (int i = 0; i < kTR; ++i) {
@@ -106,8 +123,8 @@ __global__ __launch_bounds__(kLT) void lowfield_pass1_kernel(const uint8_t* __re
             if (n < W) {
 #pragma unroll
                 for (int i = 0; i < kTR; ++i) {
-                    U[n * (2 * kTR) + i] = are[j][i] * (1.f / 255.f);
-                    U[n * (2 * kTR) + kTR + i] = aim[j][i] * (1.f / 255.f);
+                    U[n * (2 * kTR) + i] = are[j][i] * kInScale;
+                    U[n * (2 * kTR) + kTR + i] = aim[j][i] * kInScale;
                 }
             }
         }
@@ -215,14 +232,25 @@ __global__ __launch_bounds__(256) void lowfield_pass2_kernel(const float* __rest
     }
 }
 
+// float pipeline: the same renormalisation at full size, float32 out (no 2x2 mean, no uint8)
+__global__ __launch_bounds__(256) void lowfield_pass2_f32_kernel(const float* __restrict__ mag, const LfExt* __restrict__ ext,
+                                                                 float* __restrict__ out, size_t n) {
+    const int b = blockIdx.y;
+    const LfExt e = ext[b];
+    const float mn = __uint_as_float(e.m_min), mx = __uint_as_float(e.m_max);
+    const float omin = __uint_as_float(e.x_min), omax = __uint_as_float(e.x_max);
+    const float den = __fsub_rn(mx, mn), span = __fsub_rn(omax, omin);
+    const float* src = mag + (size_t)b * n;
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (size_t)gridDim.x * 256) {
+        float s = omin;                                              // max m == min m: the documented deviation
+        if (den > 0.f) s = __fadd_rn(__fmul_rn(__fdiv_rn(__fsub_rn(src[p], mn), den), span), omin);
+        out[(size_t)b * n + p] = fminf(fmaxf(s, 0.f), 1.f);         // np.clip(simulated, 0, 1)
+    }
+}
+
 static int lowfield_half_width(int n, double f) { return (int)((double)n * f) / 2; }
 
-extern "C" int mrisr_lowfield_dirichlet(int n, double crop_factor, float* re, float* im) {
-    if (!re || !im) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet: null pointer");
-    if (n < 4 || (n & 1)) MRISR_FAIL(MRISR_E_SHAPE, "lowfield_dirichlet: size %d (even, >= 4)", n);
-    if (!(crop_factor > 0.0 && crop_factor <= 1.0)) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet: crop_factor %g outside (0, 1]", crop_factor);
-    const int a = lowfield_half_width(n, crop_factor);
-    if (a == 0) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet: crop_factor %g keeps nothing of %d samples", crop_factor, n);
+static int lowfield_dirichlet_fill(int n, int a, float* re, float* im) {
     const double two_pi = 6.283185307179586476925286766559;
     for (int d = 0; d < n; ++d) {
         double sr = 0.0, si = 0.0;
@@ -238,9 +266,57 @@ extern "C" int mrisr_lowfield_dirichlet(int n, double crop_factor, float* re, fl
     return MRISR_OK;
 }
 
+extern "C" int mrisr_lowfield_dirichlet(int n, double crop_factor, float* re, float* im) {
+    if (!re || !im) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet: null pointer");
+    if (n < 4 || (n & 1)) MRISR_FAIL(MRISR_E_SHAPE, "lowfield_dirichlet: size %d (even, >= 4)", n);
+    if (!(crop_factor > 0.0 && crop_factor <= 1.0)) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet: crop_factor %g outside (0, 1]", crop_factor);
+    const int a = lowfield_half_width(n, crop_factor);
+    if (a == 0) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet: crop_factor %g keeps nothing of %d samples", crop_factor, n);
+    return lowfield_dirichlet_fill(n, a, re, im);
+}
+
+// any n >= 2: the reference's mask keeps the shifted indices [n/2 - a, n/2 + a) and n / 2 (integer division) is frequency 0
+// after fftshift for odd n too, so the kept set is k in [-a, a) whatever the parity
+extern "C" int mrisr_lowfield_dirichlet_any(int n, double crop_factor, float* re, float* im) {
+    if (!re || !im) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet_any: null pointer");
+    if (n < 2) MRISR_FAIL(MRISR_E_SHAPE, "lowfield_dirichlet_any: size %d (>= 2)", n);
+    if (!(crop_factor > 0.0 && crop_factor <= 1.0)) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet_any: crop_factor %g outside (0, 1]", crop_factor);
+    const int a = lowfield_half_width(n, crop_factor);
+    if (a == 0) MRISR_FAIL(MRISR_E_ARG, "lowfield_dirichlet_any: crop_factor %g keeps nothing of %d samples", crop_factor, n);
+    return lowfield_dirichlet_fill(n, a, re, im);
+}
+
 extern "C" size_t mrisr_lowfield_workspace_bytes(int batch, int H, int W) {
     if (batch < 1 || H < 1 || W < 1) return 0;
     return (size_t)batch * H * W * sizeof(float) + (size_t)batch * sizeof(LfExt);
+}
+
+static size_t lowfield_lds_bytes(int H, int W) {
+    return (size_t)lf_table_entries(H, W) * sizeof(float2) + (size_t)W * 2 * kTR * sizeof(float);
+}
+
+// the extrema's initial values and pass 1 for either input type
+template <typename TIn>
+static void lowfield_pass1(const TIn* high, int batch, int H, int W, const float* row_re, const float* row_im, const float* col_re,
+                           const float* col_im, float sigma, const float* noise_re, const float* noise_im,
+                           const unsigned long long* seeds_device, float* mag, LfExt* ext, hipStream_t s) {
+    const size_t lds = lowfield_lds_bytes(H, W);
+    lowfield_init_kernel<<<ceil_div(batch, 256), 256, 0, s>>>(ext, batch, sizeof(TIn) == 1 ? 255u : 0x7f800000u);
+    dim3 grid(ceil_div(H, kTR), batch);
+#define LF_LAUNCH(K, T)                                                                                                           \
+    do {                                                                                                                         \
+        if (lds > 64 * 1024)                                                                                                     \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lowfield_pass1_kernel<K, T, TIn>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        lowfield_pass1_kernel<K, T, TIn><<<grid, T, lds, s>>>(high, row_re, row_im, col_re, col_im, noise_re, noise_im, seeds_device, sigma, \
+                                                             mag, ext, H, W);                                                    \
+    } while (0)
+    // two columns per thread where the width allows it (half the LDS reads per FMA of one column); wide images take 256
+    // threads, so that a workgroup's share of LDS carries four waves
+    if (W <= 128) LF_LAUNCH(1, 128);
+    else if (W <= 256) LF_LAUNCH(2, 128);
+    else if (W <= 512) LF_LAUNCH(2, 256);
+    else LF_LAUNCH(4, 256);
+#undef LF_LAUNCH
 }
 
 extern "C" int mrisr_lowfield_simulate(const uint8_t* high, int batch, int H, int W, double crop_factor, const float* row_re,
@@ -256,31 +332,42 @@ extern "C" int mrisr_lowfield_simulate(const uint8_t* high, int batch, int H, in
     if (lowfield_half_width(H, crop_factor) == 0 || lowfield_half_width(W, crop_factor) == 0)
         MRISR_FAIL(MRISR_E_ARG, "lowfield_simulate: crop_factor %g keeps nothing of %d x %d", crop_factor, H, W);
     if (!(sigma >= 0.f)) MRISR_FAIL(MRISR_E_ARG, "lowfield_simulate: sigma %g", (double)sigma);
-    const size_t lds = (size_t)(H + 16 + W) * sizeof(float2) + (size_t)W * 2 * kTR * sizeof(float);
-    if (lds > 160 * 1024 || ceil_div(H, kTR) > 65535) MRISR_FAIL(MRISR_E_SHAPE, "lowfield_simulate: H %d W %d too large (%zu bytes of LDS)", H, W, lds);
+    if (lowfield_lds_bytes(H, W) > 160 * 1024 || ceil_div(H, kTR) > 65535)
+        MRISR_FAIL(MRISR_E_SHAPE, "lowfield_simulate: H %d W %d too large (%zu bytes of LDS)", H, W, lowfield_lds_bytes(H, W));
     hipStream_t s = (hipStream_t)stream;
     float* mag = reinterpret_cast<float*>(workspace);
     LfExt* ext = reinterpret_cast<LfExt*>(mag + (size_t)batch * H * W);
-    lowfield_init_kernel<<<ceil_div(batch, 256), 256, 0, s>>>(ext, batch);
-    dim3 grid(ceil_div(H, kTR), batch);
-#define LF_LAUNCH(K, T)                                                                                                           \
-    do {                                                                                                                         \
-        if (lds > 64 * 1024)                                                                                                     \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lowfield_pass1_kernel<K, T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        lowfield_pass1_kernel<K, T><<<grid, T, lds, s>>>(high, row_re, row_im, col_re, col_im, noise_re, noise_im, seeds_device, sigma, \
-                                                        mag, ext, H, W);                                                        \
-    } while (0)
-    // two columns per thread where the width allows it (half the LDS reads per FMA of one column); wide images take 256
-    // threads, so that a workgroup's share of LDS carries four waves
-    if (W <= 128) LF_LAUNCH(1, 128);
-    else if (W <= 256) LF_LAUNCH(2, 128);
-    else if (W <= 512) LF_LAUNCH(2, 256);
-    else LF_LAUNCH(4, 256);
-#undef LF_LAUNCH
+    lowfield_pass1(high, batch, H, W, row_re, row_im, col_re, col_im, sigma, noise_re, noise_im, seeds_device, mag, ext, s);
     const size_t n = (size_t)(H / 2) * (W / 2);
     size_t blocks = (n + 256 * 4 - 1) / (256 * 4);
     if (blocks > 1024) blocks = 1024;
     lowfield_pass2_kernel<<<dim3((unsigned)blocks, batch), 256, 0, s>>>(mag, ext, out_u8, out_f32, H / 2, W / 2);
     MRISR_CHECK_LAUNCH("lowfield_simulate");
+    return MRISR_OK;
+}
+
+extern "C" int mrisr_lowfield_simulate_f32(const float* high, int batch, int H, int W, double crop_factor, const float* row_re,
+                                           const float* row_im, const float* col_re, const float* col_im, float sigma,
+                                           const float* noise_re, const float* noise_im, const unsigned long long* seeds_device,
+                                           void* workspace, float* out_f32, void* stream) {
+    if (!high || !row_re || !row_im || !col_re || !col_im || !workspace || !out_f32) MRISR_FAIL(MRISR_E_ARG, "lowfield_simulate_f32: null pointer");
+    if ((noise_re == nullptr) != (noise_im == nullptr)) MRISR_FAIL(MRISR_E_ARG, "lowfield_simulate_f32: noise_re and noise_im go together");
+    if (batch < 1 || batch > 65535) MRISR_FAIL(MRISR_E_SHAPE, "lowfield_simulate_f32: batch %d", batch);
+    if (H < 2 || W < 2) MRISR_FAIL(MRISR_E_SHAPE, "lowfield_simulate_f32: H %d W %d (>= 2)", H, W);
+    if (!(crop_factor > 0.0 && crop_factor <= 1.0)) MRISR_FAIL(MRISR_E_ARG, "lowfield_simulate_f32: crop_factor %g outside (0, 1]", crop_factor);
+    if (lowfield_half_width(H, crop_factor) == 0 || lowfield_half_width(W, crop_factor) == 0)
+        MRISR_FAIL(MRISR_E_ARG, "lowfield_simulate_f32: crop_factor %g keeps nothing of %d x %d", crop_factor, H, W);
+    if (!(sigma >= 0.f)) MRISR_FAIL(MRISR_E_ARG, "lowfield_simulate_f32: sigma %g", (double)sigma);
+    if (lowfield_lds_bytes(H, W) > 160 * 1024 || ceil_div(H, kTR) > 65535)
+        MRISR_FAIL(MRISR_E_SHAPE, "lowfield_simulate_f32: H %d W %d too large (%zu bytes of LDS)", H, W, lowfield_lds_bytes(H, W));
+    hipStream_t s = (hipStream_t)stream;
+    float* mag = reinterpret_cast<float*>(workspace);
+    LfExt* ext = reinterpret_cast<LfExt*>(mag + (size_t)batch * H * W);
+    lowfield_pass1(high, batch, H, W, row_re, row_im, col_re, col_im, sigma, noise_re, noise_im, seeds_device, mag, ext, s);
+    const size_t n = (size_t)H * W;
+    size_t blocks = (n + 256 * 4 - 1) / (256 * 4);
+    if (blocks > 1024) blocks = 1024;
+    lowfield_pass2_f32_kernel<<<dim3((unsigned)blocks, batch), 256, 0, s>>>(mag, ext, out_f32, n);
+    MRISR_CHECK_LAUNCH("lowfield_simulate_f32");
     return MRISR_OK;
 }
