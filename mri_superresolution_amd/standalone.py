@@ -17,8 +17,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib as L
-
-GN_GROUPS, GN_EPS = 8, 1e-5
+from .launch import GN_GROUPS, Consumer, dgrad_desc, gn_finalize, marshal_consumers
 
 
 def _dtype() -> torch.dtype:
@@ -38,8 +37,7 @@ def _check(x: torch.Tensor, who: str):
 
 class _Act:
     """A tensor in NHWC compute dtype plus how a consumer must read it: as stored (RAW) or through its GroupNorm affine
-    + LeakyReLU (NORM).  ``consumers``: during a backward pass, (dL/d(conv input), channels of that input, channel offset,
-    H, W, spatial, off_y, off_x) of every convolution that read this activation."""
+    + LeakyReLU (NORM).  ``consumers``: during a backward pass, a ``launch.Consumer`` per convolution that read this activation."""
 
     def __init__(self, t, mode=L.SRC_RAW, scale=None, shift=None, meanrstd=None, shuffled=False):
         self.t, self.mode, self.scale, self.shift, self.meanrstd, self.shuffled = t, mode, scale, shift, meanrstd, shuffled
@@ -111,14 +109,8 @@ def _conv(srcs: List[Tuple[_Act, int, Tuple[int, int]]], weight, bias, ks: int, 
 def _norm(raw: torch.Tensor, stats: torch.Tensor, gn: torch.nn.GroupNorm, shuffled=False) -> _Act:
     """GroupNorm statistics -> per-(n,c) affine; the activation stays fused into whoever reads it."""
     N, H, W, Cc = raw.shape
-    dev = raw.device
-    scale = torch.empty(N * Cc, dtype=torch.float32, device=dev)
-    shift = torch.empty(N * Cc, dtype=torch.float32, device=dev)
-    meanrstd = torch.empty(N * GN_GROUPS * 2, dtype=torch.float32, device=dev)
     g, b = gn.weight.detach().to(torch.float32).contiguous(), gn.bias.detach().to(torch.float32).contiguous()
-    L.call("mrisr_gn_finalize", stats.data_ptr(), g.data_ptr(), b.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-           meanrstd.data_ptr(), N, Cc, GN_GROUPS, float((Cc // GN_GROUPS) * H * W), GN_EPS, L.stream_ptr())
-    return _Act(raw, L.SRC_NORM, scale, shift, meanrstd, shuffled)
+    return _Act(raw, L.SRC_NORM, *gn_finalize(stats, g, b, N, Cc, H, W, L.stream_ptr()), shuffled)
 
 
 def _conv_norm(tape: Optional[list], srcs, conv, gn, ks: int, H: int, W: int, dtype, out_mode=L.OUT_PLAIN) -> _Act:
@@ -165,13 +157,7 @@ def _node_backward(a: _Act, gn, dt: int, grads: dict, dbias: Optional[torch.Tens
     LeakyReLU', sums), finalize (group sums -> coefficients, dgamma / dbeta), apply."""
     dev, st = a.t.device, L.stream_ptr()
     N, H, W, Cc = a.N, a.H, a.W, a.C
-    cons = (L.Consumer * 2)()
-    if not 1 <= len(a.consumers) <= 2:
-        raise RuntimeError(f"internal: {len(a.consumers)} consumers of a block activation")
-    for i, (da, ctot, coff, ch, cw, sp, oy, ox) in enumerate(a.consumers):
-        cons[i].da = da.data_ptr()
-        cons[i].C_total, cons[i].c_off, cons[i].H, cons[i].W = ctot, coff, ch, cw
-        cons[i].spatial, cons[i].off_y, cons[i].off_x, cons[i].weight_mode = sp, oy, ox, 0
+    cons = marshal_consumers(a.consumers)
     g = torch.empty_like(a.t)
     red = torch.zeros(N * Cc * 2 + 256, dtype=torch.float32, device=dev)
     L.call("mrisr_act_bwd_reduce", dt, a.t.data_ptr(), a.scale.data_ptr(), a.shift.data_ptr(), a.meanrstd.data_ptr(),
@@ -215,20 +201,13 @@ def _conv_backward(rec: _ConvRecord, dy: torch.Tensor, dtype, grads: dict, need_
         return
     # input gradient: the same implicit-GEMM kernel on dy with mirrored, transposed weights
     w = conv.weight.detach().to(torch.float32).permute(0, 2, 3, 1).contiguous()
-    dd = L.ConvDesc()
-    dd.dtype, dd.N, dd.H, dd.W = dt, N, rec.H, rec.W
-    dd.Cin, dd.Cout, dd.ksize, dd.nsrc = cout, cin, ks, 1
-    dd.combine, dd.out_mode, dd.groups, dd.relu_out = L.COMBINE_CONCAT, L.OUT_PLAIN, 0, 0
-    dd.src[0].ptr = dy.data_ptr()
-    dd.src[0].C, dd.src[0].H, dd.src[0].W = cout, rec.H, rec.W
-    dd.src[0].mode, dd.src[0].spatial = L.SRC_RAW, L.SP_NONE
-    packed = _pack(w, dt, cout, cin, ks, 1)
     dain = torch.empty((N, rec.H, rec.W, cin), dtype=dtype, device=dev)
-    dd.wpacked, dd.out = packed.data_ptr(), dain.data_ptr()
+    packed = _pack(w, dt, cout, cin, ks, 1)      # held here: the descriptor carries its address only
+    dd = dgrad_desc(dt, dy, cin, cout, ks, packed, dain)
     L.call("mrisr_conv_forward", C.byref(dd), st)
     coff = 0
     for a, spatial, (oy, ox) in rec.srcs:
-        a.consumers.append((dain, cin, coff, rec.H, rec.W, spatial, oy, ox))
+        a.consumers.append(Consumer(dain, cin, coff, rec.H, rec.W, spatial, oy, ox))
         coff += a.C
 
 
@@ -237,21 +216,21 @@ def _input_grad(a: _Act, x: torch.Tensor, dtype) -> torch.Tensor:
     cropped (padding), scattered to the arg-max positions (2x2 max-pool in the loader) or pushed through the adjoint of the
     bilinear x2 (up-sampling in the loader)."""
     total = None
-    for dain, ctot, coff, ch, cw, sp, oy, ox in a.consumers:
-        g = dain[..., coff:coff + a.C]
-        if sp == L.SP_UP2:
+    for c in a.consumers:
+        g = c.da[..., c.c_off:c.c_off + a.C]
+        if c.spatial == L.SP_UP2:
             g = g.contiguous()
             low = torch.empty((a.N, a.H, a.W, a.C), dtype=dtype, device=g.device)
             L.call("mrisr_upsample2_adjoint", _dt(dtype), g.data_ptr(), low.data_ptr(), a.N, a.H, a.W, a.C, L.stream_ptr())
             gx = low.permute(0, 3, 1, 2).to(torch.float32)
-        elif sp == L.SP_POOL2:
+        elif c.spatial == L.SP_POOL2:
             # the pooling decisions are those of the stored (compute-dtype) tensor the convolution read
             xs = a.t.permute(0, 3, 1, 2).to(torch.float32)
             _, idx = torch.nn.functional.max_pool2d(xs, 2, return_indices=True)
             gx = torch.nn.functional.max_unpool2d(g.permute(0, 3, 1, 2).to(torch.float32).contiguous(), idx, 2,
                                                   output_size=(a.H, a.W))
         else:
-            gx = g[:, oy:oy + a.H, ox:ox + a.W, :].permute(0, 3, 1, 2).to(torch.float32)
+            gx = g[:, c.off_y:c.off_y + a.H, c.off_x:c.off_x + a.W, :].permute(0, 3, 1, 2).to(torch.float32)
         total = gx if total is None else total + gx
     a.consumers = []
     return total.contiguous()
@@ -261,7 +240,7 @@ def _backward(tape: list, out_act: _Act, gout: torch.Tensor, dtype, inputs: List
     """Walks the recorded convolutions in reverse.  Returns ({parameter address: gradient}, [dL/dx per input or None])."""
     dt = _dt(dtype)
     grads: dict = {}
-    out_act.consumers.append((_to_nhwc(gout, dtype), out_act.C, 0, out_act.H, out_act.W, L.SP_NONE, 0, 0))
+    out_act.consumers.append(Consumer(_to_nhwc(gout, dtype), out_act.C, 0, out_act.H, out_act.W, L.SP_NONE, 0, 0))
     want_input = any(need for _, _, need in inputs)
     for i in range(len(tape) - 1, -1, -1):
         rec = tape[i]

@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .launch import dgrad_desc
 
 # torchvision VGG19 configuration "E" (public architecture)
 VGG19_CFG = (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M")
@@ -205,12 +206,7 @@ class VGGEngine:
             conv = self.features[i]
             wp, _ = self._weights(i, dt, dev, 1)
             dx = torch.empty_like(inp)
-            d = L.ConvDesc()
-            d.dtype, d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.nsrc = dt, N, h, w, conv.out_channels, cin, 3, 1
-            d.combine, d.out_mode, d.groups, d.relu_out = L.COMBINE_CONCAT, L.OUT_PLAIN, 0, 0
-            d.src[0].ptr, d.src[0].C, d.src[0].H, d.src[0].W = g.data_ptr(), conv.out_channels, h, w
-            d.src[0].mode, d.src[0].spatial = L.SRC_RAW, L.SP_NONE
-            d.wpacked, d.out = wp.data_ptr(), dx.data_ptr()
+            d = dgrad_desc(dt, g, cin, conv.out_channels, 3, wp, dx)
             # the conv's input is the ReLU output of the previous conv: fuse that ReLU's backward into the epilogue
             if prev is not None and prev[0] == "conv" and prev[4]:
                 d.relu_mask = inp.data_ptr()
