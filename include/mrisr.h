@@ -280,6 +280,30 @@ int mrisr_act_bwd_apply_fused_unshuffle(int dtype, const void* x, const float* s
                                         const mrisr_consumer* consumer, const float* blend_alpha,
                                         const mrisr_gn_bwd_fin* fin, void* dx, float* dbias, int N, int H, int W, int C,
                                         void* stream);
+/* The two branches of the alpha blend (unet_model.py:202-207) through the two passes TOGETHER: both have one consumer, the
+ * same tensor da [N][H][W][C] (the blended tensor's gradient), which each pass then reads once instead of twice.  `ps` is the
+ * pixel-shuffled branch (dx_ps stored un-shuffled, [N][H/2][W/2][4C], dbias as for mrisr_act_bwd_apply_fused_unshuffle), `bil`
+ * the plain one (dx_bil [N][H][W][C]); weight_mode 1 / 2 as in mrisr_consumer.  blend_reduce = mrisr_act_bwd_reduce of both
+ * nodes with g = NULL (red [N][C][2] and alpha_slots [256] of each branch zeroed by the caller); blend_apply =
+ * mrisr_act_bwd_apply_fused_unshuffle + mrisr_act_bwd_apply_fused with fin (fin_*->red and ->alpha_slots are the branch's own).
+ * 16-bit storage, even H and W, C a multiple of 8 and at most 2048: mrisr_act_bwd_blend_ok() != 0; the entry points refuse
+ * everything else with MRISR_E_UNSUPPORTED.                                                                           */
+typedef struct mrisr_blend_branch {
+    const void* x;         /* raw conv output, NHWC at the blend's resolution                          */
+    const float* scale;    /* [N][C] GroupNorm affine of the forward pass                              */
+    const float* shift;
+    const float* meanrstd; /* [N][groups][2]                                                           */
+    float* red;            /* [N][C][2] accumulated                                                    */
+    float* alpha_slots;    /* [256] accumulated                                                        */
+    int32_t weight_mode;   /* 1: times sigmoid(alpha); 2: times 1 - sigmoid(alpha)                     */
+    int32_t reserved_;
+} mrisr_blend_branch;
+int mrisr_act_bwd_blend_ok(int dtype, int N, int H, int W, int C);
+int mrisr_act_bwd_blend_reduce(int dtype, const void* da, const mrisr_blend_branch* ps, const mrisr_blend_branch* bil,
+                               const float* blend_alpha, int N, int H, int W, int C, int groups, void* stream);
+int mrisr_act_bwd_blend_apply(int dtype, const void* da, const mrisr_blend_branch* ps, const mrisr_blend_branch* bil,
+                              const float* blend_alpha, const mrisr_gn_bwd_fin* fin_ps, const mrisr_gn_bwd_fin* fin_bil,
+                              void* dx_ps, void* dx_bil, float* dbias, int N, int H, int W, int C, void* stream);
 /* out[C] += sum over pixels of x[npix][C]  (bias gradient of nn.Conv2d(bias=True), unet_model.py:101) */
 int mrisr_channel_sum(int dtype, const void* x, float* out, size_t npix, int C, void* stream);
 /* dalpha += sigmoid'(alpha) * sum da * (act0 - act1)   (unet_model.py:206-207)               */

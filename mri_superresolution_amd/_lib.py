@@ -60,6 +60,11 @@ class GnBwdFin(C.Structure):
                 ("alpha_sign", C.c_float), ("groups", C.c_int32)]
 
 
+class BlendBranch(C.Structure):
+    _fields_ = [("x", _vp), ("scale", _fp), ("shift", _fp), ("meanrstd", _fp), ("red", _fp), ("alpha_slots", _fp),
+                ("weight_mode", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class Consumer(C.Structure):
     _fields_ = [("da", _vp), ("C_total", C.c_int32), ("c_off", C.c_int32), ("H", C.c_int32),
                 ("W", C.c_int32), ("spatial", C.c_int32), ("off_y", C.c_int32), ("off_x", C.c_int32),
@@ -106,6 +111,10 @@ SIGNATURES = {
                                    _i, _vp]),
     "mrisr_act_bwd_apply_fused_unshuffle": (_i, [_i, _vp, _fp, _fp, C.POINTER(Consumer), _fp, C.POINTER(GnBwdFin), _vp, _fp, _i,
                                                  _i, _i, _i, _vp]),
+    "mrisr_act_bwd_blend_ok": (_i, [_i, _i, _i, _i, _i]),
+    "mrisr_act_bwd_blend_reduce": (_i, [_i, _vp, C.POINTER(BlendBranch), C.POINTER(BlendBranch), _fp, _i, _i, _i, _i, _i, _vp]),
+    "mrisr_act_bwd_blend_apply": (_i, [_i, _vp, C.POINTER(BlendBranch), C.POINTER(BlendBranch), _fp, C.POINTER(GnBwdFin),
+                                       C.POINTER(GnBwdFin), _vp, _vp, _fp, _i, _i, _i, _i, _vp]),
     "mrisr_channel_sum": (_i, [_i, _vp, _fp, _sz, _i, _vp]),
     "mrisr_blend_alpha_grad": (_i, [_i, _vp, _vp, _fp, _fp, _vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "mrisr_head_forward": (_i, [_i, _vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
@@ -149,7 +158,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 308      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 309      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -198,6 +198,12 @@ class UNetEngine:
         self.layers.append(Layer("final_conv.0", f // 2, f // 2, 3, (Source(fb), Source(ps)), fc,
                                  combine=L.COMBINE_BLEND, blend_src=True))
         self.head_in = fc
+        # the other branch of every alpha blend: backward takes both branches' GroupNorm backward in one pair of launches
+        self._blend_sibling: Dict[Node, Node] = {}
+        for layer in self.layers:
+            if layer.combine == L.COMBINE_BLEND:
+                a, b = (src.node for src in layer.srcs)
+                self._blend_sibling[a], self._blend_sibling[b] = b, a
         self._packed: Dict[tuple, torch.Tensor] = {}
         self._packed_token = None      # (dtype, weights token) the packed images were built from
         self.timer: Optional[KernelTimer] = None
@@ -450,8 +456,12 @@ class UNetEngine:
             red_off[n] = (o, sz)
             o += sz
 
+        blend_dx: Dict[Node, torch.Tensor] = {}      # dx of a blend branch that was computed with its sibling (blend_pair below)
+
         def node_backward(n: Node, dbias=None) -> torch.Tensor:
             """dL/dact (gathered from consumers) -> dL/d(raw conv output), plus GN affine grads."""
+            if n in blend_dx:
+                return blend_dx.pop(n)
             s = ns[n]
             H, W, Cn = s.H, s.W, n.C
             consumers = s.consumers
@@ -539,6 +549,46 @@ class UNetEngine:
                        N, H, W, Cn, mode, L.ptr(dbias) if n.shuffled else None, st, nbytes=3 * nx)
                 return dx
 
+            def blend_pair():
+                # the two branches of the alpha blend, reached at the pixel-shuffled one: each has one consumer, and it is the same
+                # tensor (final_conv.0's dain), so both nodes go through the two passes TOGETHER and each pass reads that tensor once
+                # (csrc/norm.hip: act_bwd_blend_reduce_kernel / act_bwd_blend_apply_kernel).  The plain branch's dx waits in blend_dx
+                # for that node's own node_backward call.  None = not this case: the per-node launches below
+                sib = self._blend_sibling.get(n)
+                if sib is None or not (fused_ps and blend_branch) or sib.shuffled or sib.C != Cn or (c0.C_total, c0.c_off) != (Cn, 0):
+                    return None
+                t = ns[sib]
+                if len(t.consumers) != 1 or (t.H, t.W) != (H, W):
+                    return None
+                k = t.consumers[0]
+                if (k.da is not c0.da or k.weight_mode not in (1, 2) or k.weight_mode == c0.weight_mode or k.spatial != L.SP_NONE
+                        or (k.H, k.W, k.off_y, k.off_x, k.C_total, k.c_off) != (H, W, 0, 0, Cn, 0)):
+                    return None
+                if not L.load().mrisr_act_bwd_blend_ok(dt, N, H, W, Cn):
+                    return None
+                t.consumers = []
+                red_s = red_arena[red_off[sib][0]:red_off[sib][0] + red_off[sib][1]]
+                slots_s = red_s[SL * N * Cn * 2:]
+                bp = L.BlendBranch(s.raw.data_ptr(), s.scale.data_ptr(), s.shift.data_ptr(), s.meanrstd.data_ptr(), red.data_ptr(),
+                                   slots.data_ptr(), c0.weight_mode, 0)
+                bb = L.BlendBranch(t.raw.data_ptr(), t.scale.data_ptr(), t.shift.data_ptr(), t.meanrstd.data_ptr(), red_s.data_ptr(),
+                                   slots_s.data_ptr(), k.weight_mode, 0)
+                L.call("mrisr_act_bwd_blend_reduce", dt, c0.da.data_ptr(), C.byref(bp), C.byref(bb), alpha_ptr, N, H, W, Cn,
+                       GN_GROUPS, st, nbytes=3 * nx)
+                fp = L.GnBwdFin(*gn, slots.data_ptr(), alpha_ptr, dalpha_ptr, count, alpha_sign, GN_GROUPS)
+                fb = L.GnBwdFin(red_s.data_ptr(), params[sib.gamma].data_ptr(), t.meanrstd.data_ptr(), grads[sib.gamma].data_ptr(),
+                                grads[sib.beta].data_ptr(), slots_s.data_ptr(), alpha_ptr, dalpha_ptr, count,
+                                1.0 if k.weight_mode == 1 else -1.0, GN_GROUPS)
+                dx = torch.empty((N, H // 2, W // 2, 4 * Cn), dtype=dtype, device=dev)
+                dx_sib = torch.empty_like(t.raw)
+                L.call("mrisr_act_bwd_blend_apply", dt, c0.da.data_ptr(), C.byref(bp), C.byref(bb), alpha_ptr, C.byref(fp),
+                       C.byref(fb), dx.data_ptr(), dx_sib.data_ptr(), L.ptr(dbias), N, H, W, Cn, st, nbytes=5 * nx)
+                blend_dx[sib] = dx_sib
+                return dx
+
+            dx = blend_pair()
+            if dx is not None:
+                return dx
             # (one image's blocks - at most 256, i.e. ~86 CUs' worth of waves - must be resident together; under data parallelism
             # the RCCL kernels of the overlapped all-reduce hold CUs as well, so only nodes of <= 128 blocks per image take it)
             op_blocks = -(-(H * W) // ((256 // max(Cn // 8, 1)) * 8)) if Cn >= 8 else 1 << 30
