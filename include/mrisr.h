@@ -537,6 +537,24 @@ int mrisr_f32_resample_letterbox(const float* in, int batch, int H, int W, const
                                  int out_h, int out_w, int y_off, int x_off, float pad_value, int clip, float* out_f32,
                                  uint8_t* out_u8, void* stream);
 
+/* ---- multi-planar blend of whole-volume inference (extension; csrc/volume_blend.hip): the result of one slice pass is brought
+ *      to the full (2X, 2Y, 2Z) grid along its slice axis and accumulated into the mean of up to three passes ------------ */
+#define MRISR_VOLBLEND_SET 0        /* acc = U(plane)                                                                      */
+#define MRISR_VOLBLEND_ADD 1        /* acc = acc + U(plane)                                                                */
+#define MRISR_VOLBLEND_FINISH 2     /* out = (acc + U(plane)) / (float)count; count == 1: out = U(plane), acc is not touched */
+/* plane: the float32 result of the slice pass across `axis` of an (X, Y, Z) INPUT volume in slice-major layout [S][R][C]: S the
+ * extent of axis, R and C the DOUBLED extents of the two other axes in ascending axis order.  U doubles axis with the
+ * half-pixel-centred linear rule, replicated border: u[2s] = 0.75f e[s] + 0.25f e[max(s - 1, 0)], u[2s + 1] = 0.75f e[s] +
+ * 0.25f e[min(s + 1, S - 1)], in float32 one rounded operation at a time (product, product, sum).  acc: the (2X, 2Y, 2Z) C-order
+ * float32 accumulator (may be NULL for a FINISH with count 1); out (FINISH only): (2X, 2Y, 2Z) C-order, out_dtype
+ * MRISR_WINDOW_F32 or MRISR_WINDOW_I16 (np.rint, saturated); a float32 out may be acc itself.  count: planes in the mean, this
+ * one included (FINISH only).  Pointers as torch allocates them (the float buffers 8-byte aligned at least).
+ * One launch on stream, no host synchronisation (HIP-graph capturable).
+ * MRISR_E_ARG: null or misaligned pointer, axis outside 0..2, unknown mode or out_dtype, count below 1; MRISR_E_SHAPE: an
+ * extent below 1 or above 32767, a doubled slice 2Y x 2Z of more than 2^31 - 4 voxels for axis 0.                          */
+int mrisr_f32_volume_up2_blend(const float* plane, int axis, int X, int Y, int Z, float* acc, int mode, int count, int out_dtype,
+                               void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ COMBINE_CONCAT, COMBINE_BLEND = 0, 1
 OUT_PLAIN, OUT_PIXEL_SHUFFLE2 = 0, 1
 UP2_BILINEAR, UP2_BICUBIC, UP2_SHARP_BILINEAR = 0, 1, 2      # MRISR_UP2_*: method of mrisr_u8_upscale2
 WINDOW_F32, WINDOW_I16 = 0, 1      # MRISR_WINDOW_*: out_dtype of mrisr_f32_window_restore
+VOLBLEND_SET, VOLBLEND_ADD, VOLBLEND_FINISH = 0, 1, 2      # MRISR_VOLBLEND_*: mode of mrisr_f32_volume_up2_blend
 RESAMPLE_LINEAR, RESAMPLE_CUBIC, RESAMPLE_AREA, RESAMPLE_LANCZOS4 = 1, 2, 3, 4      # MRISR_RESAMPLE_*: method of mrisr_resample_taps
 PACK_RING = 256      # MRISR_PACK_RING: OR into transpose_flip for the ring weight layout (csrc/conv_ring.hip)
 PACK_UPADJ = 512     # MRISR_PACK_UPADJ: the W^T image of mrisr_conv_upadj (csrc/conv_upadj.hip)
@@ -155,10 +156,11 @@ SIGNATURES = {
     "mrisr_f32_percentile_bounds": (_i, [_fp, _sz, _i, _d, _d, _fp, _vp, _vp]),
     "mrisr_f32_window_normalise": (_i, [_fp, _fp, _sz, _i, _fp, _vp]),
     "mrisr_f32_window_restore": (_i, [_fp, _fp, _sz, _i, _i, _vp, _vp]),
+    "mrisr_f32_volume_up2_blend": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 309      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 310      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

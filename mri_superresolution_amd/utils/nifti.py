@@ -9,8 +9,8 @@ the stored values, scaled by ``scl_slope`` / ``scl_inter`` in float64 when a slo
 
 Geometry of the output.  The model's x2 is a half-pixel-centred upsampling: output index ``o`` along an upscaled axis sits at
 input coordinate ``o / 2 - 1 / 4``.  With the input affine's columns ``c_a`` of the upscaled axes and its translation ``t``,
-the output affine has the columns ``c_a / 2`` and the translation ``t - (c_a1 + c_a2) / 4``: the volume stays where it was
-in world space.  Applied to the sform rows when ``sform_code > 0`` and to the qform (pixdim halved, offsets moved by the same
+the output affine has the columns ``c_a / 2`` and the translation ``t`` minus a quarter of the sum of those columns (two for
+a slice pass across one axis, all three for the isotropic output): the volume stays where it was in world space.  Applied to the sform rows when ``sform_code > 0`` and to the qform (pixdim halved, offsets moved by the same
 vector built from the qform's own axes, quaternion unchanged) when ``qform_code > 0``.
 """
 from __future__ import annotations
@@ -190,7 +190,7 @@ def upscaled_affine(affine: np.ndarray, upscaled_axes: Sequence[int]) -> np.ndar
 
 def write_nifti(path: str, data: np.ndarray, header: NiftiHeader, upscaled_axes: Sequence[int] = ()):
     """Writes float32 or int16 ``data`` (3-D or 4-D) as single-file NIfTI-1 under a copy of ``header`` (its byte order kept):
-    ``dim`` from ``data.shape``, which must be the header's with the ``upscaled_axes`` (two of 0, 1, 2, or none) doubled;
+    ``dim`` from ``data.shape``, which must be the header's with the ``upscaled_axes`` (two or all three of 0, 1, 2, or none) doubled;
     their ``pixdim`` halved and the sform / qform moved as the module docstring says; ``datatype`` / ``bitpix`` set,
     ``scl_slope = 1``, ``scl_inter = 0``, ``vox_offset = 352``, magic ``n+1``.  gzip when the name ends in ``.gz``."""
     data = np.asarray(data)
@@ -200,8 +200,8 @@ def write_nifti(path: str, data: np.ndarray, header: NiftiHeader, upscaled_axes:
     if data.ndim not in (3, 4):
         raise ValueError(f"write_nifti writes 3-D or 4-D volumes, not {data.shape}")
     axes = tuple(int(a) for a in upscaled_axes)
-    if len(axes) not in (0, 2) or len(set(axes)) != len(axes) or any(a not in (0, 1, 2) for a in axes):
-        raise ValueError(f"upscaled_axes must be two different axes of 0, 1, 2 (or none), got {upscaled_axes}")
+    if len(axes) not in (0, 2, 3) or len(set(axes)) != len(axes) or any(a not in (0, 1, 2) for a in axes):
+        raise ValueError(f"upscaled_axes must be two or three different axes of 0, 1, 2 (or none), got {upscaled_axes}")
     hdr = header.copy()
     old_dim = hdr.get("dim")
     expect = tuple(old_dim[1 + a] * (2 if a in axes else 1) for a in range(data.ndim))

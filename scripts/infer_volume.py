@@ -10,6 +10,10 @@ output volume on the device (``mri_superresolution_amd/volume.py``); one downloa
 ``pixdim`` halved and the sform / qform moved so that the volume stays where it was in world space
 (``mri_superresolution_amd/utils/nifti.py``).  A 4-D file is processed timepoint by timepoint.  Checkpoint flags, checkpoint
 search order and the exit code (0 / 1, error logged) are those of ``scripts/infer.py``.
+
+``--isotropic`` doubles all three axes: the slices across axis 0, 1 and 2 are enhanced in turn, each result is interpolated
+along its own slice axis and the three are averaged on the device (``volume.enhance_volume_isotropic``,
+``csrc/volume_blend.hip``); a 1 mm scan comes out at 0.5 mm in every direction.
 """
 import argparse
 import logging
@@ -24,18 +28,20 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd.utils.nifti import read_nifti, write_nifti   # noqa: E402
-from mri_superresolution_amd.volume import enhance_volume                # noqa: E402
+from mri_superresolution_amd.volume import enhance_volume, enhance_volume_isotropic   # noqa: E402
 from scripts.infer import find_best_checkpoint, load_model               # noqa: E402
 
 logger = logging.getLogger("infer_volume")
 
 
 def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_amp=False, use_graph=True, output_dtype="float32",
-                   device="cuda"):
+                   device="cuda", isotropic=False):
     """NIfTI file -> NIfTI file; returns the output array (as written)."""
     data, header = read_nifti(input_path)
     dtype = {"float32": torch.float32, "int16": torch.int16}[output_dtype]
-    in_plane = tuple(a for a in (0, 1, 2) if a != axis)
+    in_plane = (0, 1, 2) if isotropic else tuple(a for a in (0, 1, 2) if a != axis)
+    if isotropic:
+        logger.info("Isotropic mode: slices across all three axes, every axis doubled; --axis is not used.")
     if any(data.shape[a] % 8 for a in in_plane):
         logger.warning(f"In-plane dimensions {tuple(data.shape[a] for a in in_plane)} are not divisible by 8. This might affect "
                        "performance or spatial accuracy due to model pooling layers.")
@@ -43,8 +49,13 @@ def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_am
     outs, graphs = [], {}
     for frame in frames:
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
-        outs.append(enhance_volume(model, vol, axis=axis, batch_size=batch_size, use_amp=use_amp, use_graph=use_graph,
-                                   out_dtype=dtype, graph_cache=graphs).cpu().numpy())
+        if isotropic:
+            out = enhance_volume_isotropic(model, vol, batch_size=batch_size, use_amp=use_amp, use_graph=use_graph, out_dtype=dtype,
+                                           graph_cache=graphs)
+        else:
+            out = enhance_volume(model, vol, axis=axis, batch_size=batch_size, use_amp=use_amp, use_graph=use_graph, out_dtype=dtype,
+                                 graph_cache=graphs)
+        outs.append(out.cpu().numpy())
     result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
     os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
     write_nifti(output_path, result, header, in_plane)
@@ -70,7 +81,7 @@ def main(args):
             logger.info(f"Automatically selected checkpoint: {ckpt}")
         model = load_model(args.model_type, ckpt, device, base_filters=args.base_filters)
         process_volume(model, args.input, args.output, args.axis, args.batch_size, args.use_amp, not args.no_graph,
-                       args.output_dtype, device)
+                       args.output_dtype, device, isotropic=args.isotropic)
         logger.info("Inference completed successfully!")
         return 0
     except Exception as e:
@@ -81,7 +92,7 @@ def main(args):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="MRI quality enhancement inference on whole NIfTI volumes (extension)")
     p.add_argument("--input", type=str, required=True, help="(extension) input scan: single-file NIfTI-1, .nii or .nii.gz, 3-D or 4-D")
-    p.add_argument("--output", type=str, required=True, help="(extension) output scan, .nii or .nii.gz: in-plane size doubled")
+    p.add_argument("--output", type=str, required=True, help="(extension) output scan, .nii or .nii.gz: in-plane size doubled (every axis with --isotropic)")
     p.add_argument("--checkpoint_dir", type=str, default="./checkpoints")
     p.add_argument("--checkpoint_path", type=str, default=None)
     p.add_argument("--model_type", type=str, choices=["unet"], default="unet")
@@ -91,6 +102,9 @@ def parse_args(argv=None):
     p.add_argument("--use_amp", action="store_true", help="fp16 MFMA compute (the reference's autocast)")
     p.add_argument("--axis", type=int, choices=[0, 1, 2], default=2,
                    help="(extension) slices are taken across this axis; 2 is the reference's data[:, :, idx], the orientation of training")
+    p.add_argument("--isotropic", action="store_true",
+                   help="(extension) double all three axes: the passes across axis 0, 1 and 2, each interpolated along its slice axis, "
+                        "averaged on the device; --axis is not used")
     p.add_argument("--batch_size", type=int, default=16, help="(extension) slices per forward")
     p.add_argument("--no_graph", action="store_true", help="(extension) do not replay the forward of full batches as a HIP graph")
     p.add_argument("--output_dtype", type=str, choices=["float32", "int16"], default="float32",
