@@ -555,6 +555,32 @@ int mrisr_f32_resample_letterbox(const float* in, int batch, int H, int W, const
 int mrisr_f32_volume_up2_blend(const float* plane, int axis, int X, int Y, int Z, float* acc, int mode, int count, int out_dtype,
                                void* out, void* stream);
 
+/* ---- volume evaluation (extension; csrc/volume_eval.hip, csrc/volume_metrics.hip): the x2 degradation, the x2 interpolation
+ *      baselines and SSIM / PSNR of whole volumes.  A volume is (X, Y, Z) float32 in C order; bit 0 / 1 / 2 of axes_mask
+ *      (1..7) selects axis X / Y / Z.  One launch each on stream, no host synchronisation. ------------------------------------ */
+/* dst = mean over pairs of src along the set axes (extents halved): for the set axes in ascending order v = v[even] + v[odd]
+ * in float32, then one product with 0.5^k.  Output voxel i covers source voxels 2i, 2i + 1.
+ * MRISR_E_ARG: null or misaligned pointer (src 8-byte aligned when Z is set), mask outside 1..7; MRISR_E_SHAPE: an extent below
+ * 1 or above 32767, an odd extent on a set axis.                                                                           */
+int mrisr_f32_volume_down2(const float* src, int X, int Y, int Z, int axes_mask, float* dst, void* stream);
+/* dst = src with the set axes doubled, in ascending axis order, each pass on the float32 result of the one before, border
+ * replicated.  method MRISR_RESAMPLE_LINEAR: u[2i] = 0.75f e[i] + 0.25f e[i - 1], u[2i + 1] = 0.75f e[i] + 0.25f e[i + 1];
+ * MRISR_RESAMPLE_CUBIC (Keys, A = -0.75): u[2i] = taps i - 2 .. i + 1 with (-0.03515625, 0.26171875, 0.87890625, -0.10546875),
+ * u[2i + 1] = taps i - 1 .. i + 2 with the mirrored weights; rounded products summed in ascending tap order.  X, Y, Z: the extents
+ * of src.  MRISR_E_ARG: null or misaligned pointer (dst 8-byte aligned when Z is set), mask outside 1..7, another method;
+ * MRISR_E_SHAPE: an extent below 1 or above 32767.                                                                          */
+int mrisr_f32_volume_up2(const float* src, int X, int Y, int Z, int axes_mask, int method, float* dst, void* stream);
+/* sums[3] (double, accumulated; zero it first): sums[0] += sum |a - b|, sums[1] += sum ssim_map, sums[2] += sum (a - b)^2 over
+ * the volume.  ssim_map: Gaussian-window SSIM with the window the outer product of the normalised 1-D Gaussian (sigma,
+ * window_size odd in 3..15) along all three axes, zero padding, C1 = (0.01 val_range)^2, C2 = (0.03 val_range)^2.
+ * MRISR_E_ARG: null pointer, window_size not odd in 3..15, sigma or val_range not positive; MRISR_E_SHAPE: an extent below 1
+ * or above 32767.                                                                                                            */
+int mrisr_f32_volume_metrics(const float* a, const float* b, int X, int Y, int Z, float val_range, float sigma, int window_size,
+                             double* sums, void* stream);
+/* sums[3] of mrisr_f32_volume_metrics -> out[5] doubles: ssim, mse, rmse, mae, psnr with psnr = mse < 1e-10 ? 100 :
+ * 10 log10(val_range^2 / mse); the voxel count X Y Z is formed in double.  No host read-back.                              */
+int mrisr_volume_metrics_finalize(const double* sums, int X, int Y, int Z, float val_range, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

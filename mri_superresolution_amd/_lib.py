@@ -157,10 +157,14 @@ SIGNATURES = {
     "mrisr_f32_window_normalise": (_i, [_fp, _fp, _sz, _i, _fp, _vp]),
     "mrisr_f32_window_restore": (_i, [_fp, _fp, _sz, _i, _i, _vp, _vp]),
     "mrisr_f32_volume_up2_blend": (_i, [_fp, _i, _i, _i, _i, _fp, _i, _i, _i, _vp, _vp]),
+    "mrisr_f32_volume_down2": (_i, [_fp, _i, _i, _i, _i, _fp, _vp]),
+    "mrisr_f32_volume_up2": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _vp]),
+    "mrisr_f32_volume_metrics": (_i, [_fp, _fp, _i, _i, _i, _f, _f, _i, _dp, _vp]),
+    "mrisr_volume_metrics_finalize": (_i, [_dp, _i, _i, _i, _f, _dp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 310      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 311      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

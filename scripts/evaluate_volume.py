@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Volume evaluation (extension): ground-truth NIfTI scans in, SSIM / PSNR tables of the x2 U-Net and the
+x2 interpolation baselines out.
+
+    python scripts/evaluate_volume.py --reference hr.nii.gz [more.nii.gz ...] --checkpoint_dir ./checkpoints --isotropic
+
+Every reference scan is uploaded once.  Its low-resolution volume is the mean over pairs along the doubled axes
+(``volume_eval.downsample2``) or, with ``--input``, the given scan (one reference only; half of the reference's extents on the
+doubled axes) - the way to score a simulated low-field acquisition.  The doubled axes are all three with ``--isotropic``, else
+the two in-plane axes of the slices across ``--axis``.  Methods: ``unet`` (``scripts/infer_volume.py``'s path), with
+``--isotropic`` also ``unet_axis2_linear`` (one slice pass across axis 2 plus linear through-plane interpolation: the
+alternative to the three-plane blend), ``linear`` and ``cubic``.  The metrics are 3-D: Gaussian-window SSIM over the volume,
+MSE, RMSE, MAE, PSNR with ``--data_range`` (default: max - min of the reference), all computed on the device
+(``csrc/volume_metrics.hip``).  A 4-D file is scored timepoint by timepoint.  One table per scan, the mean over scans, and the
+same rows in ``--output_csv``.  Checkpoint flags and the exit code (0 / 1, error logged) are those of ``scripts/infer_volume.py``.
+"""
+import argparse
+import csv
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
+from mri_superresolution_amd.utils.nifti import read_nifti                # noqa: E402
+from mri_superresolution_amd.volume_eval import evaluate_volume           # noqa: E402
+
+logger = logging.getLogger("evaluate_volume")
+CSV_COLUMNS = ["scan", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # the column style of scripts/evaluate.py
+
+
+def _frames(data):
+    return [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
+
+
+def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
+               use_graph=True, device="cuda", graph_cache=None):
+    """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method."""
+    ref, _ = read_nifti(reference_path)
+    low = read_nifti(input_path)[0] if input_path else None
+    if low is not None and low.ndim != ref.ndim:
+        raise ValueError(f"{input_path} has {low.ndim} axes, {reference_path} has {ref.ndim}")
+    if low is not None and low.ndim == 4 and low.shape[3] != ref.shape[3]:
+        raise ValueError(f"{input_path} has {low.shape[3]} timepoints, {reference_path} has {ref.shape[3]}")
+    ref_frames, low_frames = _frames(ref), (_frames(low) if low is not None else None)
+    graphs = graph_cache if graph_cache is not None else {}
+    name = os.path.basename(reference_path)
+    rows = []
+    for t, frame in enumerate(ref_frames):
+        vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
+        lr = torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device) if low_frames is not None else None
+        res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
+                              use_amp=use_amp, use_graph=use_graph, graph_cache=graphs)
+        values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
+        scan = name if len(ref_frames) == 1 else f"{name}[t={t}]"
+        for method, vals in zip(res, values):
+            rows.append({"scan": scan, "method": method, **dict(zip(METRIC_COLUMNS, (float(v) for v in vals)))})
+    return rows
+
+
+def format_table(title, rows):
+    lines = [title, f"{'method':18s} {'SSIM':>8s} {'PSNR':>8s} {'MSE':>12s} {'RMSE':>10s} {'MAE':>10s}"]
+    for r in rows:
+        lines.append(f"{r['method']:18s} {r['ssim']:8.4f} {r['psnr']:8.3f} {r['mse']:12.6g} {r['rmse']:10.6g} {r['mae']:10.6g}")
+    return "\n".join(lines)
+
+
+def mean_rows(rows):
+    methods = list(dict.fromkeys(r["method"] for r in rows))
+    return [{"scan": "mean", "method": m, **{k: float(np.mean([r[k] for r in rows if r["method"] == m])) for k in METRIC_COLUMNS}}
+            for m in methods]
+
+
+def main(args):
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+    try:
+        if args.cpu or not torch.cuda.is_available():
+            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
+        if args.batch_size < 1:
+            raise ValueError(f"--batch_size must be positive, got {args.batch_size}")
+        if args.input and len(args.reference) != 1:
+            raise ValueError("--input goes with exactly one --reference scan")
+        if args.data_range is not None and not args.data_range > 0:
+            raise ValueError(f"--data_range must be positive, got {args.data_range}")
+        from scripts.infer import find_best_checkpoint, load_model
+        device = torch.device("cuda")
+        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+        if args.checkpoint_path and os.path.exists(args.checkpoint_path):
+            ckpt = args.checkpoint_path
+        else:
+            ckpt = find_best_checkpoint(args.checkpoint_dir, args.model_type)
+        logger.info(f"Checkpoint: {ckpt}")
+        model = load_model(args.model_type, ckpt, device, base_filters=args.base_filters)
+        rows, graphs = [], {}
+        for path in args.reference:
+            scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
+                                   not args.no_graph, device, graphs)
+            for scan in dict.fromkeys(r["scan"] for r in scan_rows):
+                print(format_table(scan, [r for r in scan_rows if r["scan"] == scan]))
+            rows += scan_rows
+        means = mean_rows(rows)
+        print(format_table(f"mean over {len(set(r['scan'] for r in rows))} scan(s)", means))
+        if args.output_csv:
+            os.makedirs(os.path.dirname(os.path.abspath(args.output_csv)), exist_ok=True)
+            with open(args.output_csv, "w", newline="") as f:
+                wr = csv.DictWriter(f, fieldnames=CSV_COLUMNS)
+                wr.writeheader()
+                for r in rows + means:
+                    wr.writerow({k: r[k] for k in CSV_COLUMNS})
+            logger.info(f"Saved {len(rows) + len(means)} rows to {args.output_csv}")
+        return 0
+    except Exception as e:
+        logger.error(f"Error during volume evaluation: {e}")
+        return 1
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Evaluate x2 volume enhancement against interpolation baselines (extension)")
+    p.add_argument("--reference", type=str, nargs="+", required=True, help="ground-truth scan(s): single-file NIfTI-1, 3-D or 4-D")
+    p.add_argument("--input", type=str, default=None,
+                   help="low-resolution scan of the one --reference (half its extents on the doubled axes); default: the mean over pairs")
+    p.add_argument("--checkpoint_dir", type=str, default="./checkpoints")
+    p.add_argument("--checkpoint_path", type=str, default=None)
+    p.add_argument("--model_type", type=str, choices=["unet"], default="unet")
+    p.add_argument("--base_filters", type=int, default=64)
+    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    p.add_argument("--use_amp", action="store_true", help="fp16 MFMA compute (the reference's autocast)")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--isotropic", action="store_true", help="double all three axes (the three-plane blend of infer_volume.py --isotropic)")
+    g.add_argument("--axis", type=int, choices=[0, 1, 2], default=2, help="slices are taken across this axis; the two others are doubled")
+    p.add_argument("--data_range", type=float, default=None, help="R of SSIM's constants and of PSNR; default: max - min of each reference volume")
+    p.add_argument("--batch_size", type=int, default=16, help="slices per forward")
+    p.add_argument("--no_graph", action="store_true", help="do not replay the forward of full batches as a HIP graph")
+    p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
+    return p.parse_args(argv)
+
+
+if __name__ == "__main__":
+    sys.exit(main(parse_args()))
