@@ -187,11 +187,6 @@ int mrisr_norm_blend(int dtype, const void* x0, const float* scale0, const float
  * tensor this evaluates nn.Upsample -> nn.Conv2d(1x1) (unet_model.py:71-72) as conv -> upsample.           */
 int mrisr_upsample2_stats(int dtype, const void* z_low, void* z, double* stats, int N, int h, int w, int C,
                           int groups, void* stream);
-/* The same pair in ONE launch for 16-bit storage: z [N][2h][2w][Cout] = bilinear x2 of conv1x1(LeakyReLU(x*scale+shift)) and
- * the GroupNorm statistics of z, the low-resolution tensor staying in LDS (csrc/up_fused.hip).  x [N][h][w][Cin] raw,
- * scale / shift [N][Cin], wpacked = mrisr_pack_weights image of the (Cout,Cin,1,1) weight; Cin % 32 == 0, Cout % 64 == 0.   */
-int mrisr_up_conv1x1_fused(int dtype, const void* x, const float* scale, const float* shift, const void* wpacked, void* z,
-                           double* stats, int N, int h, int w, int Cin, int Cout, int groups, void* stream);
 /* adjoint of the above interpolation: dz [N][2h][2w][C] -> dz_low [N][h][w][C]                              */
 int mrisr_upsample2_adjoint(int dtype, const void* dz, void* dz_low, int N, int h, int w, int C, void* stream);
 
@@ -230,7 +225,7 @@ typedef struct {
 /* alpha_slots (optional, 256 zeroed floats; first consumer plain, blend_alpha set): receives partial sums of
  * (first consumer's unweighted gradient) * activation; mrisr_act_bwd_finalize turns them into
  * dalpha += alpha_sign * sigmoid'(alpha) * sum  (+1 for the sigmoid(alpha) branch, -1 for the other; the two branches'
- * terms add up to unet_model.py:206-207's dL/dalpha, so mrisr_blend_alpha_grad's extra pass is not needed).      */
+ * terms add up to unet_model.py:206-207's dL/dalpha: no extra pass over the activations).                         */
 int mrisr_act_bwd_reduce(int dtype, const void* x, const float* scale, const float* shift,
                          const float* meanrstd, int nconsumers, const mrisr_consumer* consumers,
                          const float* blend_alpha, void* g, float* red, float* alpha_slots, int N, int H, int W,
@@ -306,11 +301,6 @@ int mrisr_act_bwd_blend_apply(int dtype, const void* da, const mrisr_blend_branc
                               void* dx_ps, void* dx_bil, float* dbias, int N, int H, int W, int C, void* stream);
 /* out[C] += sum over pixels of x[npix][C]  (bias gradient of nn.Conv2d(bias=True), unet_model.py:101) */
 int mrisr_channel_sum(int dtype, const void* x, float* out, size_t npix, int C, void* stream);
-/* dalpha += sigmoid'(alpha) * sum da * (act0 - act1)   (unet_model.py:206-207)               */
-int mrisr_blend_alpha_grad(int dtype, const void* da, const void* x0, const float* scale0,
-                           const float* shift0, const void* x1, const float* scale1,
-                           const float* shift1, const float* alpha, float* dalpha, int N, int H,
-                           int W, int C, void* stream);
 
 /* ---- output head: GN+LReLU -> conv1x1(C->1)+bias -> sigmoid (unet_model.py:172,211) -------- */
 int mrisr_head_forward(int dtype, const void* x, const float* scale, const float* shift,
@@ -397,9 +387,6 @@ int mrisr_adam_step(float* p, const float* g, float* m, float* v, size_t n, floa
 int mrisr_adam_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int* step_device, float grad_mul,
                         const float* loss_scale_device, const float* found_inf_device, void* stream);
-
-/* ---- layout helpers ----------------------------------------------------------------------- */
-int mrisr_cast(int src_dtype, const void* src, int dst_dtype, void* dst, size_t n, void* stream);
 
 /* ---- inference pre / post-processing on the device (scripts/infer.py:97-130, 276, 331) ---- */
 /* hist[batch][256] += histogram of batch 8-bit images of pixels_per_image bytes each (zero it first).               */

@@ -98,7 +98,6 @@ SIGNATURES = {
     "mrisr_norm_upsample2": (_i, [_i, _vp, _fp, _fp, _vp, _i, _i, _i, _i, _vp]),
     "mrisr_norm_blend": (_i, [_i, _vp, _fp, _fp, _vp, _fp, _fp, _fp, _vp, _i, _i, _i, _i, _vp]),
     "mrisr_upsample2_stats": (_i, [_i, _vp, _vp, _dp, _i, _i, _i, _i, _i, _vp]),
-    "mrisr_up_conv1x1_fused": (_i, [_i, _vp, _fp, _fp, _vp, _vp, _dp, _i, _i, _i, _i, _i, _i, _vp]),
     "mrisr_upsample2_adjoint": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mrisr_act_bwd_reduce": (_i, [_i, _vp, _fp, _fp, _fp, _i, C.POINTER(Consumer), _fp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
     "mrisr_act_bwd_finalize": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _d, _fp, _fp, _fp, _f, _vp]),
@@ -117,7 +116,6 @@ SIGNATURES = {
     "mrisr_act_bwd_blend_apply": (_i, [_i, _vp, C.POINTER(BlendBranch), C.POINTER(BlendBranch), _fp, C.POINTER(GnBwdFin),
                                        C.POINTER(GnBwdFin), _vp, _vp, _fp, _i, _i, _i, _i, _vp]),
     "mrisr_channel_sum": (_i, [_i, _vp, _fp, _sz, _i, _vp]),
-    "mrisr_blend_alpha_grad": (_i, [_i, _vp, _vp, _fp, _fp, _vp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "mrisr_head_forward": (_i, [_i, _vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "mrisr_head_backward": (_i, [_i, _vp, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "mrisr_head_forward_multi": (_i, [_i, _vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
@@ -144,7 +142,6 @@ SIGNATURES = {
     "mrisr_u8_to_unit_f32": (_i, [_vp, _fp, _sz, _vp]),
     "mrisr_augment_geo_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _dp, _vp]),
     "mrisr_augment_finish_u8": (_i, [_vp, _fp, _i, _sz, _vp, _dp, _vp]),
-    "mrisr_cast": (_i, [_i, _vp, _i, _vp, _sz, _vp]),
     "mrisr_lowfield_dirichlet": (_i, [_i, _d, _fp, _fp]),
     "mrisr_lowfield_workspace_bytes": (_sz, [_i, _i, _i]),
     "mrisr_lowfield_simulate": (_i, [_vp, _i, _i, _i, _d, _fp, _fp, _fp, _fp, _f, _fp, _fp, _vp, _vp, _vp, _fp, _vp]),
@@ -164,7 +161,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 311      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 312      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

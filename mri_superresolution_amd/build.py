@@ -17,10 +17,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(os.path.dirname(HERE), "build", "mrisr")
 LIB = os.path.join(HERE, "libmrisr.so")
-SOURCES = ["api.cpp", "conv_fwd.hip", "conv_ring.hip", "conv_pc.hip", "conv1x1.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_upadj.hip", "norm.hip", "up_fused.hip", "head_stem.hip", "loss.hip", "optim.hip", "vgg.hip", "image.hip", "evalops.hip", "lowfield.hip", "percentile.hip", "resample.hip", "volume_blend.hip", "volume_eval.hip", "volume_metrics.hip"]
+SOURCES = ["api.cpp", "conv_fwd.hip", "conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_pack.hip", "conv_ring.hip", "conv_pc.hip", "conv1x1.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_upadj.hip", "norm.hip", "head_stem.hip", "loss.hip", "optim.hip", "vgg.hip", "image.hip", "evalops.hip", "lowfield.hip", "percentile.hip", "resample.hip", "volume_blend.hip", "volume_eval.hip", "volume_metrics.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
-# conv_fwd.hip: no SLP vectorisation - it turns the epilogue's statistics into v_pk_*_f32 ops plus register shuffles, and
+# conv_igemm_*.hip (the classic forward kernel) and conv_pack.hip (the packers, once in one file with it): no SLP
+# vectorisation - it turns the epilogue's statistics into v_pk_*_f32 ops plus register shuffles, and
 # packed fp32 ops issue at half speed next to the other wave's MFMA block (measured with the phase profile)
 # image.hip: no fma contraction - it restates numpy / PIL float32 arithmetic operation by operation (HIP's __fmul_rn /
 # __fadd_rn are plain operators, and under the default -ffp-contract=fast  a + alpha * (b - a)  becomes one fma: PIL's
@@ -31,7 +32,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # resample.hip: likewise (the uint8 epilogue; the tap sums are written as fmaf())
 # volume_blend.hip: likewise (the through-plane interpolation and the mean of the planes: product, product, sum, division)
 # volume_eval.hip: likewise (pair sums and interpolation taps of the volume baselines: every product and sum rounded on its own)
-FILE_FLAGS = {"conv_fwd.hip": ["-fno-slp-vectorize"], "image.hip": ["-ffp-contract=off"], "evalops.hip": ["-ffp-contract=off"],
+FILE_FLAGS = {**{f: ["-fno-slp-vectorize"] for f in ("conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_pack.hip")},
+              "image.hip": ["-ffp-contract=off"], "evalops.hip": ["-ffp-contract=off"],
               "lowfield.hip": ["-ffp-contract=off"], "percentile.hip": ["-ffp-contract=off"], "resample.hip": ["-ffp-contract=off"],
               "volume_blend.hip": ["-ffp-contract=off"], "volume_eval.hip": ["-ffp-contract=off"]}
 
@@ -56,7 +58,7 @@ def _compile(src, force):
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    with ThreadPoolExecutor(max_workers=4) as ex:
+    with ThreadPoolExecutor(max_workers=8) as ex:
         results = list(ex.map(lambda s: _compile(s, force), SOURCES))
     objs = [o for o, _ in results]
     if force or any(c for _, c in results) or not os.path.exists(LIB):

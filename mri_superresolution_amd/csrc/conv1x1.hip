@@ -127,11 +127,7 @@ __global__ __launch_bounds__(kC1Threads) void conv1x1_gemm_kernel(const ConvPara
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-#ifndef MRISR_KERNEL_ONLY
 bool conv1x1_gemm_eligible(const mrisr_conv_desc* d, const ConvParams& p) {
-#ifdef MRISR_NO_C1X1
-    return false;
-#endif
     if (d->dtype == MRISR_F32 || d->ksize != 1 || !d->wpacked) return false;
     if (d->Cin % 32 || d->Cout % 64 || d->Cin > 2048) return false;
     if (d->out_mode != MRISR_OUT_PLAIN || d->relu_mask || d->relu_out || d->bias || d->stats) return false;
@@ -176,4 +172,3 @@ int launch_conv1x1_gemm(const mrisr_conv_desc* d, const ConvParams& p, hipStream
     if (d->dtype == MRISR_BF16) return launch_c1<bf16_t>(d, p, s);
     return launch_c1<f16_t>(d, p, s);
 }
-#endif

@@ -24,14 +24,6 @@ __device__ __forceinline__ int halo_off(int row, int chunk) { return row * kHalo
 // forward kernel LDS budget: two halo tiles of kMaxHaloIter*64 rows (every commit slot has a row, so the LDS stores
 // need no bounds predicate) + the weight images + BN floats of bias
 static inline size_t conv_halo_bytes() { return (size_t)kMaxHaloIter * 64 * kHaloRowBytes; }
-// bf16 plain epilogue staging: 4 waves x 32 pixel rows x (64 couts x 2 B + 16 B pad)
-static inline size_t conv_stage_bytes() {
-#ifdef MRISR_STAGED_STORES
-    return 4 * 32 * (64 * 2 + 16);
-#else
-    return 0;
-#endif
-}
 // LDS-DMA halo variant (sources stored as-is: input gradients, materialised activations, VGG): four halo buffers (two
 // per half, double-buffered) of 340 rows x 64 B - rows are 64 B with the 16-B chunk position XOR-swizzled by
 // (row >> 2) & 3 like the weight image (an LDS-DMA piece is 1 KiB of consecutive LDS bytes, so rows cannot be padded)
@@ -39,7 +31,7 @@ constexpr int kDmaHaloRows = 340;     // max over the tile shapes: 10 x 34 (8x32
 constexpr int kDmaHaloBytes = kDmaHaloRows * 64;
 static inline size_t conv_halo_total(bool dma) { return dma ? 4 * (size_t)kDmaHaloBytes : 2 * conv_halo_bytes(); }
 static inline bool conv_weights_stationary(int nchunks, size_t wimg, bool dma = false) {
-    return nchunks * wimg + conv_halo_total(dma) + (64 + 128) * sizeof(float) + conv_stage_bytes() <= 159 * 1024;   // + bias, affine tables, staging
+    return nchunks * wimg + conv_halo_total(dma) + (64 + 128) * sizeof(float) <= 159 * 1024;   // + bias, affine tables
 }
 // wgrad kernel variant: 0 = generic, 1 / 2 / 4 = FAST with that k-step interleave (bf16 3x3 plain loader, 8x32 tiles,
 // every channel block of the launch holding the same number of 32x32 fragment pairs)
@@ -104,7 +96,7 @@ struct ConvParams {
     int cus;          // CUs the persistent grid is sized for (mrisr_conv_desc.cu_limit, else all)
     int dbg;          // tuning builds only (-DMRISR_TUNING, env MRISR_DEBUG): 1 no stores, 2 no LDS commit, 4 no global loads, 8 no MFMA
 };
-// Ablation bits exist in tuning builds only (tools/build_prof.sh): the product library never reads the environment
+// Ablation bits exist in tuning builds only (tools/build_src_variant.sh ... -DMRISR_TUNING): the product library never reads the environment
 // and compiles every `DBG(p) & bit` test away.
 #ifdef MRISR_TUNING
 #define DBG(p) ((p).dbg)
@@ -384,6 +376,15 @@ __device__ __forceinline__ void stage_halo(char* lds_halo, const HaloGeom<SPATIA
             if (BATCH < kMaxHaloIter) __builtin_amdgcn_sched_barrier(0);
         }
     }
+}
+
+constexpr int kEpiMask = 2;   // template-only epilogue kind of the classic forward kernel: plain store gated by relu_mask > 0 (VGG dgrad)
+// every source stored as-is and a plain (single / concat) loader: the halo tile can go global -> LDS by LDS-DMA
+static inline bool conv_dma_halo(const ConvParams& p, int spatial) {
+    if (spatial != MRISR_SP_NONE || p.combine == MRISR_COMBINE_BLEND) return false;
+    for (int s = 0; s < p.nsrc; ++s)
+        if (p.src[s].mode != MRISR_SRC_RAW) return false;
+    return true;
 }
 
 // tile shape for a W-wide image: TH*TW = 256

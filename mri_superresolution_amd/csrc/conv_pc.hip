@@ -40,9 +40,7 @@ __device__ unsigned long long g_pc_cycles[8][12];
 #define PPT_MARK(k)
 #define PPT_DUMP()
 #endif
-#ifndef MRISR_PC_AD
-#define MRISR_PC_AD 3        // weight-fragment prefetch distance (fragments)
-#endif
+constexpr int kPcAD = 3;         // weight-fragment prefetch distance (fragments)
 
 typedef __attribute__((ext_vector_type(2))) float pc_f32x2;      // pairs for v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32
 
@@ -523,7 +521,7 @@ __global__ __launch_bounds__(pc_threads(BLEND), 2) void conv_pc_kernel(const Con
         const char* wl = buf + a_off;
         // Fragment pipeline (conv_ring.hip): pixel fragments of tap t+1 and weight fragments up to AD steps ahead are requested
         // before the MFMAs that use the current ones are issued
-        constexpr int AD = MRISR_PC_AD;
+        constexpr int AD = kPcAD;
         frag_t af[AD + 1], bf[2][MI];
         auto load_b = [&](int tap, int set) {
             const int ky = tap / 3, kx = tap % 3;
@@ -569,7 +567,6 @@ __global__ __launch_bounds__(pc_threads(BLEND), 2) void conv_pc_kernel(const Con
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-#ifndef MRISR_KERNEL_ONLY
 #ifdef MRISR_PC_PT
 extern "C" int mrisr_debug_phase_reset() {
     static unsigned long long zeros[96];
@@ -584,9 +581,6 @@ extern "C" int mrisr_debug_phase_cycles(unsigned long long* out96) {
 // 0 = no, 4 = 128-channel blocks, 2 = 64-channel blocks on tall tiles, 1 = the narrow blend variant (Cout = 32, two activated
 // sources blended by the staging waves)
 int conv_pc_kind(const mrisr_conv_desc* d, const ConvParams& p) {
-#ifdef MRISR_NO_PC
-    return 0;
-#endif
     if (!d->wpacked_ring) return 0;
     if (d->dtype == MRISR_F32 || d->ksize != 3 || d->Cin % 16) return 0;
     if (d->out_mode != MRISR_OUT_PLAIN || d->relu_mask) return 0;
@@ -602,9 +596,6 @@ int conv_pc_kind(const mrisr_conv_desc* d, const ConvParams& p) {
     const int tiles = d->N * (d->H / 8) * (d->W / 32);
     if (d->combine == MRISR_COMBINE_CONCAT && d->Cout % kPcBN && d->Cout % 64 == 0) {
         // 64-channel blocks on tall tiles (16 x 32 pixels): the 64-channel layers and the input gradients that end in 64 channels
-#ifdef MRISR_NO_PC64
-        return 0;
-#endif
         if (d->H % 16) return 0;
         if (d->nsrc == 2 && (d->src[0].C % 16)) return 0;
         if (d->src[0].mode == MRISR_SRC_RAW && d->Cin < 128) return 0;  // (64 -> 64 input gradient at 256^2: 111 vs 101 us on the LDS-DMA kernel)
@@ -644,11 +635,7 @@ template <typename T>
 static int launch_pc_t(const mrisr_conv_desc* d, const ConvParams& cp, hipStream_t s) {
     const int kind = conv_pc_kind(d, cp);
     const int bn = kind == 1 ? 32 : kind == 2 ? 64 : kPcBN;
-#ifdef MRISR_PC_BLEND_SHORT
-    const bool tall_blend = false;
-#else
     const bool tall_blend = kind == 1 && d->H % 16 == 0;            // the blend variant on tall items: 10 % less halo per pixel
-#endif
     const int tr = (kind == 2 || tall_blend) ? 16 : 8;
     ConvParams p = cp;
     p.wpacked = d->wpacked_ring;
@@ -686,4 +673,3 @@ int launch_conv_pc(const mrisr_conv_desc* d, const ConvParams& cp, hipStream_t s
     if (d->dtype == MRISR_BF16) return launch_pc_t<bf16_t>(d, cp, s);
     return launch_pc_t<f16_t>(d, cp, s);
 }
-#endif

@@ -49,7 +49,7 @@ struct RingParams {
     int groups, relu_out;
 };
 
-// Ablation switches of tuning builds (tools/build_ring_variant.sh; results invalid by construction, timing only):
+// Ablation switches of tuning builds (tools/build_src_variant.sh NAME conv_ring.hip -DMRISR_RING_DBG=...; results invalid by construction, timing only):
 // 1 no DMA issue, 2 no MFMA, 4 no epilogue.  The product library is compiled with 0: every test folds away.
 #ifndef MRISR_RING_DBG
 #define MRISR_RING_DBG 0
@@ -64,9 +64,7 @@ __device__ unsigned long long g_ring_cycles[8][12];
 #define RPT_DECL
 #define RPT_MARK(k)
 #endif
-#ifndef MRISR_RING_AD
-#define MRISR_RING_AD 3      // weight-fragment prefetch distance (fragments), see the fragment pipeline
-#endif
+constexpr int kRingAD = 3;         // weight-fragment prefetch distance (fragments), see the fragment pipeline
 constexpr int kRingThreads = 512;
 constexpr int kRingHaloStages = 4;
 constexpr int kRingWeightStages = 2;
@@ -317,10 +315,7 @@ __global__ __launch_bounds__(kRingThreads, 2) void conv_ring_kernel(const RingPa
             dma_weight(0, 0, j);
         w_kc = p.nchunks > 1 ? 1 : 0;
     }
-#ifdef MRISR_RING_PRIO
-    // static priority for the younger half (waves 4-7 lose the arbitration to the older wave of their SIMD)
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
+    // (tried: s_setprio(1) for the younger waves 4-7, which lose the arbitration to the older wave of their SIMD; not kept)
     int ep1 = 0, ep2 = 0, ep3 = 0;     // 1 if this wave ran an epilogue (NST output stores) in the previous step / the two before it
 
     RPT_DECL
@@ -352,7 +347,7 @@ __global__ __launch_bounds__(kRingThreads, 2) void conv_ring_kernel(const RingPa
         // pipe cycles) is shorter than an LDS round trip with eight waves reading (~150-200 cycles): measured without
         // any DMA, 1.19 PFLOP/s at distance 1.  B: two sets, A: a ring of AD + 1 fragments - 16 + 4 (AD + 1) operand
         // registers beside the 128 accumulators.  One DMA per tap step is dealt out behind the reads.
-        constexpr int AD = MRISR_RING_AD;
+        constexpr int AD = kRingAD;
         frag_t af[AD + 1], bf[2][MI];
         auto load_b = [&](int tap, int set) {
             const int ky = tap / 3, kx = tap % 3;
@@ -416,7 +411,6 @@ __global__ __launch_bounds__(kRingThreads, 2) void conv_ring_kernel(const RingPa
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-#ifndef MRISR_KERNEL_ONLY
 #ifdef MRISR_RING_PT
 extern "C" int mrisr_debug_phase_reset() {
     static unsigned long long zeros[96];
@@ -450,9 +444,6 @@ static const void* ring_zeros() {
 // Does this launch take the ring kernel?  (p: filled by conv_fill_params.)  Static conditions + enough work items to fill
 // the persistent grid: a 16 x 32 tile per workgroup and one cout block of 128 means small planes leave CUs idle.
 bool conv_ring_eligible(const mrisr_conv_desc* d, const ConvParams& p) {
-#ifdef MRISR_NO_RING
-    return false;
-#endif
     if (!d->wpacked_ring) return false;
     if (mrisr_conv_ring_bn(d->dtype, d->Cout, d->Cin, d->ksize) != 128) return false;
     if (d->Cin < 256) return false;      // the ring pays from 256 input channels on (profiles/r03_ring_kernel.txt)
@@ -503,4 +494,3 @@ int launch_conv_ring(const mrisr_conv_desc* d, const ConvParams& cp, hipStream_t
     if (d->dtype == MRISR_BF16) return launch_ring_t<bf16_t>(d, cp, s);
     return launch_ring_t<f16_t>(d, cp, s);
 }
-#endif

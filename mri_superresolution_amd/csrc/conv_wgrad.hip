@@ -73,7 +73,6 @@ __global__ __launch_bounds__(kWgThreads, 2) void conv_wgrad_kernel(const ConvPar
     // land on XCD (linear id) % 8; the logical index (id % 8) * (G / 8) + id / 8 puts the channel-block pairs of one
     // k-slice - which all read the same dy / activation tiles - and the neighbouring slices behind one L2
     int bx = blockIdx.x, by = blockIdx.y;
-#ifndef MRISR_NO_XCD_REMAP
     {
         const int G = gridDim.x * gridDim.y;
         if ((G & 7) == 0) {
@@ -82,7 +81,6 @@ __global__ __launch_bounds__(kWgThreads, 2) void conv_wgrad_kernel(const ConvPar
             bx = lid - by * gridDim.x;
         }
     }
-#endif
     const int cib = bx % ncib, cob = bx / ncib;
     const int co0 = cob * BC, ci0 = cib * BC;
     const int total_tiles = p.N * p.tiles_y * p.tiles_x;
@@ -460,7 +458,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     if (tap < NTAPS && co < Cout && ci < Cin && s != 0.f) atomic_add_f32(dw + ((size_t)co * NTAPS + tap) * Cin + ci, s);
 }
 
-#ifndef MRISR_KERNEL_ONLY
 int conv_fill_params(const mrisr_conv_desc* d, ConvParams& p, const char* who);
 int num_cus();
 // conv_wgrad_rows.hip: the row-streaming producer / consumer kernel (16-bit, 3x3, 64 x 64 channel blocks)
@@ -557,4 +554,3 @@ extern "C" int mrisr_conv_wgrad(const mrisr_conv_desc* d, const void* dy, float*
     if (d->dtype == MRISR_F16) return dispatch_wgrad<f16_t>(p, d->src[0].spatial, d->ksize, s);
     return dispatch_wgrad<float>(p, d->src[0].spatial, d->ksize, s);
 }
-#endif  // MRISR_KERNEL_ONLY

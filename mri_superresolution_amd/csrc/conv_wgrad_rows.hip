@@ -104,10 +104,7 @@ __global__ __launch_bounds__(kWrThreads, 2) void conv_wgrad_rows_kernel(const Co
     // loops with the same barrier sequence, so that neither role's registers are live in the other's code (one loop with a
     // role branch keeps 144 accumulators AND 92 staging registers alive for every wave: 343 spills).
     if (!consumer) {
-#ifdef MRISR_WR_PRIO
-        // the staging waves are the younger ones of their SIMD and lose the issue arbitration to the MFMA wave
-        __builtin_amdgcn_s_setprio(MRISR_WR_PRIO);
-#endif
+        // (tried: s_setprio for these staging waves, the younger ones of their SIMD; not kept)
         // ------------------------------------------------------------------ producer (waves 4-7): 256 staging threads
         // Software pipeline per SLOT: while tile k is being multiplied, slot i of tile k+1 (requested one iteration ago)
         // is transformed and stored to LDS and the same registers immediately take the load of slot i of tile k+2 - every
@@ -417,7 +414,6 @@ __global__ __launch_bounds__(256) void wgrad_rows_reduce_kernel(const float* __r
     else if (s != 0.f) atomic_add_f32(d, s);
 }
 
-#ifndef MRISR_KERNEL_ONLY
 int num_cus();
 #ifdef MRISR_WR_PT
 extern "C" int mrisr_debug_phase_reset() {
@@ -431,9 +427,6 @@ extern "C" int mrisr_debug_phase_cycles(unsigned long long* out96) {
 
 // does mrisr_conv_wgrad take the row-streaming kernel for this descriptor?
 bool conv_wgrad_rows_ok(const mrisr_conv_desc* d) {
-#ifdef MRISR_NO_WGRAD_ROWS
-    return false;
-#endif
     if (d->dtype != MRISR_BF16 && d->dtype != MRISR_F16) return false;
     if (d->ksize != 3 || d->combine != MRISR_COMBINE_CONCAT) return false;
     if (d->Cout % 32 || d->Cin % 32 || d->H < 16 || d->W < 16) return false;
@@ -500,4 +493,3 @@ int launch_wgrad_rows(int dtype, ConvParams& p, size_t ws_floats, hipStream_t s)
     if (dtype == MRISR_BF16) return launch_wgrad_rows_d<bf16_t>(p, ws_floats, s);
     return launch_wgrad_rows_d<f16_t>(p, ws_floats, s);
 }
-#endif

@@ -1728,58 +1728,6 @@ extern "C" int mrisr_norm_blend(int dtype, const void* x0, const float* scale0, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// dalpha += sigmoid'(alpha) * sum da * (act0 - act1)        (unet_model.py:206-207)
-template <typename T>
-__global__ __launch_bounds__(256) void blend_alpha_grad_kernel(const T* __restrict__ da, const T* __restrict__ x0,
-                                                               const float* __restrict__ sc0, const float* __restrict__ sh0,
-                                                               const T* __restrict__ x1, const float* __restrict__ sc1,
-                                                               const float* __restrict__ sh1, const float* __restrict__ alpha,
-                                                               float* __restrict__ dalpha, int N, int HW, int C) {
-    constexpr int VEC = Vec16<T>::N;
-    const int nvec = C / VEC;
-    const size_t total = (size_t)N * HW * nvec;
-    float s = 0.f;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int cv = idx % nvec;
-        const size_t pix = idx / nvec;
-        const int n = pix / HW, c = cv * VEC;
-        const Vec16<T> d = load_vec16(da + pix * C + c), a = load_vec16(x0 + pix * C + c), b = load_vec16(x1 + pix * C + c);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const size_t k = (size_t)n * C + c + e;
-            s += d.get(e) * (lrelu(a.get(e) * sc0[k] + sh0[k]) - lrelu(b.get(e) * sc1[k] + sh1[k]));
-        }
-    }
-    __shared__ float part[4];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float sg = 1.f / (1.f + __expf(-alpha[0]));
-        atomic_add_f32(dalpha, (part[0] + part[1] + part[2] + part[3]) * sg * (1.f - sg));
-    }
-}
-
-extern "C" int mrisr_blend_alpha_grad(int dtype, const void* da, const void* x0, const float* scale0,
-                                      const float* shift0, const void* x1, const float* scale1, const float* shift1,
-                                      const float* alpha, float* dalpha, int N, int H, int W, int C, void* stream) {
-    if (!da || !x0 || !x1 || !scale0 || !shift0 || !scale1 || !shift1 || !alpha || !dalpha) MRISR_FAIL(MRISR_E_ARG, "blend_alpha_grad: null pointer");
-    const int vec = mrisr_vec(dtype);
-    if (C % vec) MRISR_FAIL(MRISR_E_SHAPE, "blend_alpha_grad: C %d", C);
-    const size_t total = (size_t)N * H * W * (C / vec);
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    if (dtype == MRISR_BF16)
-        blend_alpha_grad_kernel<bf16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const bf16_t*)da, (const bf16_t*)x0, scale0, shift0, (const bf16_t*)x1, scale1, shift1, alpha, dalpha, N, H * W, C);
-    else if (dtype == MRISR_F16)
-        blend_alpha_grad_kernel<f16_t><<<blocks, 256, 0, (hipStream_t)stream>>>((const f16_t*)da, (const f16_t*)x0, scale0, shift0, (const f16_t*)x1, scale1, shift1, alpha, dalpha, N, H * W, C);
-    else if (dtype == MRISR_F32)
-        blend_alpha_grad_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>((const float*)da, (const float*)x0, scale0, shift0, (const float*)x1, scale1, shift1, alpha, dalpha, N, H * W, C);
-    else MRISR_FAIL(MRISR_E_DTYPE, "blend_alpha_grad: dtype %d", dtype);
-    MRISR_CHECK_LAUNCH("blend_alpha_grad");
-    return MRISR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // out[c] += sum over pixels of x[pixel][c]   (bias gradient of nn.Conv2d(bias=True), unet_model.py:101)
 template <typename T>
 __global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ x, float* __restrict__ out, size_t npix,

@@ -95,26 +95,3 @@ extern "C" int mrisr_adam_step_amp(float* p, const float* g, float* m, float* v,
     MRISR_CHECK_LAUNCH("adam_step_amp(advance)");
     return MRISR_OK;
 }
-
-// ------------------------------------------------------------------------------------------------
-template <typename S, typename D>
-__global__ void cast_kernel(const S* __restrict__ s, D* __restrict__ d, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        d[i] = from_f32<D>(to_f32(s[i]));
-}
-
-extern "C" int mrisr_cast(int src_dtype, const void* src, int dst_dtype, void* dst, size_t n, void* stream) {
-    if (!src || !dst) MRISR_FAIL(MRISR_E_ARG, "cast: null pointer");
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipStream_t s = (hipStream_t)stream;
-    if (src_dtype == MRISR_F32 && dst_dtype == MRISR_BF16) cast_kernel<float, bf16_t><<<blocks, 256, 0, s>>>((const float*)src, (bf16_t*)dst, n);
-    else if (src_dtype == MRISR_BF16 && dst_dtype == MRISR_F32) cast_kernel<bf16_t, float><<<blocks, 256, 0, s>>>((const bf16_t*)src, (float*)dst, n);
-    else if (src_dtype == MRISR_F32 && dst_dtype == MRISR_F32) cast_kernel<float, float><<<blocks, 256, 0, s>>>((const float*)src, (float*)dst, n);
-    else if (src_dtype == MRISR_BF16 && dst_dtype == MRISR_BF16) cast_kernel<bf16_t, bf16_t><<<blocks, 256, 0, s>>>((const bf16_t*)src, (bf16_t*)dst, n);
-    else if (src_dtype == MRISR_F32 && dst_dtype == MRISR_F16) cast_kernel<float, f16_t><<<blocks, 256, 0, s>>>((const float*)src, (f16_t*)dst, n);
-    else if (src_dtype == MRISR_F16 && dst_dtype == MRISR_F32) cast_kernel<f16_t, float><<<blocks, 256, 0, s>>>((const f16_t*)src, (float*)dst, n);
-    else if (src_dtype == MRISR_F16 && dst_dtype == MRISR_F16) cast_kernel<f16_t, f16_t><<<blocks, 256, 0, s>>>((const f16_t*)src, (f16_t*)dst, n);
-    else MRISR_FAIL(MRISR_E_DTYPE, "cast: dtypes %d -> %d", src_dtype, dst_dtype);
-    MRISR_CHECK_LAUNCH("cast");
-    return MRISR_OK;
-}

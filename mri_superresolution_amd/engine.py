@@ -404,8 +404,8 @@ class UNetEngine:
             d.wpacked = self._packed[(layer.name, dt, 0)].data_ptr()
             d.wpacked_ring = L.ptr(self._packed.get((layer.name, dt, 0, "ring")))
             d.bias = params[layer.name + ".bias"].data_ptr() if layer.bias else None
-            # (the decoder's conv1x1 + bilinear x2 + statistics as ONE launch, csrc/up_fused.hip, is not scheduled: every output
-            # tile recomputes its 10 x 10 low-resolution patch and re-reads it per 64 output channels - the GEMM of
+            # (the decoder's conv1x1 + bilinear x2 + statistics as ONE launch was measured slower and removed: every output tile
+            # recomputed its 10 x 10 low-resolution patch and re-read it per 64 output channels - the GEMM of
             # csrc/conv1x1.hip + mrisr_upsample2_stats is faster)
             if layer.post_up:
                 zlow = torch.empty((N, vh, vw, oC), dtype=dtype, device=dev)

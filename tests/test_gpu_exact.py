@@ -42,7 +42,7 @@ Smallest qualifying shapes (N, Cin, Cout, H, W; cu_limit shrinks the grid the oc
 ring (1,256,128,16,32) at cu_limit 1; producer/consumer 128-channel blocks (1,64,128,8,32) at 1; 64-channel tall tiles
 (1,32,64,16,32) at 1; the 32-channel blend (1,32,32,8,32) at 1; 1x1 GEMM (1,32,64,8,16) (no occupancy rule: one 128-pixel tile).
 
-Not here (weights that are not dyadic): the bilinear x2 (MRISR_SP_UP2, mrisr_conv_upadj, mrisr_up_conv1x1_fused), the sigmoid
+Not here (weights that are not dyadic): the bilinear x2 (MRISR_SP_UP2, mrisr_conv_upadj), the sigmoid
 head, the GroupNorm backward.
 """
 import ctypes as C

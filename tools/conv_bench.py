@@ -142,7 +142,7 @@ def main():
             tot[kind] = tot.get(kind, 0.0) + us
             line += f"| {kind} {us:8.1f} us {flops / us / 1e6:7.1f} TF/s {vb.value.decode().replace('conv_', '').replace('_kernel', '')} "
             if hasattr(L.load(), "mrisr_debug_phase_cycles"):
-                # profiling build (tools/build_prof.sh, MRISR_LIB=...): s_memtime cycles of the middle workgroup's
+                # profiling build (tools/build_src_variant.sh with -DMRISR_PHASE_TIMING, MRISR_LIB=...): s_memtime cycles of the middle workgroup's
                 # two halves in the last launch: load wait, commit, issue, epilogue, barrier (vector side), MFMA block,
                 # barrier (matrix side), loop overhead
                 buf = (C.c_ulonglong * 96)()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase profile of the forward/dgrad convolution kernel inside the REAL training step (profiling build:
-tools/build_prof.sh, run with MRISR_LIB=.../libmrisr_prof.so): s_memtime cycles per tick part, summed over every
+tools/build_src_variant.sh, run with MRISR_LIB=.../libmrisr_prof.so): s_memtime cycles per tick part, summed over every
 conv_igemm launch of `--steps` steps (middle workgroup of each launch), printed per wave as shares of the total."""
 import argparse
 import ctypes as C

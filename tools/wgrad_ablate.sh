@@ -1,4 +1,5 @@
 #!/bin/bash
+# needs the ablation build:  tools/build_src_variant.sh tune conv_fwd.hip conv_igemm_bf16.hip conv_igemm_f16.hip conv_igemm_f32.hip conv_wgrad.hip -DMRISR_TUNING
 export MRISR_LIB=$PWD/mri_superresolution_amd/libmrisr_tune.so
 for d in 0 8 2 4 6 1 9 14 10; do
   echo "== MRISR_DEBUG=$d"
