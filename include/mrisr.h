@@ -567,6 +567,39 @@ int mrisr_f32_volume_metrics(const float* a, const float* b, int X, int Y, int Z
 /* sums[3] of mrisr_f32_volume_metrics -> out[5] doubles: ssim, mse, rmse, mae, psnr with psnr = mse < 1e-10 ? 100 :
  * 10 log10(val_range^2 / mse); the voxel count X Y Z is formed in double.  No host read-back.                              */
 int mrisr_volume_metrics_finalize(const double* sums, int X, int Y, int Z, float val_range, double* out, void* stream);
+/* The same pass with a foreground mask (uint8, (X, Y, Z), non-zero = foreground), still one launch that reads a and b once.
+ * sums7[7] (double, accumulated; zero it first): [0..2] as sums of mrisr_f32_volume_metrics, over the whole volume; [3..5] the
+ * same three over the mask's voxels (the SSIM map itself is unchanged - full windows, zero padding; only the sum is masked);
+ * [6] the number of mask voxels (exact below 2^53).  Errors as mrisr_f32_volume_metrics.                                     */
+int mrisr_f32_volume_metrics_masked(const float* a, const float* b, const uint8_t* mask, int X, int Y, int Z, float val_range,
+                                    float sigma, int window_size, double* sums7, void* stream);
+/* sums7 -> out11[11] doubles: ssim, mse, rmse, mae, psnr of the whole volume, the same five over the mask's voxels (every mean a
+ * division by sums7[6]: an empty mask gives five NaNs, without a host check), then the count.  No host read-back.            */
+int mrisr_volume_metrics_finalize_masked(const double* sums7, int X, int Y, int Z, float val_range, double* out11, void* stream);
+
+/* ---- foreground masks for the volume evaluation (extension; csrc/volume_mask.hip): an exact Otsu threshold on the device and 3-D
+ *      binary morphology.  A mask is a uint8 volume (X, Y, Z) in C order, non-zero = foreground. -------------------------------- */
+/* bytes of device workspace of mrisr_f32_volume_otsu_mask (any volume).  The contents need no initialisation; after the call the
+ * first 256 64-bit words hold the histogram counts n_0 .. n_255 (all zero for a degenerate range).                            */
+size_t mrisr_f32_volume_otsu_workspace_bytes(void);
+/* mask_out = bin(v) > t*, with lo, hi = min, max of vol; scale = 256.f / (hi - lo); bin(v) = min(255, (int)((v - lo) * scale)) in
+ * float32, one rounded operation at a time; n_k = voxels in bin k (exact, 64-bit); w_t, m_t = sums of n_k and k n_k over k <= t
+ * (int64), N = w_255, M = m_255; for t in 0..254 with 0 < w_t < N: mu0 = m_t / w_t, mu1 = (M - m_t) / (N - w_t), d = mu1 - mu0,
+ * s_t = (w_t (N - w_t)) (d d) in double, in this order; t* = the smallest t with the largest s_t.  hi == lo, or hi - lo or scale
+ * not finite in float32: t* = -1 and mask_out is all ones.  The mask values are 0 and 1.
+ * stats[4] doubles: lo, hi, t*, the foreground count (the threshold in intensity units is lo + (t* + 1) (hi - lo) / 256).
+ * Enqueues 5 launches on stream, clears what it needs of the workspace itself, never synchronises with the host (HIP-graph
+ * capturable).  The input must be finite (not checked).
+ * MRISR_E_ARG: null or misaligned pointer; MRISR_E_SHAPE: an extent below 1 or above 32767.                                    */
+int mrisr_f32_volume_otsu_mask(const float* vol, int X, int Y, int Z, uint8_t* mask_out, double* stats, void* workspace,
+                               void* stream);
+#define MRISR_MORPH_DILATE 0        /* dst[p] = max of src over the box |dx|, |dy|, |dz| <= radius clipped to the volume         */
+#define MRISR_MORPH_ERODE 1         /* dst[p] = min over the same clipped box (voxels outside the volume are ignored in both)    */
+/* One separable pass per axis (z: src -> dst, y: dst -> tmp, x: tmp -> dst); radius 0 copies src to dst and tmp may be NULL.
+ * src, dst and tmp are three different buffers of X Y Z bytes.  Closing = ERODE of DILATE.  No host synchronisation.
+ * MRISR_E_ARG: null pointer, two of the buffers equal, unknown op; MRISR_E_SHAPE: an extent below 1 or above 32767, radius
+ * outside 0..4.                                                                                                                 */
+int mrisr_u8_volume_morph(const uint8_t* src, int X, int Y, int Z, int radius, int op, uint8_t* dst, uint8_t* tmp, void* stream);
 
 #ifdef __cplusplus
 }

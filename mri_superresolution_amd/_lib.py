@@ -18,6 +18,7 @@ OUT_PLAIN, OUT_PIXEL_SHUFFLE2 = 0, 1
 UP2_BILINEAR, UP2_BICUBIC, UP2_SHARP_BILINEAR = 0, 1, 2      # MRISR_UP2_*: method of mrisr_u8_upscale2
 WINDOW_F32, WINDOW_I16 = 0, 1      # MRISR_WINDOW_*: out_dtype of mrisr_f32_window_restore
 VOLBLEND_SET, VOLBLEND_ADD, VOLBLEND_FINISH = 0, 1, 2      # MRISR_VOLBLEND_*: mode of mrisr_f32_volume_up2_blend
+MORPH_DILATE, MORPH_ERODE = 0, 1      # MRISR_MORPH_*: op of mrisr_u8_volume_morph
 RESAMPLE_LINEAR, RESAMPLE_CUBIC, RESAMPLE_AREA, RESAMPLE_LANCZOS4 = 1, 2, 3, 4      # MRISR_RESAMPLE_*: method of mrisr_resample_taps
 PACK_RING = 256      # MRISR_PACK_RING: OR into transpose_flip for the ring weight layout (csrc/conv_ring.hip)
 PACK_UPADJ = 512     # MRISR_PACK_UPADJ: the W^T image of mrisr_conv_upadj (csrc/conv_upadj.hip)
@@ -158,10 +159,15 @@ SIGNATURES = {
     "mrisr_f32_volume_up2": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _vp]),
     "mrisr_f32_volume_metrics": (_i, [_fp, _fp, _i, _i, _i, _f, _f, _i, _dp, _vp]),
     "mrisr_volume_metrics_finalize": (_i, [_dp, _i, _i, _i, _f, _dp, _vp]),
+    "mrisr_f32_volume_metrics_masked": (_i, [_fp, _fp, _vp, _i, _i, _i, _f, _f, _i, _dp, _vp]),
+    "mrisr_volume_metrics_finalize_masked": (_i, [_dp, _i, _i, _i, _f, _dp, _vp]),
+    "mrisr_f32_volume_otsu_workspace_bytes": (_sz, []),
+    "mrisr_f32_volume_otsu_mask": (_i, [_fp, _i, _i, _i, _vp, _dp, _vp, _vp]),
+    "mrisr_u8_volume_morph": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 312      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 313      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

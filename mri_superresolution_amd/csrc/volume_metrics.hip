@@ -20,6 +20,13 @@
 //             an SSIM term, summed in double.
 // Two barriers per plane.  Block partial sums: wave shuffle, then one double atomic per block and quantity, as loss.hip.
 //
+// Masked form (mrisr_f32_volume_metrics_masked; the kernel is a template on kMasked, every addition under if constexpr, so that the
+// kMasked = false instantiation is the kernel it was): a uint8 mask volume is read as well and seven sums are kept - the three above
+// over the whole volume, the same three over the mask's voxels, and the number of mask voxels.  |a - b| and (a - b)^2 take the
+// mask byte of the staged interior voxel (fetched one plane ahead with a and b, for planes of the chunk only); the SSIM term takes
+// the byte of the voxel it belongs to, (x - h, gy + o, gz), with one direct global read per output issued before the filter passes.
+// The SSIM map itself is the unmasked one (full windows, zero padding): only the averaging is masked.
+//
 // LDS banks (ds_read_b32 / ds_write_b32: bank = dword address mod 32... conflicts within a 32-lane half): the z pass puts
 // lane (row r, segment s) on dword r * P + 4 s + k; with the pitch P = 1 (mod 4) the four rows of a half wave start on
 // 4 different residues mod 4 and the 32 lanes on 32 different banks.  The y pass reads 32 consecutive dwords per half wave.
@@ -48,17 +55,32 @@ static GaussWin3 make_window(float sigma, int win) {   // losses.py:10-18 in fp3
     return w;
 }
 
-template <int kWin>
+// One SSIM term from the five filtered moments.  Every rounding is spelled out (no contraction left to the compiler), so that
+// the masked and the unmasked instantiation of the kernel form bit-equal terms whatever else surrounds this code: one product
+// is fused - mu1^2 into mu1^2 + mu2^2, the form the compiler chose for this expression under -ffp-contract=fast before there
+// was a second instantiation - and every other product, difference and sum is rounded on its own.
+__device__ __forceinline__ float ssim_term(float mu1, float mu2, float e11, float e22, float e12, float c1, float c2) {
+#pragma clang fp contract(off)
+    const float mu1sq = mu1 * mu1, mu2sq = mu2 * mu2, mu12 = mu1 * mu2;
+    const float s11 = e11 - mu1sq, s22 = e22 - mu2sq, s12 = e12 - mu12;
+    const float A1 = 2.f * mu12 + c1, A2 = 2.f * s12 + c2, B1 = fmaf(mu1, mu1, mu2sq) + c1, B2 = s11 + s22 + c2;
+    return A1 * A2 / (B1 * B2);
+}
+
+// kMasked: mask (uint8, non-zero = foreground; the LAST parameter, so that the kernel arguments of the unmasked instantiation
+// sit where they always sat) is read as well and sums has 7 entries instead of 3 (see the top of the file)
+template <int kWin, bool kMasked>
 __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __restrict__ a, const float* __restrict__ b, int X, int Y, int Z,
                                                              int chunk, float c1, float c2, const GaussWin3 win,
-                                                             double* __restrict__ sums) {
+                                                             double* __restrict__ sums, const uint8_t* __restrict__ mask) {
+    constexpr int kSums = kMasked ? 7 : 3;
     constexpr int kH = kWin / 2, kRows = kTY + 2 * kH, kCols = kTZ + 2 * kH;
     constexpr int kP = (kCols + 3) / 4 * 4 + 1;                    // 1 (mod 4): see above
     constexpr int kElems = kRows * kCols, kLoads = (kElems + 255) / 256;
     static_assert(kRows * (kTZ / 4) <= 256, "one z-pass segment per thread");
     __shared__ float ta[kRows * kP], tb[kRows * kP];
     __shared__ __attribute__((aligned(16))) float hz[5][kRows][kTZ];
-    __shared__ double part[4][3];
+    __shared__ double part[4][kSums];
     const int t = threadIdx.x;
     const int z0 = blockIdx.x * kTZ, y0 = blockIdx.y * kTY;
     const int x0 = blockIdx.z * chunk, x1 = min(x0 + chunk, X);
@@ -78,6 +100,7 @@ __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __rest
         interior[l] = in && r >= kH && r < kH + kTY && c >= kH && c < kH + kTZ;
     }
     float ra[kLoads], rb[kLoads];
+    uint8_t rm[kMasked ? kLoads : 1];                              // mask bytes of the interior voxels of a plane of the chunk
     auto fetch = [&](int x) {
         const bool plane = x < X;
         const size_t base = (size_t)(plane ? x : 0) * Y * Z;
@@ -86,6 +109,7 @@ __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __rest
             const bool in = plane && poff[l] >= 0;
             ra[l] = in ? a[base + poff[l]] : 0.f;
             rb[l] = in ? b[base + poff[l]] : 0.f;
+            if constexpr (kMasked) rm[l] = x >= x0 && x < x1 && interior[l] ? mask[base + poff[l]] : (uint8_t)0;
         }
     };
 
@@ -97,6 +121,8 @@ __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __rest
 #pragma unroll
             for (int j = 0; j < kWin; ++j) acc[o][q][j] = 0.f;
     double s_abs = 0.0, s_ssim = 0.0, s_sq = 0.0;
+    double m_abs = 0.0, m_ssim = 0.0, m_sq = 0.0;                  // kMasked: the same three over the mask's voxels
+    unsigned m_count = 0u;                                         // at most kLoads voxels per plane and thread: 32 bits suffice
     const int lz = t & (kTZ - 1), ly = (t >> 5) * 2;               // y / x pass: column lz, rows ly, ly + 1 of the tile
     const int gz = z0 + lz, gy = y0 + ly;
 
@@ -104,6 +130,17 @@ __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __rest
     for (int x = xs; x <= xlast; ++x) {
         const bool plane = x < X;                                  // uniform over the block
         float P[2][5];
+        // the SSIM output plane lags the staged plane by kH: its mask bytes are those of plane x - kH, read directly (one byte per
+        // voxel against the eight of a and b) at the top of the iteration, so that the filter passes hide the latency.  An LDS
+        // ring of the last kH + 1 planes' bytes was measured 1 to 6 % slower (profiles/NOTES.md): LDS is what bounds this kernel
+        uint8_t mk[2] = {0, 0};
+        if constexpr (kMasked) {
+            if (x - kH >= x0 && gz < Z) {
+                const size_t mbase = (size_t)(x - kH) * Y * Z + (size_t)gy * Z + gz;
+                if (gy < Y) mk[0] = mask[mbase];
+                if (gy + 1 < Y) mk[1] = mask[mbase + Z];
+            }
+        }
         if (plane) {
             const bool own = x >= x0 && x < x1;
 #pragma unroll
@@ -116,6 +153,13 @@ __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __rest
                     const double d = (double)ra[l] - (double)rb[l];      // exact
                     s_abs += fabs(d);
                     s_sq += d * d;
+                    if constexpr (kMasked) {
+                        if (rm[l]) {
+                            m_abs += fabs(d);
+                            m_sq += d * d;
+                            ++m_count;
+                        }
+                    }
                 }
             }
             __syncthreads();
@@ -182,11 +226,9 @@ __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __rest
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
                 if (gy + o < Y) {
-                    const float mu1 = acc[o][0][0], mu2 = acc[o][1][0];
-                    const float mu1sq = mu1 * mu1, mu2sq = mu2 * mu2, mu12 = mu1 * mu2;
-                    const float s11 = acc[o][2][0] - mu1sq, s22 = acc[o][3][0] - mu2sq, s12 = acc[o][4][0] - mu12;
-                    const float A1 = 2.f * mu12 + c1, A2 = 2.f * s12 + c2, B1 = mu1sq + mu2sq + c1, B2 = s11 + s22 + c2;
-                    s_ssim += (double)(A1 * A2 / (B1 * B2));
+                    const double term = (double)ssim_term(acc[o][0][0], acc[o][1][0], acc[o][2][0], acc[o][3][0], acc[o][4][0], c1, c2);
+                    s_ssim += term;
+                    if constexpr (kMasked) m_ssim += mk[o] ? term : 0.0;      // a select, no branch: the float32 code above stays the unmasked one
                 }
             }
         }
@@ -194,27 +236,38 @@ __global__ __launch_bounds__(256) void volume_metrics_kernel(const float* __rest
     s_abs = wave_sum_d(s_abs);
     s_ssim = wave_sum_d(s_ssim);
     s_sq = wave_sum_d(s_sq);
+    double m_cnt = 0.0;
+    if constexpr (kMasked) {
+        m_abs = wave_sum_d(m_abs);
+        m_ssim = wave_sum_d(m_ssim);
+        m_sq = wave_sum_d(m_sq);
+        m_cnt = wave_sum_d((double)m_count);                       // integers below 2^53: exact in any order
+    }
     if ((t & 63) == 0) {
         part[t >> 6][0] = s_abs; part[t >> 6][1] = s_ssim; part[t >> 6][2] = s_sq;
+        if constexpr (kMasked) {
+            part[t >> 6][3] = m_abs; part[t >> 6][4] = m_ssim; part[t >> 6][5] = m_sq; part[t >> 6][6] = m_cnt;
+        }
     }
     __syncthreads();
-    if (t < 3) atomic_add_f64(&sums[t], part[0][t] + part[1][t] + part[2][t] + part[3][t]);
+    if (t < kSums) atomic_add_f64(&sums[t], part[0][t] + part[1][t] + part[2][t] + part[3][t]);
 }
 
 template <int WIN>
-static void launch_volume_metrics(dim3 grid, hipStream_t s, const float* a, const float* b, int X, int Y, int Z, int chunk, float c1,
-                                  float c2, float sigma, double* sums) {
-    volume_metrics_kernel<WIN><<<grid, 256, 0, s>>>(a, b, X, Y, Z, chunk, c1, c2, make_window(sigma, WIN), sums);
+static void launch_volume_metrics(dim3 grid, hipStream_t s, const float* a, const float* b, const uint8_t* mask, int X, int Y, int Z,
+                                  int chunk, float c1, float c2, float sigma, double* sums) {
+    if (mask) volume_metrics_kernel<WIN, true><<<grid, 256, 0, s>>>(a, b, X, Y, Z, chunk, c1, c2, make_window(sigma, WIN), sums, mask);
+    else volume_metrics_kernel<WIN, false><<<grid, 256, 0, s>>>(a, b, X, Y, Z, chunk, c1, c2, make_window(sigma, WIN), sums, nullptr);
 }
 
-extern "C" int mrisr_f32_volume_metrics(const float* a, const float* b, int X, int Y, int Z, float val_range, float sigma,
-                                        int window_size, double* sums, void* stream) {
-    if (!a || !b || !sums) MRISR_FAIL(MRISR_E_ARG, "f32_volume_metrics: null pointer");
+// the checks and the launch of both entry points; mask == nullptr: the unmasked kernel
+static int volume_metrics_run(const char* name, const float* a, const float* b, const uint8_t* mask, int X, int Y, int Z, float val_range,
+                              float sigma, int window_size, double* sums, void* stream) {
     if (window_size < 3 || window_size > kMaxWin || !(window_size & 1))
-        MRISR_FAIL(MRISR_E_ARG, "f32_volume_metrics: window_size %d (odd, 3..15)", window_size);
-    if (!(sigma > 0.f) || !(val_range > 0.f)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_metrics: sigma %g, val_range %g (both positive)", sigma, val_range);
+        MRISR_FAIL(MRISR_E_ARG, "%s: window_size %d (odd, 3..15)", name, window_size);
+    if (!(sigma > 0.f) || !(val_range > 0.f)) MRISR_FAIL(MRISR_E_ARG, "%s: sigma %g, val_range %g (both positive)", name, sigma, val_range);
     if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_metrics: volume %d x %d x %d (every axis 1..%d)", X, Y, Z, kMaxDim);
+        MRISR_FAIL(MRISR_E_SHAPE, "%s: volume %d x %d x %d (every axis 1..%d)", name, X, Y, Z, kMaxDim);
     const int tz = ceil_div(Z, kTZ), ty = ceil_div(Y, kTY);
     // x chunks: enough workgroups to fill the device, none shorter than kMinChunk planes
     long long want = (kTargetBlocks + (long long)tz * ty - 1) / ((long long)tz * ty);
@@ -225,7 +278,7 @@ extern "C" int mrisr_f32_volume_metrics(const float* a, const float* b, int X, i
     const float c1 = (0.01f * val_range) * (0.01f * val_range), c2 = (0.03f * val_range) * (0.03f * val_range);
     dim3 grid(tz, ty, nchunks);
     hipStream_t s = (hipStream_t)stream;
-#define MRISR_CALL(WIN) launch_volume_metrics<WIN>(grid, s, a, b, X, Y, Z, chunk, c1, c2, sigma, sums)
+#define MRISR_CALL(WIN) launch_volume_metrics<WIN>(grid, s, a, b, mask, X, Y, Z, chunk, c1, c2, sigma, sums)
     switch (window_size) {
         case 3: MRISR_CALL(3); break;
         case 5: MRISR_CALL(5); break;
@@ -236,8 +289,20 @@ extern "C" int mrisr_f32_volume_metrics(const float* a, const float* b, int X, i
         default: MRISR_CALL(15); break;
     }
 #undef MRISR_CALL
-    MRISR_CHECK_LAUNCH("f32_volume_metrics");
+    MRISR_CHECK_LAUNCH(name);
     return MRISR_OK;
+}
+
+extern "C" int mrisr_f32_volume_metrics(const float* a, const float* b, int X, int Y, int Z, float val_range, float sigma,
+                                        int window_size, double* sums, void* stream) {
+    if (!a || !b || !sums) MRISR_FAIL(MRISR_E_ARG, "f32_volume_metrics: null pointer");
+    return volume_metrics_run("f32_volume_metrics", a, b, nullptr, X, Y, Z, val_range, sigma, window_size, sums, stream);
+}
+
+extern "C" int mrisr_f32_volume_metrics_masked(const float* a, const float* b, const uint8_t* mask, int X, int Y, int Z, float val_range,
+                                               float sigma, int window_size, double* sums7, void* stream) {
+    if (!a || !b || !mask || !sums7) MRISR_FAIL(MRISR_E_ARG, "f32_volume_metrics_masked: null pointer");
+    return volume_metrics_run("f32_volume_metrics_masked", a, b, mask, X, Y, Z, val_range, sigma, window_size, sums7, stream);
 }
 
 // out = (ssim, mse, rmse, mae, psnr); the voxel count is carried in double (a volume may hold more than 2^31 voxels)
@@ -257,5 +322,35 @@ extern "C" int mrisr_volume_metrics_finalize(const double* sums, int X, int Y, i
     volume_metrics_finalize_kernel<<<1, 64, 0, (hipStream_t)stream>>>(sums, 1.0 / ((double)X * (double)Y * (double)Z),
                                                                        (double)val_range * (double)val_range, out);
     MRISR_CHECK_LAUNCH("volume_metrics_finalize");
+    return MRISR_OK;
+}
+
+// out[0..4]: the five metrics of the whole volume (as above); out[5..9]: the same five over the mask's voxels, every mean a
+// division by the count sums[6], so that an empty mask gives five NaNs (0 / 0) without a host check; out[10]: the count
+__global__ void volume_metrics_finalize_masked_kernel(const double* __restrict__ sums, double inv_voxels, double range2,
+                                                      double* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double count = sums[6];
+#pragma unroll
+    for (int region = 0; region < 2; ++region) {
+        const double* q = sums + 3 * region;
+        const double mae = region ? q[0] / count : q[0] * inv_voxels, ssim = region ? q[1] / count : q[1] * inv_voxels;
+        const double mse = region ? q[2] / count : q[2] * inv_voxels;
+        double* o = out + 5 * region;
+        o[0] = ssim;
+        o[1] = mse;
+        o[2] = __dsqrt_rn(mse);
+        o[3] = mae;
+        o[4] = mse < 1e-10 ? 100.0 : 10.0 * log10(range2 / mse);      // NaN < 1e-10 is false: NaN stays NaN
+    }
+    out[10] = count;
+}
+
+extern "C" int mrisr_volume_metrics_finalize_masked(const double* sums7, int X, int Y, int Z, float val_range, double* out11, void* stream) {
+    if (!sums7 || !out11) MRISR_FAIL(MRISR_E_ARG, "volume_metrics_finalize_masked: null pointer");
+    if (X < 1 || Y < 1 || Z < 1) MRISR_FAIL(MRISR_E_SHAPE, "volume_metrics_finalize_masked: volume %d x %d x %d", X, Y, Z);
+    volume_metrics_finalize_masked_kernel<<<1, 64, 0, (hipStream_t)stream>>>(sums7, 1.0 / ((double)X * (double)Y * (double)Z),
+                                                                              (double)val_range * (double)val_range, out11);
+    MRISR_CHECK_LAUNCH("volume_metrics_finalize_masked");
     return MRISR_OK;
 }

@@ -13,6 +13,13 @@ alternative to the three-plane blend), ``linear`` and ``cubic``.  The metrics ar
 MSE, RMSE, MAE, PSNR with ``--data_range`` (default: max - min of the reference), all computed on the device
 (``csrc/volume_metrics.hip``).  A 4-D file is scored timepoint by timepoint.  One table per scan, the mean over scans, and the
 same rows in ``--output_csv``.  Checkpoint flags and the exit code (0 / 1, error logged) are those of ``scripts/infer_volume.py``.
+
+``--mask otsu`` scores every method inside a foreground mask as well: an exact Otsu threshold on the reference volume's 256-bin
+histogram, closed with a box of ``--mask_close`` voxels (``csrc/volume_mask.hip``); ``--mask PATH`` takes the mask from a NIfTI-1
+file of the reference's spatial shape instead (any voxel type, non-zero = foreground; a 3-D mask serves every timepoint).  Each
+scan then prints a second table headed "foreground" (voxel count, share of the volume, Otsu threshold), the means come for both
+regions, and the CSV gains a ``region`` column (``whole`` / ``foreground``).  Still one pass over the volumes per method and one
+download per volume.
 """
 import argparse
 import csv
@@ -29,19 +36,35 @@ if REPO not in sys.path:
 
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
 from mri_superresolution_amd.utils.nifti import read_nifti                # noqa: E402
-from mri_superresolution_amd.volume_eval import evaluate_volume           # noqa: E402
+from mri_superresolution_amd.volume_eval import evaluate_volume, otsu_threshold_value      # noqa: E402
 
 logger = logging.getLogger("evaluate_volume")
 CSV_COLUMNS = ["scan", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # the column style of scripts/evaluate.py
+CSV_COLUMNS_MASKED = ["scan", "region", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # with --mask
+REGIONS = ("whole", "foreground")
 
 
 def _frames(data):
     return [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
 
 
+def load_mask(mask_path, ref, reference_path):
+    """-> one uint8 frame per timepoint of the reference (a 3-D mask serves them all)."""
+    data, _ = read_nifti(mask_path)
+    if data.ndim not in (3, 4) or tuple(data.shape[:3]) != tuple(ref.shape[:3]):
+        raise ValueError(f"mask {mask_path} has shape {tuple(data.shape)}, {reference_path} has {tuple(ref.shape)}")
+    frames = [np.ascontiguousarray((f != 0).astype(np.uint8)) for f in _frames(data)]
+    count = 1 if ref.ndim == 3 else ref.shape[3]
+    if data.ndim == 4 and len(frames) != count:
+        raise ValueError(f"mask {mask_path} has {len(frames)} timepoints, {reference_path} has {count}")
+    return frames if data.ndim == 4 else frames * count
+
+
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
-               use_graph=True, device="cuda", graph_cache=None):
-    """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method."""
+               use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0):
+    """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
+    rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
+    ``"threshold"``."""
     ref, _ = read_nifti(reference_path)
     low = read_nifti(input_path)[0] if input_path else None
     if low is not None and low.ndim != ref.ndim:
@@ -49,18 +72,33 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     if low is not None and low.ndim == 4 and low.shape[3] != ref.shape[3]:
         raise ValueError(f"{input_path} has {low.shape[3]} timepoints, {reference_path} has {ref.shape[3]}")
     ref_frames, low_frames = _frames(ref), (_frames(low) if low is not None else None)
+    mask_frames = load_mask(mask, ref, reference_path) if mask not in (None, "otsu") else None
     graphs = graph_cache if graph_cache is not None else {}
     name = os.path.basename(reference_path)
     rows = []
     for t, frame in enumerate(ref_frames):
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
         lr = torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device) if low_frames is not None else None
+        m = mask if mask_frames is None else torch.from_numpy(mask_frames[t]).to(device)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
-                              use_amp=use_amp, use_graph=use_graph, graph_cache=graphs)
-        values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
+                              use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close)
         scan = name if len(ref_frames) == 1 else f"{name}[t={t}]"
-        for method, vals in zip(res, values):
-            rows.append({"scan": scan, "method": method, **dict(zip(METRIC_COLUMNS, (float(v) for v in vals)))})
+        if mask is None:
+            values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
+            for method, vals in zip(res, values):
+                rows.append({"scan": scan, "method": method, **dict(zip(METRIC_COLUMNS, (float(v) for v in vals)))})
+            continue
+        # the (2, 5) results of every method, the mask's voxel count and the four mask statistics: still one download per volume
+        stats = res.mask_stats if res.mask_stats is not None else torch.full((4,), float("nan"), dtype=torch.float64, device=device)
+        down = torch.cat([v.reshape(10) for v in res.values()] + [res.mask_count.reshape(1), stats]).cpu().numpy()
+        lo, hi, tstar, _ = down[-4:]
+        extra = {"voxels": int(res.mask.numel()), "mask_voxels": int(down[-5]),
+                 "threshold": otsu_threshold_value(lo, hi, int(tstar)) if res.mask_stats is not None else None}
+        for r, region in enumerate(REGIONS):
+            for i, method in enumerate(res):
+                vals = down[10 * i + 5 * r:10 * i + 5 * r + 5]
+                rows.append({"scan": scan, "region": region, "method": method, **extra,
+                             **dict(zip(METRIC_COLUMNS, (float(v) for v in vals)))})
     return rows
 
 
@@ -77,6 +115,12 @@ def mean_rows(rows):
             for m in methods]
 
 
+def foreground_title(rows):
+    r = rows[0]
+    title = f"foreground: {r['mask_voxels']} voxels, {100.0 * r['mask_voxels'] / r['voxels']:.1f} % of the volume"
+    return title + (f", Otsu threshold {r['threshold']:.6g}" if r["threshold"] is not None else "")
+
+
 def main(args):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     try:
@@ -88,6 +132,10 @@ def main(args):
             raise ValueError("--input goes with exactly one --reference scan")
         if args.data_range is not None and not args.data_range > 0:
             raise ValueError(f"--data_range must be positive, got {args.data_range}")
+        if args.mask is None and args.mask_close != 0:
+            raise ValueError("--mask_close goes with --mask")
+        if not 0 <= args.mask_close <= 4:
+            raise ValueError(f"--mask_close must be in 0..4, got {args.mask_close}")
         from scripts.infer import find_best_checkpoint, load_model
         device = torch.device("cuda")
         logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
@@ -98,21 +146,32 @@ def main(args):
         logger.info(f"Checkpoint: {ckpt}")
         model = load_model(args.model_type, ckpt, device, base_filters=args.base_filters)
         rows, graphs = [], {}
+        regions = REGIONS if args.mask else (None,)
         for path in args.reference:
             scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
-                                   not args.no_graph, device, graphs)
+                                   not args.no_graph, device, graphs, args.mask, args.mask_close)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
-                print(format_table(scan, [r for r in scan_rows if r["scan"] == scan]))
+                for region in regions:
+                    part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
+                    print(format_table(foreground_title(part) if region == "foreground" else scan, part))
             rows += scan_rows
-        means = mean_rows(rows)
-        print(format_table(f"mean over {len(set(r['scan'] for r in rows))} scan(s)", means))
+        means = []
+        for region in regions:
+            part = [r for r in rows if r.get("region") == region]
+            title = f"mean over {len(set(r['scan'] for r in part))} scan(s)"
+            mean = mean_rows(part)
+            if region is not None:
+                mean = [{**r, "region": region} for r in mean]
+            print(format_table(f"foreground, {title}" if region == "foreground" else title, mean))
+            means += mean
         if args.output_csv:
             os.makedirs(os.path.dirname(os.path.abspath(args.output_csv)), exist_ok=True)
+            columns = CSV_COLUMNS_MASKED if args.mask else CSV_COLUMNS
             with open(args.output_csv, "w", newline="") as f:
-                wr = csv.DictWriter(f, fieldnames=CSV_COLUMNS)
+                wr = csv.DictWriter(f, fieldnames=columns)
                 wr.writeheader()
                 for r in rows + means:
-                    wr.writerow({k: r[k] for k in CSV_COLUMNS})
+                    wr.writerow({k: r[k] for k in columns})
             logger.info(f"Saved {len(rows) + len(means)} rows to {args.output_csv}")
         return 0
     except Exception as e:
@@ -137,6 +196,10 @@ def parse_args(argv=None):
     p.add_argument("--data_range", type=float, default=None, help="R of SSIM's constants and of PSNR; default: max - min of each reference volume")
     p.add_argument("--batch_size", type=int, default=16, help="slices per forward")
     p.add_argument("--no_graph", action="store_true", help="do not replay the forward of full batches as a HIP graph")
+    p.add_argument("--mask", type=str, default=None,
+                   help="score inside a foreground mask as well: 'otsu' (exact Otsu threshold of each reference volume, on the device) or "
+                        "a NIfTI-1 mask of the reference's spatial shape (non-zero = foreground)")
+    p.add_argument("--mask_close", type=int, default=0, help="close the mask with a box of this radius in voxels (0..4; needs --mask)")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

@@ -11,6 +11,12 @@ Per shape, on a pair of float32 volumes in [0, 1] ("truth plus error"):
     and three reductions, all float32 on the device; the two SSIM values are printed side by side;
 (c) ``upscale2`` linear and cubic of the volume HALVED on every axis (so that the output has the shape above), against
     ``F.interpolate(mode="trilinear")`` for the linear one; traffic model: input once, output once.
+(d) the foreground mask (csrc/volume_mask.hip): ``otsu_mask`` (five launches; the volume read three times, the mask written once:
+    13 bytes per voxel), ``binary_close`` at radius 2 (six passes, each reads and writes one byte per voxel), and
+    ``foreground_mask(close_radius=2)`` as a whole, next to one metrics launch;
+(e) ``volume_metrics(mask=...)`` - the masked instantiation, 9 bytes per voxel - alternating with the unmasked call in one loop,
+    so that the ratio of the two is taken on one box in one run.  ``--parent_lib PATH`` adds the unmasked kernel of another
+    build of the library (called through ctypes, nothing else of it is used) to the same alternation.
 Prints one JSON line (profiles/NOTES.md, "Volume evaluation")."""
 import argparse
 import json
@@ -40,6 +46,40 @@ def event_times(fn, reps, warmup):
         e1.synchronize()
         times.append(e0.elapsed_time(e1) * 1e3)
     return {"us_median": round(statistics.median(times), 1), "us_min": round(min(times), 1)}
+
+
+def alternating_times(fns, reps, warmup):
+    """{name: times} of several callables timed in turn, round after round: what they share of the box's state they share alike."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3)
+    return {k: {"us_median": round(statistics.median(v), 1), "us_min": round(min(v), 1)} for k, v in times.items()}
+
+
+def parent_metrics_call(path, pred, ref):
+    """The unmasked fused pass of another build of libmrisr.so on the same pair (window 11, sigma 1.5, range 1)."""
+    import ctypes as C
+    lib = C.CDLL(path)
+    fn = lib.mrisr_f32_volume_metrics
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+    sums = torch.zeros(3, dtype=torch.float64, device=pred.device)
+
+    def call():
+        sums.zero_()
+        rc = fn(pred.data_ptr(), ref.data_ptr(), *pred.shape, 1.0, 1.5, 11, sums.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, rc
+    return call, sums
 
 
 def rate(nbytes, t):
@@ -73,10 +113,11 @@ def main():
     p.add_argument("--reps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--skip_torch", action="store_true")
+    p.add_argument("--parent_lib", type=str, default=None, help="another build of libmrisr.so: its unmasked metrics kernel joins (e)")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("volume_eval_bench needs the MI355X: there is nothing to time on a CPU")
-    from mri_superresolution_amd.volume_eval import upscale2, volume_metrics
+    from mri_superresolution_amd.volume_eval import binary_close, foreground_mask, otsu_mask, upscale2, volume_metrics
 
     res = {"gpu": torch.cuda.get_device_name(0), "window": 11, "shapes": {}}
     for text in args.shapes:
@@ -102,8 +143,32 @@ def main():
         if not args.skip_torch:
             r["trilinear_torch"] = event_times(
                 lambda: F.interpolate(low[None, None], scale_factor=2, mode="trilinear", align_corners=False), max(3, args.reps // 2), 1)
+        # (d) the mask of a head-like volume: a bright ball in a dark noisy background, about half of the voxels
+        x, y, z = torch.meshgrid(*(torch.linspace(-1, 1, n, device="cuda") for n in shape), indexing="ij")
+        head = torch.where(x * x + y * y + z * z < 0.95, 600.0 + 200.0 * torch.rand(shape, device="cuda", generator=g),
+                           40.0 * torch.rand(shape, device="cuda", generator=g)).contiguous()
+        del x, y, z
+        mask0 = otsu_mask(head)[0]
+        r["otsu_mask"] = event_times(lambda: otsu_mask(head), args.reps, args.warmup)
+        r["otsu_mask"].update(rate(13 * voxels, r["otsu_mask"]))
+        r["binary_close_r2"] = event_times(lambda: binary_close(mask0, 2), args.reps, args.warmup)
+        r["binary_close_r2"].update(rate(12 * voxels, r["binary_close_r2"]))
+        r["foreground_mask_r2"] = event_times(lambda: foreground_mask(head, 2), args.reps, args.warmup)
+        mask = foreground_mask(head, 2)[0]
+        r["mask_share"] = round(float(mask.count_nonzero()) / voxels, 4)
+        # (e) masked against unmasked, alternating
+        fns = {"unmasked": lambda: volume_metrics(pred, ref, 1.0), "masked": lambda: volume_metrics(pred, ref, 1.0, mask=mask)}
+        if args.parent_lib:
+            fns["parent_unmasked_kernel"], psums = parent_metrics_call(args.parent_lib, pred, ref)
+        r["alternating"] = alternating_times(fns, args.reps, args.warmup)
+        r["masked_over_unmasked"] = round(r["alternating"]["masked"]["us_median"] / r["alternating"]["unmasked"]["us_median"], 4)
+        r["mask_build_over_metrics"] = round(r["foreground_mask_r2"]["us_median"] / r["alternating"]["unmasked"]["us_median"], 4)
+        both = volume_metrics(pred, ref, 1.0, mask=mask).cpu()
+        r["ssim_whole_masked_call"], r["ssim_foreground"] = float(both[0, 0]), float(both[1, 0])
+        if args.parent_lib:
+            r["ssim_parent_kernel"] = float(psums[1]) / voxels
         res["shapes"][text] = r
-        del ref, pred, low
+        del ref, pred, low, head, mask, mask0
     print(json.dumps(res))
 
 
