@@ -601,6 +601,34 @@ int mrisr_f32_volume_otsu_mask(const float* vol, int X, int Y, int Z, uint8_t* m
  * outside 0..4.                                                                                                                 */
 int mrisr_u8_volume_morph(const uint8_t* src, int X, int Y, int Z, int radius, int op, uint8_t* dst, uint8_t* tmp, void* stream);
 
+/* ---- connected components of a mask (extension; csrc/volume_label.hip).  A voxel's index is its C-order linear index (Z fastest).
+ *      THE LABEL of a foreground voxel is 1 + the smallest index of its component, background is 0: deterministic and bit-exact,
+ *      no renumbering.  connectivity 6 (faces) or 26 (faces, edges, corners).  plane_axis -1: the volume; 0..2: only neighbours
+ *      inside the planes across that axis count (4 for connectivity 6, 8 for 26).  Union-find: tiles in LDS, a merge launch across
+ *      tile borders, a flattening launch; no host synchronisation, no workgroup waits for another (HIP-graph capturable).
+ *      Common refusals, all before any launch: MRISR_E_ARG null or misaligned pointer, connectivity not 6 / 26, plane_axis outside
+ *      -1..2, invert not 0 / 1, dst == mask; MRISR_E_SHAPE an extent below 1 or above 32767; MRISR_E_UNSUPPORTED more than
+ *      2^31 - 2 voxels (labels are int32). ----------------------------------------------------------------------------------- */
+/* labels (int32, X Y Z of them, 4-byte aligned) = the labels of the non-zero voxels of mask, or with invert = 1 of its zero voxels
+ * (the complement is never formed).  labels is also the working array (the union-find parents): no workspace.  3 launches.      */
+int mrisr_u8_volume_label(const uint8_t* mask, int X, int Y, int Z, int connectivity, int plane_axis, int invert, int32_t* labels,
+                          void* stream);
+/* bytes of device workspace of mrisr_u8_volume_keep_largest and mrisr_u8_volume_fill_holes: 64 + 8 X Y Z (a header, the int32
+ * labels, one 32-bit word per voxel for the sizes or the border marks); 0 for a shape the two refuse.  16-byte aligned; the
+ * contents need no initialisation.                                                                                            */
+size_t mrisr_u8_volume_label_workspace_bytes(int X, int Y, int Z);
+/* dst = 1 on the largest component of mask (plane_axis -1), 0 elsewhere; of components of one size the one with the smaller label
+ * is kept; an empty mask gives dst = 0.  stats3[3] doubles: the number of components, the size and the label of the kept one
+ * (0, 0 when there is none).  5 launches.                                                                                      */
+int mrisr_u8_volume_keep_largest(const uint8_t* mask, int X, int Y, int Z, int connectivity, uint8_t* dst, double* stats3,
+                                 void* workspace, void* stream);
+/* dst = (mask != 0) or every zero voxel whose component of zero voxels - 6-connected - owns no voxel on a face of the volume:
+ * scipy.ndimage.binary_fill_holes.  With plane_axis 0..2 the zero voxels are 4-connected inside the planes across that axis and
+ * the test is "owns no voxel on an edge of its plane": binary_fill_holes plane by plane.  stats1[1] double: the voxels filled.
+ * 4 launches.                                                                                                                  */
+int mrisr_u8_volume_fill_holes(const uint8_t* mask, int X, int Y, int Z, int plane_axis, uint8_t* dst, double* stats1, void* workspace,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

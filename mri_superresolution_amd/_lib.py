@@ -164,10 +164,14 @@ SIGNATURES = {
     "mrisr_f32_volume_otsu_workspace_bytes": (_sz, []),
     "mrisr_f32_volume_otsu_mask": (_i, [_fp, _i, _i, _i, _vp, _dp, _vp, _vp]),
     "mrisr_u8_volume_morph": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mrisr_u8_volume_label": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mrisr_u8_volume_label_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mrisr_u8_volume_keep_largest": (_i, [_vp, _i, _i, _i, _i, _vp, _dp, _vp, _vp]),
+    "mrisr_u8_volume_fill_holes": (_i, [_vp, _i, _i, _i, _i, _vp, _dp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 313      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 314      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

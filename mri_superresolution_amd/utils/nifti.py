@@ -189,14 +189,14 @@ def upscaled_affine(affine: np.ndarray, upscaled_axes: Sequence[int]) -> np.ndar
 
 
 def write_nifti(path: str, data: np.ndarray, header: NiftiHeader, upscaled_axes: Sequence[int] = ()):
-    """Writes float32 or int16 ``data`` (3-D or 4-D) as single-file NIfTI-1 under a copy of ``header`` (its byte order kept):
+    """Writes float32, int16 or uint8 ``data`` (3-D or 4-D) as single-file NIfTI-1 under a copy of ``header`` (its byte order kept):
     ``dim`` from ``data.shape``, which must be the header's with the ``upscaled_axes`` (two or all three of 0, 1, 2, or none) doubled;
     their ``pixdim`` halved and the sform / qform moved as the module docstring says; ``datatype`` / ``bitpix`` set,
     ``scl_slope = 1``, ``scl_inter = 0``, ``vox_offset = 352``, magic ``n+1``.  gzip when the name ends in ``.gz``."""
     data = np.asarray(data)
-    codes = {np.dtype(np.float32): 16, np.dtype(np.int16): 4}
+    codes = {np.dtype(np.float32): 16, np.dtype(np.int16): 4, np.dtype(np.uint8): 2}
     if data.dtype not in codes:
-        raise ValueError(f"write_nifti writes float32 or int16, not {data.dtype}")
+        raise ValueError(f"write_nifti writes float32, int16 or uint8, not {data.dtype}")
     if data.ndim not in (3, 4):
         raise ValueError(f"write_nifti writes 3-D or 4-D volumes, not {data.shape}")
     axes = tuple(int(a) for a in upscaled_axes)

@@ -12,6 +12,9 @@ interpolation, and does the three-plane blend beat one slice pass plus linear th
                      With ``mask=`` the one pass also sums over the mask's voxels: (2, 5), whole volume and foreground.
 ``foreground_mask``  exact Otsu threshold on a 256-bin histogram plus an optional 3-D binary closing, all on the device
                      (``csrc/volume_mask.hip``), bit-equal to ``foreground_mask_np``.
+``label_components`` connected components of a mask (``csrc/volume_label.hip``: union-find in LDS tiles, a merge launch across tile
+                     borders, a flattening launch), bit-equal to ``label_components_np``; ``largest_component`` and ``fill_holes``
+                     are the two clean-up steps built on it, which ``foreground_mask`` applies on request.
 ``evaluate_volume``  U-Net against the baselines on one ground-truth volume, optionally inside a foreground mask.
 
 There is no CPU path: CPU tensors raise.  The ``*_np`` functions are the specifications the kernels are tested against.
@@ -225,13 +228,132 @@ def _check_radius(r):
     return int(r)
 
 
-def foreground_mask_np(v: np.ndarray, close_radius: int = 0, return_stats: bool = False):
+def _check_connectivity(connectivity):
+    if isinstance(connectivity, bool) or connectivity not in (6, 26):
+        raise ValueError(f"connectivity must be 6 or 26, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _check_plane_axis(axis, what="plane_axis"):
+    """None -> -1, else the axis 0..2."""
+    if axis is None:
+        return -1
+    if not isinstance(axis, (int, np.integer)) or isinstance(axis, bool) or axis not in (0, 1, 2):
+        raise ValueError(f"{what} must be None, 0, 1 or 2, got {axis!r}")
+    return int(axis)
+
+
+def _check_fill(fill):
+    """``fill_holes=`` of ``foreground_mask``: None -> None, "3d" -> -1, an axis -> that axis."""
+    if fill is None:
+        return None
+    if isinstance(fill, str):
+        if fill == "3d":
+            return -1
+        raise ValueError(f"fill_holes must be None, '3d', 0, 1 or 2, got {fill!r}")
+    return _check_plane_axis(fill, "fill_holes")
+
+
+def _check_mask_np(mask, what):
+    mask = np.asarray(mask)
+    if mask.ndim != 3 or mask.size == 0:
+        raise ValueError(f"{what}: expected a non-empty mask (X,Y,Z), got {mask.shape}")
+    return mask
+
+
+def backward_offsets(connectivity: int, plane_axis: int = -1):
+    """The neighbour offsets that come before the centre in C order (every pair of neighbours once): 13 of the 26, 3 of the 6;
+    with ``plane_axis`` 0..2 only those with no step along that axis (4 of the 8, 2 of the 4)."""
+    out = []
+    for k in range(13):
+        d = (k // 9 - 1, k // 3 % 3 - 1, k % 3 - 1)
+        if connectivity == 6 and sum(c != 0 for c in d) != 1:
+            continue
+        if plane_axis >= 0 and d[plane_axis] != 0:
+            continue
+        out.append(d)
+    return out
+
+
+def label_components_np(mask: np.ndarray, connectivity: int = 26, plane_axis=None, invert: bool = False) -> np.ndarray:
+    """The specification of ``label_components``: int32 labels of the non-zero voxels of ``mask`` (of its zero voxels with
+    ``invert``), a voxel's label ``1 + the smallest C-order linear index of its component``, 0 elsewhere.  ``connectivity`` 6 or
+    26; with ``plane_axis`` only neighbours inside the planes across that axis count.  Exact, without scipy: the edge list per
+    neighbour offset, then rounds of hooking the larger root under the smaller (``np.minimum.at``) and pointer jumping until no
+    edge joins two roots."""
+    mask = _check_mask_np(mask, "label_components_np")
+    conn, axis = _check_connectivity(connectivity), _check_plane_axis(plane_axis)
+    fg = (mask != 0) != bool(invert)
+    n = fg.size
+    if n > 2 ** 31 - 2:
+        raise ValueError(f"label_components_np: {n} voxels, labels are int32 (at most 2^31 - 2)")
+    idx = np.arange(n, dtype=np.int64).reshape(fg.shape)
+    hi, lo = [], []
+    for d in backward_offsets(conn, axis):
+        a = tuple(slice(max(0, -c), s - max(0, c)) for c, s in zip(d, fg.shape))       # the voxel
+        b = tuple(slice(max(0, c), s - max(0, -c)) for c, s in zip(d, fg.shape))       # its neighbour at + d (earlier in C order)
+        both = fg[a] & fg[b]
+        hi.append(idx[a][both])
+        lo.append(idx[b][both])
+    hi, lo = np.concatenate(hi), np.concatenate(lo)
+    parent = np.arange(n, dtype=np.int64)
+    while hi.size:
+        ra, rb = parent[hi], parent[lo]                         # roots: the forest is flat at this point
+        open_ = ra != rb
+        if not open_.any():
+            break
+        hi, lo, ra, rb = hi[open_], lo[open_], ra[open_], rb[open_]
+        np.minimum.at(parent, np.maximum(ra, rb), np.minimum(ra, rb))
+        while True:                                             # pointer jumping
+            nxt = parent[parent]
+            if np.array_equal(nxt, parent):
+                break
+            parent = nxt
+    return np.where(fg.reshape(-1), parent + 1, 0).astype(np.int32).reshape(fg.shape)
+
+
+def largest_component_np(mask: np.ndarray, connectivity: int = 26):
+    """-> (uint8 mask of the largest component - of several of one size the one with the smallest label -, float64 array
+    [components, kept size, kept label]); an empty mask gives zeros and [0, 0, 0]."""
+    lab = label_components_np(mask, connectivity)
+    flat = lab.reshape(-1)
+    roots = np.flatnonzero(flat == np.arange(1, flat.size + 1))
+    if roots.size == 0:
+        return np.zeros(lab.shape, dtype=np.uint8), np.zeros(3)
+    sizes = np.bincount(flat, minlength=flat.size + 1)[roots + 1]
+    k = int(np.argmax(sizes))                                   # the first of the largest: the smallest label
+    return (lab == roots[k] + 1).astype(np.uint8), np.array([roots.size, sizes[k], roots[k] + 1], dtype=np.float64)
+
+
+def fill_holes_np(mask: np.ndarray, axis=None):
+    """-> (uint8 ``mask != 0`` plus every zero voxel whose 6-connected component of zero voxels owns no voxel on a face of the
+    volume, the number of voxels filled): ``scipy.ndimage.binary_fill_holes``.  With ``axis`` 0..2 plane by plane across that
+    axis: the zero voxels 4-connected inside the plane, the test "owns no voxel on an edge of its plane"."""
+    mask = _check_mask_np(mask, "fill_holes_np")
+    a = _check_plane_axis(axis, "axis")
+    lab = label_components_np(mask, 6, axis, invert=True)
+    border = np.zeros(lab.shape, dtype=bool)
+    for ax in range(3):
+        if ax != a:
+            sl = [slice(None)] * 3
+            for edge in (0, -1):
+                sl[ax] = edge
+                border[tuple(sl)] = True
+    touches = np.zeros(lab.size + 1, dtype=bool)
+    touches[lab[border]] = True
+    filled = (lab != 0) & ~touches[lab]
+    return ((mask != 0) | filled).astype(np.uint8), int(filled.sum())
+
+
+def foreground_mask_np(v: np.ndarray, close_radius: int = 0, return_stats: bool = False, largest: bool = False, fill_holes=None):
     """The specification of ``foreground_mask``: ``mask = bin(v) > t*`` (uint8, 0 / 1) with the bins of ``otsu_bins_np`` and the
     ``t*`` of ``otsu_threshold_np`` on their counts - an integer comparison, exactly consistent with the histogram - then, for
     ``close_radius`` r in 1..4, the closing ``erode_np(dilate_np(mask, r), r)``.  A degenerate range gives ``t* = -1`` and a mask of
     ones.  ``return_stats``: -> (mask, dict(lo, hi, t, count, counts)), the count and the 256 counts those of the Otsu mask
-    before the closing."""
-    r = _check_radius(close_radius)
+    before the closing.  Then, on request: ``largest`` keeps the largest 26-connected component (``largest_component_np``), and
+    ``fill_holes`` (``"3d"`` or an axis 0..2) fills the holes of what is left (``fill_holes_np``); with either the dict gains
+    ``cleanup``: [components found, kept size, voxels filled], NaN for a step that is off."""
+    r, fill = _check_radius(close_radius), _check_fill(fill_holes)
     lo, hi, bins = otsu_bins_np(v)
     if bins is None:
         t, counts = -1, np.zeros(256, dtype=np.int64)
@@ -243,6 +365,14 @@ def foreground_mask_np(v: np.ndarray, close_radius: int = 0, return_stats: bool 
     stats = dict(lo=lo, hi=hi, t=t, count=int(mask.sum(dtype=np.int64)), counts=counts)
     if r:
         mask = erode_np(dilate_np(mask, r), r)
+    if largest or fill is not None:
+        cleanup = np.full(3, np.nan)
+        if largest:
+            mask, st3 = largest_component_np(mask, 26)
+            cleanup[:2] = st3[:2]
+        if fill is not None:
+            mask, cleanup[2] = fill_holes_np(mask, None if fill < 0 else fill)
+        stats["cleanup"] = cleanup
     return (mask, stats) if return_stats else mask
 
 
@@ -344,12 +474,80 @@ def binary_close(mask: torch.Tensor, radius: int) -> torch.Tensor:
     return _morph(grown, r, L.MORPH_ERODE, torch.empty_like(m), tmp)
 
 
-def foreground_mask(vol: torch.Tensor, close_radius: int = 0):
+def _label_workspace(m):
+    nbytes = int(L.load().mrisr_u8_volume_label_workspace_bytes(*m.shape))
+    if nbytes == 0:
+        raise ValueError(f"a mask of {tuple(m.shape)} has more than 2^31 - 2 voxels: labels are int32")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=m.device)
+
+
+def label_components(mask: torch.Tensor, connectivity: int = 26, plane_axis=None, invert: bool = False) -> torch.Tensor:
+    """mask: (X,Y,Z) uint8 / bool CUDA tensor -> int32 CUDA tensor of labels, bit-equal to ``label_components_np``: a foreground
+    voxel's label is 1 + the smallest C-order linear index of its component.  Three launches, no host synchronisation."""
+    conn, axis = _check_connectivity(connectivity), _check_plane_axis(plane_axis)
+    m = _check_mask(mask, None, "label_components")
+    if m.numel() > 2 ** 31 - 2:
+        raise ValueError(f"a mask of {tuple(m.shape)} has more than 2^31 - 2 voxels: labels are int32")
+    labels = torch.empty(m.shape, dtype=torch.int32, device=m.device)
+    L.call("mrisr_u8_volume_label", m.data_ptr(), *m.shape, conn, axis, int(bool(invert)), labels.data_ptr(), L.stream_ptr())
+    return labels
+
+
+def _largest(m, conn):
+    dst, stats = torch.empty_like(m), torch.empty(3, dtype=torch.float64, device=m.device)
+    ws = _label_workspace(m)
+    L.call("mrisr_u8_volume_keep_largest", m.data_ptr(), *m.shape, conn, dst.data_ptr(), stats.data_ptr(), ws.data_ptr(), L.stream_ptr())
+    return dst, stats
+
+
+def _fill(m, axis):
+    dst, filled = torch.empty_like(m), torch.empty(1, dtype=torch.float64, device=m.device)
+    ws = _label_workspace(m)
+    L.call("mrisr_u8_volume_fill_holes", m.data_ptr(), *m.shape, axis, dst.data_ptr(), filled.data_ptr(), ws.data_ptr(), L.stream_ptr())
+    return dst, filled
+
+
+def largest_component(mask: torch.Tensor, connectivity: int = 26):
+    """-> (uint8 CUDA mask of the largest component, (3,) float64 CUDA tensor: components, kept size, kept label), bit-equal to
+    ``largest_component_np``.  No host synchronisation."""
+    conn = _check_connectivity(connectivity)
+    return _largest(_check_mask(mask, None, "largest_component"), conn)
+
+
+def fill_holes(mask: torch.Tensor, axis=None):
+    """-> (uint8 CUDA mask with its holes filled, 0-d float64 CUDA tensor: the voxels filled), bit-equal to ``fill_holes_np``; the
+    volume's holes, or with ``axis`` 0..2 those of every plane across that axis.  No host synchronisation."""
+    a = _check_plane_axis(axis, "axis")
+    dst, filled = _fill(_check_mask(mask, None, "fill_holes"), a)
+    return dst, filled[0]
+
+
+def _clean_mask(m, largest, fill):
+    """largest (26-connected), then fill (None, -1 or an axis) -> (mask, (3,) float64 CUDA tensor [components, kept size, filled]
+    with NaN for a step that is off; None when both are off)."""
+    if not largest and fill is None:
+        return m, None
+    cleanup = torch.full((3,), float("nan"), dtype=torch.float64, device=m.device)
+    if largest:
+        m, st3 = _largest(m, 26)
+        cleanup[:2] = st3[:2]
+    if fill is not None:
+        m, filled = _fill(m, fill)
+        cleanup[2:] = filled
+    return m, cleanup
+
+
+def foreground_mask(vol: torch.Tensor, close_radius: int = 0, largest: bool = False, fill_holes=None):
     """vol: (X,Y,Z) float32 CUDA tensor -> (mask uint8 CUDA tensor, stats (4,) float64 CUDA tensor: lo, hi, t*, and the foreground
-    count of the Otsu mask before the closing).  Bit-equal to ``foreground_mask_np``.  No host synchronisation."""
-    r = _check_radius(close_radius)
+    count of the Otsu mask before the closing).  Bit-equal to ``foreground_mask_np``.  No host synchronisation.
+
+    ``largest`` keeps the largest 26-connected component of the closed mask, ``fill_holes`` (``"3d"`` or an axis 0..2) then fills
+    its holes; with either, ``stats.cleanup`` is the (3,) float64 CUDA tensor [components found, kept size, voxels filled] (NaN
+    for a step that is off) - a convenience of THIS object, ``None`` otherwise."""
+    r, fill = _check_radius(close_radius), _check_fill(fill_holes)
     mask, stats, _ = otsu_mask(vol)
-    return binary_close(mask, r), stats
+    mask, stats.cleanup = _clean_mask(binary_close(mask, r), bool(largest), fill)
+    return mask, stats
 
 
 def volume_metrics(pred: torch.Tensor, ref: torch.Tensor, val_range: float, window_size: int = 11, sigma: float = 1.5,
@@ -388,16 +586,18 @@ def volume_metrics(pred: torch.Tensor, ref: torch.Tensor, val_range: float, wind
 class VolumeScores(OrderedDict):
     """What ``evaluate_volume`` returns: ``{method: metrics tensor}`` in method order.  With a mask it also carries ``mask``
     (the uint8 CUDA tensor every method was scored with), ``mask_count`` (its voxel count, 0-d float64 CUDA tensor) and
-    ``mask_stats`` (``foreground_mask``'s (4,) float64 CUDA tensor lo, hi, t*, count for ``"otsu"``); all three ``None`` otherwise."""
+    ``mask_stats`` (``foreground_mask``'s (4,) float64 CUDA tensor lo, hi, t*, count for ``"otsu"``); all three ``None`` otherwise.
+    ``mask_cleanup``: the (3,) float64 CUDA tensor [components found, kept size, voxels filled] of the mask's clean-up (NaN for a
+    step that is off), ``None`` when neither ``mask_largest`` nor ``mask_fill_holes`` is on."""
 
     def __init__(self):
         super().__init__()
-        self.mask = self.mask_count = self.mask_stats = None
+        self.mask = self.mask_count = self.mask_stats = self.mask_cleanup = None
 
 
 def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic: bool = False, axis: int = 2, val_range: float = None,
                     batch_size: int = 16, use_amp: bool = False, use_graph: bool = True, graph_cache: dict = None, mask=None,
-                    mask_close: int = 0) -> "VolumeScores":
+                    mask_close: int = 0, mask_largest: bool = False, mask_fill_holes=None) -> "VolumeScores":
     """Scores the U-Net and the interpolation baselines against the ground truth ``ref`` (float32 CUDA volume).
 
     The doubled axes are all three with ``isotropic``, else the two in-plane axes of the slices across ``axis``.  ``lr=None``
@@ -412,7 +612,9 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     and shared by every method) or a uint8 / bool CUDA tensor of ``ref``'s shape (it gets the reference's crop; ``mask_close`` is
     applied to it as well, with a log line).  With a mask every value is the (2, 5) tensor of ``volume_metrics(mask=...)`` - row 0 the whole
     volume, row 1 the foreground - and the returned ``VolumeScores`` carries ``.mask``, ``.mask_count`` and ``.mask_stats``.
-    Without one nothing changes."""
+    Without one nothing changes.  ``mask_largest`` / ``mask_fill_holes`` (``"3d"`` or an axis 0..2) clean the mask after the closing,
+    ``"otsu"`` and a given tensor alike (``foreground_mask``'s ``largest`` / ``fill_holes``); ``.mask_cleanup`` then holds what they
+    found.  Both need a mask."""
     # the checks that need no data come first, the device check after them
     if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or ref.dim() != 3 or ref.numel() == 0:
         raise ValueError(f"expected a non-empty float32 volume (X,Y,Z), got {getattr(ref, 'dtype', type(ref))} "
@@ -426,8 +628,11 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     if mask is None:
         if mask_close != 0:
             raise ValueError("mask_close needs a mask")
+        if mask_largest or mask_fill_holes is not None:
+            raise ValueError("mask_largest and mask_fill_holes need a mask")
     else:
         _check_radius(mask_close)
+        fill = _check_fill(mask_fill_holes)
         if isinstance(mask, str):
             if mask != "otsu":
                 raise ValueError(f"mask must be None, 'otsu' or a tensor, got {mask!r}")
@@ -467,11 +672,13 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     score = {}                                                    # the mask, once per volume, for every method
     if mask is not None:
         if isinstance(mask, str):
-            score["mask"], results.mask_stats = foreground_mask(ref, mask_close)
+            score["mask"], results.mask_stats = foreground_mask(ref, mask_close, bool(mask_largest), mask_fill_holes)
+            results.mask_cleanup = results.mask_stats.cleanup
         else:
             if mask_close:
                 logger.info(f"Closing the given mask with radius {mask_close}.")
-            score["mask"] = binary_close(_check_mask(mask, ref.shape, "evaluate_volume"), mask_close)
+            closed = binary_close(_check_mask(mask, ref.shape, "evaluate_volume"), mask_close)
+            score["mask"], results.mask_cleanup = _clean_mask(closed, bool(mask_largest), fill)
         results.mask = score["mask"]
     if isotropic:
         results["unet"] = volume_metrics(enhance_volume_isotropic(model, lr, **common), ref, val_range, **score)

@@ -20,6 +20,12 @@ file of the reference's spatial shape instead (any voxel type, non-zero = foregr
 scan then prints a second table headed "foreground" (voxel count, share of the volume, Otsu threshold), the means come for both
 regions, and the CSV gains a ``region`` column (``whole`` / ``foreground``).  Still one pass over the volumes per method and one
 download per volume.
+
+``--mask_largest`` keeps the largest 26-connected component of the (closed) mask - specks of background above the threshold go -
+and ``--mask_fill_holes 3d|0|1|2`` then fills its holes, those of the volume or of every plane across an axis - CSF, sinuses and
+ventricles come back (``csrc/volume_label.hip``: connected components on the device).  The "foreground" title then also says
+"N components, kept K voxels, filled F".  ``--save_mask PATH`` writes the mask that was actually scored, after crop and clean-up,
+as a uint8 NIfTI under the reference's header (one reference only; a 4-D reference gives a 4-D mask).  All three need ``--mask``.
 """
 import argparse
 import csv
@@ -35,7 +41,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
-from mri_superresolution_amd.utils.nifti import read_nifti                # noqa: E402
+from mri_superresolution_amd.utils.nifti import read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_eval import evaluate_volume, otsu_threshold_value      # noqa: E402
 
 logger = logging.getLogger("evaluate_volume")
@@ -61,11 +67,13 @@ def load_mask(mask_path, ref, reference_path):
 
 
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
-               use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0):
+               use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
+               save_mask=None):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
-    ``"threshold"``."""
-    ref, _ = read_nifti(reference_path)
+    ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
+    step that is off).  ``save_mask``: the masks scored go to this NIfTI file."""
+    ref, ref_header = read_nifti(reference_path)
     low = read_nifti(input_path)[0] if input_path else None
     if low is not None and low.ndim != ref.ndim:
         raise ValueError(f"{input_path} has {low.ndim} axes, {reference_path} has {ref.ndim}")
@@ -75,30 +83,44 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     mask_frames = load_mask(mask, ref, reference_path) if mask not in (None, "otsu") else None
     graphs = graph_cache if graph_cache is not None else {}
     name = os.path.basename(reference_path)
-    rows = []
+    rows, saved = [], []
     for t, frame in enumerate(ref_frames):
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
         lr = torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device) if low_frames is not None else None
         m = mask if mask_frames is None else torch.from_numpy(mask_frames[t]).to(device)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
-                              use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close)
+                              use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
+                              mask_fill_holes=mask_fill_holes)
         scan = name if len(ref_frames) == 1 else f"{name}[t={t}]"
         if mask is None:
             values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
             for method, vals in zip(res, values):
                 rows.append({"scan": scan, "method": method, **dict(zip(METRIC_COLUMNS, (float(v) for v in vals)))})
             continue
-        # the (2, 5) results of every method, the mask's voxel count and the four mask statistics: still one download per volume
+        # the (2, 5) results of every method, the clean-up's three numbers, the mask's voxel count and the four mask statistics:
+        # still one download per volume
         stats = res.mask_stats if res.mask_stats is not None else torch.full((4,), float("nan"), dtype=torch.float64, device=device)
-        down = torch.cat([v.reshape(10) for v in res.values()] + [res.mask_count.reshape(1), stats]).cpu().numpy()
+        cleanup = res.mask_cleanup if res.mask_cleanup is not None else torch.full((3,), float("nan"), dtype=torch.float64, device=device)
+        down = torch.cat([v.reshape(10) for v in res.values()] + [cleanup, res.mask_count.reshape(1), stats]).cpu().numpy()
         lo, hi, tstar, _ = down[-4:]
         extra = {"voxels": int(res.mask.numel()), "mask_voxels": int(down[-5]),
-                 "threshold": otsu_threshold_value(lo, hi, int(tstar)) if res.mask_stats is not None else None}
+                 "threshold": otsu_threshold_value(lo, hi, int(tstar)) if res.mask_stats is not None else None,
+                 "cleanup": tuple(float(c) for c in down[-8:-5]) if res.mask_cleanup is not None else None}
+        if save_mask:
+            saved.append(res.mask.cpu().numpy())
         for r, region in enumerate(REGIONS):
             for i, method in enumerate(res):
                 vals = down[10 * i + 5 * r:10 * i + 5 * r + 5]
                 rows.append({"scan": scan, "region": region, "method": method, **extra,
                              **dict(zip(METRIC_COLUMNS, (float(v) for v in vals)))})
+    if save_mask:
+        data = saved[0] if ref.ndim == 3 else np.stack(saved, axis=3)
+        header = ref_header.copy()                              # the reference's, with the extents left after the crop
+        dim = list(header.get("dim"))
+        dim[1:4] = data.shape[:3]
+        header.set("dim", dim)
+        write_nifti(save_mask, data, header)
+        logger.info(f"Saved the mask {tuple(data.shape)} to {save_mask}")
     return rows
 
 
@@ -118,7 +140,13 @@ def mean_rows(rows):
 def foreground_title(rows):
     r = rows[0]
     title = f"foreground: {r['mask_voxels']} voxels, {100.0 * r['mask_voxels'] / r['voxels']:.1f} % of the volume"
-    return title + (f", Otsu threshold {r['threshold']:.6g}" if r["threshold"] is not None else "")
+    title += f", Otsu threshold {r['threshold']:.6g}" if r["threshold"] is not None else ""
+    if r.get("cleanup") is not None:
+        found, kept, filled = r["cleanup"]
+        parts = [f"{int(found)} components, kept {int(kept)} voxels"] if found == found else []      # NaN: that step is off
+        parts += [f"filled {int(filled)}"] if filled == filled else []
+        title += ", " + ", ".join(parts)
+    return title
 
 
 def main(args):
@@ -134,6 +162,10 @@ def main(args):
             raise ValueError(f"--data_range must be positive, got {args.data_range}")
         if args.mask is None and args.mask_close != 0:
             raise ValueError("--mask_close goes with --mask")
+        if args.mask is None and (args.mask_largest or args.mask_fill_holes is not None or args.save_mask):
+            raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
+        if args.save_mask and len(args.reference) != 1:
+            raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
             raise ValueError(f"--mask_close must be in 0..4, got {args.mask_close}")
         from scripts.infer import find_best_checkpoint, load_model
@@ -145,11 +177,12 @@ def main(args):
             ckpt = find_best_checkpoint(args.checkpoint_dir, args.model_type)
         logger.info(f"Checkpoint: {ckpt}")
         model = load_model(args.model_type, ckpt, device, base_filters=args.base_filters)
+        fill = args.mask_fill_holes if args.mask_fill_holes in (None, "3d") else int(args.mask_fill_holes)
         rows, graphs = [], {}
         regions = REGIONS if args.mask else (None,)
         for path in args.reference:
             scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
-                                   not args.no_graph, device, graphs, args.mask, args.mask_close)
+                                   not args.no_graph, device, graphs, args.mask, args.mask_close, args.mask_largest, fill, args.save_mask)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -200,6 +233,12 @@ def parse_args(argv=None):
                    help="score inside a foreground mask as well: 'otsu' (exact Otsu threshold of each reference volume, on the device) or "
                         "a NIfTI-1 mask of the reference's spatial shape (non-zero = foreground)")
     p.add_argument("--mask_close", type=int, default=0, help="close the mask with a box of this radius in voxels (0..4; needs --mask)")
+    p.add_argument("--mask_largest", action="store_true", help="keep the largest 26-connected component of the mask (needs --mask)")
+    p.add_argument("--mask_fill_holes", type=str, choices=["3d", "0", "1", "2"], default=None,
+                   help="fill the holes of the mask: those of the volume (3d) or of every plane across this axis (needs --mask)")
+    p.add_argument("--save_mask", type=str, default=None,
+                   help="write the mask that was scored, after crop and clean-up, as a uint8 NIfTI with the reference's header (one "
+                        "--reference; needs --mask)")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

@@ -17,6 +17,12 @@ Per shape, on a pair of float32 volumes in [0, 1] ("truth plus error"):
 (e) ``volume_metrics(mask=...)`` - the masked instantiation, 9 bytes per voxel - alternating with the unmasked call in one loop,
     so that the ratio of the two is taken on one box in one run.  ``--parent_lib PATH`` adds the unmasked kernel of another
     build of the library (called through ctypes, nothing else of it is used) to the same alternation.
+(f) connected components of that mask (csrc/volume_label.hip): ``label_components`` (26-connected; 3 launches), ``largest_component``
+    (5 launches) and ``fill_holes`` of the volume (4 launches), each with its time and voxels per second, and their sum next to one
+    masked metrics pass.  Algorithmic traffic, bytes per voxel: the local pass reads the mask and writes the labels (5; 9 with the
+    cleared side array), the merge pass reads the labels of the voxels on tile surfaces and their neighbours across (about 4 x 0.47
+    plus atomics), the flatten pass reads and writes the labels (8, plus one atomic per run of a wave), then 8 (largest: labels and
+    sizes) + 5 (select) or 9 (fill: mask, labels, marks gathered by root; mask written).
 Prints one JSON line (profiles/NOTES.md, "Volume evaluation")."""
 import argparse
 import json
@@ -117,7 +123,8 @@ def main():
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("volume_eval_bench needs the MI355X: there is nothing to time on a CPU")
-    from mri_superresolution_amd.volume_eval import binary_close, foreground_mask, otsu_mask, upscale2, volume_metrics
+    from mri_superresolution_amd.volume_eval import (binary_close, fill_holes, foreground_mask, label_components, largest_component,
+                                                     otsu_mask, upscale2, volume_metrics)
 
     res = {"gpu": torch.cuda.get_device_name(0), "window": 11, "shapes": {}}
     for text in args.shapes:
@@ -167,6 +174,17 @@ def main():
         r["ssim_whole_masked_call"], r["ssim_foreground"] = float(both[0, 0]), float(both[1, 0])
         if args.parent_lib:
             r["ssim_parent_kernel"] = float(psums[1]) / voxels
+        # (f) connected components of the head phantom's mask
+        for name, fn in (("label_components", lambda: label_components(mask, 26)), ("largest_component", lambda: largest_component(mask, 26)),
+                         ("fill_holes_3d", lambda: fill_holes(mask))):
+            r[name] = event_times(fn, args.reps, args.warmup)
+            r[name]["Gvoxels_per_s"] = round(voxels / (r[name]["us_median"] * 1e-6) / 1e9, 3)
+        kept, st3 = largest_component(mask, 26)
+        r["components"], r["kept_share"] = int(st3[0]), round(float(st3[1]) / voxels, 4)
+        r["filled"] = int(fill_holes(mask)[1])
+        r["cleanup_over_masked_metrics"] = round((r["largest_component"]["us_median"] + r["fill_holes_3d"]["us_median"])
+                                                 / r["alternating"]["masked"]["us_median"], 4)
+        del kept
         res["shapes"][text] = r
         del ref, pred, low, head, mask, mask0
     print(json.dumps(res))
