@@ -503,6 +503,7 @@ int mrisr_f32_window_restore(const float* y, const float* lohi, size_t pixels_pe
 #define MRISR_RESAMPLE_CUBIC 2      /* 4 taps, Keys kernel with A = -0.75                                                 */
 #define MRISR_RESAMPLE_AREA 3       /* dst <= src: box overlap weights; dst > src: the LINEAR taps (deviation)            */
 #define MRISR_RESAMPLE_LANCZOS4 4   /* 8 taps, sinc(x) sinc(x / 4), normalised to sum 1                                   */
+#define MRISR_RESAMPLE_NEAREST 5    /* 1 tap; mrisr_f32_volume_reslice only (mrisr_resample_taps refuses it)              */
 /* HOST helper, computed in double: for output sample d of a src -> dst resize, with scale = src / dst and
  * s = (d + 0.5) scale - 0.5, the *ntaps consecutive source samples around floor(s) (LANCZOS4: floor(s) - 3 .. floor(s) + 4)
  * clamped to [0, src - 1] (replicated border) and their weights; AREA: sample i weighs
@@ -628,6 +629,24 @@ int mrisr_u8_volume_keep_largest(const uint8_t* mask, int X, int Y, int Z, int c
  * 4 launches.                                                                                                                  */
 int mrisr_u8_volume_fill_holes(const uint8_t* mask, int X, int Y, int Z, int plane_axis, uint8_t* dst, double* stats1, void* workspace,
                                void* stream);
+
+/* ---- reslicing between voxel grids (extension; csrc/volume_reslice.hip).  m12: HOST pointer to the row-major 3 x 4 double matrix
+ *      that maps a destination voxel index (i, j, k) to a continuous source voxel index; it is read at the call and travels in the
+ *      kernel arguments.  Per axis a: p_a = ((m[a][0] i + m[a][1] j) + m[a][2] k) + m[a][3] in double, one rounded operation at a
+ *      time; a voxel with -0.5 <= p_a <= n_a - 0.5 on all three axes (tested in double) is interpolated, every other is `fill`.
+ *      MRISR_RESAMPLE_NEAREST: source index clip(floor(p_a + 0.5), 0, n_a - 1).  _LINEAR: f_a = floor(p_a), t_a = (float)(p_a - f_a),
+ *      weights (1 - t_a, t_a) on the taps f_a, f_a + 1.  _CUBIC: taps f_a - 1 .. f_a + 2, Keys weights (A = -0.75) in float32 at the
+ *      distances 1 + t, t, 1 - t, 2 - t: x <= 1: ((1.25 x - 2.25) x) x + 1, else ((-0.75 x + 3.75) x - 6) x + 3, not renormalised.
+ *      Taps are clamped to the volume (border replicated).  Reduction along z, then y, then x, each stage
+ *      ((w0 v0 + w1 v1) + w2 v2) + w3 v3 in float32, every product and sum rounded.  One launch on stream, one thread per
+ *      destination voxel, no host synchronisation (HIP-graph capturable).
+ *      Refusals, all before any launch: MRISR_E_ARG null pointer, a matrix entry that is not finite, another method;
+ *      MRISR_E_SHAPE an extent below 1; MRISR_E_UNSUPPORTED more than 2^31 - 1 voxels in src or in dst. --------------------------- */
+int mrisr_f32_volume_reslice(const float* src, int SX, int SY, int SZ, float* dst, int DX, int DY, int DZ, const double* m12,
+                             int method, float fill, void* stream);
+/* The NEAREST rule on uint8 volumes (masks, label maps).                                                                        */
+int mrisr_u8_volume_reslice_nearest(const uint8_t* src, int SX, int SY, int SZ, uint8_t* dst, int DX, int DY, int DZ,
+                                    const double* m12, uint8_t fill, void* stream);
 
 #ifdef __cplusplus
 }

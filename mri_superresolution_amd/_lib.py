@@ -20,6 +20,7 @@ WINDOW_F32, WINDOW_I16 = 0, 1      # MRISR_WINDOW_*: out_dtype of mrisr_f32_wind
 VOLBLEND_SET, VOLBLEND_ADD, VOLBLEND_FINISH = 0, 1, 2      # MRISR_VOLBLEND_*: mode of mrisr_f32_volume_up2_blend
 MORPH_DILATE, MORPH_ERODE = 0, 1      # MRISR_MORPH_*: op of mrisr_u8_volume_morph
 RESAMPLE_LINEAR, RESAMPLE_CUBIC, RESAMPLE_AREA, RESAMPLE_LANCZOS4 = 1, 2, 3, 4      # MRISR_RESAMPLE_*: method of mrisr_resample_taps
+RESAMPLE_NEAREST = 5      # MRISR_RESAMPLE_NEAREST: mrisr_f32_volume_reslice only
 PACK_RING = 256      # MRISR_PACK_RING: OR into transpose_flip for the ring weight layout (csrc/conv_ring.hip)
 PACK_UPADJ = 512     # MRISR_PACK_UPADJ: the W^T image of mrisr_conv_upadj (csrc/conv_upadj.hip)
 STAT_SLOTS = 16      # = MRISR_STAT_SLOTS of include/mrisr.h; load() replaces it with the library's compiled value
@@ -168,10 +169,12 @@ SIGNATURES = {
     "mrisr_u8_volume_label_workspace_bytes": (_sz, [_i, _i, _i]),
     "mrisr_u8_volume_keep_largest": (_i, [_vp, _i, _i, _i, _i, _vp, _dp, _vp, _vp]),
     "mrisr_u8_volume_fill_holes": (_i, [_vp, _i, _i, _i, _i, _vp, _dp, _vp, _vp]),
+    "mrisr_f32_volume_reslice": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, _f, _vp]),
+    "mrisr_u8_volume_reslice_nearest": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, C.POINTER(C.c_double), C.c_uint8, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 314      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 315      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

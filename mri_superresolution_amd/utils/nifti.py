@@ -3,6 +3,8 @@ numpy, ``struct`` and ``gzip`` - no nibabel.
 
 ``read_nifti(path)``                                  -> ``(float32 array in the file's index order, NiftiHeader)``
 ``write_nifti(path, data, header, upscaled_axes)``    the x2 output under the input's header, geometry moved with it
+``grid_matrix``, ``downscaled_affine``, ``respaced_grid``, ``header_for_grid``    grid arithmetic for reslicing one scan onto
+                                                      another's grid (``volume_reslice.py``), float64
 
 What the reference sees of a volume is ``nib.load(path).get_fdata().astype(np.float32)`` (``utils/extraction_utils.py:118``):
 the stored values, scaled by ``scl_slope`` / ``scl_inter`` in float64 when a slope is set, cast to float32.
@@ -186,6 +188,87 @@ def upscaled_affine(affine: np.ndarray, upscaled_axes: Sequence[int]) -> np.ndar
         out[:3, 3] -= 0.25 * src[:3, a]
         out[:3, a] = 0.5 * src[:3, a]
     return out
+
+
+def downscaled_affine(affine: np.ndarray, axes: Sequence[int]) -> np.ndarray:
+    """The exact inverse of ``upscaled_affine``: columns of ``axes`` doubled, translation moved by plus a quarter of the NEW
+    columns - the grid on which a x2 pass over ``axes`` expects its low-resolution input."""
+    src = np.asarray(affine, dtype=np.float64)
+    out = src.copy()
+    for a in axes:
+        out[:3, a] = 2.0 * src[:3, a]
+        out[:3, 3] += 0.25 * out[:3, a]
+    return out
+
+
+def _check_affine(affine, what) -> np.ndarray:
+    a = np.asarray(affine, dtype=np.float64)
+    if a.shape != (4, 4):
+        raise ValueError(f"{what} must be a 4 x 4 index -> world affine, got shape {a.shape}")
+    return a
+
+
+def grid_matrix(src_affine: np.ndarray, dst_affine: np.ndarray) -> np.ndarray:
+    """(3, 4) float64: the first three rows of ``inv(src_affine) @ dst_affine`` (``np.linalg.solve``) - a voxel index of the
+    destination grid -> the continuous voxel index of the source grid.  A singular or non-finite ``src_affine`` (or a non-finite
+    ``dst_affine``) is a ``ValueError``."""
+    src, dst = _check_affine(src_affine, "src_affine"), _check_affine(dst_affine, "dst_affine")
+    if not np.isfinite(src).all() or not np.isfinite(dst).all():
+        raise ValueError("grid_matrix: an affine has an entry that is not finite")
+    try:
+        with np.errstate(all="ignore"):
+            m = np.linalg.solve(src, dst)
+    except np.linalg.LinAlgError as e:
+        raise ValueError(f"grid_matrix: the source affine is singular ({e})") from None
+    if not np.isfinite(m).all() or np.linalg.matrix_rank(src) < 4:
+        raise ValueError("grid_matrix: the source affine is singular")
+    return np.ascontiguousarray(m[:3])
+
+
+def respaced_grid(affine: np.ndarray, shape: Sequence[int], spacing: Sequence[float]):
+    """-> ``(affine', shape')``: the grid of ``(affine, shape)`` with the voxel size of axis ``a`` changed to ``spacing[a]`` (``None``
+    or 0 keeps the axis).  Voxels are cells with their centres at the integer indices.  Per axis: ``s = |affine[:3, a]|``,
+    ``n' = max(1, ceil(n s / s' - 1e-6))``, ``col' = col s' / s``; translation ``t' = t - sum(col) / 2 + sum(col') / 2``: the
+    corner of the first cell stays where it was in world space.  Halving the spacing of two or three axes gives
+    ``upscaled_affine`` and the doubled shape."""
+    src = _check_affine(affine, "affine")
+    shape = tuple(int(d) for d in shape)
+    if len(shape) != 3 or any(d < 1 for d in shape) or len(tuple(spacing)) != 3:
+        raise ValueError(f"respaced_grid takes three positive extents and three spacings, got {shape} and {tuple(spacing)}")
+    out, new_shape = src.copy(), list(shape)
+    for a, want in enumerate(spacing):
+        if want is None or want == 0:
+            continue
+        s = float(np.linalg.norm(src[:3, a]))
+        if not (np.isfinite(want) and want > 0) or not (np.isfinite(s) and s > 0):
+            raise ValueError(f"respaced_grid: spacing {want} for axis {a} of voxel size {s} (both must be positive and finite)")
+        new_shape[a] = max(1, int(np.ceil(shape[a] * s / float(want) - 1e-6)))
+        out[:3, a] = src[:3, a] * (float(want) / s)
+    out[:3, 3] = src[:3, 3] - 0.5 * src[:3, :3].sum(axis=1) + 0.5 * out[:3, :3].sum(axis=1)
+    return out, tuple(new_shape)
+
+
+def header_for_grid(header: NiftiHeader, shape: Sequence[int], affine: np.ndarray) -> NiftiHeader:
+    """A copy of ``header`` for a volume on the grid ``(affine, shape)``: ``dim[1..3]`` from ``shape``, ``pixdim[1..3]`` the
+    column norms of ``affine``, ``srow_*`` its rows, ``sform_code`` kept when positive (else 1) and ``qform_code = 0`` - a
+    general affine has no quaternion form, the sform alone then defines the grid.  ``dim[0]``, ``dim[4]``, the byte order and
+    everything else are kept; ``write_nifti(path, data, that_header)`` takes it as it is."""
+    aff = _check_affine(affine, "affine")
+    shape = tuple(int(d) for d in shape)
+    if len(shape) != 3 or any(not 1 <= d <= 32767 for d in shape) or not np.isfinite(aff).all():
+        raise ValueError(f"header_for_grid takes three extents in 1..32767 and a finite affine, got {shape}")
+    hdr = header.copy()
+    dim, pix = list(hdr.get("dim")), list(hdr.get("pixdim"))
+    dim[1:4] = shape
+    pix[1:4] = [float(np.linalg.norm(aff[:3, a])) for a in range(3)]
+    hdr.set("dim", dim)
+    hdr.set("pixdim", pix)
+    for row, name in enumerate(("srow_x", "srow_y", "srow_z")):
+        hdr.set(name, [float(v) for v in aff[row]])
+    if hdr.get("sform_code") <= 0:
+        hdr.set("sform_code", 1)
+    hdr.set("qform_code", 0)
+    return hdr
 
 
 def write_nifti(path: str, data: np.ndarray, header: NiftiHeader, upscaled_axes: Sequence[int] = ()):

@@ -26,6 +26,13 @@ and ``--mask_fill_holes 3d|0|1|2`` then fills its holes, those of the volume or 
 ventricles come back (``csrc/volume_label.hip``: connected components on the device).  The "foreground" title then also says
 "N components, kept K voxels, filled F".  ``--save_mask PATH`` writes the mask that was actually scored, after crop and clean-up,
 as a uint8 NIfTI under the reference's header (one reference only; a 4-D reference gives a 4-D mask).  All three need ``--mask``.
+
+``--align header`` (with ``--input``) lifts the demand of exactly half the extents: the input scan is resliced on the device through
+the two headers' affines (``volume_reslice.reslice``, ``--align_interp linear|cubic``) onto the grid a x2 pass expects -
+``utils.nifti.downscaled_affine`` of the reference's affine over the doubled axes, the reference's extents (after its crop to even
+ones) halved on them - whatever its spacing, field of view, axis order or rotation; the share of that grid the input covers is
+logged.  A ``--mask PATH`` on another grid is then resliced onto the reference's grid with ``nearest``.  The transform is never
+estimated: the headers are taken as they are.
 """
 import argparse
 import csv
@@ -41,8 +48,9 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
-from mri_superresolution_amd.utils.nifti import read_nifti, write_nifti   # noqa: E402
+from mri_superresolution_amd.utils.nifti import downscaled_affine, grid_matrix, read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_eval import evaluate_volume, otsu_threshold_value      # noqa: E402
+from mri_superresolution_amd.volume_reslice import covered_share, reslice, reslice_mask    # noqa: E402
 
 logger = logging.getLogger("evaluate_volume")
 CSV_COLUMNS = ["scan", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # the column style of scripts/evaluate.py
@@ -54,40 +62,73 @@ def _frames(data):
     return [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
 
 
-def load_mask(mask_path, ref, reference_path):
-    """-> one uint8 frame per timepoint of the reference (a 3-D mask serves them all)."""
-    data, _ = read_nifti(mask_path)
-    if data.ndim not in (3, 4) or tuple(data.shape[:3]) != tuple(ref.shape[:3]):
+def load_mask(mask_path, ref, reference_path, ref_affine=None):
+    """-> one uint8 frame per timepoint of the reference (a 3-D mask serves them all).  ``ref_affine`` (``--align header``): the
+    mask may lie on any grid and is resliced onto the reference's through the two affines with ``nearest``, on the device; the
+    frames are then CUDA tensors."""
+    data, mask_header = read_nifti(mask_path)
+    if ref_affine is None and (data.ndim not in (3, 4) or tuple(data.shape[:3]) != tuple(ref.shape[:3])):
         raise ValueError(f"mask {mask_path} has shape {tuple(data.shape)}, {reference_path} has {tuple(ref.shape)}")
     frames = [np.ascontiguousarray((f != 0).astype(np.uint8)) for f in _frames(data)]
     count = 1 if ref.ndim == 3 else ref.shape[3]
     if data.ndim == 4 and len(frames) != count:
         raise ValueError(f"mask {mask_path} has {len(frames)} timepoints, {reference_path} has {count}")
+    if ref_affine is not None:
+        m = grid_matrix(mask_header.affine(), ref_affine)
+        frames = [reslice_mask(torch.from_numpy(f).cuda(), m, ref.shape[:3]) for f in frames]
+        logger.info(f"Mask {mask_path} {tuple(data.shape[:3])} resliced onto the reference grid {tuple(ref.shape[:3])} (nearest).")
     return frames if data.ndim == 4 else frames * count
 
 
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
-               save_mask=None):
+               save_mask=None, align=None, align_interp="linear"):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
-    step that is off).  ``save_mask``: the masks scored go to this NIfTI file."""
+    step that is off).  ``save_mask``: the masks scored go to this NIfTI file.  ``align="header"``: ``input_path`` (and a mask file)
+    may lie on any grid and are resliced through the headers' affines (module docstring)."""
+    if align not in (None, "header"):
+        raise ValueError(f"align must be None or 'header', got {align!r}")
+    if align and not input_path:
+        raise ValueError("--align goes with --input")
+    if align and align_interp not in ("linear", "cubic"):
+        raise ValueError(f"--align_interp must be linear or cubic, got {align_interp}")
     ref, ref_header = read_nifti(reference_path)
-    low = read_nifti(input_path)[0] if input_path else None
+    low, low_header = read_nifti(input_path) if input_path else (None, None)
     if low is not None and low.ndim != ref.ndim:
         raise ValueError(f"{input_path} has {low.ndim} axes, {reference_path} has {ref.ndim}")
     if low is not None and low.ndim == 4 and low.shape[3] != ref.shape[3]:
         raise ValueError(f"{input_path} has {low.shape[3]} timepoints, {reference_path} has {ref.shape[3]}")
     ref_frames, low_frames = _frames(ref), (_frames(low) if low is not None else None)
-    mask_frames = load_mask(mask, ref, reference_path) if mask not in (None, "otsu") else None
+    mask_frames = load_mask(mask, ref, reference_path, ref_header.affine() if align else None) if mask not in (None, "otsu") else None
+    if align:
+        # the grid a x2 pass over the doubled axes expects its input on; the crop takes trailing voxels, so the affine stays
+        axes = (0, 1, 2) if isotropic else tuple(a for a in (0, 1, 2) if a != axis)
+        crop = tuple(d - d % 2 if a in axes else d for a, d in enumerate(ref.shape[:3]))
+        if 0 in crop:
+            raise ValueError(f"nothing is left of the reference volume {tuple(ref.shape[:3])} after cropping to even extents")
+        if crop != tuple(ref.shape[:3]):
+            logger.warning(f"Reference volume {tuple(ref.shape[:3])} has an odd extent on a doubled axis: cropped to {crop}.")
+            ref_frames = [f[:crop[0], :crop[1], :crop[2]] for f in ref_frames]
+            if mask_frames is not None:
+                mask_frames = [f[:crop[0], :crop[1], :crop[2]].contiguous() for f in mask_frames]
+        low_shape = tuple(d // 2 if a in axes else d for a, d in enumerate(crop))
+        m = grid_matrix(low_header.affine(), downscaled_affine(ref_header.affine(), axes))
+        low_frames = [reslice(torch.from_numpy(np.ascontiguousarray(f)).to(device), m, low_shape, align_interp) for f in low_frames]
+        share = float(covered_share(low.shape[:3], m, low_shape, device))
+        logger.info(f"{input_path} {tuple(low.shape[:3])} resliced onto the low-resolution grid {low_shape} of {reference_path} "
+                    f"({align_interp}); it covers {100.0 * share:.2f} % of that grid.")
     graphs = graph_cache if graph_cache is not None else {}
     name = os.path.basename(reference_path)
     rows, saved = [], []
     for t, frame in enumerate(ref_frames):
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
-        lr = torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device) if low_frames is not None else None
-        m = mask if mask_frames is None else torch.from_numpy(mask_frames[t]).to(device)
+        lr, m = None, mask
+        if low_frames is not None:      # with --align the frames are on the device already
+            lr = low_frames[t] if align else torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device)
+        if mask_frames is not None:
+            m = mask_frames[t] if align else torch.from_numpy(mask_frames[t]).to(device)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
                               mask_fill_holes=mask_fill_holes)
@@ -164,6 +205,8 @@ def main(args):
             raise ValueError("--mask_close goes with --mask")
         if args.mask is None and (args.mask_largest or args.mask_fill_holes is not None or args.save_mask):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
+        if args.align and not args.input:
+            raise ValueError("--align goes with --input")
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -182,7 +225,8 @@ def main(args):
         regions = REGIONS if args.mask else (None,)
         for path in args.reference:
             scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
-                                   not args.no_graph, device, graphs, args.mask, args.mask_close, args.mask_largest, fill, args.save_mask)
+                                   not args.no_graph, device, graphs, args.mask, args.mask_close, args.mask_largest, fill, args.save_mask,
+                                   args.align, args.align_interp)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -239,6 +283,10 @@ def parse_args(argv=None):
     p.add_argument("--save_mask", type=str, default=None,
                    help="write the mask that was scored, after crop and clean-up, as a uint8 NIfTI with the reference's header (one "
                         "--reference; needs --mask)")
+    p.add_argument("--align", type=str, choices=["header"], default=None,
+                   help="reslice --input (and a --mask file) through the NIfTI headers' affines onto the grid the reference implies, "
+                        "instead of demanding exactly half its extents (needs --input)")
+    p.add_argument("--align_interp", type=str, choices=["linear", "cubic"], default="linear", help="interpolation of the --align reslice")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

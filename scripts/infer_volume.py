@@ -14,6 +14,11 @@ search order and the exit code (0 / 1, error logged) are those of ``scripts/infe
 ``--isotropic`` doubles all three axes: the slices across axis 0, 1 and 2 are enhanced in turn, each result is interpolated
 along its own slice axis and the three are averaged on the device (``volume.enhance_volume_isotropic``,
 ``csrc/volume_blend.hip``); a 1 mm scan comes out at 0.5 mm in every direction.
+
+``--spacing SX SY SZ`` (mm, 0 keeps an axis) reslices the uploaded volume to that voxel size on the device before windowing and
+enhancement (``volume_reslice.reslice``, ``--spacing_interp linear|cubic``): a 1.5 x 1.5 x 5 mm scan with
+``--spacing 0 0 1.5 --isotropic`` comes out at 0.75 mm in every direction.  The output header is that of the respaced grid
+(``utils.nifti.respaced_grid`` / ``header_for_grid``) after the x2 write.
 """
 import argparse
 import logging
@@ -27,28 +32,41 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import read_nifti, write_nifti   # noqa: E402
+from mri_superresolution_amd.utils.nifti import grid_matrix, header_for_grid, read_nifti, respaced_grid, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume import enhance_volume, enhance_volume_isotropic   # noqa: E402
+from mri_superresolution_amd.volume_reslice import reslice               # noqa: E402
 from scripts.infer import find_best_checkpoint, load_model               # noqa: E402
 
 logger = logging.getLogger("infer_volume")
 
 
 def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_amp=False, use_graph=True, output_dtype="float32",
-                   device="cuda", isotropic=False):
-    """NIfTI file -> NIfTI file; returns the output array (as written)."""
+                   device="cuda", isotropic=False, spacing=None, spacing_interp="linear"):
+    """NIfTI file -> NIfTI file; returns the output array (as written).  ``spacing`` (three voxel sizes in mm, 0 or ``None`` keeps
+    an axis): every volume is resliced to that spacing on the device before it is windowed and enhanced."""
     data, header = read_nifti(input_path)
     dtype = {"float32": torch.float32, "int16": torch.int16}[output_dtype]
     in_plane = (0, 1, 2) if isotropic else tuple(a for a in (0, 1, 2) if a != axis)
     if isotropic:
         logger.info("Isotropic mode: slices across all three axes, every axis doubled; --axis is not used.")
-    if any(data.shape[a] % 8 for a in in_plane):
-        logger.warning(f"In-plane dimensions {tuple(data.shape[a] for a in in_plane)} are not divisible by 8. This might affect "
+    shape, regrid = tuple(data.shape[:3]), None
+    if spacing is not None and any(spacing):
+        if spacing_interp not in ("linear", "cubic"):
+            raise ValueError(f"--spacing_interp must be linear or cubic, got {spacing_interp}")
+        affine = header.affine()
+        new_affine, shape = respaced_grid(affine, shape, spacing)
+        regrid = grid_matrix(affine, new_affine)
+        header = header_for_grid(header, shape, new_affine)
+        logger.info(f"Reslicing {tuple(data.shape[:3])} to {shape} voxels ({spacing_interp}) before enhancement.")
+    if any(shape[a] % 8 for a in in_plane):
+        logger.warning(f"In-plane dimensions {tuple(shape[a] for a in in_plane)} are not divisible by 8. This might affect "
                        "performance or spatial accuracy due to model pooling layers.")
     frames = [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
     outs, graphs = [], {}
     for frame in frames:
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
+        if regrid is not None:
+            vol = reslice(vol, regrid, shape, spacing_interp)
         if isotropic:
             out = enhance_volume_isotropic(model, vol, batch_size=batch_size, use_amp=use_amp, use_graph=use_graph, out_dtype=dtype,
                                            graph_cache=graphs)
@@ -81,7 +99,8 @@ def main(args):
             logger.info(f"Automatically selected checkpoint: {ckpt}")
         model = load_model(args.model_type, ckpt, device, base_filters=args.base_filters)
         process_volume(model, args.input, args.output, args.axis, args.batch_size, args.use_amp, not args.no_graph,
-                       args.output_dtype, device, isotropic=args.isotropic)
+                       args.output_dtype, device, isotropic=args.isotropic, spacing=getattr(args, "spacing", None),
+                       spacing_interp=getattr(args, "spacing_interp", "linear"))
         logger.info("Inference completed successfully!")
         return 0
     except Exception as e:
@@ -109,6 +128,11 @@ def parse_args(argv=None):
     p.add_argument("--no_graph", action="store_true", help="(extension) do not replay the forward of full batches as a HIP graph")
     p.add_argument("--output_dtype", type=str, choices=["float32", "int16"], default="float32",
                    help="(extension) stored type of the output: float32, or int16 rounded half to even and saturated")
+    # absent from the namespace unless given: the parsed defaults are those of a build without the two flags
+    p.add_argument("--spacing", type=float, nargs=3, default=argparse.SUPPRESS, metavar=("SX", "SY", "SZ"),
+                   help="(extension) reslice the volume to this voxel size in mm on the device before enhancement; 0 keeps an axis")
+    p.add_argument("--spacing_interp", type=str, choices=["linear", "cubic"], default=argparse.SUPPRESS,
+                   help="(extension) interpolation of the --spacing reslice (default: linear)")
     return p.parse_args(argv)
 
 
