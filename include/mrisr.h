@@ -648,6 +648,28 @@ int mrisr_f32_volume_reslice(const float* src, int SX, int SY, int SZ, float* ds
 int mrisr_u8_volume_reslice_nearest(const uint8_t* src, int SX, int SY, int SZ, uint8_t* dst, int DX, int DY, int DZ,
                                     const double* m12, uint8_t fill, void* stream);
 
+/* ---- rigid registration: the similarity measure (extension; csrc/volume_register.hip).  The joint histogram of `fixed` and `moving`
+ *      under K candidate matrices at once.  m12s: HOST pointer to K row-major 3 x 4 double matrices, fixed voxel index -> continuous
+ *      moving voxel index; they are read at the call and travel in the kernel arguments.  The samples are the fixed voxels
+ *      (i s, j s, k s), s = stride; with m' = m, its first three columns times s, the coordinate, the inside test and the moving value
+ *      of sample (i, j, k) are those of mrisr_f32_volume_reslice(MRISR_RESAMPLE_LINEAR) under m'.  The bin of a value v with range
+ *      (lo, hi), both converted to float32: x = (v - lo) * scale in float32, scale = (float)bins / (hi - lo);
+ *      bin = min(bins - 1, (int)clamp(x, 0, bins)).  A sample counts when it is inside and neither value is NaN:
+ *      hist[c][bin_fixed][bin_moving] += 1.  hist: DEVICE int64 [K][bins][bins], zeroed by the call (whatever it held).  A memset and
+ *      one launch on stream, no host synchronisation (HIP-graph capturable).
+ *      Refusals, all before any launch: MRISR_E_ARG null pointer, K outside 1..16, stride not 1, 2, 4 or 8, bins not 16, 32 or 64, a
+ *      range that is not finite in float32 or has hi <= lo or an infinite scale, a matrix entry that is not finite (after the
+ *      scaling by stride); MRISR_E_SHAPE an extent below 1; MRISR_E_UNSUPPORTED more than 2^31 - 1 voxels in fixed or in moving. */
+int mrisr_f32_volume_joint_histogram(const float* fixed, int FX, int FY, int FZ, const float* moving, int MX, int MY, int MZ,
+                                     const double* m12s, int K, int stride, int bins, double fixed_lo, double fixed_hi, double moving_lo,
+                                     double moving_hi, long long* hist, void* stream);
+/* Normalised mutual information of K joint histograms (DEVICE int64 [K][bins][bins]), one workgroup each: N = sum H, P = H / N,
+ * entropies -sum p ln p over the positive cells of the row sums (H_f), the column sums (H_m) and the cells (H_fm), in double;
+ * values[c] = (H_f + H_m) / H_fm, 0.0 where H_fm == 0, -infinity where N < max(min_count, 1); counts[c] = N.  values, counts:
+ * DEVICE, K doubles and K int64.  MRISR_E_ARG: null pointer, K outside 1..16, bins not 16, 32 or 64, min_count negative.          */
+int mrisr_joint_histogram_nmi(const long long* hist, int K, int bins, long long min_count, double* values, long long* counts,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

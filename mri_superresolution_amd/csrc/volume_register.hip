@@ -1,0 +1,261 @@
+// The similarity measure of rigid registration on the device (gfx950; extension): the joint histogram of a
+// fixed volume and a moving volume seen through up to 16 candidate matrices, and the normalised mutual information of each.
+//
+// Restates joint_histogram_np / nmi_np of mri_superresolution_amd/volume_register.py; the histograms are equal to the
+// specification's as integers (compiled with -ffp-contract=off).  A volume is (X, Y, Z) in C order, Z fastest.
+//
+//   samples      the fixed voxels (i s, j s, k s), s = stride: the sample grid has ceil(F_a / s) points along axis a
+//   coordinate   m' = m with its first three columns times s (exact: s is a power of two; done on the host).
+//                p_a = ((m'[a][0] i + m'[a][1] j) + m'[a][2] k) + m'[a][3] in double from the sample index (i, j, k), never stepped
+//   inside       -0.5 <= p_a <= n_a - 0.5 on all three axes of the moving volume, in double
+//   moving value the LINEAR rule of volume_reslice.hip through the same functions (volume_taps.h): taps f_a, f_a + 1 clamped,
+//                weights (1 - t_a, t_a) in float32, reduction along z, then y, then x
+//   bin          x = (v - lo) * scale in float32, scale = (float)bins / (hi - lo) (host, float32);
+//                bin = min(bins - 1, (int)clamp(x, 0, bins)): the Otsu histogram's rule, clamped at both ends before the
+//                conversion, so that +-infinity and huge values have a defined bin
+//   counted      inside, and neither the fixed nor the moving value is NaN:  H[k][bin_fixed][bin_moving] += 1
+//
+// A workgroup of 256 threads owns a compact kBX x kBY x kBZ brick of samples (under any rotation its moving footprint is a small box)
+// and one candidate (blockIdx.y), unless built with -DMRISR_REGISTER_KLOOP=1: then it loops over all K candidates and loads the
+// fixed value and its bin once (profiles/NOTES.md, "Register", has both timings).  A thread walks kWalk consecutive samples along
+// x at one (y, z) - neighbours in smooth anatomy fall into the same cell - and merges a run of equal cells in a register before
+// the atomic on the workgroup's 32-bit LDS histogram (bins^2 words, 16 KiB at 64 bins; a brick has 1024 samples: 32 bits
+// suffice).  The non-zero cells of the LDS histogram go to the 64-bit global histogram with one atomic each.  The matrices travel
+// by value in the kernel arguments (K x 96 bytes); the call zeroes `hist` with a memset node on the stream: nothing is uploaded,
+// nothing synchronises.  Every loop has a compile-time or argument bound; no workgroup waits for another.
+//
+// nmi: one workgroup per candidate.  Row and column sums and N as integers; P = H / N; the entropies -sum p ln p over the
+// positive cells in double; value = (H_f + H_m) / H_fm, 0.0 where H_fm == 0, -infinity where N < max(min_count, 1).
+#include "volume_taps.h"
+
+#ifndef MRISR_REGISTER_KLOOP
+#define MRISR_REGISTER_KLOOP 0
+#endif
+constexpr bool kLoopCandidates = MRISR_REGISTER_KLOOP != 0;
+constexpr int kMaxCandidates = 16, kMaxBins = 64;
+constexpr int kBX = 8, kBY = 8, kBZ = 16;                  // the brick of samples (x, y, z)
+constexpr int kSegs = 256 / (kBY * kBZ), kWalk = kBX / kSegs;      // x segments per brick, samples a thread walks
+static_assert(kSegs * kBY * kBZ == 256 && kSegs * kWalk == kBX, "256 threads cover a brick in kWalk steps");
+constexpr long long kMaxVoxels = 2147483647LL;             // 2^31 - 1 on either side
+
+struct Candidates {
+    double m[kMaxCandidates][12];                          // row-major 3 x 4 each, the columns already times the stride
+};
+struct BinRule {
+    float lo, scale, top;                                  // top = (float)bins
+    int bins;
+};
+
+__device__ __forceinline__ int value_bin(float v, const BinRule& r) {
+    const float x = __fmul_rn(__fsub_rn(v, r.lo), r.scale);
+    return min(r.bins - 1, (int)fminf(fmaxf(x, 0.f), r.top));      // truncation; fmaxf(NaN, 0) = 0
+}
+
+// a run of equal cells in a register: flushed to the LDS histogram when the cell changes
+struct CellRun {
+    int cell;
+    unsigned len;
+    __device__ __forceinline__ void add(int c, unsigned* hist) {
+        if (c == cell) {
+            ++len;
+        } else {
+            if (len) atomicAdd(&hist[cell], len);
+            cell = c;
+            len = 1u;
+        }
+    }
+    __device__ __forceinline__ void flush(unsigned* hist) {
+        if (len) atomicAdd(&hist[cell], len);
+        len = 0u;
+    }
+};
+
+// the moving value at sample (i, j, k) under matrix m; false: outside
+__device__ __forceinline__ bool moving_value(const float* __restrict__ mov, int MX, int MY, int MZ, const double* m, int i, int j, int k,
+                                             float* out) {
+    const double di = (double)i, dj = (double)j, dk = (double)k;
+    const int n[3] = {MX, MY, MZ};
+    double p[3];
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        p[a] = grid_coordinate(m + 4 * a, di, dj, dk);
+        inside = inside && p[a] >= -0.5 && p[a] <= (double)n[a] - 0.5;
+    }
+    if (!inside) return false;
+    int ix[2], iy[2], iz[2];
+    float wx[2], wy[2], wz[2];
+    axis_taps<kLinear>(p[0], MX, ix, wx);
+    axis_taps<kLinear>(p[1], MY, iy, wy);
+    axis_taps<kLinear>(p[2], MZ, iz, wz);
+    float rx[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        float ry[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const float* row = mov + ((size_t)ix[a] * MY + iy[b]) * MZ;
+            const float v[2] = {row[iz[0]], row[iz[1]]};
+            ry[b] = weighted_sum<2>(wz, v);
+        }
+        rx[a] = weighted_sum<2>(wy, ry);
+    }
+    *out = weighted_sum<2>(wx, rx);
+    return true;
+}
+
+// grid (bricks, K) - or (bricks, 1) with the candidate loop; (SX, SY, SZ): the sample grid
+__global__ __launch_bounds__(256) void joint_histogram_kernel(const float* __restrict__ fix, int FY, int FZ, int SX, int SY, int SZ,
+                                                              int stride, const float* __restrict__ mov, int MX, int MY, int MZ,
+                                                              Candidates cand, int K, BinRule rf, BinRule rm,
+                                                              unsigned long long* __restrict__ hist, unsigned nby, unsigned nbz) {
+    __shared__ unsigned lds[kMaxBins * kMaxBins];
+    const int tid = threadIdx.x, cells = rf.bins * rf.bins;
+    const unsigned bz = blockIdx.x % nbz, rest = blockIdx.x / nbz, by = rest % nby, bx = rest / nby;
+    const int k = (int)bz * kBZ + tid % kBZ, j = (int)by * kBY + tid / kBZ % kBY, i0 = (int)bx * kBX + tid / (kBZ * kBY) * kWalk;
+    const bool column = j < SY && k < SZ;
+    // the fixed values of this thread's walk and their bins: once, whatever the number of candidates
+    int fbin[kWalk];
+#pragma unroll
+    for (int w = 0; w < kWalk; ++w) {
+        fbin[w] = -1;                                                     // no sample, or a NaN
+        if (column && i0 + w < SX) {
+            const float fv = fix[((size_t)(i0 + w) * stride * FY + (size_t)j * stride) * FZ + (size_t)k * stride];
+            if (fv == fv) fbin[w] = value_bin(fv, rf);
+        }
+    }
+    const int kfirst = kLoopCandidates ? 0 : (int)blockIdx.y, klast = kLoopCandidates ? K : kfirst + 1;
+    for (int c = kfirst; c < klast; ++c) {                                 // at most 16 rounds
+        for (int e = tid; e < cells; e += 256) lds[e] = 0u;
+        __syncthreads();
+        CellRun run{0, 0u};
+#pragma unroll
+        for (int w = 0; w < kWalk; ++w) {
+            float mv;
+            if (fbin[w] >= 0 && moving_value(mov, MX, MY, MZ, cand.m[c], i0 + w, j, k, &mv) && mv == mv)
+                run.add(fbin[w] * rf.bins + value_bin(mv, rm), lds);
+        }
+        run.flush(lds);
+        __syncthreads();
+        unsigned long long* out = hist + (size_t)c * cells;
+        for (int e = tid; e < cells; e += 256) {
+            const unsigned n = lds[e];
+            if (n) atomicAdd(&out[e], (unsigned long long)n);
+        }
+        if (kLoopCandidates) __syncthreads();                             // the next round clears what this one read
+    }
+}
+
+static bool bin_rule(double lo, double hi, int bins, BinRule* r) {
+    if (!isfinite(lo) || !isfinite(hi)) return false;
+    const float lo32 = (float)lo, hi32 = (float)hi;
+    const float width = hi32 - lo32;                                      // float32, as the specification
+    const float scale = (float)bins / width;
+    if (!isfinite(lo32) || !isfinite(hi32) || !(hi32 > lo32) || !isfinite(scale)) return false;
+    r->lo = lo32;
+    r->scale = scale;
+    r->top = (float)bins;
+    r->bins = bins;
+    return true;
+}
+
+extern "C" int mrisr_f32_volume_joint_histogram(const float* fixed, int FX, int FY, int FZ, const float* moving, int MX, int MY, int MZ,
+                                                const double* m12s, int K, int stride, int bins, double fixed_lo, double fixed_hi,
+                                                double moving_lo, double moving_hi, long long* hist, void* stream) {
+    const char* name = "f32_volume_joint_histogram";
+    if (!fixed || !moving || !m12s || !hist) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (K < 1 || K > kMaxCandidates) MRISR_FAIL(MRISR_E_ARG, "%s: %d candidate matrices (1..%d)", name, K, kMaxCandidates);
+    if (stride != 1 && stride != 2 && stride != 4 && stride != 8) MRISR_FAIL(MRISR_E_ARG, "%s: stride %d (1, 2, 4 or 8)", name, stride);
+    if (bins != 16 && bins != 32 && bins != 64) MRISR_FAIL(MRISR_E_ARG, "%s: %d bins (16, 32 or 64)", name, bins);
+    BinRule rf, rm;
+    if (!bin_rule(fixed_lo, fixed_hi, bins, &rf) || !bin_rule(moving_lo, moving_hi, bins, &rm))
+        MRISR_FAIL(MRISR_E_ARG, "%s: ranges (%g, %g) and (%g, %g): finite in float32 with hi > lo and a finite bins / (hi - lo)", name,
+                   fixed_lo, fixed_hi, moving_lo, moving_hi);
+    Candidates cand;
+    memset(&cand, 0, sizeof(cand));
+    for (int c = 0; c < K; ++c)
+        for (int e = 0; e < 12; ++e) {
+            const double v = e % 4 == 3 ? m12s[12 * c + e] : m12s[12 * c + e] * (double)stride;      // exact unless it overflows
+            if (!isfinite(v)) MRISR_FAIL(MRISR_E_ARG, "%s: matrix %d entry [%d][%d] is not finite", name, c, e / 4, e % 4);
+            cand.m[c][e] = v;
+        }
+    if (FX < 1 || FY < 1 || FZ < 1 || MX < 1 || MY < 1 || MZ < 1)
+        MRISR_FAIL(MRISR_E_SHAPE, "%s: fixed %d x %d x %d, moving %d x %d x %d (every extent at least 1)", name, FX, FY, FZ, MX, MY, MZ);
+    const long long fxy = (long long)FX * FY, mxy = (long long)MX * MY;
+    if (fxy > kMaxVoxels || fxy * FZ > kMaxVoxels || mxy > kMaxVoxels || mxy * MZ > kMaxVoxels)
+        MRISR_FAIL(MRISR_E_UNSUPPORTED, "%s: fixed %d x %d x %d, moving %d x %d x %d: more than 2^31 - 1 voxels on one side", name, FX,
+                   FY, FZ, MX, MY, MZ);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)K * bins * bins * sizeof(long long), st) != hipSuccess)
+        MRISR_FAIL(MRISR_E_HIP, "%s: clearing the histograms failed", name);
+    const int SX = ceil_div(FX, stride), SY = ceil_div(FY, stride), SZ = ceil_div(FZ, stride);
+    // at most 2^31 / 1024 bricks plus the remainder bricks of every row: far inside the 2^31 - 1 blocks of grid.x
+    const unsigned nbx = ceil_div(SX, kBX), nby = ceil_div(SY, kBY), nbz = ceil_div(SZ, kBZ);
+    joint_histogram_kernel<<<dim3(nbx * nby * nbz, kLoopCandidates ? 1 : K), dim3(256), 0, st>>>(
+        fixed, FY, FZ, SX, SY, SZ, stride, moving, MX, MY, MZ, cand, K, rf, rm, (unsigned long long*)hist, nby, nbz);
+    MRISR_CHECK_LAUNCH(name);
+    return MRISR_OK;
+}
+
+// ---------------------------------------------------------------- normalised mutual information
+
+__device__ __forceinline__ double block_sum_d(double v, double* part) {      // 256 threads; every thread gets the sum
+    v = wave_sum_d(v);
+    __syncthreads();                                                         // part may still be read from the previous sum
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return __dadd_rn(__dadd_rn(part[0], part[1]), __dadd_rn(part[2], part[3]));
+}
+
+__device__ __forceinline__ double plogp(long long n, double total) {
+    if (n <= 0) return 0.0;
+    const double p = __ddiv_rn((double)n, total);
+    return __dmul_rn(p, log(p));
+}
+
+__global__ __launch_bounds__(256) void joint_histogram_nmi_kernel(const long long* __restrict__ hist, int bins, long long min_count,
+                                                                  double* __restrict__ values, long long* __restrict__ counts) {
+    __shared__ long long marg[2 * kMaxBins];                                 // row sums (fixed), column sums (moving)
+    __shared__ double part[4];
+    const int tid = threadIdx.x, cells = bins * bins;
+    const long long* h = hist + (size_t)blockIdx.x * cells;
+    if (tid < 2 * bins) {
+        const bool col = tid >= bins;
+        const int a = col ? tid - bins : tid;
+        long long s = 0;
+        for (int b = 0; b < bins; ++b) s += col ? h[b * bins + a] : h[a * bins + b];
+        marg[tid] = s;
+    }
+    __syncthreads();
+    long long N = 0;
+    for (int a = 0; a < bins; ++a) N += marg[a];
+    if (N < (min_count > 1 ? min_count : 1)) {                               // uniform over the workgroup
+        if (tid == 0) {
+            values[blockIdx.x] = -INFINITY;
+            counts[blockIdx.x] = N;
+        }
+        return;
+    }
+    const double total = (double)N;
+    double joint = 0.0;
+    for (int e = tid; e < cells; e += 256) joint = __dadd_rn(joint, plogp(h[e], total));
+    const double hfm = -block_sum_d(joint, part);
+    const double hf = -block_sum_d(tid < bins ? plogp(marg[tid], total) : 0.0, part);
+    const double hm = -block_sum_d(tid < bins ? plogp(marg[bins + tid], total) : 0.0, part);
+    if (tid == 0) {
+        values[blockIdx.x] = hfm == 0.0 ? 0.0 : __ddiv_rn(__dadd_rn(hf, hm), hfm);
+        counts[blockIdx.x] = N;
+    }
+}
+
+extern "C" int mrisr_joint_histogram_nmi(const long long* hist, int K, int bins, long long min_count, double* values, long long* counts,
+                                         void* stream) {
+    const char* name = "joint_histogram_nmi";
+    if (!hist || !values || !counts) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (K < 1 || K > kMaxCandidates) MRISR_FAIL(MRISR_E_ARG, "%s: %d histograms (1..%d)", name, K, kMaxCandidates);
+    if (bins != 16 && bins != 32 && bins != 64) MRISR_FAIL(MRISR_E_ARG, "%s: %d bins (16, 32 or 64)", name, bins);
+    if (min_count < 0) MRISR_FAIL(MRISR_E_ARG, "%s: min_count %lld is negative", name, min_count);
+    joint_histogram_nmi_kernel<<<dim3(K), dim3(256), 0, (hipStream_t)stream>>>(hist, bins, min_count, values, counts);
+    MRISR_CHECK_LAUNCH(name);
+    return MRISR_OK;
+}

@@ -19,11 +19,9 @@
 // z fastest (a wave stores runs of min(kBZ, 64) floats), so that under any rotation its source footprint is a small box - the 64 taps
 // of CUBIC are served by the vector cache and L2, not by HBM.  The bricks are numbered along z, then y, then x in a 1-D grid.  The
 // matrix travels by value in the kernel arguments: nothing is uploaded, nothing synchronises (HIP-graph capturable).
-#include "common.h"
+// The clamp, the Keys weights, the taps of an axis and the tap sum live in volume_taps.h (shared with volume_register.hip).
+#include "volume_taps.h"
 
-#include <math.h>
-
-constexpr int kNearest = MRISR_RESAMPLE_NEAREST, kLinear = MRISR_RESAMPLE_LINEAR, kCubic = MRISR_RESAMPLE_CUBIC;
 // the brick (x, y, z): 256 voxels, one wave per 64-voxel run along z.  2 x 2 x 64 measured against 1 x 4 x 64, 2 x 4 x 32,
 // 4 x 4 x 16 and 8 x 8 x 4 (profiles/NOTES.md, "Reslice"); tools/reslice_bench.py --variant_libs times builds with other values
 #ifndef MRISR_RESLICE_BX
@@ -38,44 +36,6 @@ constexpr long long kMaxVoxels = 2147483647LL;      // 2^31 - 1 on either side
 struct GridMatrix {
     double m[3][4];
 };
-
-__device__ __forceinline__ int clampi(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
-
-// Keys, A = -0.75, at distance x >= 0
-__device__ __forceinline__ float keys_weight(float x) {
-    const float wn = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(1.25f, x), 2.25f), x), x), 1.0f);
-    const float wf = __fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(__fmul_rn(-0.75f, x), 3.75f), x), 6.0f), x), 3.0f);
-    return x <= 1.0f ? wn : wf;
-}
-
-// taps and weights of one axis; p is inside [-0.5, n - 0.5]
-template <int METHOD>
-__device__ __forceinline__ void axis_taps(double p, int n, int* idx, float* w) {
-    const double f = floor(p);
-    const float t = (float)(p - f);      // the difference is exact in double
-    const int fi = (int)f;               // -1 .. n - 1
-    if constexpr (METHOD == kLinear) {
-        idx[0] = clampi(fi, n);
-        idx[1] = clampi(fi + 1, n);
-        w[0] = __fsub_rn(1.0f, t);
-        w[1] = t;
-    } else {
-#pragma unroll
-        for (int d = 0; d < 4; ++d) idx[d] = clampi(fi - 1 + d, n);
-        w[0] = keys_weight(__fadd_rn(1.0f, t));
-        w[1] = keys_weight(t);
-        w[2] = keys_weight(__fsub_rn(1.0f, t));
-        w[3] = keys_weight(__fsub_rn(2.0f, t));
-    }
-}
-
-template <int N>
-__device__ __forceinline__ float weighted_sum(const float* w, const float* v) {
-    float acc = __fmul_rn(w[0], v[0]);
-#pragma unroll
-    for (int d = 1; d < N; ++d) acc = __fadd_rn(acc, __fmul_rn(w[d], v[d]));
-    return acc;
-}
 
 template <int METHOD, typename T>
 __global__ __launch_bounds__(256) void volume_reslice_kernel(const T* __restrict__ src, int SX, int SY, int SZ, T* __restrict__ dst,

@@ -11,8 +11,8 @@ NIfTI affines alone.
 The matrix ``m`` maps a destination voxel index ``(i, j, k)`` to a continuous source voxel index.  Voxels are cells with their
 centres at the integer indices (the half-pixel convention of ``utils.nifti.upscaled_affine``): the volume covers
 ``[-0.5, n - 0.5]`` along an axis of extent ``n``; a destination voxel whose centre falls outside is ``fill``, one inside is
-interpolated with the border replicated.  There is no CPU path: CPU tensors raise.  Estimating the transform between two scans
-(registration) is not built: the affines are taken as they are.
+interpolated with the border replicated.  There is no CPU path: CPU tensors raise.  The affines are taken as they are here;
+``volume_register`` estimates a rigid transform between two scans.
 """
 from __future__ import annotations
 

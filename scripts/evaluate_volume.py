@@ -31,8 +31,15 @@ as a uint8 NIfTI under the reference's header (one reference only; a 4-D referen
 the two headers' affines (``volume_reslice.reslice``, ``--align_interp linear|cubic``) onto the grid a x2 pass expects -
 ``utils.nifti.downscaled_affine`` of the reference's affine over the doubled axes, the reference's extents (after its crop to even
 ones) halved on them - whatever its spacing, field of view, axis order or rotation; the share of that grid the input covers is
-logged.  A ``--mask PATH`` on another grid is then resliced onto the reference's grid with ``nearest``.  The transform is never
+logged.  A ``--mask PATH`` on another grid is then resliced onto the reference's grid with ``nearest``.  The transform is not
 estimated: the headers are taken as they are.
+
+``--align rigid`` estimates it: the input is first registered to the reference - six rigid parameters, normalised mutual
+information, starting from the two headers (``volume_register.register_rigid``, ``--align_bins``; frame 0 of a 4-D pair) - and
+then resliced ONCE onto the same low-resolution grid through ``inv(A_input) W A_low``, ``W`` the estimated reference world ->
+input world matrix: never two interpolations.  The parameters found and the NMI before and after are logged.  Two scans of one
+head from two scanners or two sessions never share a world frame to sub-voxel accuracy; with ``--align header`` their table
+measures patient positioning, with ``--align rigid`` the methods.
 """
 import argparse
 import csv
@@ -50,6 +57,7 @@ if REPO not in sys.path:
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
 from mri_superresolution_amd.utils.nifti import downscaled_affine, grid_matrix, read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_eval import evaluate_volume, otsu_threshold_value      # noqa: E402
+from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice, reslice_mask    # noqa: E402
 
 logger = logging.getLogger("evaluate_volume")
@@ -82,14 +90,15 @@ def load_mask(mask_path, ref, reference_path, ref_affine=None):
 
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
-               save_mask=None, align=None, align_interp="linear"):
+               save_mask=None, align=None, align_interp="linear", align_bins=64):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
     step that is off).  ``save_mask``: the masks scored go to this NIfTI file.  ``align="header"``: ``input_path`` (and a mask file)
-    may lie on any grid and are resliced through the headers' affines (module docstring)."""
-    if align not in (None, "header"):
-        raise ValueError(f"align must be None or 'header', got {align!r}")
+    may lie on any grid and are resliced through the headers' affines (module docstring); ``align="rigid"``: the input is registered
+    to the reference first and resliced once through the estimated transform."""
+    if align not in (None, "header", "rigid"):
+        raise ValueError(f"align must be None, 'header' or 'rigid', got {align!r}")
     if align and not input_path:
         raise ValueError("--align goes with --input")
     if align and align_interp not in ("linear", "cubic"):
@@ -114,7 +123,19 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             if mask_frames is not None:
                 mask_frames = [f[:crop[0], :crop[1], :crop[2]].contiguous() for f in mask_frames]
         low_shape = tuple(d // 2 if a in axes else d for a, d in enumerate(crop))
-        m = grid_matrix(low_header.affine(), downscaled_affine(ref_header.affine(), axes))
+        low_grid = downscaled_affine(ref_header.affine(), axes)
+        if align == "rigid":
+            # fixed = the reference, moving = the input, from the headers as they are (p0 = 0); W: reference world -> input world
+            fixed = torch.from_numpy(np.ascontiguousarray(_frames(ref)[0], dtype=np.float32)).to(device)
+            moving = torch.from_numpy(np.ascontiguousarray(low_frames[0], dtype=np.float32)).to(device)
+            found = register_rigid(fixed, ref_header.affine(), moving, low_header.affine(), bins=align_bins)
+            p = found.p
+            logger.info(f"{input_path} registered to {reference_path}: t = ({p[0]:.4f}, {p[1]:.4f}, {p[2]:.4f}) mm, r = ({p[3]:.4f}, "
+                        f"{p[4]:.4f}, {p[5]:.4f}) degrees, NMI {found.trace[0]['best']:.6f} -> {found.value:.6f} in "
+                        f"{found.n_evaluations} evaluations.")
+            low_grid = found.world @ low_grid
+            del fixed, moving
+        m = grid_matrix(low_header.affine(), low_grid)
         low_frames = [reslice(torch.from_numpy(np.ascontiguousarray(f)).to(device), m, low_shape, align_interp) for f in low_frames]
         share = float(covered_share(low.shape[:3], m, low_shape, device))
         logger.info(f"{input_path} {tuple(low.shape[:3])} resliced onto the low-resolution grid {low_shape} of {reference_path} "
@@ -226,7 +247,7 @@ def main(args):
         for path in args.reference:
             scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
                                    not args.no_graph, device, graphs, args.mask, args.mask_close, args.mask_largest, fill, args.save_mask,
-                                   args.align, args.align_interp)
+                                   args.align, args.align_interp, args.align_bins)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -283,10 +304,12 @@ def parse_args(argv=None):
     p.add_argument("--save_mask", type=str, default=None,
                    help="write the mask that was scored, after crop and clean-up, as a uint8 NIfTI with the reference's header (one "
                         "--reference; needs --mask)")
-    p.add_argument("--align", type=str, choices=["header"], default=None,
+    p.add_argument("--align", type=str, choices=["header", "rigid"], default=None,
                    help="reslice --input (and a --mask file) through the NIfTI headers' affines onto the grid the reference implies, "
-                        "instead of demanding exactly half its extents (needs --input)")
+                        "instead of demanding exactly half its extents (needs --input); rigid: register the input to the reference "
+                        "first (six parameters, mutual information) and reslice it once through the estimated transform")
     p.add_argument("--align_interp", type=str, choices=["linear", "cubic"], default="linear", help="interpolation of the --align reslice")
+    p.add_argument("--align_bins", type=int, choices=[16, 32, 64], default=64, help="bins per axis of --align rigid's joint histogram")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

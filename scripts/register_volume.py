@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Rigid registration of a NIfTI scan to another on the device (extension).
+
+    python scripts/register_volume.py --fixed highfield.nii.gz --moving lowfield.nii.gz --output lowfield_on_fixed.nii.gz \
+        --interp cubic --save_transform fixed_to_moving.txt
+
+The six parameters of a rigid transform between the two scans' world frames are estimated by maximising the normalised mutual
+information of their joint histogram (``volume_register.register_rigid``: ``csrc/volume_register.hip``, ``--bins`` 16, 32 or
+64), starting from the two headers as they are.  The output is the moving scan resliced ONCE onto the fixed scan's grid through the
+estimated transform (``--interp linear|cubic``, voxels outside the moving scan are ``--fill``), float32 under
+``utils.nifti.header_for_grid`` of the moving scan's header.  ``--save_transform`` writes the 4 x 4 fixed world -> moving world
+matrix as text (``numpy.loadtxt`` reads it back).  A 4-D file is registered on its frame 0 and the transform is applied to every
+frame.  Exit code 0 / 1 (error logged), as ``scripts/infer_volume.py``.
+"""
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from mri_superresolution_amd.utils.nifti import header_for_grid, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.volume_register import register_rigid                             # noqa: E402
+from mri_superresolution_amd.volume_reslice import covered_share, reslice                      # noqa: E402
+
+logger = logging.getLogger("register_volume")
+
+
+def describe(result):
+    p = result.p
+    return (f"t = ({p[0]:.4f}, {p[1]:.4f}, {p[2]:.4f}) mm, r = ({p[3]:.4f}, {p[4]:.4f}, {p[5]:.4f}) degrees, NMI "
+            f"{result.trace[0]['best']:.6f} -> {result.value:.6f} in {result.n_evaluations} evaluations")
+
+
+def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64, save_transform=None, fill=0.0, device="cuda"):
+    """NIfTI files -> the moving scan on the fixed scan's grid (written and returned), and the ``RigidResult``."""
+    fixed, fixed_header = read_nifti(fixed_path)
+    moving, moving_header = read_nifti(moving_path)
+    frames = [moving] if moving.ndim == 3 else [moving[..., t] for t in range(moving.shape[3])]
+    frames = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)).to(device) for f in frames]
+    fixed0 = fixed if fixed.ndim == 3 else fixed[..., 0]
+    fixed0 = torch.from_numpy(np.ascontiguousarray(fixed0, dtype=np.float32)).to(device)
+    fixed_affine, shape = fixed_header.affine(), tuple(fixed.shape[:3])
+    result = register_rigid(fixed0, fixed_affine, frames[0], moving_header.affine(), bins=bins)
+    logger.info(f"Registered {moving_path} to {fixed_path}: {describe(result)}")
+    outs = [reslice(f, result.matrix, shape, interp, fill) for f in frames]
+    share = covered_share(moving.shape[:3], result.matrix, shape, device)
+    data = outs[0].cpu().numpy() if moving.ndim == 3 else np.stack([o.cpu().numpy() for o in outs], axis=3)
+    logger.info(f"{100.0 * (1.0 - float(share)):.2f} % of the output voxels fell outside the moving scan (set to {fill:g}).")
+    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
+    write_nifti(output_path, data, header_for_grid(moving_header, shape, fixed_affine))
+    logger.info(f"Moving scan {tuple(moving.shape)} -> {tuple(data.shape)} ({interp}) saved to {output_path}")
+    if save_transform:
+        os.makedirs(os.path.dirname(os.path.abspath(save_transform)), exist_ok=True)
+        np.savetxt(save_transform, result.world, fmt="%.17g", header="fixed world -> moving world (mm), 4 x 4")
+        logger.info(f"Transform saved to {save_transform}")
+    return data, result
+
+
+def main(args):
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+    try:
+        if args.cpu or not torch.cuda.is_available():
+            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
+        device = torch.device("cuda")
+        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+        register_file(args.fixed, args.moving, args.output, args.interp, args.bins, args.save_transform, args.fill, device)
+        return 0
+    except Exception as e:
+        logger.error(f"Error during registration: {e}")
+        return 1
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Rigid registration of a NIfTI volume to another (extension)")
+    p.add_argument("--fixed", type=str, required=True, help="the scan whose grid the output lands on: single-file NIfTI-1, 3-D or 4-D")
+    p.add_argument("--moving", type=str, required=True, help="the scan to bring onto it: single-file NIfTI-1, 3-D or 4-D")
+    p.add_argument("--output", type=str, required=True, help="the moving scan on the fixed grid, .nii or .nii.gz, float32")
+    p.add_argument("--interp", type=str, choices=["linear", "cubic"], default="linear", help="interpolation of the final reslice")
+    p.add_argument("--bins", type=int, choices=[16, 32, 64], default=64, help="bins per axis of the joint histogram")
+    p.add_argument("--save_transform", type=str, default=None, help="write the 4 x 4 fixed world -> moving world matrix as text")
+    p.add_argument("--fill", type=float, default=0.0, help="value of the output voxels whose centre lies outside the moving scan")
+    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    return p.parse_args(argv)
+
+
+if __name__ == "__main__":
+    sys.exit(main(parse_args()))
