@@ -669,6 +669,20 @@ int mrisr_f32_volume_joint_histogram(const float* fixed, int FX, int FY, int FZ,
  * DEVICE, K doubles and K int64.  MRISR_E_ARG: null pointer, K outside 1..16, bins not 16, 32 or 64, min_count negative.          */
 int mrisr_joint_histogram_nmi(const long long* hist, int K, int bins, long long min_count, double* values, long long* counts,
                               void* stream);
+/* mrisr_f32_volume_joint_histogram with a mask on the fixed side: fixed_mask is a DEVICE uint8 volume of the fixed shape (C order); a
+ * sample (i s, j s, k s) counts only if the unmasked rule counts it AND fixed_mask at that voxel is non-zero (any non-zero value).
+ * The mask byte is read first: a masked-out sample fetches neither the fixed value nor the moving taps.  An all-ones mask gives the
+ * unmasked entry's histograms bit for bit.  The same memset and one launch, the same refusals, and MRISR_E_ARG for a null mask.   */
+int mrisr_f32_volume_joint_histogram_masked(const float* fixed, int FX, int FY, int FZ, const unsigned char* fixed_mask,
+                                            const float* moving, int MX, int MY, int MZ, const double* m12s, int K, int stride, int bins,
+                                            double fixed_lo, double fixed_hi, double moving_lo, double moving_hi, long long* hist,
+                                            void* stream);
+/* out4 (DEVICE, 4 int64, 8-byte aligned, zeroed by the call) = (N, sum i, sum j, sum k) over the non-zero voxels (i, j, k) of the
+ * DEVICE uint8 volume mask (X, Y, Z in C order): the moments of a mask's centre of mass, exact integers whatever the order of the
+ * additions (64-bit integer atomics).  A memset and one launch on stream, no host synchronisation (HIP-graph capturable).
+ * Refusals, all before any launch: MRISR_E_ARG null or misaligned pointer; MRISR_E_SHAPE an extent outside 1..32767;
+ * MRISR_E_UNSUPPORTED more than 2^31 - 1 voxels (inside these bounds no sum can overflow: sum i < 2^31 2^15).                      */
+int mrisr_u8_volume_mask_moments(const unsigned char* mask, int X, int Y, int Z, long long* out4, void* stream);
 
 #ifdef __cplusplus
 }

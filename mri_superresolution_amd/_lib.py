@@ -173,10 +173,13 @@ SIGNATURES = {
     "mrisr_u8_volume_reslice_nearest": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, C.POINTER(C.c_double), C.c_uint8, _vp]),
     "mrisr_f32_volume_joint_histogram": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, _i, _i, _d, _d, _d, _d, _vp, _vp]),
     "mrisr_joint_histogram_nmi": (_i, [_vp, _i, _i, C.c_longlong, _dp, _vp, _vp]),
+    "mrisr_f32_volume_joint_histogram_masked": (_i, [_fp, _i, _i, _i, _vp, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, _i, _i, _d, _d, _d,
+                                                     _d, _vp, _vp]),
+    "mrisr_u8_volume_mask_moments": (_i, [_vp, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 316      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 317      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

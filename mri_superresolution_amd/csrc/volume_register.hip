@@ -14,6 +14,7 @@
 //                bin = min(bins - 1, (int)clamp(x, 0, bins)): the Otsu histogram's rule, clamped at both ends before the
 //                conversion, so that +-infinity and huge values have a defined bin
 //   counted      inside, and neither the fixed nor the moving value is NaN:  H[k][bin_fixed][bin_moving] += 1
+//   masked       (mrisr_f32_volume_joint_histogram_masked) ... and the byte of `fixed_mask` at the sample's voxel is non-zero
 //
 // A workgroup of 256 threads owns a compact kBX x kBY x kBZ brick of samples (under any rotation its moving footprint is a small box)
 // and one candidate (blockIdx.y), unless built with -DMRISR_REGISTER_KLOOP=1: then it loops over all K candidates and loads the
@@ -23,9 +24,17 @@
 // suffice).  The non-zero cells of the LDS histogram go to the 64-bit global histogram with one atomic each.  The matrices travel
 // by value in the kernel arguments (K x 96 bytes); the call zeroes `hist` with a memset node on the stream: nothing is uploaded,
 // nothing synchronises.  Every loop has a compile-time or argument bound; no workgroup waits for another.
+// The masked instantiation (kMasked) reads the mask byte first: a thread whose byte is zero fetches neither the fixed value nor
+// the moving taps, and a workgroup whose samples are all masked out (or NaN) leaves before it touches its LDS histogram - a head
+// is about a quarter of its box.  The unmasked instantiation is the kernel as it was.
 //
 // nmi: one workgroup per candidate.  Row and column sums and N as integers; P = H / N; the entropies -sum p ln p over the
 // positive cells in double; value = (H_f + H_m) / H_fm, 0.0 where H_fm == 0, -infinity where N < max(min_count, 1).
+//
+// mask moments: (N, sum i, sum j, sum k) over the non-zero voxels of a uint8 volume, exact integers.  A thread takes kMomentRuns
+// runs of 16 consecutive voxels (one 16-byte load where the run is whole and aligned, guarded byte loads at the two ends), steps
+// (i, j, k) along the run without dividing, and adds into 64-bit accumulators; wavefront shuffle, LDS across the four wavefronts,
+// then one 64-bit integer atomic per workgroup and value: integer sums do not depend on the order.
 #include "volume_taps.h"
 
 #ifndef MRISR_REGISTER_KLOOP
@@ -104,11 +113,13 @@ __device__ __forceinline__ bool moving_value(const float* __restrict__ mov, int 
     return true;
 }
 
-// grid (bricks, K) - or (bricks, 1) with the candidate loop; (SX, SY, SZ): the sample grid
-__global__ __launch_bounds__(256) void joint_histogram_kernel(const float* __restrict__ fix, int FY, int FZ, int SX, int SY, int SZ,
-                                                              int stride, const float* __restrict__ mov, int MX, int MY, int MZ,
-                                                              Candidates cand, int K, BinRule rf, BinRule rm,
-                                                              unsigned long long* __restrict__ hist, unsigned nby, unsigned nbz) {
+// grid (bricks, K) - or (bricks, 1) with the candidate loop; (SX, SY, SZ): the sample grid; fmask: only read when kMasked
+template <bool kMasked>
+__global__ __launch_bounds__(256) void joint_histogram_kernel(const float* __restrict__ fix, const unsigned char* __restrict__ fmask,
+                                                              int FY, int FZ, int SX, int SY, int SZ, int stride,
+                                                              const float* __restrict__ mov, int MX, int MY, int MZ, Candidates cand,
+                                                              int K, BinRule rf, BinRule rm, unsigned long long* __restrict__ hist,
+                                                              unsigned nby, unsigned nbz) {
     __shared__ unsigned lds[kMaxBins * kMaxBins];
     const int tid = threadIdx.x, cells = rf.bins * rf.bins;
     const unsigned bz = blockIdx.x % nbz, rest = blockIdx.x / nbz, by = rest % nby, bx = rest / nby;
@@ -116,13 +127,22 @@ __global__ __launch_bounds__(256) void joint_histogram_kernel(const float* __res
     const bool column = j < SY && k < SZ;
     // the fixed values of this thread's walk and their bins: once, whatever the number of candidates
     int fbin[kWalk];
+    bool any = false;
 #pragma unroll
     for (int w = 0; w < kWalk; ++w) {
-        fbin[w] = -1;                                                     // no sample, or a NaN
+        fbin[w] = -1;                                                     // no sample, masked out, or a NaN
         if (column && i0 + w < SX) {
-            const float fv = fix[((size_t)(i0 + w) * stride * FY + (size_t)j * stride) * FZ + (size_t)k * stride];
+            const size_t at = ((size_t)(i0 + w) * stride * FY + (size_t)j * stride) * FZ + (size_t)k * stride;
+            if constexpr (kMasked) {
+                if (fmask[at] == 0) continue;                             // the byte first: no fixed value, no moving taps
+            }
+            const float fv = fix[at];
             if (fv == fv) fbin[w] = value_bin(fv, rf);
+            any = any || fbin[w] >= 0;
         }
+    }
+    if constexpr (kMasked) {
+        if (!__syncthreads_or(any)) return;                               // uniform: nothing of this brick counts, hist is zeroed
     }
     const int kfirst = kLoopCandidates ? 0 : (int)blockIdx.y, klast = kLoopCandidates ? K : kfirst + 1;
     for (int c = kfirst; c < klast; ++c) {                                 // at most 16 rounds
@@ -159,11 +179,11 @@ static bool bin_rule(double lo, double hi, int bins, BinRule* r) {
     return true;
 }
 
-extern "C" int mrisr_f32_volume_joint_histogram(const float* fixed, int FX, int FY, int FZ, const float* moving, int MX, int MY, int MZ,
-                                                const double* m12s, int K, int stride, int bins, double fixed_lo, double fixed_hi,
-                                                double moving_lo, double moving_hi, long long* hist, void* stream) {
-    const char* name = "f32_volume_joint_histogram";
-    if (!fixed || !moving || !m12s || !hist) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+// both entries; fixed_mask is only looked at when `masked`
+static int joint_histogram(const char* name, bool masked, const float* fixed, int FX, int FY, int FZ, const unsigned char* fixed_mask,
+                           const float* moving, int MX, int MY, int MZ, const double* m12s, int K, int stride, int bins, double fixed_lo,
+                           double fixed_hi, double moving_lo, double moving_hi, long long* hist, void* stream) {
+    if (!fixed || !moving || !m12s || !hist || (masked && !fixed_mask)) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
     if (K < 1 || K > kMaxCandidates) MRISR_FAIL(MRISR_E_ARG, "%s: %d candidate matrices (1..%d)", name, K, kMaxCandidates);
     if (stride != 1 && stride != 2 && stride != 4 && stride != 8) MRISR_FAIL(MRISR_E_ARG, "%s: stride %d (1, 2, 4 or 8)", name, stride);
     if (bins != 16 && bins != 32 && bins != 64) MRISR_FAIL(MRISR_E_ARG, "%s: %d bins (16, 32 or 64)", name, bins);
@@ -191,8 +211,113 @@ extern "C" int mrisr_f32_volume_joint_histogram(const float* fixed, int FX, int 
     const int SX = ceil_div(FX, stride), SY = ceil_div(FY, stride), SZ = ceil_div(FZ, stride);
     // at most 2^31 / 1024 bricks plus the remainder bricks of every row: far inside the 2^31 - 1 blocks of grid.x
     const unsigned nbx = ceil_div(SX, kBX), nby = ceil_div(SY, kBY), nbz = ceil_div(SZ, kBZ);
-    joint_histogram_kernel<<<dim3(nbx * nby * nbz, kLoopCandidates ? 1 : K), dim3(256), 0, st>>>(
-        fixed, FY, FZ, SX, SY, SZ, stride, moving, MX, MY, MZ, cand, K, rf, rm, (unsigned long long*)hist, nby, nbz);
+    const dim3 grid(nbx * nby * nbz, kLoopCandidates ? 1 : K);
+    if (masked)
+        joint_histogram_kernel<true><<<grid, dim3(256), 0, st>>>(fixed, fixed_mask, FY, FZ, SX, SY, SZ, stride, moving, MX, MY, MZ, cand,
+                                                                 K, rf, rm, (unsigned long long*)hist, nby, nbz);
+    else
+        joint_histogram_kernel<false><<<grid, dim3(256), 0, st>>>(fixed, nullptr, FY, FZ, SX, SY, SZ, stride, moving, MX, MY, MZ, cand, K,
+                                                                  rf, rm, (unsigned long long*)hist, nby, nbz);
+    MRISR_CHECK_LAUNCH(name);
+    return MRISR_OK;
+}
+
+extern "C" int mrisr_f32_volume_joint_histogram(const float* fixed, int FX, int FY, int FZ, const float* moving, int MX, int MY, int MZ,
+                                                const double* m12s, int K, int stride, int bins, double fixed_lo, double fixed_hi,
+                                                double moving_lo, double moving_hi, long long* hist, void* stream) {
+    return joint_histogram("f32_volume_joint_histogram", false, fixed, FX, FY, FZ, nullptr, moving, MX, MY, MZ, m12s, K, stride, bins,
+                           fixed_lo, fixed_hi, moving_lo, moving_hi, hist, stream);
+}
+
+extern "C" int mrisr_f32_volume_joint_histogram_masked(const float* fixed, int FX, int FY, int FZ, const unsigned char* fixed_mask,
+                                                       const float* moving, int MX, int MY, int MZ, const double* m12s, int K, int stride,
+                                                       int bins, double fixed_lo, double fixed_hi, double moving_lo, double moving_hi,
+                                                       long long* hist, void* stream) {
+    return joint_histogram("f32_volume_joint_histogram_masked", true, fixed, FX, FY, FZ, fixed_mask, moving, MX, MY, MZ, m12s, K, stride,
+                           bins, fixed_lo, fixed_hi, moving_lo, moving_hi, hist, stream);
+}
+
+// ---------------------------------------------------------------- mask moments
+
+constexpr int kMomentRuns = 4, kRunBytes = 16;                             // a thread: 4 runs of 16 voxels
+constexpr long long kMomentBlockRuns = 256LL * kMomentRuns;                // runs per workgroup
+
+// `off`: mask's address modulo 16; run q covers the voxels [16 q - off, 16 q - off + 16) cut to [0, n): whole runs are aligned
+__global__ __launch_bounds__(256) void mask_moments_kernel(const unsigned char* __restrict__ mask, int Y, int Z, long long n, int off,
+                                                           unsigned long long* __restrict__ out4) {
+    __shared__ unsigned long long part[4][4];
+    const int tid = threadIdx.x, yz = Y * Z;                                // yz < 2^30
+    unsigned long long acc[4] = {0ull, 0ull, 0ull, 0ull};                   // N, sum i, sum j, sum k
+#pragma unroll
+    for (int r = 0; r < kMomentRuns; ++r) {
+        const long long q = (long long)blockIdx.x * kMomentBlockRuns + r * 256 + tid;
+        const long long first = q * kRunBytes - off, lo = first < 0 ? 0 : first;
+        const long long hi = first + kRunBytes < n ? first + kRunBytes : n;      // [lo, hi): this run's voxels
+        if (lo >= hi) continue;
+        unsigned word[4];
+        const bool whole = hi - lo == kRunBytes;
+        if (whole) {
+            const u32x4 v = *reinterpret_cast<const u32x4*>(mask + first);         // 16-byte aligned, inside [0, n)
+            word[0] = v[0], word[1] = v[1], word[2] = v[2], word[3] = v[3];
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) word[b] = 0u;
+#pragma unroll
+            for (int b = 0; b < kRunBytes; ++b) {
+                const long long idx = first + b;
+                if (idx >= lo && idx < hi) word[b >> 2] |= (unsigned)mask[idx] << (8 * (b & 3));
+            }
+        }
+        if ((word[0] | word[1] | word[2] | word[3]) == 0u) continue;
+        int i = (int)((unsigned)lo / (unsigned)yz);                           // lo < 2^31: 32-bit divisions
+        const int rem = (int)(lo - (long long)i * yz);
+        int j = rem / Z, k = rem - j * Z;
+#pragma unroll
+        for (int b = 0; b < kRunBytes; ++b) {
+            const long long idx = first + b;
+            if (idx < lo || idx >= hi) continue;
+            if ((word[b >> 2] >> (8 * (b & 3))) & 255u) {
+                acc[0] += 1ull;
+                acc[1] += (unsigned long long)i;
+                acc[2] += (unsigned long long)j;
+                acc[3] += (unsigned long long)k;
+            }
+            if (++k == Z) {
+                k = 0;
+                if (++j == Y) {
+                    j = 0;
+                    ++i;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o, 64);
+        if ((tid & 63) == 0) part[tid >> 6][a] = acc[a];
+    }
+    __syncthreads();
+    if (tid < 4) {
+        const unsigned long long total = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+        if (total) atomicAdd(&out4[tid], total);
+    }
+}
+
+extern "C" int mrisr_u8_volume_mask_moments(const unsigned char* mask, int X, int Y, int Z, long long* out4, void* stream) {
+    const char* name = "u8_volume_mask_moments";
+    if (!mask || !out4) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (((uintptr_t)out4 & 7) != 0) MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer (out4: 8 bytes)", name);
+    if (X < 1 || Y < 1 || Z < 1 || X > 32767 || Y > 32767 || Z > 32767)
+        MRISR_FAIL(MRISR_E_SHAPE, "%s: volume %d x %d x %d (every extent in 1..32767)", name, X, Y, Z);
+    const long long n = (long long)X * Y * Z;                                // < 2^45
+    if (n > kMaxVoxels) MRISR_FAIL(MRISR_E_UNSUPPORTED, "%s: volume %d x %d x %d: more than 2^31 - 1 voxels", name, X, Y, Z);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(out4, 0, 4 * sizeof(long long), st) != hipSuccess) MRISR_FAIL(MRISR_E_HIP, "%s: clearing the moments failed", name);
+    const int off = (int)((uintptr_t)mask & (kRunBytes - 1));
+    const long long runs = (n + off + kRunBytes - 1) / kRunBytes;           // at most 2^27 + 1
+    const unsigned blocks = (unsigned)((runs + kMomentBlockRuns - 1) / kMomentBlockRuns);
+    mask_moments_kernel<<<dim3(blocks), dim3(256), 0, st>>>(mask, Y, Z, n, off, (unsigned long long*)out4);
     MRISR_CHECK_LAUNCH(name);
     return MRISR_OK;
 }

@@ -8,14 +8,19 @@ taken from the two NIfTI headers.
 ``rigid_world``         the 4 x 4 fixed world -> moving world matrix of the parameters ``(tx, ty, tz mm; rx, ry, rz degrees)``.
 ``candidate_matrix``    the (3, 4) fixed voxel index -> moving voxel index matrix of the parameters and the two affines.
 ``compass_search``      the search: ONE function for the specification and the device path, only ``cost_batch`` differs.
+``mask_moments_np``, ``mask_centre_world``, ``rotation_grid``, ``coarse_start``   the start from far apart (``init="global"``): the
+                        two masks' centres of mass brought together under every rotation of a coarse grid, all scored at stride 4.
 ``register_rigid_np``   the specification of the whole operation (numpy cost).
-``joint_histogram``, ``nmi``, ``register_rigid``   the device path.  There is no CPU path: CPU tensors raise.
+``joint_histogram``, ``nmi``, ``mask_moments``, ``register_rigid``   the device path.  There is no CPU path: CPU tensors raise.
 
-Not built: affine or deformable transforms, smoothing of the histogram (Parzen windows), masks in the cost, a coarse global
-search - the capture range is what a start from the headers (``p0 = 0``) allows.
+A fixed-side mask in the cost (``fixed_mask`` / ``mask_cost=True``): a sample counts only where the mask is non-zero.
+
+Not built: affine or deformable transforms, smoothing of the histogram (Parzen windows), a moving-side mask in the cost,
+principal-axes starts.  With ``init="header"`` the capture range is what a start from the headers (``p0 = 0``) allows.
 """
 from __future__ import annotations
 
+import itertools
 import logging
 from typing import NamedTuple
 
@@ -33,6 +38,8 @@ STRIDES = (1, 2, 4, 8)
 MAX_CANDIDATES = 16
 MIN_SAMPLES_PER_AXIS = 8
 MAX_ITERATIONS = 1000      # per level: a bound on the search loop, far above what a registration takes
+MAX_GRID = 1000            # rotations of a coarse grid
+COARSE_STRIDE = 4
 
 
 class RigidResult(NamedTuple):
@@ -41,7 +48,7 @@ class RigidResult(NamedTuple):
     matrix: np.ndarray           # (3, 4): fixed voxel index -> continuous moving voxel index (``reslice``'s matrix)
     value: float                 # the normalised mutual information reached, at the last level's stride
     n_evaluations: int
-    trace: list                  # one dict per ``cost_batch`` call (``compass_search``)
+    trace: list                  # one dict per ``cost_batch`` call (``compass_search``), after the ``coarse`` entry of ``init="global"``
 
 
 # ---------------------------------------------------------------- numpy specification
@@ -81,10 +88,18 @@ def strided_matrix(m, stride: int) -> np.ndarray:
     return _check_matrix(ms)
 
 
-def joint_histogram_np(fixed, moving, m, bins, stride, fixed_range, moving_range) -> np.ndarray:
+def _check_mask_np(mask, shape, what):
+    mask = np.asarray(mask)
+    if mask.dtype not in (np.uint8, np.bool_) or mask.shape != tuple(shape):
+        raise ValueError(f"{what} must be a uint8 or bool volume of shape {tuple(shape)}, got {mask.dtype} {mask.shape}")
+    return mask
+
+
+def joint_histogram_np(fixed, moving, m, bins, stride, fixed_range, moving_range, fixed_mask=None) -> np.ndarray:
     """int64 (bins, bins).  The samples are ``fixed[::s, ::s, ::s]``; with ``m' = strided_matrix(m, s)`` their moving values are
     ``reslice_np(moving, m', sampled shape, "linear")`` and the inside test is ``source_coordinates_np(m', ...)``.  A sample counts
-    when it is inside and neither value is NaN: ``H[bin_np(fixed value), bin_np(moving value)] += 1``."""
+    when it is inside and neither value is NaN: ``H[bin_np(fixed value), bin_np(moving value)] += 1``.  ``fixed_mask`` (uint8 or
+    bool, the fixed shape): a sample counts only if ``fixed_mask[::s, ::s, ::s]`` is non-zero there as well."""
     fixed, moving = np.asarray(fixed), np.asarray(moving)
     for v, what in ((fixed, "fixed"), (moving, "moving")):
         if v.dtype != np.float32 or v.ndim != 3 or v.size == 0:
@@ -97,6 +112,8 @@ def joint_histogram_np(fixed, moving, m, bins, stride, fixed_range, moving_range
     mv = reslice_np(moving, ms, fs.shape, "linear")
     _, inside = source_coordinates_np(ms, fs.shape, moving.shape)
     ok = inside & ~np.isnan(fs) & ~np.isnan(mv)
+    if fixed_mask is not None:
+        ok &= _check_mask_np(fixed_mask, fixed.shape, "fixed_mask")[::stride, ::stride, ::stride] != 0
     cell = bin_np(fs[ok], flo, fscale, bins) * bins + bin_np(mv[ok], mlo, mscale, bins)
     return np.bincount(cell, minlength=bins * bins).astype(np.int64).reshape(bins, bins)
 
@@ -239,35 +256,136 @@ def sample_count(shape, stride: int) -> int:
     return int(np.prod([-(-int(n) // stride) for n in shape[:3]]))
 
 
-def _prepare(fixed_shape, fixed_affine, moving_affine, bins, levels, p0):
+# ---------------------------------------------------------------- the start from far apart
+
+def mask_moments_np(mask) -> np.ndarray:
+    """int64 (4,): ``(N, sum i, sum j, sum k)`` over the non-zero voxels ``(i, j, k)`` of a uint8 or bool volume."""
+    mask = np.asarray(mask)
+    if mask.dtype not in (np.uint8, np.bool_) or mask.ndim != 3 or mask.size == 0:
+        raise ValueError(f"mask_moments_np takes a non-empty uint8 or bool volume (X,Y,Z), got {mask.dtype} {mask.shape}")
+    nz = mask != 0
+    per_axis = [nz.sum(axis=tuple(b for b in range(3) if b != a), dtype=np.int64) for a in range(3)]
+    return np.array([per_axis[0].sum()] + [(c * np.arange(len(c), dtype=np.int64)).sum() for c in per_axis], dtype=np.int64)
+
+
+def mask_centre_world(moments, affine) -> np.ndarray:
+    """(3,) float64: the world position ``A[:3, :3] @ (sums / N) + A[:3, 3]`` of a mask's centre of mass from its moments."""
+    mo = np.asarray(moments)
+    if mo.shape != (4,) or mo.dtype.kind not in "iu":
+        raise ValueError(f"the moments of a mask are four integers (N, sum i, sum j, sum k), got {mo.dtype} {mo.shape}")
+    if int(mo[0]) <= 0:
+        raise ValueError("the mask is empty: it has no centre of mass")
+    a = _check_affine(affine, "affine")
+    return a[:3, :3] @ (mo[1:].astype(np.float64) / float(mo[0])) + a[:3, 3]
+
+
+def rotation_grid(limit_deg, step_deg) -> np.ndarray:
+    """(n^3, 3) float64: the angle triples ``(rx, ry, rz)`` over ``np.arange(-limit, limit + 1e-9, step)`` per axis, in the order of
+    ``itertools.product`` (``rx`` slowest).  At most 1000 triples."""
+    limit, step = float(limit_deg), float(step_deg)
+    if not (np.isfinite(limit) and np.isfinite(step) and step > 0 and limit >= 0):
+        raise ValueError(f"a rotation grid takes a non-negative limit and a positive step in degrees, got {limit_deg} and {step_deg}")
+    if 2 * limit / step + 1 >= 12:                       # before np.arange: no huge allocation for a tiny step
+        raise ValueError(f"a rotation grid of +-{limit} degrees in steps of {step} has more than {MAX_GRID} rotations")
+    angles = np.arange(-limit, limit + 1e-9, step)
+    if len(angles) ** 3 > MAX_GRID:
+        raise ValueError(f"a rotation grid of +-{limit} degrees in steps of {step} has {len(angles) ** 3} rotations (at most {MAX_GRID})")
+    return np.array(list(itertools.product(angles, repeat=3)), dtype=np.float64).reshape(-1, 3)
+
+
+def coarse_start(cost_batch_many, centre_fixed, centre_moving, c, grid, stride):
+    """The best of a grid of rotations, each with the translation that brings the two centres of mass together ->
+    ``(p0, value, entry)``.  ONE function for the specification and the device path, only ``cost_batch_many`` differs.
+
+    For every rotation ``R = rotation_np(*grid[n])`` the candidate is ``p = (t, rx, ry, rz)`` with
+    ``t = centre_moving - (R (centre_fixed - c) + c)``: under ``rigid_world(p, c)`` the fixed centre lands on the moving one.
+    ``cost_batch_many(ps, stride)``: ``ps`` (n, 6), any n -> n values.  The first argmax wins; a best value of ``-inf`` (no
+    candidate had enough samples) raises.  ``entry``: ``kind`` ``"coarse"``, ``stride``, ``n_candidates``, ``values``,
+    ``accepted`` (the index taken), ``best``."""
+    cf, cm, c = (np.asarray(x, dtype=np.float64).reshape(3) for x in (centre_fixed, centre_moving, c))
+    grid = np.asarray(grid, dtype=np.float64)
+    if grid.ndim != 2 or grid.shape[1] != 3 or not 1 <= len(grid) <= MAX_GRID or not np.isfinite(grid).all():
+        raise ValueError(f"the grid is 1..{MAX_GRID} finite angle triples, got shape {grid.shape}")
+    ps = np.array([np.concatenate([cm - (rotation_np(*r) @ (cf - c) + c), r]) for r in grid])
+    vals = np.asarray(cost_batch_many(ps.copy(), stride), dtype=np.float64).reshape(len(ps))
+    j = int(np.argmax(vals))                                          # the first of equal maxima
+    best = float(vals[j])
+    if best == float("-inf"):
+        raise ValueError(f"none of the {len(ps)} coarse candidates at stride {stride} had enough samples inside the moving volume")
+    entry = {"kind": "coarse", "stride": stride, "n_candidates": len(ps), "values": tuple(float(v) for v in vals), "accepted": j,
+             "best": best}
+    return _check_p(ps[j]), best, entry
+
+
+def global_levels(fixed_affine, init_step):
+    """The levels after a coarse start: ``default_levels`` with the first level's rotation step at half the grid's."""
+    v = voxel_size(fixed_affine)
+    return [(4, (2 * v,) * 3 + (float(init_step) / 2,) * 3, 0.5 * v), (2, (0.5 * v,) * 3 + (0.5,) * 3, v / 16)]
+
+
+def _prepare(fixed_shape, fixed_affine, moving_affine, bins, levels, p0, init="header", init_limit=40.0, init_step=20.0):
+    """-> (A_fix, A_mov, levels, p0, centre, grid): ``grid`` the rotations of ``init="global"``, else None."""
     if bins not in BINS:
         raise ValueError(f"bins must be one of {BINS}, got {bins}")
+    if init not in ("header", "global"):
+        raise ValueError(f"init must be 'header' or 'global', got {init!r}")
     fa, ma = _check_affine(fixed_affine, "fixed_affine"), _check_affine(moving_affine, "moving_affine")
+    grid = None
+    if init == "global":
+        if p0 is not None:
+            raise ValueError("init='global' finds its own start: p0 goes with init='header'")
+        grid = rotation_grid(init_limit, init_step)
+        levels = global_levels(fa, init_step) if levels is None else list(levels)
     levels = default_levels(fa) if levels is None else list(levels)
     levels = [(effective_stride(fixed_shape, int(s)), step, min_t) for s, step, min_t in levels]
     p0 = np.zeros(6) if p0 is None else _check_p(p0)
-    return fa, ma, levels, p0, volume_centre(fa, fixed_shape)
+    return fa, ma, levels, p0, volume_centre(fa, fixed_shape), grid
 
 
-def _result(search, fa, ma, centre) -> RigidResult:
+def _result(search, fa, ma, centre, coarse=None) -> RigidResult:
     p, value, n_eval, trace = search
+    if coarse is not None:
+        n_eval, trace = n_eval + coarse["n_candidates"], [coarse] + trace
     return RigidResult(p, rigid_world(p, centre), candidate_matrix(p, fa, ma, centre), value, n_eval, trace)
 
 
-def register_rigid_np(fixed, fixed_affine, moving, moving_affine, bins=64, levels=None, p0=None) -> RigidResult:
+def register_rigid_np(fixed, fixed_affine, moving, moving_affine, bins=64, levels=None, p0=None, fixed_mask=None, moving_mask=None,
+                      mask_cost=False, init="header", init_limit=40.0, init_step=20.0) -> RigidResult:
     """The specification of ``register_rigid``: ``compass_search`` over ``nmi_np(joint_histogram_np(...))``.  The ranges are the
     (NaN-ignoring) minimum and maximum of each volume; ``min_count`` is a quarter of the level's sample count; ``levels``
-    defaults to ``default_levels(fixed_affine)``, every stride through ``effective_stride``."""
+    defaults to ``default_levels(fixed_affine)``, every stride through ``effective_stride``.
+
+    ``init="global"``: the search starts from ``coarse_start`` - the centres of mass of the two masks (a missing one is
+    ``volume_eval.foreground_mask_np`` of its volume: Otsu, no closing), the rotations ``rotation_grid(init_limit, init_step)``,
+    all scored at ``effective_stride(shape, 4)`` - and ``levels`` defaults to ``global_levels(fixed_affine, init_step)``; the
+    trace begins with the ``coarse`` entry and ``n_evaluations`` includes the grid.  ``mask_cost=True``: every evaluation counts
+    only the samples inside ``fixed_mask`` (computed as above when missing) and ``min_count`` is a quarter of
+    ``count_nonzero(fixed_mask[::s, ::s, ::s])``.  The moving mask serves only its centre of mass."""
+    from .volume_eval import foreground_mask_np
     fixed, moving = np.asarray(fixed), np.asarray(moving)
-    fa, ma, levels, p0, centre = _prepare(fixed.shape, fixed_affine, moving_affine, bins, levels, p0)
+    fa, ma, levels, p0, centre, grid = _prepare(fixed.shape, fixed_affine, moving_affine, bins, levels, p0, init, init_limit, init_step)
     franges = (float(np.nanmin(fixed)), float(np.nanmax(fixed)))
     mranges = (float(np.nanmin(moving)), float(np.nanmax(moving)))
+    if fixed_mask is None and (mask_cost or grid is not None):
+        fixed_mask = foreground_mask_np(fixed)
+    if fixed_mask is not None:
+        fixed_mask = _check_mask_np(fixed_mask, fixed.shape, "fixed_mask")
+    cost_mask = fixed_mask if mask_cost else None
+
+    def min_count(stride):
+        if cost_mask is None:
+            return sample_count(fixed.shape, stride) // 4
+        return int(np.count_nonzero(cost_mask[::stride, ::stride, ::stride])) // 4
 
     def cost_batch(ps, stride):
-        min_count = sample_count(fixed.shape, stride) // 4
-        return [nmi_np(joint_histogram_np(fixed, moving, candidate_matrix(p, fa, ma, centre), bins, stride, franges, mranges),
-                       min_count)[0] for p in ps]
-    return _result(compass_search(cost_batch, p0, levels), fa, ma, centre)
+        return [nmi_np(joint_histogram_np(fixed, moving, candidate_matrix(p, fa, ma, centre), bins, stride, franges, mranges, cost_mask),
+                       min_count(stride))[0] for p in ps]
+    coarse = None
+    if grid is not None:
+        moving_mask = foreground_mask_np(moving) if moving_mask is None else _check_mask_np(moving_mask, moving.shape, "moving_mask")
+        cf, cm = mask_centre_world(mask_moments_np(fixed_mask), fa), mask_centre_world(mask_moments_np(moving_mask), ma)
+        p0, _, coarse = coarse_start(cost_batch, cf, cm, centre, grid, effective_stride(fixed.shape, COARSE_STRIDE))
+    return _result(compass_search(cost_batch, p0, levels), fa, ma, centre, coarse)
 
 
 # ---------------------------------------------------------------- device
@@ -281,10 +399,19 @@ def _matrices_arg(ms):
     return ms.shape[0], (L.C.c_double * (12 * ms.shape[0]))(*ms.reshape(-1).tolist())
 
 
-def joint_histogram(fixed: torch.Tensor, moving: torch.Tensor, ms, bins, stride, fixed_range, moving_range, out=None) -> torch.Tensor:
+def _check_mask_tensor(mask, shape, what):
+    m = _check_tensor(mask, (torch.uint8,), what)
+    if shape is not None and tuple(m.shape) != tuple(shape):
+        raise ValueError(f"{what}: the mask must have its volume's shape {tuple(shape)}, got {tuple(m.shape)}")
+    return m
+
+
+def joint_histogram(fixed: torch.Tensor, moving: torch.Tensor, ms, bins, stride, fixed_range, moving_range, fixed_mask=None,
+                    out=None) -> torch.Tensor:
     """fixed, moving: contiguous (X,Y,Z) float32 CUDA tensors; ms: (K, 3, 4) or (3, 4), K <= 16 (host, float64) -> the int64 CUDA
-    tensor (K, bins, bins), equal to ``joint_histogram_np`` of every matrix.  ``out``: such a tensor to overwrite.  A memset and
-    one launch, no host synchronisation."""
+    tensor (K, bins, bins), equal to ``joint_histogram_np`` of every matrix.  ``fixed_mask``: a contiguous uint8 CUDA tensor of the
+    fixed shape (the masked entry; ``None``: the unmasked one).  ``out``: such a tensor to overwrite.  A memset and one launch, no
+    host synchronisation."""
     f, mv = _check_tensor(fixed, (torch.float32,), "joint_histogram"), _check_tensor(moving, (torch.float32,), "joint_histogram")
     _check_bins_stride(bins, stride)
     _check_range(fixed_range, bins, "fixed_range")
@@ -295,8 +422,13 @@ def joint_histogram(fixed: torch.Tensor, moving: torch.Tensor, ms, bins, stride,
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (k, bins, bins)
               and out.is_contiguous()):
         raise ValueError(f"out must be a contiguous int64 CUDA tensor of shape {(k, bins, bins)}")
-    L.call("mrisr_f32_volume_joint_histogram", f.data_ptr(), *f.shape, mv.data_ptr(), *mv.shape, arg, k, int(stride), int(bins),
-           float(fixed_range[0]), float(fixed_range[1]), float(moving_range[0]), float(moving_range[1]), out.data_ptr(), L.stream_ptr())
+    tail = (arg, k, int(stride), int(bins), float(fixed_range[0]), float(fixed_range[1]), float(moving_range[0]), float(moving_range[1]),
+            out.data_ptr(), L.stream_ptr())
+    if fixed_mask is None:
+        L.call("mrisr_f32_volume_joint_histogram", f.data_ptr(), *f.shape, mv.data_ptr(), *mv.shape, *tail)
+    else:
+        fm = _check_mask_tensor(fixed_mask, f.shape, "joint_histogram")
+        L.call("mrisr_f32_volume_joint_histogram_masked", f.data_ptr(), *f.shape, fm.data_ptr(), mv.data_ptr(), *mv.shape, *tail)
     return out
 
 
@@ -317,6 +449,15 @@ def nmi(hist: torch.Tensor, min_count=0):
     return values, counts
 
 
+def mask_moments(mask: torch.Tensor) -> torch.Tensor:
+    """mask: contiguous (X,Y,Z) uint8 CUDA tensor -> the int64 CUDA tensor (4,) ``(N, sum i, sum j, sum k)`` over its non-zero
+    voxels, equal to ``mask_moments_np``.  A memset and one launch, no host synchronisation."""
+    m = _check_mask_tensor(mask, None, "mask_moments")
+    out = torch.empty(4, dtype=torch.int64, device=m.device)
+    L.call("mrisr_u8_volume_mask_moments", m.data_ptr(), *m.shape, out.data_ptr(), L.stream_ptr())
+    return out
+
+
 def volume_range(v: torch.Tensor):
     """(lo, hi) host floats of a CUDA volume, NaN ignored: one read (not on the hot path)."""
     finite = torch.where(torch.isnan(v), v.new_tensor(float("inf")), v).amin(), torch.where(torch.isnan(v), v.new_tensor(float("-inf")), v).amax()
@@ -324,24 +465,59 @@ def volume_range(v: torch.Tensor):
     return lo, hi
 
 
-def register_rigid(fixed: torch.Tensor, fixed_affine, moving: torch.Tensor, moving_affine, bins=64, levels=None, p0=None) -> RigidResult:
+def register_rigid(fixed: torch.Tensor, fixed_affine, moving: torch.Tensor, moving_affine, bins=64, levels=None, p0=None, fixed_mask=None,
+                   moving_mask=None, mask_cost=False, init="header", init_limit=40.0, init_step=20.0) -> RigidResult:
     """The device path of ``register_rigid_np``: the same ``compass_search`` over a ``cost_batch`` that launches
     ``joint_histogram`` and ``nmi`` for the K candidates and reads their K values back - ONE device-to-host read per search
-    iteration (``trace[i]["host_reads"] == 1``).  The ranges of the two volumes are read once per registration."""
+    iteration (``trace[i]["host_reads"] == 1``).  The ranges of the two volumes are read once per registration.
+
+    ``init="global"`` (``register_rigid_np``): missing masks are ``volume_eval.foreground_mask`` of their volumes; the 8 moments of
+    the two masks are read at once; the grid's candidates go out in chunks of 16 (``joint_histogram`` + ``nmi`` each) into one
+    values tensor that is read once - the ``coarse`` entry of the trace has ``host_reads == 1`` too.  ``mask_cost=True``: the masked
+    histogram entry everywhere; the masked sample counts behind ``min_count`` are read once, before the search."""
+    from .volume_eval import foreground_mask
     f, mv = _check_tensor(fixed, (torch.float32,), "register_rigid"), _check_tensor(moving, (torch.float32,), "register_rigid")
-    fa, ma, levels, p0, centre = _prepare(f.shape, fixed_affine, moving_affine, bins, levels, p0)
+    fa, ma, levels, p0, centre, grid = _prepare(f.shape, fixed_affine, moving_affine, bins, levels, p0, init, init_limit, init_step)
     franges, mranges = volume_range(f), volume_range(mv)
+    if fixed_mask is None and (mask_cost or grid is not None):
+        fixed_mask = foreground_mask(f)[0]
+    if fixed_mask is not None:
+        fixed_mask = _check_mask_tensor(fixed_mask, f.shape, "register_rigid")
+    cost_mask = fixed_mask if mask_cost else None
+    coarse_stride = effective_stride(f.shape, COARSE_STRIDE)
+    strides = sorted({s for s, _, _ in levels} | ({coarse_stride} if grid is not None else set()))
+    if cost_mask is None:
+        min_counts = {s: sample_count(f.shape, s) // 4 for s in strides}
+    else:                                                            # one read for all the distinct strides, before the loop
+        counted = torch.stack([torch.count_nonzero(cost_mask[::s, ::s, ::s]) for s in strides]).cpu().tolist()
+        min_counts = {s: int(n) // 4 for s, n in zip(strides, counted)}
     hist = torch.empty((MAX_CANDIDATES, bins, bins), dtype=torch.int64, device=f.device)
     reads = []
 
-    def cost_batch(ps, stride):
+    def launch(ps, stride):
         ms = np.stack([candidate_matrix(p, fa, ma, centre) for p in ps])
-        values, _ = nmi(joint_histogram(f, mv, ms, bins, stride, franges, mranges, out=hist[:len(ps)]), sample_count(f.shape, stride) // 4)
-        host = values.cpu().numpy()                                  # the one synchronisation of this iteration
+        return nmi(joint_histogram(f, mv, ms, bins, stride, franges, mranges, fixed_mask=cost_mask, out=hist[:len(ps)]), min_counts[stride])[0]
+
+    def cost_batch(ps, stride):
+        host = launch(ps, stride).cpu().numpy()                      # the one synchronisation of this iteration
         reads.append(1)
         return host
-    search = compass_search(cost_batch, p0, levels)
-    for entry, n in zip(search[3], reads):
+
+    def cost_batch_many(ps, stride):
+        values = torch.empty(len(ps), dtype=torch.float64, device=f.device)
+        for at in range(0, len(ps), MAX_CANDIDATES):                 # nmi has read hist before the next chunk's memset: one stream
+            values[at:at + MAX_CANDIDATES] = launch(ps[at:at + MAX_CANDIDATES], stride)
+        host = values.cpu().numpy()                                  # the one synchronisation of the coarse stage
+        reads.append(1)
+        return host
+    coarse = None
+    if grid is not None:
+        moving_mask = foreground_mask(mv)[0] if moving_mask is None else _check_mask_tensor(moving_mask, mv.shape, "register_rigid")
+        moments = torch.stack([mask_moments(fixed_mask), mask_moments(moving_mask)]).cpu().numpy()      # one read of the 8 integers
+        cf, cm = mask_centre_world(moments[0], fa), mask_centre_world(moments[1], ma)
+        p0, _, coarse = coarse_start(cost_batch_many, cf, cm, centre, grid, coarse_stride)
+    result = _result(compass_search(cost_batch, p0, levels), fa, ma, centre, coarse)
+    assert len(result.trace) == len(reads)
+    for entry, n in zip(result.trace, reads):
         entry["host_reads"] = n
-    assert len(search[3]) == len(reads)
-    return _result(search, fa, ma, centre)
+    return result

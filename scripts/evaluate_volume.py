@@ -39,7 +39,10 @@ information, starting from the two headers (``volume_register.register_rigid``, 
 then resliced ONCE onto the same low-resolution grid through ``inv(A_input) W A_low``, ``W`` the estimated reference world ->
 input world matrix: never two interpolations.  The parameters found and the NMI before and after are logged.  Two scans of one
 head from two scanners or two sessions never share a world frame to sub-voxel accuracy; with ``--align header`` their table
-measures patient positioning, with ``--align rigid`` the methods.
+measures patient positioning, with ``--align rigid`` the methods.  ``--align_init global`` starts the registration from the best of a
+coarse grid of rotations about the two Otsu masks' centres of mass (world frames centimetres and tens of degrees apart, where the
+start from the headers ends in a wrong local optimum); ``--align_mask otsu`` counts only the samples inside the reference's Otsu
+foreground in its cost.  Both go with ``--align rigid`` only.
 """
 import argparse
 import csv
@@ -90,19 +93,25 @@ def load_mask(mask_path, ref, reference_path, ref_affine=None):
 
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
-               save_mask=None, align=None, align_interp="linear", align_bins=64):
+               save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none"):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
     step that is off).  ``save_mask``: the masks scored go to this NIfTI file.  ``align="header"``: ``input_path`` (and a mask file)
     may lie on any grid and are resliced through the headers' affines (module docstring); ``align="rigid"``: the input is registered
-    to the reference first and resliced once through the estimated transform."""
+    to the reference first and resliced once through the estimated transform; ``align_init="global"`` starts that registration
+    from a coarse grid of rotations about the masks' centres of mass, ``align_mask="otsu"`` puts the reference's Otsu mask in its
+    cost (``volume_register.register_rigid``)."""
     if align not in (None, "header", "rigid"):
         raise ValueError(f"align must be None, 'header' or 'rigid', got {align!r}")
     if align and not input_path:
         raise ValueError("--align goes with --input")
     if align and align_interp not in ("linear", "cubic"):
         raise ValueError(f"--align_interp must be linear or cubic, got {align_interp}")
+    if align_init not in ("header", "global") or align_mask not in ("none", "otsu"):
+        raise ValueError(f"--align_init is header or global and --align_mask none or otsu, got {align_init} and {align_mask}")
+    if align != "rigid" and (align_init != "header" or align_mask != "none"):
+        raise ValueError("--align_init and --align_mask go with --align rigid")
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
     if low is not None and low.ndim != ref.ndim:
@@ -128,7 +137,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             # fixed = the reference, moving = the input, from the headers as they are (p0 = 0); W: reference world -> input world
             fixed = torch.from_numpy(np.ascontiguousarray(_frames(ref)[0], dtype=np.float32)).to(device)
             moving = torch.from_numpy(np.ascontiguousarray(low_frames[0], dtype=np.float32)).to(device)
-            found = register_rigid(fixed, ref_header.affine(), moving, low_header.affine(), bins=align_bins)
+            found = register_rigid(fixed, ref_header.affine(), moving, low_header.affine(), bins=align_bins, init=align_init,
+                                   mask_cost=align_mask == "otsu")
             p = found.p
             logger.info(f"{input_path} registered to {reference_path}: t = ({p[0]:.4f}, {p[1]:.4f}, {p[2]:.4f}) mm, r = ({p[3]:.4f}, "
                         f"{p[4]:.4f}, {p[5]:.4f}) degrees, NMI {found.trace[0]['best']:.6f} -> {found.value:.6f} in "
@@ -228,6 +238,8 @@ def main(args):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
         if args.align and not args.input:
             raise ValueError("--align goes with --input")
+        if args.align != "rigid" and (args.align_init != "header" or args.align_mask != "none"):
+            raise ValueError("--align_init and --align_mask go with --align rigid")
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -247,7 +259,7 @@ def main(args):
         for path in args.reference:
             scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
                                    not args.no_graph, device, graphs, args.mask, args.mask_close, args.mask_largest, fill, args.save_mask,
-                                   args.align, args.align_interp, args.align_bins)
+                                   args.align, args.align_interp, args.align_bins, args.align_init, args.align_mask)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -310,6 +322,11 @@ def parse_args(argv=None):
                         "first (six parameters, mutual information) and reslice it once through the estimated transform")
     p.add_argument("--align_interp", type=str, choices=["linear", "cubic"], default="linear", help="interpolation of the --align reslice")
     p.add_argument("--align_bins", type=int, choices=[16, 32, 64], default=64, help="bins per axis of --align rigid's joint histogram")
+    p.add_argument("--align_init", type=str, choices=["header", "global"], default="header",
+                   help="--align rigid: start from the headers, or (global) from the best of a coarse grid of rotations about the two "
+                        "Otsu masks' centres of mass, for scans centimetres and tens of degrees apart")
+    p.add_argument("--align_mask", type=str, choices=["none", "otsu"], default="none",
+                   help="--align rigid: otsu counts only the samples inside the reference's Otsu foreground in the registration's cost")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

@@ -6,7 +6,9 @@
 
 The six parameters of a rigid transform between the two scans' world frames are estimated by maximising the normalised mutual
 information of their joint histogram (``volume_register.register_rigid``: ``csrc/volume_register.hip``, ``--bins`` 16, 32 or
-64), starting from the two headers as they are.  The output is the moving scan resliced ONCE onto the fixed scan's grid through the
+64), starting from the two headers as they are - or, with ``--init global``, from the best of a coarse grid of rotations
+(``--init_limit``, ``--init_step`` degrees) about the two foreground masks' centres of mass, for scans whose world frames are
+centimetres and tens of degrees apart; ``--mask otsu`` counts only the samples inside the fixed scan's Otsu foreground.  The output is the moving scan resliced ONCE onto the fixed scan's grid through the
 estimated transform (``--interp linear|cubic``, voxels outside the moving scan are ``--fill``), float32 under
 ``utils.nifti.header_for_grid`` of the moving scan's header.  ``--save_transform`` writes the 4 x 4 fixed world -> moving world
 matrix as text (``numpy.loadtxt`` reads it back).  A 4-D file is registered on its frame 0 and the transform is applied to every
@@ -37,8 +39,19 @@ def describe(result):
             f"{result.trace[0]['best']:.6f} -> {result.value:.6f} in {result.n_evaluations} evaluations")
 
 
-def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64, save_transform=None, fill=0.0, device="cuda"):
+def describe_coarse(result):
+    """The coarse stage of ``--init global``: the candidate taken (the start of the search) and its value."""
+    entry = result.trace[0]
+    p = result.trace[1]["p"]
+    return (f"coarse stage: candidate {entry['accepted']} of {entry['n_candidates']} at stride {entry['stride']}, t = ({p[0]:.4f}, "
+            f"{p[1]:.4f}, {p[2]:.4f}) mm, r = ({p[3]:.4f}, {p[4]:.4f}, {p[5]:.4f}) degrees, NMI {entry['best']:.6f}")
+
+
+def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64, save_transform=None, fill=0.0, device="cuda",
+                  init="header", init_limit=40.0, init_step=20.0, mask="none"):
     """NIfTI files -> the moving scan on the fixed scan's grid (written and returned), and the ``RigidResult``."""
+    if mask not in ("none", "otsu"):
+        raise ValueError(f"--mask must be none or otsu, got {mask}")
     fixed, fixed_header = read_nifti(fixed_path)
     moving, moving_header = read_nifti(moving_path)
     frames = [moving] if moving.ndim == 3 else [moving[..., t] for t in range(moving.shape[3])]
@@ -46,7 +59,10 @@ def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64
     fixed0 = fixed if fixed.ndim == 3 else fixed[..., 0]
     fixed0 = torch.from_numpy(np.ascontiguousarray(fixed0, dtype=np.float32)).to(device)
     fixed_affine, shape = fixed_header.affine(), tuple(fixed.shape[:3])
-    result = register_rigid(fixed0, fixed_affine, frames[0], moving_header.affine(), bins=bins)
+    result = register_rigid(fixed0, fixed_affine, frames[0], moving_header.affine(), bins=bins, mask_cost=mask == "otsu", init=init,
+                            init_limit=init_limit, init_step=init_step)
+    if init == "global":
+        logger.info(f"Registering {moving_path} to {fixed_path}, {describe_coarse(result)}")
     logger.info(f"Registered {moving_path} to {fixed_path}: {describe(result)}")
     outs = [reslice(f, result.matrix, shape, interp, fill) for f in frames]
     share = covered_share(moving.shape[:3], result.matrix, shape, device)
@@ -69,7 +85,8 @@ def main(args):
             raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
         device = torch.device("cuda")
         logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        register_file(args.fixed, args.moving, args.output, args.interp, args.bins, args.save_transform, args.fill, device)
+        register_file(args.fixed, args.moving, args.output, args.interp, args.bins, args.save_transform, args.fill, device, args.init,
+                      args.init_limit, args.init_step, args.mask)
         return 0
     except Exception as e:
         logger.error(f"Error during registration: {e}")
@@ -83,6 +100,13 @@ def parse_args(argv=None):
     p.add_argument("--output", type=str, required=True, help="the moving scan on the fixed grid, .nii or .nii.gz, float32")
     p.add_argument("--interp", type=str, choices=["linear", "cubic"], default="linear", help="interpolation of the final reslice")
     p.add_argument("--bins", type=int, choices=[16, 32, 64], default=64, help="bins per axis of the joint histogram")
+    p.add_argument("--init", type=str, choices=["header", "global"], default="header",
+                   help="header: start from the two headers as they are; global: start from the best of a coarse grid of rotations "
+                        "about the two Otsu masks' centres of mass (scans centimetres and tens of degrees apart)")
+    p.add_argument("--init_limit", type=float, default=40.0, help="--init global: the grid spans +- this many degrees per axis")
+    p.add_argument("--init_step", type=float, default=20.0, help="--init global: the grid's step in degrees")
+    p.add_argument("--mask", type=str, choices=["none", "otsu"], default="none",
+                   help="otsu: only the samples inside the fixed scan's Otsu foreground mask enter the cost")
     p.add_argument("--save_transform", type=str, default=None, help="write the 4 x 4 fixed world -> moving world matrix as text")
     p.add_argument("--fill", type=float, default=0.0, help="value of the output voxels whose centre lies outside the moving scan")
     p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")

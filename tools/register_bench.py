@@ -2,6 +2,7 @@
 """Cost of the registration cost function (csrc/volume_register.hip) next to the same work written with torch.
 
     python tools/register_bench.py [--reps 20] [--warmup 3] [--inner 5] [--size 256] [--skip_torch] [--variant_libs name=path ...]
+    python tools/register_bench.py --global_init [--reps 20] [--warmup 3] [--inner 5] [--size 256]
 
 A 12-candidate evaluation - the unit of ``volume_register.compass_search`` - on a ``--size``^3 float32 phantom against a rotated,
 shifted, contrast-inverted copy: ``joint_histogram`` of the 12 probe matrices around a point plus ``nmi``, at strides 4 and 2 with
@@ -13,6 +14,10 @@ box in one run; its histograms are compared with the kernel's by total count onl
 coordinates in float32 and has no inside test).  ``--variant_libs``: other builds of libmrisr.so (``-DMRISR_REGISTER_KLOOP=1``: a
 workgroup loops over all candidates instead of serving one) join the alternation through ctypes; ``raw`` is this build's entry
 called the same way.  ``registration``: the wall time of one whole ``register_rigid`` of the pair and what it found.
+``--global_init`` times what ``register_rigid(init="global", mask_cost=True)`` adds instead: the 125-candidate coarse stage
+(8 chunks of 16 ``joint_histogram`` + ``nmi`` launches at stride 4, no read-back inside the window) and one 12-candidate
+evaluation at strides 4 and 2, each with the fixed-side mask in the cost and without, alternating in one loop.  The mask is an
+ellipsoid that fills about 25 % of the box; ``mask_moments`` of it is timed as well.
 Prints one JSON line (profiles/NOTES.md, "Register")."""
 import argparse
 import ctypes as C
@@ -68,7 +73,55 @@ def alternating_times(fns, reps, warmup, inner):
             e1.record()
             e1.synchronize()
             times[k].append(e0.elapsed_time(e1) * 1e3 / inner)
-    return {k: {"us_median": round(statistics.median(v), 2), "us_min": round(min(v), 2)} for k, v in times.items()}
+    return {k: {"us_median": round(statistics.median(v), 2), "us_min": round(min(v), 2), "us_max": round(max(v), 2)} for k, v in times.items()}
+
+
+def ellipsoid_mask(n, device, semi=0.78):
+    """uint8 n^3: an ellipsoid with semi-axes ``semi`` of the half extent (pi / 6 * 0.78^3 = 24.8 % of the box)."""
+    ax = torch.linspace(-1, 1, n, device=device)
+    x, y, z = torch.meshgrid(ax, ax, ax, indexing="ij")
+    return ((x * x + y * y + z * z) <= semi * semi).to(torch.uint8).contiguous()
+
+
+def global_init_case(args, G, fixed, moving, affine, centre):
+    """The coarse stage and a 12-candidate evaluation, masked against unmasked."""
+    n, shape = args.size, tuple(fixed.shape)
+    mask = ellipsoid_mask(n, "cuda")
+    franges, mranges = G.volume_range(fixed), G.volume_range(moving)
+    res = {"gpu": torch.cuda.get_device_name(0), "size": n, "bins": BINS, "inner": args.inner, "reps": args.reps,
+           "mask_share": round(float(mask.float().mean()), 4)}
+    grid = G.rotation_grid(40.0, 20.0)
+    coarse_ps = np.hstack([np.zeros((len(grid), 3)), grid])
+    step = np.array([2.0] * 6)
+    probe_ps = np.zeros((12, 6))
+    for a in range(6):
+        probe_ps[2 * a, a], probe_ps[2 * a + 1, a] = step[a], -step[a]
+    hist = torch.empty((G.MAX_CANDIDATES, BINS, BINS), dtype=torch.int64, device="cuda")
+
+    def evaluation(ps, stride, fixed_mask, min_count):
+        ms = np.stack([G.candidate_matrix(q, affine, affine, centre) for q in ps])
+        values = torch.empty(len(ps), dtype=torch.float64, device="cuda")
+        chunks = [(at, ms[at:at + G.MAX_CANDIDATES]) for at in range(0, len(ms), G.MAX_CANDIDATES)]
+
+        def run():
+            for at, m in chunks:
+                h = G.joint_histogram(fixed, moving, m, BINS, stride, franges, mranges, fixed_mask=fixed_mask, out=hist[:len(m)])
+                values[at:at + len(m)] = G.nmi(h, min_count)[0]
+            return values
+        return run
+
+    for name, ps, strides in (("coarse_125", coarse_ps, (4,)), ("probe_12", probe_ps, (4, 2))):
+        for stride in strides:
+            samples = G.sample_count(shape, stride)
+            inside = int(torch.count_nonzero(mask[::stride, ::stride, ::stride]))
+            fns = {"unmasked": evaluation(ps, stride, None, samples // 4), "masked": evaluation(ps, stride, mask, inside // 4)}
+            r = {"samples": samples, "masked_samples": inside, "times": alternating_times(fns, args.reps, args.warmup, args.inner)}
+            r["masked_over_unmasked"] = round(r["times"]["masked"]["us_median"] / r["times"]["unmasked"]["us_median"], 4)
+            r["finite_values"] = {k: int(torch.isfinite(fn()).sum()) for k, fn in fns.items()}
+            res[f"{name}_stride{stride}"] = r
+    res["mask_moments"] = alternating_times({"kernel": lambda: G.mask_moments(mask)}, args.reps, args.warmup, args.inner)["kernel"]
+    res["mask_moments"]["moments"] = G.mask_moments(mask).cpu().tolist()
+    return res
 
 
 def raw_call(path, fixed, moving, ms, stride, franges, mranges, hist, values, counts, min_count):
@@ -100,6 +153,7 @@ def main():
     p.add_argument("--skip_torch", action="store_true")
     p.add_argument("--skip_registration", action="store_true")
     p.add_argument("--variant_libs", type=str, nargs="*", default=[], help="name=path of other builds of libmrisr.so")
+    p.add_argument("--global_init", action="store_true", help="time the coarse stage and the masked cost instead (module docstring)")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("register_bench needs the MI355X: there is nothing to time on a CPU")
@@ -114,6 +168,9 @@ def main():
     p_true = np.array([3.2, -2.4, 1.7, 4.0, -3.0, 5.0]) * np.array([n / 64] * 3 + [1] * 3)
     fixed = phantom(n, "cuda")
     moving = (1.0 - reslice(fixed, np.linalg.inv(G.rigid_world(p_true, centre))[:3], shape, "linear").clamp_min(0).sqrt()).contiguous()
+    if args.global_init:
+        print(json.dumps(global_init_case(args, G, fixed, moving, affine, centre)))
+        return
     franges, mranges = G.volume_range(fixed), G.volume_range(moving)
     # the 12 probes of a first search iteration around p = 0
     step = np.array([2.0] * 6)
