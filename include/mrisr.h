@@ -684,6 +684,31 @@ int mrisr_f32_volume_joint_histogram_masked(const float* fixed, int FX, int FY, 
  * MRISR_E_UNSUPPORTED more than 2^31 - 1 voxels (inside these bounds no sum can overflow: sum i < 2^31 2^15).                      */
 int mrisr_u8_volume_mask_moments(const unsigned char* mask, int X, int Y, int Z, long long* out4, void* stream);
 
+/* ---- intensity standardisation between scans (extension; csrc/volume_intensity.hip): Nyul-Udupa landmarks - percentiles of the
+ *      voxels inside a mask - and the piecewise-linear map that sends one scan's landmarks onto another's. ---------------------- */
+/* bytes of device workspace mrisr_f32_volume_masked_percentiles needs for nq quantiles (any volume size); 0 for nq outside 1..16.
+ * The contents need no initialisation and one workspace may serve call after call on one stream; 16-byte aligned.                */
+size_t mrisr_f32_masked_percentiles_workspace_bytes(int nq);
+/* out[i] = np.percentile(values, q[i]), method 'linear', numpy's float32 arithmetic, over the counted voxels of the DEVICE float32
+ * volume vol (n voxels): those whose mask byte is non-zero (any non-zero value; mask NULL: every voxel) and whose value is not NaN.
+ * count[0] = their number.  q: HOST pointer to nq values in [0, 100], non-decreasing, read at the call.  The rule is
+ * mrisr_f32_percentile_bounds': v = float32(count - 1) * (float32(q) / 100), the order statistics k = min(floor(v), count - 1) and
+ * min(k + 1, count - 1) by an exact radix select, t = v - floor(v), numpy's two-branch interpolation - but count, the ranks and
+ * the weights are derived ON THE DEVICE from the first pass's histogram.  out: DEVICE, nq floats; count: DEVICE, one int64.
+ * count == 0: every out[i] is NaN.  -0.0 and +0.0 are equal values and either may be returned.  Enqueues 9 launches on stream,
+ * clears what it needs of the workspace itself, never synchronises with the host (HIP-graph capturable).
+ * MRISR_E_SHAPE: n == 0 or n > 2^32 - 1; MRISR_E_ARG: null pointer (mask excepted), a workspace that is not 16-byte aligned, nq
+ * outside 1..16, q not non-decreasing within [0, 100].                                                                            */
+int mrisr_f32_volume_masked_percentiles(const float* vol, const unsigned char* mask, size_t n, const double* q, int nq, float* out,
+                                        long long* count, void* workspace, void* stream);
+/* dst[j] = d[i] + (v - s[i]) * slope_i for every voxel v = src[j], with s = src_landmarks, d = dst_landmarks (both DEVICE, L floats,
+ * L in 2..16), i = clamp(#{j : s[j] <= v} - 1, 0, L - 2), w = s[i+1] - s[i], slope_i = (w == 0) ? 0 : (d[i+1] - d[i]) / w, all in
+ * float32, every operation rounded on its own.  Below s[0] and above s[L-1] the first and the last segment extend linearly (no
+ * clamp); a NaN voxel gives NaN.  dst may equal src.  One launch.  MRISR_E_ARG: null pointer, L outside 2..16; MRISR_E_SHAPE:
+ * n == 0.                                                                                                                         */
+int mrisr_f32_volume_piecewise_map(const float* src, size_t n, const float* src_landmarks, const float* dst_landmarks, int L,
+                                   float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,10 +176,13 @@ SIGNATURES = {
     "mrisr_f32_volume_joint_histogram_masked": (_i, [_fp, _i, _i, _i, _vp, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, _i, _i, _d, _d, _d,
                                                      _d, _vp, _vp]),
     "mrisr_u8_volume_mask_moments": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "mrisr_f32_masked_percentiles_workspace_bytes": (_sz, [_i]),
+    "mrisr_f32_volume_masked_percentiles": (_i, [_fp, _vp, _sz, C.POINTER(C.c_double), _i, _fp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_piecewise_map": (_i, [_fp, _sz, _fp, _fp, _i, _fp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 317      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 318      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

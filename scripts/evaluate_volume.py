@@ -43,6 +43,16 @@ measures patient positioning, with ``--align rigid`` the methods.  ``--align_ini
 coarse grid of rotations about the two Otsu masks' centres of mass (world frames centimetres and tens of degrees apart, where the
 start from the headers ends in a wrong local optimum); ``--align_mask otsu`` counts only the samples inside the reference's Otsu
 foreground in its cost.  Both go with ``--align rigid`` only.
+
+``--match_intensity landmarks|range`` (with ``--input``) handles what geometry does not: MR intensities are in arbitrary units, and
+on a real pair the input differs from the reference by a scale, an offset and usually a monotone contrast curve - MSE, RMSE, MAE and
+PSNR then measure the gain setting of two scanners, and so do SSIM's luminance and contrast terms.  After the ``--align`` reslice,
+if there is one, and once, before any method sees it, every input frame is mapped onto its reference frame's intensity scale: the
+piecewise-linear function that sends the percentiles 1, 10, ..., 90, 99 (``range``: 1 and 99) of the input's foreground onto those
+of the reference's (``volume_intensity.match_intensity``, Nyul-Udupa; ``csrc/volume_intensity.hip``).  Each side's foreground is
+its own Otsu mask (``volume_eval.foreground_mask``, no closing), whatever ``--mask`` says; the voxels a reslice left at the fill
+value 0 fall below Otsu's threshold and do not move the landmarks.  The landmarks and the voxel counts are logged.  The default,
+``none``, leaves a run as it was.
 """
 import argparse
 import csv
@@ -59,7 +69,8 @@ if REPO not in sys.path:
 
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
 from mri_superresolution_amd.utils.nifti import downscaled_affine, grid_matrix, read_nifti, write_nifti   # noqa: E402
-from mri_superresolution_amd.volume_eval import evaluate_volume, otsu_threshold_value      # noqa: E402
+from mri_superresolution_amd.volume_eval import evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
+from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity    # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice, reslice_mask    # noqa: E402
 
@@ -93,7 +104,8 @@ def load_mask(mask_path, ref, reference_path, ref_affine=None):
 
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
-               save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none"):
+               save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
+               match="none"):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -101,7 +113,12 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     may lie on any grid and are resliced through the headers' affines (module docstring); ``align="rigid"``: the input is registered
     to the reference first and resliced once through the estimated transform; ``align_init="global"`` starts that registration
     from a coarse grid of rotations about the masks' centres of mass, ``align_mask="otsu"`` puts the reference's Otsu mask in its
-    cost (``volume_register.register_rigid``)."""
+    cost (``volume_register.register_rigid``).  ``match`` (``"landmarks"`` / ``"range"``): every input frame is mapped onto its
+    reference frame's intensity scale before any method sees it (module docstring)."""
+    if match not in ("none", "landmarks", "range"):
+        raise ValueError(f"--match_intensity is none, range or landmarks, got {match!r}")
+    if match != "none" and not input_path:
+        raise ValueError("--match_intensity goes with --input")
     if align not in (None, "header", "rigid"):
         raise ValueError(f"align must be None, 'header' or 'rigid', got {align!r}")
     if align and not input_path:
@@ -160,6 +177,12 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             lr = low_frames[t] if align else torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device)
         if mask_frames is not None:
             m = mask_frames[t] if align else torch.from_numpy(mask_frames[t]).to(device)
+        if match != "none":
+            lr, found = match_intensity(lr, vol, foreground_mask(lr)[0], foreground_mask(vol)[0],
+                                        LANDMARKS if match == "landmarks" else RANGE)
+            marks = "  ".join(f"{q:g}%: {a:.6g} -> {b:.6g}" for q, a, b in zip(found.percentiles, found.source_landmarks, found.target_landmarks))
+            logger.info(f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''} mapped onto the intensity scale of {reference_path} ({match}): "
+                        f"{found.source_count} input and {found.target_count} reference foreground voxels; landmarks {marks}")
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
                               mask_fill_holes=mask_fill_holes)
@@ -240,6 +263,8 @@ def main(args):
             raise ValueError("--align goes with --input")
         if args.align != "rigid" and (args.align_init != "header" or args.align_mask != "none"):
             raise ValueError("--align_init and --align_mask go with --align rigid")
+        if args.match_intensity != "none" and not args.input:
+            raise ValueError("--match_intensity goes with --input")
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -259,7 +284,7 @@ def main(args):
         for path in args.reference:
             scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
                                    not args.no_graph, device, graphs, args.mask, args.mask_close, args.mask_largest, fill, args.save_mask,
-                                   args.align, args.align_interp, args.align_bins, args.align_init, args.align_mask)
+                                   args.align, args.align_interp, args.align_bins, args.align_init, args.align_mask, args.match_intensity)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -327,6 +352,9 @@ def parse_args(argv=None):
                         "Otsu masks' centres of mass, for scans centimetres and tens of degrees apart")
     p.add_argument("--align_mask", type=str, choices=["none", "otsu"], default="none",
                    help="--align rigid: otsu counts only the samples inside the reference's Otsu foreground in the registration's cost")
+    p.add_argument("--match_intensity", type=str, choices=["none", "range", "landmarks"], default="none",
+                   help="map every --input frame onto its reference frame's intensity scale before any method sees it: the percentiles "
+                        "1, 10, ..., 90, 99 (landmarks) or 1 and 99 (range) of the two Otsu foregrounds (needs --input)")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Bring a NIfTI scan onto another scan's intensity scale on the device (extension).
+
+    python scripts/match_intensity.py --input lowfield.nii.gz --like reference.nii.gz --output matched.nii.gz
+    python scripts/match_intensity.py --input a.nii.gz --like b.nii.gz --output c.nii.gz --mode range --mask none --like_mask brain.nii.gz
+
+MR intensities are in arbitrary units: two scanners or two sessions differ by a scale, an offset and usually a monotone contrast
+curve.  ``--mode landmarks`` (Nyul-Udupa) takes the percentiles 1, 10, 20, ..., 90, 99 of each scan's foreground and maps the
+input through the piecewise-linear function that sends its landmarks onto those of ``--like``; ``--mode range`` uses the
+percentiles 1 and 99 alone (one linear map); ``--percentiles P ...`` gives 2..16 of them.  Below the first and above the last
+landmark the first and the last segment extend linearly.  The two scans need not share a grid: only their histograms meet.
+``--mask`` (the input's) and ``--like_mask``: ``otsu`` (default; ``volume_eval.foreground_mask`` of each scan on its own, no
+closing), ``none`` (every voxel) or a NIfTI-1 file of that scan's spatial shape (non-zero = foreground).  A 4-D input is matched
+frame by frame; a 3-D ``--like`` (or mask) serves every frame, a 4-D one must have as many frames.  The output keeps the input's
+header, as float32.  ``--save_landmarks F.txt``: three text columns - percentile, source landmark, target landmark - one block per
+frame.  The percentiles are selected exactly on the device (``csrc/volume_intensity.hip``, equal to
+``volume_intensity.match_intensity_np``).  Exit code 0 / 1 (error logged), as ``scripts/reslice_volume.py``.
+"""
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from mri_superresolution_amd.utils.nifti import read_nifti, write_nifti                          # noqa: E402
+from mri_superresolution_amd.volume_eval import foreground_mask                                  # noqa: E402
+from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity          # noqa: E402
+
+logger = logging.getLogger("match_intensity")
+MODES = {"landmarks": LANDMARKS, "range": RANGE}
+
+
+def _frames(data):
+    return [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
+
+
+def _mask_frames(spec, data, path, count, what):
+    """-> ``count`` entries: ``"otsu"``, None, or a uint8 array of the scan's spatial shape."""
+    if spec == "otsu":
+        return ["otsu"] * count
+    if spec == "none":
+        return [None] * count
+    mask = read_nifti(spec)[0]
+    if mask.ndim not in (3, 4) or tuple(mask.shape[:3]) != tuple(data.shape[:3]):
+        raise ValueError(f"{what} {spec} has shape {tuple(mask.shape)}, {path} has {tuple(data.shape)}")
+    frames = [np.ascontiguousarray((f != 0).astype(np.uint8)) for f in _frames(mask)]
+    if len(frames) not in (1, count):
+        raise ValueError(f"{what} {spec} has {len(frames)} timepoints, {count} are needed")
+    return frames * count if len(frames) == 1 else frames
+
+
+def _on_device(frame, mask, device):
+    vol = torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(device)
+    if isinstance(mask, str):
+        return vol, foreground_mask(vol)[0]
+    return vol, (None if mask is None else torch.from_numpy(mask).to(device))
+
+
+def format_landmarks(found):
+    return "  ".join(f"{q:g}%: {s:.6g} -> {t:.6g}" for q, s, t in zip(found.percentiles, found.source_landmarks, found.target_landmarks))
+
+
+def match_file(input_path, like_path, output_path, percentiles=LANDMARKS, mask="otsu", like_mask="otsu", save_landmarks=None, device="cuda"):
+    """NIfTI file -> NIfTI file on the intensity scale of ``like_path``; returns (the output array as written, one
+    ``IntensityMatch`` per frame)."""
+    data, header = read_nifti(input_path)
+    like = read_nifti(like_path)[0]
+    frames, like_frames = _frames(data), _frames(like)
+    if len(like_frames) not in (1, len(frames)):
+        raise ValueError(f"{like_path} has {len(like_frames)} timepoints, {input_path} has {len(frames)}")
+    masks = _mask_frames(mask, data, input_path, len(frames), "--mask")
+    like_masks = _mask_frames(like_mask, like, like_path, len(like_frames), "--like_mask")
+    outs, founds = [], []
+    target = None
+    for t, frame in enumerate(frames):
+        src, smask = _on_device(frame, masks[t], device)
+        if t == 0 or len(like_frames) > 1:                       # a 3-D --like is uploaded (and masked) once
+            target = _on_device(like_frames[t], like_masks[t], device)
+        out, found = match_intensity(src, target[0], smask, target[1], percentiles)
+        logger.info(f"{'frame ' + str(t) + ': ' if len(frames) > 1 else ''}{found.source_count} source and {found.target_count} target "
+                    f"voxels; landmarks {format_landmarks(found)}")
+        outs.append(out.cpu().numpy())
+        founds.append(found)
+    result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
+    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
+    write_nifti(output_path, result, header)
+    if save_landmarks:
+        os.makedirs(os.path.dirname(os.path.abspath(save_landmarks)), exist_ok=True)
+        with open(save_landmarks, "w") as f:
+            for t, found in enumerate(founds):
+                f.write(f"# frame {t}: percentile, source landmark, target landmark ({found.source_count} / {found.target_count} voxels)\n")
+                for q, s, d in zip(found.percentiles, found.source_landmarks, found.target_landmarks):
+                    f.write(f"{q:.17g} {float(s):.9g} {float(d):.9g}\n")
+        logger.info(f"Saved the landmarks to {save_landmarks}")
+    logger.info(f"Matched volume {tuple(data.shape)} saved to {output_path}")
+    return result, founds
+
+
+def main(args):
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+    try:
+        if args.cpu or not torch.cuda.is_available():
+            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
+        if args.percentiles is not None and args.mode is not None:
+            raise ValueError("--percentiles goes without --mode")
+        percentiles = tuple(args.percentiles) if args.percentiles is not None else MODES[args.mode or "landmarks"]
+        device = torch.device("cuda")
+        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+        match_file(args.input, args.like, args.output, percentiles, args.mask, args.like_mask, args.save_landmarks, device)
+        return 0
+    except Exception as e:
+        logger.error(f"Error during intensity matching: {e}")
+        return 1
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Map a NIfTI volume onto another volume's intensity scale (extension)")
+    p.add_argument("--input", type=str, required=True, help="input scan: single-file NIfTI-1, .nii or .nii.gz, 3-D or 4-D")
+    p.add_argument("--like", type=str, required=True, help="the scan whose intensity scale is taken (any grid)")
+    p.add_argument("--output", type=str, required=True, help="output scan, .nii or .nii.gz, float32, the input's header")
+    p.add_argument("--mode", type=str, choices=sorted(MODES), default=None,
+                   help="landmarks (default): percentiles 1, 10, ..., 90, 99 (Nyul-Udupa); range: percentiles 1 and 99")
+    p.add_argument("--percentiles", type=float, nargs="+", default=None, help="2..16 non-decreasing percentiles instead of a --mode")
+    p.add_argument("--mask", type=str, default="otsu", help="foreground of the input: otsu (default), none, or a NIfTI-1 mask")
+    p.add_argument("--like_mask", type=str, default="otsu", help="foreground of --like: otsu (default), none, or a NIfTI-1 mask")
+    p.add_argument("--save_landmarks", type=str, default=None, help="write percentile, source landmark, target landmark as text")
+    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    return p.parse_args(argv)
+
+
+if __name__ == "__main__":
+    sys.exit(main(parse_args()))
