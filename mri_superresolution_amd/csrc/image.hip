@@ -9,7 +9,7 @@
 // float32 path operation by operation (np.percentile(method='linear') on a float32 array: virtual index (n-1) q / 100 in
 // float32, _lerp's two branches; then float32 subtract and divide) - checked against numpy in
 // tests/test_gpu_image.py.
-#include "common.h"
+#include "volume_common.h"
 
 __global__ __launch_bounds__(256) void u8_histogram_kernel(const uint8_t* __restrict__ img, size_t n, unsigned* __restrict__ hist) {
     __shared__ unsigned h[256];
@@ -92,15 +92,10 @@ __global__ __launch_bounds__(256) void f32_to_u8_kernel(const float* __restrict_
     }
 }
 
-static int blocks_for(size_t n, size_t per_block, int cap) {
-    size_t b = (n + per_block - 1) / per_block;
-    return (int)(b < 1 ? 1 : (b > (size_t)cap ? (size_t)cap : b));
-}
-
 extern "C" int mrisr_u8_histogram(const uint8_t* img, size_t pixels_per_image, int batch, unsigned* hist, void* stream) {
     if (!img || !hist) MRISR_FAIL(MRISR_E_ARG, "u8_histogram: null pointer");
     if (batch < 1 || batch > 65535 || pixels_per_image == 0) MRISR_FAIL(MRISR_E_SHAPE, "u8_histogram: batch %d, %zu pixels", batch, pixels_per_image);
-    dim3 grid(blocks_for(pixels_per_image, 256 * 64, 256), batch);
+    dim3 grid(capped_grid(pixels_per_image, 256 * 64, 256), batch);
     u8_histogram_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(img, pixels_per_image, hist);
     MRISR_CHECK_LAUNCH("u8_histogram");
     return MRISR_OK;
@@ -111,7 +106,7 @@ extern "C" int mrisr_u8_percentile_normalise(const uint8_t* img, const unsigned*
     if (!img || !hist || !out) MRISR_FAIL(MRISR_E_ARG, "u8_percentile_normalise: null pointer");
     if (batch < 1 || batch > 65535 || pixels_per_image == 0) MRISR_FAIL(MRISR_E_SHAPE, "u8_percentile_normalise: batch %d, %zu pixels", batch, pixels_per_image);
     if (!(q_lo >= 0.0 && q_lo <= q_hi && q_hi <= 100.0)) MRISR_FAIL(MRISR_E_ARG, "u8_percentile_normalise: percentiles %g, %g", q_lo, q_hi);
-    dim3 grid(blocks_for(pixels_per_image, 256 * 16, 512), batch);
+    dim3 grid(capped_grid(pixels_per_image, 256 * 16, 512), batch);
     u8_percentile_normalise_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(img, hist, pixels_per_image, q_lo, q_hi, out, lohi);
     MRISR_CHECK_LAUNCH("u8_percentile_normalise");
     return MRISR_OK;
@@ -120,7 +115,7 @@ extern "C" int mrisr_u8_percentile_normalise(const uint8_t* img, const unsigned*
 extern "C" int mrisr_f32_to_u8(const float* x, uint8_t* out, size_t n, void* stream) {
     if (!x || !out) MRISR_FAIL(MRISR_E_ARG, "f32_to_u8: null pointer");
     if (n == 0) return MRISR_OK;
-    f32_to_u8_kernel<<<blocks_for(n, 256 * 8, 4096), 256, 0, (hipStream_t)stream>>>(x, out, n);
+    f32_to_u8_kernel<<<capped_grid(n, 256 * 8, 4096), 256, 0, (hipStream_t)stream>>>(x, out, n);
     MRISR_CHECK_LAUNCH("f32_to_u8");
     return MRISR_OK;
 }
@@ -190,7 +185,7 @@ extern "C" int mrisr_augment_geo_u8(const uint8_t* in, uint8_t* out, int batch, 
                                     const double* mean_device, void* stream) {
     if (!in || !out || !params_device || in == out) MRISR_FAIL(MRISR_E_ARG, "augment_geo_u8: null / aliased pointer");
     if (batch < 1 || batch > 65535 || H < 1 || W < 1) MRISR_FAIL(MRISR_E_SHAPE, "augment_geo_u8: batch %d H %d W %d", batch, H, W);
-    dim3 grid(blocks_for((size_t)H * W, 256 * 8, 256), batch);
+    dim3 grid(capped_grid((size_t)H * W, 256 * 8, 256), batch);
     augment_geo_u8_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(in, out, H, W, params_device, mean_device);
     MRISR_CHECK_LAUNCH("augment_geo_u8");
     return MRISR_OK;
@@ -200,7 +195,7 @@ extern "C" int mrisr_augment_finish_u8(const uint8_t* in, float* out, int batch,
                                        const mrisr_aug_photo* params_device, const double* mean_device, void* stream) {
     if (!in || !out || !params_device) MRISR_FAIL(MRISR_E_ARG, "augment_finish_u8: null pointer");
     if (batch < 1 || batch > 65535 || pixels_per_image == 0) MRISR_FAIL(MRISR_E_SHAPE, "augment_finish_u8: batch %d, %zu pixels", batch, pixels_per_image);
-    dim3 grid(blocks_for(pixels_per_image, 256 * 8, 256), batch);
+    dim3 grid(capped_grid(pixels_per_image, 256 * 8, 256), batch);
     augment_finish_u8_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(in, out, pixels_per_image, params_device, mean_device);
     MRISR_CHECK_LAUNCH("augment_finish_u8");
     return MRISR_OK;

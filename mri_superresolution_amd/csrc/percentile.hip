@@ -17,12 +17,10 @@
 //   f32_window_restore      clamp(y, 0, 1) * (hi - lo) + lo -> float32 or int16 (np.rint, saturated)
 //
 // The arithmetic restates numpy's float32 path operation by operation (compiled with -ffp-contract=off): for a float32
-// array np.percentile carries the quantile and the virtual index in float32 (q32 = float32(q) / 100, v = float32(n - 1) * q32;
-// the same rule as np_percentile_u8 of image.hip), gamma = v - floor(v), and _lerp's two branches.  The specification is
-// utils/imageops.percentile_bounds_np, itself tested against np.percentile (tests/test_percentile_host.py).
-#include "common.h"
-
-#include <math.h>
+// array np.percentile carries the quantile and the virtual index in float32 (the same rule as np_percentile_u8 of image.hip) and
+// ends in _lerp's two branches: np_virtual_index and np_lerp_f32 of volume_common.h, where the key lives too.  The specification
+// is utils/imageops.percentile_bounds_np, itself tested against np.percentile (tests/test_percentile_host.py).
+#include "volume_common.h"
 
 constexpr int kTargets = 4;                  // order statistics per image: (k, k + 1) of q_lo, (k, k + 1) of q_hi
 constexpr int kBins = 256;                   // 8-bit digits
@@ -31,13 +29,6 @@ constexpr int kImageWords = kTargets * kBins + 2 * kTargets;    // workspace wor
 
 struct RankSet { unsigned k[kTargets]; };
 
-__device__ __forceinline__ unsigned f32_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float f32_from_key(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 // first target whose prefix equals target t's: the one that owns their common histogram
 __device__ __forceinline__ int owner_of(const unsigned* prefix, int t) {
     int o = t;
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(256) void f32_select_hist_kernel(const float* __res
     __syncthreads();
     const int shift = 24 - 8 * pass;
     auto count = [&](float v) {
-        const unsigned key = f32_key(v);
+        const unsigned key = f32_order_key(v);
         const unsigned high = pass == 0 ? 0u : key >> (shift + 8);
         const unsigned digit = (key >> shift) & 255u;
 #pragma unroll
@@ -131,13 +122,8 @@ __global__ __launch_bounds__(256) void f32_select_pick_kernel(unsigned* __restri
         w[kTargets * kBins + kTargets + t] = s_new_rank[t];
     }
     if (pass == kPasses - 1 && t < 2) {
-        // numpy's _lerp in float32: a + (b - a) * t, and b - (b - a) * (1 - t) where t >= 0.5
-        const float a = f32_from_key(s_new_prefix[2 * t]), c = f32_from_key(s_new_prefix[2 * t + 1]);
-        const float g = t == 0 ? t_lo : t_hi;
-        const float diff = __fsub_rn(c, a);
-        float r = __fadd_rn(a, __fmul_rn(diff, g));
-        if (g >= 0.5f) r = __fsub_rn(c, __fmul_rn(diff, __fsub_rn(1.f, g)));
-        lohi[2 * (size_t)b + t] = r;
+        const float a = f32_from_order_key(s_new_prefix[2 * t]), c = f32_from_order_key(s_new_prefix[2 * t + 1]);
+        lohi[2 * (size_t)b + t] = np_lerp_f32(a, c, t == 0 ? t_lo : t_hi);
     }
 }
 
@@ -171,26 +157,9 @@ __global__ __launch_bounds__(256) void f32_window_restore_kernel(const float* __
     }
 }
 
-static int grid_x(size_t n, size_t per_block, int cap) {
-    size_t b = (n + per_block - 1) / per_block;
-    return (int)(b < 1 ? 1 : (b > (size_t)cap ? (size_t)cap : b));
-}
-
 extern "C" size_t mrisr_f32_percentile_workspace_bytes(int batch) {
     if (batch < 1 || batch > 65535) return 0;
     return (size_t)batch * kImageWords * sizeof(unsigned);
-}
-
-// rank of the lower order statistic, its upper neighbour and the interpolation weight of np.percentile(float32[n], q)
-static void np_virtual_index(size_t n, double q, unsigned* k0, unsigned* k1, float* gamma) {
-    const float q32 = (float)q / 100.f;
-    const float virt = (float)(n - 1) * q32;
-    const float prev = floorf(virt);
-    size_t k = (size_t)prev;
-    if (k > n - 1) k = n - 1;             // float32(n - 1) may round up past the last index when n > 2^24
-    *k0 = (unsigned)k;
-    *k1 = (unsigned)(k + 1 < n ? k + 1 : n - 1);
-    *gamma = virt - prev;
 }
 
 extern "C" int mrisr_f32_percentile_bounds(const float* x, size_t pixels_per_image, int batch, double q_lo, double q_hi, float* lohi,
@@ -201,13 +170,14 @@ extern "C" int mrisr_f32_percentile_bounds(const float* x, size_t pixels_per_ima
     if (!(q_lo >= 0.0 && q_lo <= q_hi && q_hi <= 100.0)) MRISR_FAIL(MRISR_E_ARG, "f32_percentile_bounds: percentiles %g, %g", q_lo, q_hi);
     RankSet ranks;
     float t_lo, t_hi;
-    np_virtual_index(pixels_per_image, q_lo, &ranks.k[0], &ranks.k[1], &t_lo);
-    np_virtual_index(pixels_per_image, q_hi, &ranks.k[2], &ranks.k[3], &t_hi);
+    const unsigned n = (unsigned)pixels_per_image;      // checked above: 1 .. 2^32 - 1
+    np_virtual_index(n, (float)q_lo / 100.f, &ranks.k[0], &ranks.k[1], &t_lo);
+    np_virtual_index(n, (float)q_hi / 100.f, &ranks.k[2], &ranks.k[3], &t_hi);
     unsigned* ws = (unsigned*)workspace;
     hipStream_t st = (hipStream_t)stream;
     f32_select_init_kernel<<<batch, 256, 0, st>>>(ws, ranks);
     MRISR_CHECK_LAUNCH("f32_percentile_bounds (init)");
-    const dim3 grid(grid_x(pixels_per_image, 256 * 16, 64), batch);
+    const dim3 grid(capped_grid(pixels_per_image, 256 * 16, 64), batch);
     for (int pass = 0; pass < kPasses; ++pass) {
         f32_select_hist_kernel<<<grid, 256, 0, st>>>(x, pixels_per_image, ws, pass);
         MRISR_CHECK_LAUNCH("f32_percentile_bounds (histogram)");
@@ -220,7 +190,7 @@ extern "C" int mrisr_f32_percentile_bounds(const float* x, size_t pixels_per_ima
 extern "C" int mrisr_f32_window_normalise(const float* x, const float* lohi, size_t pixels_per_image, int batch, float* out, void* stream) {
     if (!x || !lohi || !out) MRISR_FAIL(MRISR_E_ARG, "f32_window_normalise: null pointer");
     if (batch < 1 || batch > 65535 || pixels_per_image == 0) MRISR_FAIL(MRISR_E_SHAPE, "f32_window_normalise: batch %d, %zu pixels", batch, pixels_per_image);
-    const dim3 grid(grid_x(pixels_per_image, 256 * 8, 256), batch);
+    const dim3 grid(capped_grid(pixels_per_image, 256 * 8, 256), batch);
     f32_window_normalise_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, lohi, pixels_per_image, out);
     MRISR_CHECK_LAUNCH("f32_window_normalise");
     return MRISR_OK;
@@ -230,7 +200,7 @@ extern "C" int mrisr_f32_window_restore(const float* y, const float* lohi, size_
                                         void* stream) {
     if (!y || !lohi || !out) MRISR_FAIL(MRISR_E_ARG, "f32_window_restore: null pointer");
     if (batch < 1 || batch > 65535 || pixels_per_image == 0) MRISR_FAIL(MRISR_E_SHAPE, "f32_window_restore: batch %d, %zu pixels", batch, pixels_per_image);
-    const dim3 grid(grid_x(pixels_per_image, 256 * 8, 256), batch);
+    const dim3 grid(capped_grid(pixels_per_image, 256 * 8, 256), batch);
     if (out_dtype == MRISR_WINDOW_F32)
         f32_window_restore_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(y, lohi, pixels_per_image, (float*)out);
     else if (out_dtype == MRISR_WINDOW_I16)

@@ -28,7 +28,7 @@
 //                                banks whatever the row pitch.  The read puts lane l of a half on dword (l + k) * P + c: the 32
 //                                lanes are on 32 different banks iff P is odd, and all on ONE bank with the unpadded P = 32.
 //                                Tile 64 (s) x 32 (c), pitch P = kTileC + 1 = 33 dwords: (64 + 2) * 33 * 4 = 8712 bytes.
-#include "common.h"
+#include "volume_common.h"
 
 #include <math.h>
 
@@ -37,7 +37,6 @@ constexpr int kRun = 8;            // slices a thread of the stream form walks
 constexpr int kTileS = 64;         // transposing form: slices per tile = lanes of a wave along z
 constexpr int kTileC = 32;         // columns per tile
 constexpr int kPitch = kTileC + 1; // odd: see above
-constexpr int kMaxDim = 32767;     // input extent per axis: doubled extents and tile counts stay inside int and the grid limits
 
 template <int N> struct VecOf {
     typedef float __attribute__((ext_vector_type(N))) f32;
@@ -163,7 +162,8 @@ static void launch_transpose(const float* plane, int S, int R, int C, float* acc
     up2_blend_transpose_kernel<MODE, T><<<grid, 256, 0, st>>>(plane, S, R, C, acc, (T*)out, count);
 }
 
-static bool aligned(const void* p, size_t bytes) { return p == nullptr || ((uintptr_t)p & (bytes - 1)) == 0; }
+// acc and out are optional in some modes: a pointer that is not there is not misaligned
+static bool aligned(const void* p, size_t bytes) { return p == nullptr || aligned_to(p, bytes); }
 
 extern "C" int mrisr_f32_volume_up2_blend(const float* plane, int axis, int X, int Y, int Z, float* acc, int mode, int count,
                                           int out_dtype, void* out, void* stream) {
@@ -175,8 +175,7 @@ extern "C" int mrisr_f32_volume_up2_blend(const float* plane, int axis, int X, i
     if (finish && count < 1) MRISR_FAIL(MRISR_E_ARG, "f32_volume_up2_blend: count %d", count);
     const bool needs_acc = !finish || count > 1;      // a single-plane FINISH neither reads nor writes it
     if (!plane || (finish && !out) || (needs_acc && !acc)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_up2_blend: null pointer");
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_up2_blend: volume %d x %d x %d (every axis 1..%d)", X, Y, Z, kMaxDim);
+    if (const int rc = check_volume_extents("f32_volume_up2_blend", X, Y, Z)) return rc;
     if (!finish) out = nullptr;
     const size_t out_elem = finish && out_dtype == MRISR_WINDOW_I16 ? 2 : 4;
     hipStream_t st = (hipStream_t)stream;

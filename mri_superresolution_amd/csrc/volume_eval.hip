@@ -21,16 +21,13 @@
 //                            the float32 value the per-axis specification holds at that place, so the result is bit-equal.
 //                            Lanes run along z: a wave reads runs of 256 contiguous bytes and stores runs of 512 (z doubled:
 //                            one 8-byte pair per lane).
-#include "common.h"
+#include "volume_common.h"
 
 #include <math.h>
 
-constexpr int kMaxDim = 32767;     // extent per axis: doubled extents and block counts stay inside int and the grid limits
 constexpr int kLinear = MRISR_RESAMPLE_LINEAR, kCubic = MRISR_RESAMPLE_CUBIC;
 
 typedef float __attribute__((ext_vector_type(2))) f32x2;
-
-static bool aligned(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
 // ---------------------------------------------------------------- down2
 template <bool AX, bool AY, bool AZ>
@@ -70,12 +67,11 @@ __global__ __launch_bounds__(256) void volume_down2_kernel(const float* __restri
 extern "C" int mrisr_f32_volume_down2(const float* src, int X, int Y, int Z, int axes_mask, float* dst, void* stream) {
     if (!src || !dst) MRISR_FAIL(MRISR_E_ARG, "f32_volume_down2: null pointer");
     if (axes_mask < 1 || axes_mask > 7) MRISR_FAIL(MRISR_E_ARG, "f32_volume_down2: axes_mask %d (1..7)", axes_mask);
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_down2: volume %d x %d x %d (every axis 1..%d)", X, Y, Z, kMaxDim);
+    if (const int rc = check_volume_extents("f32_volume_down2", X, Y, Z)) return rc;
     const bool ax = axes_mask & 1, ay = axes_mask & 2, az = axes_mask & 4;
     if ((ax && (X & 1)) || (ay && (Y & 1)) || (az && (Z & 1)))
         MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_down2: volume %d x %d x %d has an odd extent on an axis of mask %d", X, Y, Z, axes_mask);
-    if (!aligned(src, az ? 8 : 4) || !aligned(dst, 4)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_down2: misaligned pointer");
+    if (!aligned_to(src, az ? 8 : 4) || !aligned_to(dst, 4)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_down2: misaligned pointer");
     const int OX = ax ? X / 2 : X, OY = ay ? Y / 2 : Y, OZ = az ? Z / 2 : Z;
     const float scale = 1.0f / (float)(1 << ((int)ax + (int)ay + (int)az));
     const dim3 block(64, 4), grid(ceil_div(OZ, 64), ceil_div(OY, 4), OX);
@@ -194,9 +190,8 @@ extern "C" int mrisr_f32_volume_up2(const float* src, int X, int Y, int Z, int a
     if (axes_mask < 1 || axes_mask > 7) MRISR_FAIL(MRISR_E_ARG, "f32_volume_up2: axes_mask %d (1..7)", axes_mask);
     if (method != kLinear && method != kCubic)
         MRISR_FAIL(MRISR_E_ARG, "f32_volume_up2: method %d (MRISR_RESAMPLE_LINEAR or MRISR_RESAMPLE_CUBIC)", method);
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_up2: volume %d x %d x %d (every axis 1..%d)", X, Y, Z, kMaxDim);
-    if (!aligned(src, 4) || !aligned(dst, (axes_mask & 4) ? 8 : 4)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_up2: misaligned pointer");
+    if (const int rc = check_volume_extents("f32_volume_up2", X, Y, Z)) return rc;
+    if (!aligned_to(src, 4) || !aligned_to(dst, (axes_mask & 4) ? 8 : 4)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_up2: misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     if (method == kLinear) launch_up2<kLinear>(src, X, Y, Z, axes_mask, dst, st);
     else launch_up2<kCubic>(src, X, Y, Z, axes_mask, dst, st);

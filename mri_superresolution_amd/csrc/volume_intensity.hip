@@ -1,7 +1,8 @@
 // Intensity standardisation between scans on the device (gfx950; extension): Nyul-Udupa landmarks.
 //
 //   f32_volume_masked_percentiles   np.percentile(vol[(mask != 0) & ~isnan(vol)], q) for up to 16 quantiles q at once.  The
-//                                   MSD radix select of percentile.hip (order-preserving 32-bit key, four passes of 8 bits) with
+//                                   MSD radix select of percentile.hip (four passes of 8 bits over the order-preserving key; the
+//                                   key, the rank rule and the interpolation are volume_common.h's) with
 //                                   two changes.  The number of counted voxels is known only on the device: pass 0's histogram is
 //                                   common to all targets and its total IS the count, so the first pick kernel derives the
 //                                   2 nq ranks and the nq weights from it before it picks.  And there are up to 32 targets (two
@@ -14,9 +15,7 @@
 //
 // The arithmetic restates numpy's float32 path operation by operation (compiled with -ffp-contract=off); the specification is
 // volume_intensity.landmarks_np / piecewise_map_np, itself tested against np.percentile (tests/test_volume_intensity_host.py).
-#include "common.h"
-
-#include <math.h>
+#include "volume_common.h"
 
 constexpr int kMaxQ = 16;                    // quantiles per call
 constexpr int kMaxT = 2 * kMaxQ;             // targets: the order statistics (k, k + 1) of every quantile
@@ -39,14 +38,6 @@ struct QuantileSet {
     float q32[kMaxQ];        // float32(q) / 100, as numpy carries the quantile of a float32 array
 };
 
-__device__ __forceinline__ unsigned vi_key(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float vi_from_key(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __global__ __launch_bounds__(256) void masked_select_init_kernel(unsigned* __restrict__ ws) {
     for (int i = threadIdx.x; i < kHistWords; i += 256) ws[i] = 0u;
 }
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(256) void masked_select_hist_kernel(const float* __
     unsigned run = 0u;
     auto count = [&](float v, unsigned m) {
         if (!m || v != v) return;
-        const unsigned key = vi_key(v);
+        const unsigned key = f32_order_key(v);
         const unsigned digit = (key >> shift) & 255u;
         int g = 0;
         if (pass != 0) {
@@ -132,18 +123,9 @@ __global__ __launch_bounds__(256) void masked_select_pick_kernel(unsigned* __res
         __syncthreads();
         const unsigned total = s_total;
         if (t < qs.nq) {
-            // np.percentile of float32[total]: v = float32(total - 1) * q32, the order statistics floor(v) and its upper neighbour
             unsigned k0 = 0u, k1 = 0u;
             float gamma = 0.f;
-            if (total) {
-                const float virt = __fmul_rn((float)(total - 1u), qs.q32[t]);
-                const float prev = floorf(virt);
-                unsigned long long k = (unsigned long long)prev;
-                if (k > total - 1u) k = total - 1u;      // float32(total - 1) may round up past the last index when total > 2^24
-                k0 = (unsigned)k;
-                k1 = k + 1 < total ? (unsigned)(k + 1) : total - 1u;
-                gamma = __fsub_rn(virt, prev);
-            }
+            if (total) np_virtual_index(total, qs.q32[t], &k0, &k1, &gamma);
             s_rank[2 * t] = k0;
             s_rank[2 * t + 1] = k1;
             ws[kOffGamma + t] = __float_as_uint(gamma);
@@ -203,12 +185,8 @@ __global__ __launch_bounds__(256) void masked_select_pick_kernel(unsigned* __res
             ws[kOffGroups] = groups;
         }
     } else if (t < qs.nq) {
-        // numpy's _lerp in float32: a + (b - a) * t, and b - (b - a) * (1 - t) where t >= 0.5
-        const float a = vi_from_key(s_new_prefix[2 * t]), c = vi_from_key(s_new_prefix[2 * t + 1]);
-        const float g = __uint_as_float(ws[kOffGamma + t]);
-        const float diff = __fsub_rn(c, a);
-        float r = __fadd_rn(a, __fmul_rn(diff, g));
-        if (g >= 0.5f) r = __fsub_rn(c, __fmul_rn(diff, __fsub_rn(1.f, g)));
+        const float a = f32_from_order_key(s_new_prefix[2 * t]), c = f32_from_order_key(s_new_prefix[2 * t + 1]);
+        const float r = np_lerp_f32(a, c, __uint_as_float(ws[kOffGamma + t]));
         out[t] = ws[kOffCount] ? r : __uint_as_float(0x7fc00000u);      // nothing counted: NaN
     }
 }
@@ -244,11 +222,6 @@ __global__ __launch_bounds__(256) void piecewise_map_kernel(const float* src, si
     for (size_t i = nv * 4 + (size_t)blockIdx.x * 256 + t; i < n; i += (size_t)gridDim.x * 256) dst[i] = map(src[i]);
 }
 
-static int vi_grid(size_t n, size_t per_block, int cap) {
-    size_t b = (n + per_block - 1) / per_block;
-    return (int)(b < 1 ? 1 : (b > (size_t)cap ? (size_t)cap : b));
-}
-
 extern "C" size_t mrisr_f32_masked_percentiles_workspace_bytes(int nq) {
     if (nq < 1 || nq > kMaxQ) return 0;
     return (size_t)kWsWords * sizeof(unsigned);
@@ -259,7 +232,7 @@ extern "C" int mrisr_f32_volume_masked_percentiles(const float* vol, const unsig
     if (!vol || !q || !out || !count || !workspace) MRISR_FAIL(MRISR_E_ARG, "f32_volume_masked_percentiles: null pointer");
     if (nq < 1 || nq > kMaxQ) MRISR_FAIL(MRISR_E_ARG, "f32_volume_masked_percentiles: %d percentiles (1..%d)", nq, kMaxQ);
     if (n == 0 || n > 0xffffffffull) MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_masked_percentiles: %zu voxels", n);
-    if (((uintptr_t)workspace & 15) != 0) MRISR_FAIL(MRISR_E_ARG, "f32_volume_masked_percentiles: the workspace must be 16-byte aligned");
+    if (!aligned_to(workspace, 16)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_masked_percentiles: the workspace must be 16-byte aligned");
     QuantileSet qs;
     memset(&qs, 0, sizeof(qs));
     qs.nq = nq;
@@ -272,7 +245,7 @@ extern "C" int mrisr_f32_volume_masked_percentiles(const float* vol, const unsig
     hipStream_t st = (hipStream_t)stream;
     masked_select_init_kernel<<<1, 256, 0, st>>>(ws);
     MRISR_CHECK_LAUNCH("f32_volume_masked_percentiles (init)");
-    const int grid = vi_grid(n, 256 * 16, 1024);
+    const int grid = capped_grid(n, 256 * 16, 1024);
     for (int pass = 0; pass < kPasses; ++pass) {
         masked_select_hist_kernel<<<grid, 256, 0, st>>>(vol, mask, n, ws, pass);
         MRISR_CHECK_LAUNCH("f32_volume_masked_percentiles (histogram)");
@@ -287,7 +260,7 @@ extern "C" int mrisr_f32_volume_piecewise_map(const float* src, size_t n, const 
     if (!src || !src_landmarks || !dst_landmarks || !dst) MRISR_FAIL(MRISR_E_ARG, "f32_volume_piecewise_map: null pointer");
     if (L < 2 || L > kMaxL) MRISR_FAIL(MRISR_E_ARG, "f32_volume_piecewise_map: %d landmarks (2..%d)", L, kMaxL);
     if (n == 0) MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_piecewise_map: no voxels");
-    piecewise_map_kernel<<<vi_grid(n, 256 * 8, 2048), 256, 0, (hipStream_t)stream>>>(src, n, src_landmarks, dst_landmarks, L, dst);
+    piecewise_map_kernel<<<capped_grid(n, 256 * 8, 2048), 256, 0, (hipStream_t)stream>>>(src, n, src_landmarks, dst_landmarks, L, dst);
     MRISR_CHECK_LAUNCH("f32_volume_piecewise_map");
     return MRISR_OK;
 }

@@ -39,9 +39,8 @@
 // fill_holes     labels the ZERO voxels (invert, 6-connected, or 4-connected in the planes across plane_axis), marks during
 //                flatten the components that own a voxel on a face of the volume (an edge of the plane), then
 //                dst = mask != 0 or (zero voxel whose component is unmarked); the filled voxels are counted per workgroup.
-#include "common.h"
+#include "volume_common.h"
 
-constexpr int kMaxDim = 32767;
 constexpr long long kMaxVoxels = 2147483646ll;          // 2^31 - 2: index + 1 fits a positive int32
 constexpr int kTX = 8, kTY = 8, kTZ = 32;                // the tile; kTX * kTY * kTZ = 8 voxels for each of 256 threads
 constexpr int kTile = kTX * kTY * kTZ;
@@ -337,11 +336,8 @@ __global__ __launch_bounds__(256) void label_fill_kernel(const uint8_t* __restri
 
 // ---------------------------------------------------------------- host
 
-static bool aligned_to(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
-
 static int check_shape(const char* name, int X, int Y, int Z) {
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "%s: volume %d x %d x %d (every axis 1..%d)", name, X, Y, Z, kMaxDim);
+    if (const int rc = check_volume_extents(name, X, Y, Z)) return rc;
     if ((long long)X * Y * Z > kMaxVoxels)
         MRISR_FAIL(MRISR_E_UNSUPPORTED, "%s: volume %d x %d x %d has more than 2^31 - 2 voxels (labels are int32)", name, X, Y, Z);
     return MRISR_OK;
@@ -381,7 +377,7 @@ static int label_launches(const char* name, const uint8_t* mask, int X, int Y, i
 }
 
 extern "C" size_t mrisr_u8_volume_label_workspace_bytes(int X, int Y, int Z) {
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim || (long long)X * Y * Z > kMaxVoxels) return 0;
+    if (!volume_extents_ok(X, Y, Z) || (long long)X * Y * Z > kMaxVoxels) return 0;      // a size query sets no error text
     return sizeof(LabelHeader) + 8 * ((size_t)X * Y * Z);
 }
 

@@ -8,11 +8,11 @@
 //
 // Otsu mask, five launches, no host synchronisation:
 //   init      clears the workspace: 256 64-bit counts, the two extrema keys.
-//   extrema   lo, hi by integer atomic min / max on an order-preserving 32-bit key of the float (the trick of lowfield.hip,
-//             extended to negative values: key = bits ^ (sign ? 0xffffffff : 0x80000000)); order-independent, hence exact.
+//   extrema   lo, hi by integer atomic min / max on the order-preserving 32-bit key of the float (the map of f32_order_key in
+//             volume_common.h: the trick of lowfield.hip, extended to negative values); order-independent, hence exact.
 //   counts    bin(v) = min(255, int((v - lo) * scale)), scale = 256.f / (hi - lo), all float32.  A thread merges runs of
-//             equal bins in a register before it touches the workgroup's 32-bit LDS histogram (background voxels come in
-//             long runs of one bin, and same-address LDS atomics serialise); the workgroup's non-zero bins go to the 64-bit
+//             equal bins in a register before it touches the workgroup's 32-bit LDS histogram (RunCounter of volume_common.h:
+//             background voxels come in long runs of one bin); the workgroup's non-zero bins go to the 64-bit
 //             global counts with one atomic each.  A workgroup sees at most 2^45 / 2^20 + 2^14 voxels: 32 bits suffice.
 //   otsu      ONE thread: exact int64 prefix sums, the between-class variance s_t in double in the order of the specification,
 //             t* = the smallest t with the largest s_t; writes stats (lo, hi, t*, foreground count = N - w_t*).
@@ -31,11 +31,8 @@
 //                    1-byte) column, walks kMorphRun outputs along the filtered axis with the 2r + 1 taps in a register ring
 //                    (static indices) and loads kMorphRun + 2r words per kMorphRun stores.  Axis 1: [X][Y][Z]; axis 0 is the same
 //                    map with one slab and columns of Y * Z.
-#include "common.h"
+#include "volume_common.h"
 
-#include <math.h>
-
-constexpr int kMaxDim = 32767;
 constexpr int kBins = 256;
 constexpr int kHistPerBlock = 16384;       // voxels a workgroup of the counts pass takes per grid-stride step
 constexpr int kMaxHistBlocks = 1 << 20;
@@ -46,7 +43,10 @@ struct OtsuWs {                            // the workspace; counts first (docum
     int tstar, pad_;
 };
 
-__device__ __forceinline__ unsigned otsu_key(float v) {                 // order-preserving; -0.0 -> +0.0 first
+// f32_order_key(v + 0.f) and f32_from_order_key of volume_common.h, in the XOR wording: the compiler selects other instructions
+// for the two wordings, and the kernels below are kept as they were built.  v + 0.f folds -0.0 into +0.0: the two are equal to
+// the specification's min / max, their keys are not.
+__device__ __forceinline__ unsigned otsu_key(float v) {
     const unsigned b = __float_as_uint(v + 0.f);
     return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
@@ -124,28 +124,13 @@ __global__ __launch_bounds__(256) void otsu_extrema_kernel(const float* __restri
     }
 }
 
-// a run of equal bins in a register: flushed to the LDS histogram when the bin changes
-struct BinRun {
-    int bin;
-    unsigned len;
-    __device__ __forceinline__ void add(int b, unsigned* hist) {
-        if (b == bin) {
-            ++len;
-        } else {
-            if (len) atomicAdd(&hist[bin], len);
-            bin = b;
-            len = 1u;
-        }
-    }
-};
-
 __global__ __launch_bounds__(256) void otsu_counts_kernel(const float* __restrict__ v, size_t n, int vec, OtsuWs* __restrict__ ws) {
     __shared__ unsigned hist[kBins];
     const OtsuRange r = otsu_range(ws);
     if (r.degenerate) return;                                            // uniform over the grid
     hist[threadIdx.x] = 0u;
     __syncthreads();
-    BinRun run{0, 0u};
+    RunCounter run{0, 0u};
     const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
     if (vec) {
         const size_t n4 = n / 4;
@@ -158,7 +143,7 @@ __global__ __launch_bounds__(256) void otsu_counts_kernel(const float* __restric
     } else {
         for (size_t i = tid; i < n; i += stride) run.add(otsu_bin(v[i], r), hist);
     }
-    if (run.len) atomicAdd(&hist[run.bin], run.len);
+    run.flush(hist);
     __syncthreads();
     const unsigned c = hist[threadIdx.x];
     if (c) atomicAdd(&ws->counts[threadIdx.x], (unsigned long long)c);
@@ -220,8 +205,6 @@ __global__ __launch_bounds__(256) void otsu_mask_kernel(const float* __restrict_
     }
 }
 
-static bool aligned_to(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
-
 extern "C" size_t mrisr_f32_volume_otsu_workspace_bytes(void) { return sizeof(OtsuWs); }
 
 extern "C" int mrisr_f32_volume_otsu_mask(const float* vol, int X, int Y, int Z, uint8_t* mask_out, double* stats, void* workspace,
@@ -229,14 +212,11 @@ extern "C" int mrisr_f32_volume_otsu_mask(const float* vol, int X, int Y, int Z,
     if (!vol || !mask_out || !stats || !workspace) MRISR_FAIL(MRISR_E_ARG, "f32_volume_otsu_mask: null pointer");
     if (!aligned_to(vol, 4) || !aligned_to(stats, 8) || !aligned_to(workspace, 8))
         MRISR_FAIL(MRISR_E_ARG, "f32_volume_otsu_mask: misaligned pointer");
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "f32_volume_otsu_mask: volume %d x %d x %d (every axis 1..%d)", X, Y, Z, kMaxDim);
+    if (const int rc = check_volume_extents("f32_volume_otsu_mask", X, Y, Z)) return rc;
     const size_t n = (size_t)X * Y * Z;
     OtsuWs* ws = (OtsuWs*)workspace;
     hipStream_t s = (hipStream_t)stream;
-    size_t blocks = (n + kHistPerBlock - 1) / kHistPerBlock;
-    if (blocks > (size_t)kMaxHistBlocks) blocks = kMaxHistBlocks;
-    const int grid = (int)blocks;
+    const int grid = capped_grid(n, kHistPerBlock, kMaxHistBlocks);
     const int vec_in = aligned_to(vol, 16) ? 1 : 0, vec_out = vec_in && aligned_to(mask_out, 4) ? 1 : 0;
     otsu_init_kernel<<<1, 256, 0, s>>>(ws);
     MRISR_CHECK_LAUNCH("f32_volume_otsu_mask (init)");
@@ -396,8 +376,7 @@ extern "C" int mrisr_u8_volume_morph(const uint8_t* src, int X, int Y, int Z, in
     if (!src || !dst || (radius != 0 && !tmp)) MRISR_FAIL(MRISR_E_ARG, "u8_volume_morph: null pointer");
     if (src == dst || src == tmp || dst == tmp) MRISR_FAIL(MRISR_E_ARG, "u8_volume_morph: src, dst and tmp must be three buffers");
     if (op != MRISR_MORPH_DILATE && op != MRISR_MORPH_ERODE) MRISR_FAIL(MRISR_E_ARG, "u8_volume_morph: op %d", op);
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "u8_volume_morph: volume %d x %d x %d (every axis 1..%d)", X, Y, Z, kMaxDim);
+    if (const int rc = check_volume_extents("u8_volume_morph", X, Y, Z)) return rc;
     if (radius < 0 || radius > 4) MRISR_FAIL(MRISR_E_SHAPE, "u8_volume_morph: radius %d (0..4)", radius);
     hipStream_t s = (hipStream_t)stream;
     const bool mn = op == MRISR_MORPH_ERODE;

@@ -30,7 +30,7 @@
 // LDS banks (ds_read_b32 / ds_write_b32: bank = dword address mod 32... conflicts within a 32-lane half): the z pass puts
 // lane (row r, segment s) on dword r * P + 4 s + k; with the pitch P = 1 (mod 4) the four rows of a half wave start on
 // 4 different residues mod 4 and the 32 lanes on 32 different banks.  The y pass reads 32 consecutive dwords per half wave.
-#include "common.h"
+#include "volume_common.h"
 
 #include <math.h>
 
@@ -38,7 +38,6 @@ constexpr int kMaxWin = 15;                        // odd window sizes 3 .. 15 (
 constexpr int kTY = 16, kTZ = 32;                  // tile: 256 threads = 32 z columns x 8 pairs of y rows
 constexpr int kMinChunk = 32;                      // shortest x chunk: bounds the x halo overhead to (32 + 2h) / 32
 constexpr int kTargetBlocks = 2048;                // 256 CUs x 8
-constexpr int kMaxDim = 32767;
 
 struct GaussWin3 { float g[kMaxWin]; };
 
@@ -266,8 +265,7 @@ static int volume_metrics_run(const char* name, const float* a, const float* b, 
     if (window_size < 3 || window_size > kMaxWin || !(window_size & 1))
         MRISR_FAIL(MRISR_E_ARG, "%s: window_size %d (odd, 3..15)", name, window_size);
     if (!(sigma > 0.f) || !(val_range > 0.f)) MRISR_FAIL(MRISR_E_ARG, "%s: sigma %g, val_range %g (both positive)", name, sigma, val_range);
-    if (X < 1 || Y < 1 || Z < 1 || X > kMaxDim || Y > kMaxDim || Z > kMaxDim)
-        MRISR_FAIL(MRISR_E_SHAPE, "%s: volume %d x %d x %d (every axis 1..%d)", name, X, Y, Z, kMaxDim);
+    if (const int rc = check_volume_extents(name, X, Y, Z)) return rc;
     const int tz = ceil_div(Z, kTZ), ty = ceil_div(Y, kTY);
     // x chunks: enough workgroups to fill the device, none shorter than kMinChunk planes
     long long want = (kTargetBlocks + (long long)tz * ty - 1) / ((long long)tz * ty);

@@ -35,6 +35,7 @@
 // runs of 16 consecutive voxels (one 16-byte load where the run is whole and aligned, guarded byte loads at the two ends), steps
 // (i, j, k) along the run without dividing, and adds into 64-bit accumulators; wavefront shuffle, LDS across the four wavefronts,
 // then one 64-bit integer atomic per workgroup and value: integer sums do not depend on the order.
+#include "volume_common.h"
 #include "volume_taps.h"
 
 #ifndef MRISR_REGISTER_KLOOP
@@ -59,25 +60,6 @@ __device__ __forceinline__ int value_bin(float v, const BinRule& r) {
     const float x = __fmul_rn(__fsub_rn(v, r.lo), r.scale);
     return min(r.bins - 1, (int)fminf(fmaxf(x, 0.f), r.top));      // truncation; fmaxf(NaN, 0) = 0
 }
-
-// a run of equal cells in a register: flushed to the LDS histogram when the cell changes
-struct CellRun {
-    int cell;
-    unsigned len;
-    __device__ __forceinline__ void add(int c, unsigned* hist) {
-        if (c == cell) {
-            ++len;
-        } else {
-            if (len) atomicAdd(&hist[cell], len);
-            cell = c;
-            len = 1u;
-        }
-    }
-    __device__ __forceinline__ void flush(unsigned* hist) {
-        if (len) atomicAdd(&hist[cell], len);
-        len = 0u;
-    }
-};
 
 // the moving value at sample (i, j, k) under matrix m; false: outside
 __device__ __forceinline__ bool moving_value(const float* __restrict__ mov, int MX, int MY, int MZ, const double* m, int i, int j, int k,
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(256) void joint_histogram_kernel(const float* __res
     for (int c = kfirst; c < klast; ++c) {                                 // at most 16 rounds
         for (int e = tid; e < cells; e += 256) lds[e] = 0u;
         __syncthreads();
-        CellRun run{0, 0u};
+        RunCounter run{0, 0u};
 #pragma unroll
         for (int w = 0; w < kWalk; ++w) {
             float mv;
@@ -307,9 +289,8 @@ __global__ __launch_bounds__(256) void mask_moments_kernel(const unsigned char* 
 extern "C" int mrisr_u8_volume_mask_moments(const unsigned char* mask, int X, int Y, int Z, long long* out4, void* stream) {
     const char* name = "u8_volume_mask_moments";
     if (!mask || !out4) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
-    if (((uintptr_t)out4 & 7) != 0) MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer (out4: 8 bytes)", name);
-    if (X < 1 || Y < 1 || Z < 1 || X > 32767 || Y > 32767 || Z > 32767)
-        MRISR_FAIL(MRISR_E_SHAPE, "%s: volume %d x %d x %d (every extent in 1..32767)", name, X, Y, Z);
+    if (!aligned_to(out4, 8)) MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer (out4: 8 bytes)", name);
+    if (const int rc = check_volume_extents(name, X, Y, Z)) return rc;
     const long long n = (long long)X * Y * Z;                                // < 2^45
     if (n > kMaxVoxels) MRISR_FAIL(MRISR_E_UNSUPPORTED, "%s: volume %d x %d x %d: more than 2^31 - 1 voxels", name, X, Y, Z);
     hipStream_t st = (hipStream_t)stream;

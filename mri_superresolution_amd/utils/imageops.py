@@ -116,27 +116,30 @@ def restore_window(y: torch.Tensor, lohi: torch.Tensor, dtype=torch.float32, out
     return out
 
 
+def np_percentile_f32(sorted_values: np.ndarray, q: float) -> np.float32:
+    """``np.percentile(values, q)`` of a non-empty float32 array for a SCALAR ``q``, from the sorted values, in the explicit form
+    the kernels implement (csrc/volume_common.h).  For a float32 array numpy carries the quantile and the virtual index in float32:
+    ``v = float32(n - 1) * (float32(q) / float32(100))``; the order statistics are ``k = min(floor(v), n - 1)`` (float32(n - 1) may
+    round up past the last index when n > 2^24) and ``min(k + 1, n - 1)``, the weight ``t = v - floor(v)``, and ``_lerp`` interpolates
+    in float32: ``a + (b - a) * t``, and ``b - (b - a) * (1 - t)`` where ``t >= 0.5``.  (It is not the float64 interpolation
+    rounded, and a float64 array of ``q`` takes a float64 path: both differ in the last place.)"""
+    f32 = np.float32
+    s, n = sorted_values, sorted_values.size
+    v = f32(n - 1) * (f32(q) / f32(100))
+    prev = np.floor(v)
+    k = min(int(prev), n - 1)
+    lo, hi, t = s[k], s[min(k + 1, n - 1)], f32(v - prev)
+    d = f32(hi - lo)
+    return f32(hi - f32(d * f32(f32(1) - t))) if t >= f32(0.5) else f32(lo + f32(d * t))
+
+
 def percentile_bounds_np(a: np.ndarray, q_lo: float = 0.5, q_hi: float = 99.5) -> np.ndarray:
-    """``(np.percentile(a, q_lo), np.percentile(a, q_hi))`` of one float32 image as float32, restated in the explicit form the
-    kernel implements.  For a float32 array numpy carries the quantile and the virtual index in float32:
-    ``v = float32(n - 1) * (float32(q) / float32(100))``; the order statistics are ``k = floor(v)`` and ``min(k + 1, n - 1)``,
-    the weight ``t = v - k``, and ``_lerp`` interpolates in float32: ``a + (b - a) * t``, and ``b - (b - a) * (1 - t)`` where
-    ``t >= 0.5``.  (It is not the float64 interpolation rounded: the two differ in the last place.)"""
+    """``(np.percentile(a, q_lo), np.percentile(a, q_hi))`` of one float32 image as float32: ``np_percentile_f32`` twice."""
     a = np.asarray(a)
     if a.dtype != np.float32 or a.size == 0:
         raise ValueError(f"expected a non-empty float32 array, got {a.dtype} {a.shape}")
-    f32 = np.float32
     s = np.sort(a.ravel())
-    n = s.size
-    res = np.empty(2, dtype=np.float32)
-    for i, q in enumerate((q_lo, q_hi)):
-        v = f32(n - 1) * (f32(q) / f32(100))
-        prev = np.floor(v)
-        k = min(int(prev), n - 1)
-        lo, hi, t = s[k], s[min(k + 1, n - 1)], f32(v - prev)
-        d = f32(hi - lo)
-        res[i] = f32(hi - f32(d * f32(f32(1) - t))) if t >= f32(0.5) else f32(lo + f32(d * t))
-    return res
+    return np.array([np_percentile_f32(s, q_lo), np_percentile_f32(s, q_hi)], dtype=np.float32)
 
 
 def to_uint8(x: torch.Tensor) -> torch.Tensor:

@@ -3,6 +3,7 @@ numpy, ``struct`` and ``gzip`` - no nibabel.
 
 ``read_nifti(path)``                                  -> ``(float32 array in the file's index order, NiftiHeader)``
 ``write_nifti(path, data, header, upscaled_axes)``    the x2 output under the input's header, geometry moved with it
+``frames(data)``, ``mask_frames(path, ...)``          a 3-D / 4-D array as 3-D timepoints; a mask file as one uint8 frame each
 ``grid_matrix``, ``downscaled_affine``, ``respaced_grid``, ``header_for_grid``    grid arithmetic for reslicing one scan onto
                                                       another's grid (``volume_reslice.py``), float64
 
@@ -178,6 +179,25 @@ def read_nifti(path: str):
         logger.warning(f"{path}: {int(bad.sum())} non-finite voxel(s) set to 0")
         data[bad] = 0
     return data, hdr
+
+
+def frames(data: np.ndarray) -> list:
+    """A 3-D array as ``[data]``, a 4-D array as the list of its timepoints ``data[..., t]`` (views)."""
+    return [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
+
+
+def mask_frames(path: str, spatial_shape, count: int, what: str = "mask"):
+    """-> (``count`` contiguous uint8 arrays, 1 where the file is non-zero, one per timepoint of the scan the mask belongs to; the
+    file's ``NiftiHeader``).  A 3-D mask serves every timepoint (one array, ``count`` times), a 4-D one needs ``count`` of its own.
+    ``spatial_shape``: the three extents the mask must have, None for a mask that may lie on any grid.  ``what`` names the mask in
+    the errors."""
+    data, header = read_nifti(path)
+    if spatial_shape is not None and tuple(data.shape[:3]) != tuple(spatial_shape):
+        raise ValueError(f"{what} {path} has shape {tuple(data.shape)}, a scan of {tuple(spatial_shape)} voxels needs the same")
+    out = [np.ascontiguousarray((f != 0).astype(np.uint8)) for f in frames(data)]
+    if data.ndim == 4 and len(out) != count:
+        raise ValueError(f"{what} {path} has {len(out)} timepoints, {count} are needed")
+    return (out if data.ndim == 4 else out * count), header
 
 
 def upscaled_affine(affine: np.ndarray, upscaled_axes: Sequence[int]) -> np.ndarray:

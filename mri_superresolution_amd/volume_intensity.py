@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .utils.imageops import np_percentile_f32
 
 logger = logging.getLogger(__name__)
 
@@ -72,27 +73,15 @@ def _landmarks_np(vol, mask, q):
         keep &= _check_mask_np(mask, vol.shape, "landmarks_np") != 0
     s = np.sort(vol[keep].ravel())
     n = int(s.size)
-    out = np.full(len(q), np.nan, dtype=np.float32)
     if n == 0:
-        return out, 0
-    f32 = np.float32
-    for i, p in enumerate(q):
-        v = f32(n - 1) * (f32(p) / f32(100))
-        prev = np.floor(v)
-        k = min(int(prev), n - 1)                        # float32(n - 1) may round up past the last index when n > 2^24
-        lo, hi, t = s[k], s[min(k + 1, n - 1)], f32(v - prev)
-        d = f32(hi - lo)
-        out[i] = f32(hi - f32(d * f32(f32(1) - t))) if t >= f32(0.5) else f32(lo + f32(d * t))
-    return out, n
+        return np.full(len(q), np.nan, dtype=np.float32), 0
+    return np.array([np_percentile_f32(s, p) for p in q], dtype=np.float32), n
 
 
 def landmarks_np(vol, mask=None, percentiles=LANDMARKS):
     """-> (float32 (L,), int count): ``np.percentile(values, q)`` for every ``q`` of ``percentiles`` over
-    ``values = vol[(mask != 0) & ~isnan(vol)]`` (``mask`` None: every voxel), ``count`` their number.  For a float32 array numpy
-    carries the quantile and the virtual index in float32: ``v = float32(count - 1) * (float32(q) / float32(100))``; the order
-    statistics are ``k = min(floor(v), count - 1)`` and ``min(k + 1, count - 1)``, the weight ``t = v - floor(v)``, and ``_lerp``
-    interpolates in float32: ``a + (b - a) * t``, and ``b - (b - a) * (1 - t)`` where ``t >= 0.5``.  That is what ``np.percentile``
-    gives for a SCALAR ``q`` (a float64 array of ``q`` takes a float64 path and differs in the last place).  ``count == 0``: NaNs."""
+    ``values = vol[(mask != 0) & ~isnan(vol)]`` (``mask`` None: every voxel), ``count`` their number.  numpy's float32 path for a
+    SCALAR ``q``, as ``utils.imageops.np_percentile_f32`` states it.  ``count == 0``: NaNs."""
     return _landmarks_np(_check_vol_np(vol, "landmarks_np"), mask, _check_percentiles(percentiles))
 
 

@@ -68,7 +68,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
-from mri_superresolution_amd.utils.nifti import downscaled_affine, grid_matrix, read_nifti, write_nifti   # noqa: E402
+from mri_superresolution_amd.utils.nifti import downscaled_affine, frames, grid_matrix, mask_frames, read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_eval import evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity    # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
@@ -80,26 +80,37 @@ CSV_COLUMNS_MASKED = ["scan", "region", "method", "ssim", "psnr", "mse", "rmse",
 REGIONS = ("whole", "foreground")
 
 
-def _frames(data):
-    return [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
-
-
-def load_mask(mask_path, ref, reference_path, ref_affine=None):
-    """-> one uint8 frame per timepoint of the reference (a 3-D mask serves them all).  ``ref_affine`` (``--align header``): the
-    mask may lie on any grid and is resliced onto the reference's through the two affines with ``nearest``, on the device; the
-    frames are then CUDA tensors."""
-    data, mask_header = read_nifti(mask_path)
-    if ref_affine is None and (data.ndim not in (3, 4) or tuple(data.shape[:3]) != tuple(ref.shape[:3])):
-        raise ValueError(f"mask {mask_path} has shape {tuple(data.shape)}, {reference_path} has {tuple(ref.shape)}")
-    frames = [np.ascontiguousarray((f != 0).astype(np.uint8)) for f in _frames(data)]
+def load_mask(mask_path, ref, ref_affine=None):
+    """-> one uint8 frame per timepoint of the reference (``utils.nifti.mask_frames``).  ``ref_affine`` (``--align``): the mask may
+    lie on any grid and is resliced onto the reference's through the two affines with ``nearest``, on the device; the frames are
+    then CUDA tensors."""
     count = 1 if ref.ndim == 3 else ref.shape[3]
-    if data.ndim == 4 and len(frames) != count:
-        raise ValueError(f"mask {mask_path} has {len(frames)} timepoints, {reference_path} has {count}")
-    if ref_affine is not None:
-        m = grid_matrix(mask_header.affine(), ref_affine)
-        frames = [reslice_mask(torch.from_numpy(f).cuda(), m, ref.shape[:3]) for f in frames]
-        logger.info(f"Mask {mask_path} {tuple(data.shape[:3])} resliced onto the reference grid {tuple(ref.shape[:3])} (nearest).")
-    return frames if data.ndim == 4 else frames * count
+    masks, header = mask_frames(mask_path, None if ref_affine is not None else ref.shape[:3], count, "--mask")
+    if ref_affine is None:
+        return masks
+    m = grid_matrix(header.affine(), ref_affine)
+    distinct = masks if len(header.shape) == 4 else masks[:1]      # a 3-D mask is resliced once
+    out = [reslice_mask(torch.from_numpy(f).cuda(), m, ref.shape[:3]) for f in distinct]
+    logger.info(f"Mask {mask_path} {tuple(masks[0].shape)} resliced onto the reference grid {tuple(ref.shape[:3])} (nearest).")
+    return out if len(header.shape) == 4 else out * count
+
+
+def check_options(input_path, align, align_interp, align_init, align_mask, match):
+    """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
+    if match not in ("none", "landmarks", "range"):
+        raise ValueError(f"--match_intensity is none, range or landmarks, got {match!r}")
+    if match != "none" and not input_path:
+        raise ValueError("--match_intensity goes with --input")
+    if align not in (None, "header", "rigid"):
+        raise ValueError(f"align must be None, 'header' or 'rigid', got {align!r}")
+    if align and not input_path:
+        raise ValueError("--align goes with --input")
+    if align and align_interp not in ("linear", "cubic"):
+        raise ValueError(f"--align_interp must be linear or cubic, got {align_interp}")
+    if align_init not in ("header", "global") or align_mask not in ("none", "otsu"):
+        raise ValueError(f"--align_init is header or global and --align_mask none or otsu, got {align_init} and {align_mask}")
+    if align != "rigid" and (align_init != "header" or align_mask != "none"):
+        raise ValueError("--align_init and --align_mask go with --align rigid")
 
 
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
@@ -115,28 +126,15 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     from a coarse grid of rotations about the masks' centres of mass, ``align_mask="otsu"`` puts the reference's Otsu mask in its
     cost (``volume_register.register_rigid``).  ``match`` (``"landmarks"`` / ``"range"``): every input frame is mapped onto its
     reference frame's intensity scale before any method sees it (module docstring)."""
-    if match not in ("none", "landmarks", "range"):
-        raise ValueError(f"--match_intensity is none, range or landmarks, got {match!r}")
-    if match != "none" and not input_path:
-        raise ValueError("--match_intensity goes with --input")
-    if align not in (None, "header", "rigid"):
-        raise ValueError(f"align must be None, 'header' or 'rigid', got {align!r}")
-    if align and not input_path:
-        raise ValueError("--align goes with --input")
-    if align and align_interp not in ("linear", "cubic"):
-        raise ValueError(f"--align_interp must be linear or cubic, got {align_interp}")
-    if align_init not in ("header", "global") or align_mask not in ("none", "otsu"):
-        raise ValueError(f"--align_init is header or global and --align_mask none or otsu, got {align_init} and {align_mask}")
-    if align != "rigid" and (align_init != "header" or align_mask != "none"):
-        raise ValueError("--align_init and --align_mask go with --align rigid")
+    check_options(input_path, align, align_interp, align_init, align_mask, match)
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
     if low is not None and low.ndim != ref.ndim:
         raise ValueError(f"{input_path} has {low.ndim} axes, {reference_path} has {ref.ndim}")
     if low is not None and low.ndim == 4 and low.shape[3] != ref.shape[3]:
         raise ValueError(f"{input_path} has {low.shape[3]} timepoints, {reference_path} has {ref.shape[3]}")
-    ref_frames, low_frames = _frames(ref), (_frames(low) if low is not None else None)
-    mask_frames = load_mask(mask, ref, reference_path, ref_header.affine() if align else None) if mask not in (None, "otsu") else None
+    ref_frames, low_frames = frames(ref), (frames(low) if low is not None else None)
+    masks = load_mask(mask, ref, ref_header.affine() if align else None) if mask not in (None, "otsu") else None
     if align:
         # the grid a x2 pass over the doubled axes expects its input on; the crop takes trailing voxels, so the affine stays
         axes = (0, 1, 2) if isotropic else tuple(a for a in (0, 1, 2) if a != axis)
@@ -146,13 +144,13 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
         if crop != tuple(ref.shape[:3]):
             logger.warning(f"Reference volume {tuple(ref.shape[:3])} has an odd extent on a doubled axis: cropped to {crop}.")
             ref_frames = [f[:crop[0], :crop[1], :crop[2]] for f in ref_frames]
-            if mask_frames is not None:
-                mask_frames = [f[:crop[0], :crop[1], :crop[2]].contiguous() for f in mask_frames]
+            if masks is not None:
+                masks = [f[:crop[0], :crop[1], :crop[2]].contiguous() for f in masks]
         low_shape = tuple(d // 2 if a in axes else d for a, d in enumerate(crop))
         low_grid = downscaled_affine(ref_header.affine(), axes)
         if align == "rigid":
             # fixed = the reference, moving = the input, from the headers as they are (p0 = 0); W: reference world -> input world
-            fixed = torch.from_numpy(np.ascontiguousarray(_frames(ref)[0], dtype=np.float32)).to(device)
+            fixed = torch.from_numpy(np.ascontiguousarray(frames(ref)[0], dtype=np.float32)).to(device)
             moving = torch.from_numpy(np.ascontiguousarray(low_frames[0], dtype=np.float32)).to(device)
             found = register_rigid(fixed, ref_header.affine(), moving, low_header.affine(), bins=align_bins, init=align_init,
                                    mask_cost=align_mask == "otsu")
@@ -175,8 +173,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
         lr, m = None, mask
         if low_frames is not None:      # with --align the frames are on the device already
             lr = low_frames[t] if align else torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device)
-        if mask_frames is not None:
-            m = mask_frames[t] if align else torch.from_numpy(mask_frames[t]).to(device)
+        if masks is not None:
+            m = masks[t] if align else torch.from_numpy(masks[t]).to(device)
         if match != "none":
             lr, found = match_intensity(lr, vol, foreground_mask(lr)[0], foreground_mask(vol)[0],
                                         LANDMARKS if match == "landmarks" else RANGE)
@@ -259,12 +257,7 @@ def main(args):
             raise ValueError("--mask_close goes with --mask")
         if args.mask is None and (args.mask_largest or args.mask_fill_holes is not None or args.save_mask):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
-        if args.align and not args.input:
-            raise ValueError("--align goes with --input")
-        if args.align != "rigid" and (args.align_init != "header" or args.align_mask != "none"):
-            raise ValueError("--align_init and --align_mask go with --align rigid")
-        if args.match_intensity != "none" and not args.input:
-            raise ValueError("--match_intensity goes with --input")
+        check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity)
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -282,9 +275,12 @@ def main(args):
         rows, graphs = [], {}
         regions = REGIONS if args.mask else (None,)
         for path in args.reference:
-            scan_rows = score_scan(model, path, args.input, args.isotropic, args.axis, args.data_range, args.batch_size, args.use_amp,
-                                   not args.no_graph, device, graphs, args.mask, args.mask_close, args.mask_largest, fill, args.save_mask,
-                                   args.align, args.align_interp, args.align_bins, args.align_init, args.align_mask, args.match_intensity)
+            scan_rows = score_scan(model, path, input_path=args.input, isotropic=args.isotropic, axis=args.axis, data_range=args.data_range,
+                                   batch_size=args.batch_size, use_amp=args.use_amp, use_graph=not args.no_graph, device=device,
+                                   graph_cache=graphs, mask=args.mask, mask_close=args.mask_close, mask_largest=args.mask_largest,
+                                   mask_fill_holes=fill, save_mask=args.save_mask, align=args.align, align_interp=args.align_interp,
+                                   align_bins=args.align_bins, align_init=args.align_init, align_mask=args.align_mask,
+                                   match=args.match_intensity)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]

@@ -32,7 +32,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import grid_matrix, header_for_grid, read_nifti, respaced_grid, write_nifti   # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames, grid_matrix, header_for_grid, read_nifti, respaced_grid, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume import enhance_volume, enhance_volume_isotropic   # noqa: E402
 from mri_superresolution_amd.volume_reslice import reslice               # noqa: E402
 from scripts.infer import find_best_checkpoint, load_model               # noqa: E402
@@ -61,9 +61,8 @@ def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_am
     if any(shape[a] % 8 for a in in_plane):
         logger.warning(f"In-plane dimensions {tuple(shape[a] for a in in_plane)} are not divisible by 8. This might affect "
                        "performance or spatial accuracy due to model pooling layers.")
-    frames = [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
     outs, graphs = [], {}
-    for frame in frames:
+    for frame in frames(data):
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
         if regrid is not None:
             vol = reslice(vol, regrid, shape, spacing_interp)

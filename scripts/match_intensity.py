@@ -28,7 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import read_nifti, write_nifti                          # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames as frames_of, mask_frames, read_nifti, write_nifti      # noqa: E402
 from mri_superresolution_amd.volume_eval import foreground_mask                                  # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity          # noqa: E402
 
@@ -36,23 +36,13 @@ logger = logging.getLogger("match_intensity")
 MODES = {"landmarks": LANDMARKS, "range": RANGE}
 
 
-def _frames(data):
-    return [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
-
-
-def _mask_frames(spec, data, path, count, what):
+def _mask_frames(spec, data, count, what):
     """-> ``count`` entries: ``"otsu"``, None, or a uint8 array of the scan's spatial shape."""
     if spec == "otsu":
         return ["otsu"] * count
     if spec == "none":
         return [None] * count
-    mask = read_nifti(spec)[0]
-    if mask.ndim not in (3, 4) or tuple(mask.shape[:3]) != tuple(data.shape[:3]):
-        raise ValueError(f"{what} {spec} has shape {tuple(mask.shape)}, {path} has {tuple(data.shape)}")
-    frames = [np.ascontiguousarray((f != 0).astype(np.uint8)) for f in _frames(mask)]
-    if len(frames) not in (1, count):
-        raise ValueError(f"{what} {spec} has {len(frames)} timepoints, {count} are needed")
-    return frames * count if len(frames) == 1 else frames
+    return mask_frames(spec, data.shape[:3], count, what)[0]
 
 
 def _on_device(frame, mask, device):
@@ -71,11 +61,11 @@ def match_file(input_path, like_path, output_path, percentiles=LANDMARKS, mask="
     ``IntensityMatch`` per frame)."""
     data, header = read_nifti(input_path)
     like = read_nifti(like_path)[0]
-    frames, like_frames = _frames(data), _frames(like)
+    frames, like_frames = frames_of(data), frames_of(like)
     if len(like_frames) not in (1, len(frames)):
         raise ValueError(f"{like_path} has {len(like_frames)} timepoints, {input_path} has {len(frames)}")
-    masks = _mask_frames(mask, data, input_path, len(frames), "--mask")
-    like_masks = _mask_frames(like_mask, like, like_path, len(like_frames), "--like_mask")
+    masks = _mask_frames(mask, data, len(frames), "--mask")
+    like_masks = _mask_frames(like_mask, like, len(like_frames), "--like_mask")
     outs, founds = [], []
     target = None
     for t, frame in enumerate(frames):

@@ -26,7 +26,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import header_for_grid, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames as frames_of, header_for_grid, read_nifti, write_nifti      # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                             # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice                      # noqa: E402
 
@@ -54,8 +54,7 @@ def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64
         raise ValueError(f"--mask must be none or otsu, got {mask}")
     fixed, fixed_header = read_nifti(fixed_path)
     moving, moving_header = read_nifti(moving_path)
-    frames = [moving] if moving.ndim == 3 else [moving[..., t] for t in range(moving.shape[3])]
-    frames = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)).to(device) for f in frames]
+    frames = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)).to(device) for f in frames_of(moving)]
     fixed0 = fixed if fixed.ndim == 3 else fixed[..., 0]
     fixed0 = torch.from_numpy(np.ascontiguousarray(fixed0, dtype=np.float32)).to(device)
     fixed_affine, shape = fixed_header.affine(), tuple(fixed.shape[:3])

@@ -25,7 +25,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import grid_matrix, header_for_grid, read_nifti, respaced_grid, write_nifti   # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames, grid_matrix, header_for_grid, read_nifti, respaced_grid, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice                                              # noqa: E402
 
 logger = logging.getLogger("reslice_volume")
@@ -41,8 +41,7 @@ def reslice_file(input_path, output_path, like=None, spacing=None, interp="linea
     else:
         dst_affine, dst_shape = respaced_grid(src_affine, data.shape[:3], spacing)
     m = grid_matrix(src_affine, dst_affine)
-    frames = [data] if data.ndim == 3 else [data[..., t] for t in range(data.shape[3])]
-    outs = [reslice(torch.from_numpy(np.ascontiguousarray(f)).to(device), m, dst_shape, interp, fill) for f in frames]
+    outs = [reslice(torch.from_numpy(np.ascontiguousarray(f)).to(device), m, dst_shape, interp, fill) for f in frames(data)]
     share = covered_share(data.shape[:3], m, dst_shape, device)
     result = outs[0].cpu().numpy() if data.ndim == 3 else np.stack([o.cpu().numpy() for o in outs], axis=3)
     logger.info(f"{100.0 * (1.0 - float(share)):.2f} % of the output voxels fell outside the input (set to {fill:g}).")

@@ -26,8 +26,11 @@ def _img(rng, h, w):
     return np.clip(a, 0, 255).astype(np.uint8)
 
 
-def _run(img, flip=0, angle=None, brightness=1.0, contrast=1.0, sigma=0.0, seed=0):
-    x = torch.from_numpy(img[None]).cuda()
+def _run(img, flip=0, angle=None, brightness=1.0, contrast=1.0, sigma=0.0, seed=0, off=0):
+    """``off``: the image and the stage start this many bytes past a 16-byte boundary."""
+    buf = torch.zeros(img.size + off, dtype=torch.uint8, device="cuda")
+    buf[off:] = torch.from_numpy(img).cuda().reshape(-1)
+    x = buf[off:].view((1,) + img.shape)
     geo = (L.AugGeo * 1)()
     g = geo[0]
     g.cos_a, g.sin_a, g.rotate, g.flip, g.fill, g.brightness = 1.0, 0.0, 0, flip, 0, brightness
@@ -39,7 +42,8 @@ def _run(img, flip=0, angle=None, brightness=1.0, contrast=1.0, sigma=0.0, seed=
     gd = torch.frombuffer(bytearray(bytes(geo)), dtype=torch.uint8).cuda()
     pd = torch.frombuffer(bytearray(bytes(pho)), dtype=torch.uint8).cuda()
     st = L.stream_ptr()
-    stage = torch.empty_like(x)
+    stage = torch.zeros(img.size + off, dtype=torch.uint8, device="cuda")[off:].view(x.shape)
+    assert x.data_ptr() % 16 == off and stage.data_ptr() % 16 == off
     L.call("mrisr_augment_geo_u8", x.data_ptr(), stage.data_ptr(), 1, img.shape[0], img.shape[1], gd.data_ptr(),
            _u8_means(x).data_ptr(), st)
     out = torch.empty((1, 1) + img.shape, dtype=torch.float32, device="cuda")
@@ -79,6 +83,19 @@ def test_augmentation_stages_match_pil():
     stage, _ = _run(img, flip=1, angle=4.0, brightness=1.05)
     ref = ImageEnhance.Brightness(pil.transpose(Image.FLIP_LEFT_RIGHT).rotate(4.0, resample=Image.NEAREST, fillcolor=fill)).enhance(1.05)
     assert (stage != np.asarray(ref)).mean() <= 0.005
+
+
+def test_augmentation_stages_off_a_16_byte_boundary():
+    """37 x 53 = 1961 pixels (no multiple of 4), image and stage 1 byte past a 16-byte boundary: the exact stages against PIL."""
+    from PIL import Image, ImageEnhance
+    img = _img(np.random.default_rng(4), 37, 53)
+    pil = Image.fromarray(img)
+    stage, out = _run(img, off=1)
+    assert np.array_equal(stage, img) and np.array_equal(out, img.astype(np.float32) / 255.0)
+    stage, _ = _run(img, flip=1, brightness=1.061, off=1)
+    assert np.array_equal(stage, np.asarray(ImageEnhance.Brightness(pil.transpose(Image.FLIP_LEFT_RIGHT)).enhance(1.061)))
+    _, out = _run(img, contrast=0.937, off=1)
+    assert np.array_equal(out, np.asarray(ImageEnhance.Contrast(pil).enhance(0.937)).astype(np.float32) / 255.0)
 
 
 def test_noise_is_gaussian_in_uint8_units_and_seeded():

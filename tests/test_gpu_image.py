@@ -57,6 +57,25 @@ def test_percentile_normalise_matches_numpy_bit_for_bit(kind, shape):
     assert np.array_equal(one[0, 0], out[0, 0])
 
 
+def test_percentile_normalise_and_to_uint8_off_a_16_byte_boundary():
+    """4099 elements (one more than whole 4096-element steps, no multiple of 4) at a base 1 element past a 16-byte boundary."""
+    n = 4099
+    img = _images(np.random.default_rng(11), 1, 1, n, "mri")
+    buf = torch.zeros(n + 1, dtype=torch.uint8, device="cuda")
+    buf[1:] = torch.from_numpy(img).cuda().reshape(-1)
+    x = buf[1:].view(1, 1, n)
+    assert x.data_ptr() % 16 == 1
+    out, lohi = imageops.normalise_percentile_u8(x, return_bounds=True)
+    a = img[0].astype(np.float32)
+    assert lohi[0, 0].item() == np.percentile(a, 0.5) and lohi[0, 1].item() == np.percentile(a, 99.5)
+    assert np.array_equal(out[0, 0].cpu().numpy(), infer.normalise_percentile(a))
+    v = np.random.default_rng(12).uniform(-0.2, 1.2, n).astype(np.float32)
+    fbuf = torch.zeros(n + 1, dtype=torch.float32, device="cuda")
+    fbuf[1:] = torch.from_numpy(v).cuda()
+    assert fbuf[1:].data_ptr() % 16 == 4
+    assert np.array_equal(imageops.to_uint8(fbuf[1:]).cpu().numpy(), (np.clip(v, 0.0, 1.0) * 255).astype(np.uint8))
+
+
 def test_to_uint8_truncates_like_astype():
     rng = np.random.default_rng(3)
     x = np.concatenate([rng.uniform(-0.2, 1.2, 5000), np.arange(256) / 255.0, (np.arange(256) + 0.999) / 255.0,

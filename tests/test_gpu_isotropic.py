@@ -42,19 +42,30 @@ def random_planes(dims, seed, scale=3000.0, step=None):
     return planes
 
 
-def slice_major(e, axis):
-    return torch.from_numpy(np.ascontiguousarray(np.moveaxis(e, axis, 0))).cuda()
+def off_boundary(shape, dtype, fill, off):
+    """A contiguous tensor of this shape whose base lies off elements past a 16-byte boundary."""
+    n = int(np.prod(shape))
+    return torch.full((n + off,), fill, dtype=dtype, device="cuda")[off:].view(shape)
 
 
-def run_blend(planes, dims, out_dtype):
-    """SET -> ADD -> FINISH over the planes in ascending order; a float32 result is finished in place (out is acc)."""
+def slice_major(e, axis, off=0):
+    e = np.ascontiguousarray(np.moveaxis(e, axis, 0))
+    x = off_boundary(e.shape, torch.float32, 0.0, off)
+    x.copy_(torch.from_numpy(e))
+    return x
+
+
+def run_blend(planes, dims, out_dtype, off=0):
+    """SET -> ADD -> FINISH over the planes in ascending order; a float32 result is finished in place (out is acc).  ``off``: every
+    float32 buffer starts that many floats, the int16 output twice as many values, past a 16-byte boundary."""
     full = tuple(2 * d for d in dims)
     axes = sorted(planes)
-    acc = torch.full(full, float("nan"), dtype=torch.float32, device="cuda")          # SET must not read it
-    out = acc if out_dtype == torch.float32 else torch.full(full, -1, dtype=torch.int16, device="cuda")
+    acc = off_boundary(full, torch.float32, float("nan"), off)                         # SET must not read it
+    out = acc if out_dtype == torch.float32 else off_boundary(full, torch.int16, -1, 2 * off)
+    assert acc.data_ptr() % 16 == 4 * off and out.data_ptr() % 16 == 4 * off
     for i, a in enumerate(axes):
         last = i == len(axes) - 1
-        up2_blend(slice_major(planes[a], a), a, acc, L.VOLBLEND_FINISH if last else (L.VOLBLEND_SET if i == 0 else L.VOLBLEND_ADD),
+        up2_blend(slice_major(planes[a], a, off), a, acc, L.VOLBLEND_FINISH if last else (L.VOLBLEND_SET if i == 0 else L.VOLBLEND_ADD),
                   len(axes), out if last else None)
     return out.cpu().numpy()
 
@@ -81,6 +92,16 @@ def test_blend_sequence_is_bit_equal_to_the_numpy_specification(dims):
             assert same_bits(got, want), (dims, axis, dtype)
     two = {0: planes[0], 2: planes[2]}                          # a mean of two: SET -> FINISH with count 2
     assert same_bits(run_blend(two, dims, torch.float32), combine_planes_np(two))
+
+
+def test_blend_sequence_off_a_16_byte_boundary():
+    """5 x 7 x 9 input voxels (no multiple of 4); planes, accumulator and output 8 bytes past a 16-byte boundary: the stream
+    form takes its 8-byte path, the transposing form pairs."""
+    dims = (5, 7, 9)
+    planes = random_planes(dims, seed=sum(dims))
+    for np_dtype, dtype in ((np.float32, torch.float32), (np.int16, torch.int16)):
+        got, want = run_blend(planes, dims, dtype, off=2), combine_planes_np(planes, np_dtype)
+        assert same_bits(got, want), (dtype, int((got != want).sum()))
 
 
 def test_finish_into_a_separate_float_buffer_and_without_an_accumulator():

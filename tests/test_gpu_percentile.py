@@ -53,6 +53,17 @@ def test_images_of_different_classes_in_one_batch_get_their_own_bounds():
         _check_bounds(imgs, got.cpu().numpy(), 0.5, 99.5, hw)
 
 
+def test_bounds_of_an_image_whose_base_is_off_a_16_byte_boundary():
+    n = 4099                              # one more than a workgroup's 4096-element step, no multiple of 4
+    img = input_class("normal", (1, n), seed=7)
+    buf = torch.zeros(n + 1, dtype=torch.float32, device="cuda")
+    buf[1:] = torch.from_numpy(img).cuda().reshape(-1)
+    x = buf[1:].view(1, 1, n)
+    assert x.data_ptr() % 16 == 4
+    for q_lo, q_hi in PAIRS:
+        _check_bounds(img[None], imageops.percentile_bounds_f32(x, q_lo, q_hi).cpu().numpy(), q_lo, q_hi, ("unaligned", q_lo, q_hi))
+
+
 def test_one_workspace_serves_call_after_call_without_clearing():
     nbytes = int(L.load().mrisr_f32_percentile_workspace_bytes(3))
     assert nbytes > 0 and L.load().mrisr_f32_percentile_workspace_bytes(0) == 0
@@ -120,6 +131,31 @@ def test_restore_is_bit_equal_to_numpy_float32():
         assert want.dtype == np.float32 and np.array_equal(got[b].cpu().numpy(), want), b
     got3 = imageops.restore_window(torch.from_numpy(y[:, 0]).cuda(), torch.from_numpy(lohi).cuda())       # (B,H,W) input
     assert torch.equal(got3, got[:, 0])
+
+
+def test_normalise_and_restore_off_a_16_byte_boundary():
+    """One image of 4099 floats (one more than whole 4096-element steps, no multiple of 4), input and output of both calls at a
+    base 4 bytes past a 16-byte boundary."""
+    n = 4099
+    img = input_class("normal", (1, n), seed=8)
+    buf = torch.zeros(n + 1, dtype=torch.float32, device="cuda")
+    buf[1:] = torch.from_numpy(img).cuda().reshape(-1)
+    x = buf[1:].view(1, 1, n)
+    assert x.data_ptr() % 16 == 4
+    out, lohi = imageops.normalise_percentile_f32(x, return_bounds=True)
+    want = _window_np(img)
+    assert np.array_equal(out[0, 0].cpu().numpy().view(np.uint32), want.view(np.uint32))
+    buf[1:] = out.reshape(-1)                                  # the normalised image, off the boundary too
+    lo, hi = lohi[0].cpu().numpy()
+    for dtype in (torch.float32, torch.int16):
+        obuf = torch.zeros(n + 8, dtype=dtype, device="cuda")
+        k = 1 if dtype == torch.float32 else 2                 # 4 bytes past the boundary
+        dst = obuf[k:k + n].view(1, 1, n)
+        assert dst.data_ptr() % 16 == 4
+        imageops.restore_window(x, lohi, dtype=dtype, out=dst)
+        r = np.clip(want, np.float32(0), np.float32(1)) * np.float32(hi - lo) + lo
+        r = r if dtype == torch.float32 else np.clip(np.rint(r), -32768, 32767).astype(np.int16)
+        assert np.array_equal(dst.cpu().numpy().reshape(1, n), r), dtype
 
 
 def test_restore_int16_rounds_half_to_even_and_saturates():

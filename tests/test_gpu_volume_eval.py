@@ -92,6 +92,37 @@ def test_upscale2_is_bit_equal_to_the_specification(method, shape):
         assert same_bits(got, want), (method, shape, mask, int((got != want).sum()))
 
 
+def off_boundary(v, k):
+    """The float32 volume v on the device, its base k floats past a 16-byte boundary."""
+    buf = torch.zeros(v.size + k, dtype=torch.float32, device="cuda")
+    buf[k:] = torch.from_numpy(v).cuda().reshape(-1)
+    x = buf[k:].view(v.shape)
+    assert x.is_contiguous() and x.data_ptr() % 16 == 4 * k
+    return x
+
+
+def test_down2_up2_and_metrics_off_a_16_byte_boundary():
+    """Volumes of at most 5 x 7 x 9 voxels (315: no multiple of 4; down2 needs even extents on its set axes) at a base 4 bytes past
+    a 16-byte boundary, 8 bytes where pairs along z are read as one load."""
+    v = values((5, 7, 9), seed=21)
+    for method in ("linear", "cubic"):
+        for mask in MASKS:
+            got = V.upscale2(off_boundary(v, 1), method, axes_of(mask)).cpu().numpy()
+            assert same_bits(got, V.upscale2_np(v, method, axes_of(mask))), (method, mask)
+    for shape, mask in (((4, 6, 9), 3), ((4, 7, 9), 1), ((5, 6, 9), 2), ((5, 7, 6), 4), ((4, 6, 6), 7)):
+        v = values(shape, seed=sum(shape))
+        got = V.downsample2(off_boundary(v, 2 if mask & 4 else 1), axes_of(mask)).cpu().numpy()
+        assert same_bits(got, V.downsample2_np(v, axes_of(mask))), (shape, mask)
+    a, b = make_pair((5, 7, 9), seed=21)
+    want = V.volume_metrics_np(a, b, 1.0, 3)
+    dev = abs(ssim_float32_torch(a, b, 1.0, 3) - want[0])
+    got = V.volume_metrics(off_boundary(a, 1), off_boundary(b, 1), 1.0, 3).cpu().numpy()
+    plain = V.volume_metrics(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), 1.0, 3).cpu().numpy()
+    assert np.allclose(got, plain, rtol=1e-12, atol=0)          # the order of the double atomics is free
+    assert abs(got[0] - want[0]) <= (4 * dev if dev > 5e-6 / 4 else 5e-6)        # the bar of metric_cases
+    assert abs(got[1] - want[1]) <= 1e-6 * want[1] and abs(got[3] - want[3]) <= 1e-6 * want[3]
+
+
 # ---------------------------------------------------------------- metrics kernel
 
 # the kernel's tile is 16 (y) x 32 (z) with x chunks of at least 32 planes: (70, 37, 45) is 2 x-chunks of 35, 3 y-tiles (16, 16, 5)

@@ -141,6 +141,11 @@ def test_entry_points_inside_guard_cells_and_off_alignment():
     assert lib.mrisr_u8_volume_keep_largest(src.data_ptr(), *shape, 26, src.data_ptr(), stats.data_ptr(), ws.data_ptr(), st) == -1
     assert lib.mrisr_u8_volume_fill_holes(src.data_ptr(), *shape, 3, src.data_ptr() + 4, stats.data_ptr(), ws.data_ptr(), st) == -1
     assert lib.mrisr_u8_volume_label(src.data_ptr(), 70, 0, 45, 26, -1, 0, ws.data_ptr(), st) == -2
+    dst = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    for bad in ((0, 37, 45), (70, 32768, 45), (70, 37, -1)):
+        assert lib.mrisr_u8_volume_keep_largest(src.data_ptr(), *bad, 26, dst.data_ptr(), stats.data_ptr(), ws.data_ptr(), st) == -2
+        assert lib.mrisr_u8_volume_fill_holes(src.data_ptr(), *bad, -1, dst.data_ptr(), stats.data_ptr(), ws.data_ptr(), st) == -2
+        assert lib.mrisr_u8_volume_label_workspace_bytes(*bad) == 0
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=str)

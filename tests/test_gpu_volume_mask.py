@@ -97,6 +97,12 @@ def test_otsu_mask_on_an_unaligned_volume_and_with_guard_cells():
         g = guard.cpu().numpy()
         assert (g[:margin] == 7).all() and (g[margin + n:] == 7).all()
         assert np.array_equal(g[margin:margin + n].reshape(shape), want)
+    # an extent outside 1..32767 is refused before any launch: MRISR_E_SHAPE, the buffers untouched
+    before = guard.clone()
+    for bad in ((0, 37, 45), (70, 32768, 45), (70, 37, -1)):
+        assert lib.mrisr_f32_volume_otsu_mask(y.data_ptr(), *bad, guard.data_ptr() + margin, stats.data_ptr(), ws.data_ptr(), st) == -2
+        assert lib.mrisr_u8_volume_morph(guard.data_ptr(), *bad, 1, L.MORPH_DILATE, before.data_ptr(), ws.data_ptr(), st) == -2
+    assert torch.equal(guard, before)
 
 
 def test_foreground_mask_returns_the_closed_mask_and_refuses_bad_arguments():

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import farpairutil as F                                                      # noqa: E402
 import registerutil as U                                                     # noqa: E402
+from mri_superresolution_amd import _lib as L                                # noqa: E402
 from mri_superresolution_amd import volume_register as G                     # noqa: E402
 from mri_superresolution_amd.volume_reslice import source_coordinates_np     # noqa: E402
 
@@ -189,6 +190,10 @@ def test_wrappers_refuse():
     for bad in (mask.cpu(), mask.bool(), mask.float(), wide[:, :, ::2], mask[0], mask.cpu().numpy()):
         with pytest.raises(ValueError):
             G.mask_moments(bad)
+    out4 = torch.full((4,), -7, dtype=torch.int64, device="cuda")
+    for bad in ((0, 6, 5), (4, 32768, 5), (4, 6, -1)):           # MRISR_E_SHAPE before the memset
+        assert L.load().mrisr_u8_volume_mask_moments(mask.data_ptr(), *bad, out4.data_ptr(), L.stream_ptr()) == -2
+    assert out4.cpu().tolist() == [-7] * 4
     for bad in bad_masks[:5]:
         with pytest.raises(ValueError):
             G.register_rigid(f, np.eye(4), f, np.eye(4), bins=16, fixed_mask=bad, mask_cost=True)

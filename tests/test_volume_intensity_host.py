@@ -52,6 +52,34 @@ def test_landmarks_equal_scalar_np_percentile(name):
                 assert np.array_equal(got, want), (name, shape, mname, qs, got, want)
 
 
+def test_landmarks_and_window_bounds_are_one_rule():
+    """landmarks_np and utils/imageops.percentile_bounds_np state np.percentile's float32 rule through one function: bit-equal to
+    each other on every array, and to np.percentile with a scalar q wherever the array is finite (with infinities in it the
+    interpolation meets inf - inf).  -0.0 is in the arrays of 2, 3 and 257 elements.  The array of one element holds -3.5: of a
+    lone -0.0 the rule gives -0.0 + 0.0 * t = +0.0 at every q, here and in the kernels, where numpy 2.2 returns -0.0 - the one
+    divergence, in the sign of a zero, which the last assertion records."""
+    from mri_superresolution_amd.utils.imageops import percentile_bounds_np
+    pool = np.array([-0.0, -np.inf, np.inf, -3.5, -3.5, 0.0, 2.25, -1e-30, 7.0, 7.0, 7.0, -4096.0, 1.0 + 2.0 ** -23], dtype=np.float32)
+    bits = lambda x: np.asarray(x, dtype=np.float32).view(np.uint32)                 # noqa: E731
+    for n in (1, 2, 3, 257):
+        with_inf = pool[np.arange(n) % pool.size] if n > 1 else pool[3:4].copy()
+        with_inf[13:] *= np.float32(0.5) ** (np.arange(13, n) // 13).astype(np.float32)      # 257: the pool at several scales
+        finite = np.where(np.isinf(with_inf), np.copysign(np.float32(3e38), with_inf), with_inf)
+        for a in (with_inf, finite):
+            a = np.random.default_rng(n).permutation(a)
+            for q_lo, q_hi in ((0, 100), (0.5, 99.5), (50, 50)):
+                with np.errstate(invalid="ignore"):
+                    got = I.landmarks_np(a, None, (q_lo, q_hi))[0]
+                    bounds = percentile_bounds_np(a, q_lo, q_hi)
+                assert got.dtype == bounds.dtype == np.float32
+                assert (bits(got) == bits(bounds)).all(), (n, q_lo, q_hi, got, bounds)
+                if np.isfinite(a).all():
+                    want = [np.percentile(a, float(q_lo)), np.percentile(a, float(q_hi))]
+                    assert (bits(got) == bits(want)).all(), (n, q_lo, q_hi, got, want)
+    lone = np.array([-0.0], dtype=np.float32)
+    assert (bits(I.landmarks_np(lone, None, (0, 100))[0]) == 0).all() and I.landmarks_np(lone, None, (0, 100))[0][0] == np.percentile(lone, 0.0)
+
+
 def test_landmarks_exclude_nan_and_empty_mask_gives_nan():
     v = volume("normal", (7, 5, 3)).copy()
     v[0, 0, 0] = v[3, 2, 1] = v[6, 4, 2] = np.nan
