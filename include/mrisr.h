@@ -709,6 +709,36 @@ int mrisr_f32_volume_masked_percentiles(const float* vol, const unsigned char* m
 int mrisr_f32_volume_piecewise_map(const float* src, size_t n, const float* src_landmarks, const float* dst_landmarks, int L,
                                    float* dst, void* stream);
 
+/* ---- bias-field matching between scans (extension; csrc/volume_bias.hip): the masked Gaussian low-pass of a volume and the field
+ *      formed from one low-pass (homomorphic unsharp masking) or two (differential bias correction). ---------------------------- */
+#define MRISR_BIAS_PAIR 0    /* field = L_ref / L_src, out = src * field */
+#define MRISR_BIAS_HUM 1     /* field = L / p50,       out = src / field */
+#define MRISR_BIAS_LOWPASS 2 /* out = L (NaN where it is undefined); no field */
+/* num, den (DEVICE, X Y Z floats each) = the separable Gaussian of a and of b, where for every voxel of the DEVICE float32 volume
+ * vol (X, Y, Z in C order)  keep = mask != 0 (and mask2 != 0 when mask2 is not NULL; DEVICE uint8 volumes, any non-zero value) and
+ * vol is not NaN,  a = keep ? vol : 0,  b = keep ? 1 : 0.  Three passes, over axis 2 with taps2 (2 r2 + 1 DEVICE floats), then
+ * axis 1 with taps1, then axis 0 with taps0; in each pass and for each voxel acc = 0, then acc = acc + w[k] * x[i + k] for
+ * k = -r..r ascending, the product rounded to float32, then the sum (never an fma), a tap outside the volume contributing zero;
+ * the intermediates are float32.  a and b are formed inside the first pass.  tmp: DEVICE, 2 X Y Z floats of scratch.  vol, num, den
+ * and tmp are four buffers.  Three launches on stream, no host synchronisation (HIP-graph capturable).
+ * MRISR_E_SHAPE: a radius outside 0..128, a null taps pointer, an extent outside 1..32767; MRISR_E_ARG: another null pointer
+ * (mask2 excepted), a float pointer off a 4-byte boundary, buffers that coincide.  Nothing is launched on a refusal.              */
+int mrisr_f32_volume_smooth_masked(const float* vol, const unsigned char* mask, const unsigned char* mask2, int X, int Y, int Z,
+                                   const float* taps0, int r0, const float* taps1, int r1, const float* taps2, int r2, float* num,
+                                   float* den, float* tmp, void* stream);
+/* One elementwise launch over n voxels (all pointers DEVICE).  L = num / den (a correctly rounded float32 division) where
+ * den >= 1e-3f, else undefined; lo = 1.f / limit, clamp(f) = f > limit ? limit : (f >= lo ? f : lo).
+ * MRISR_BIAS_PAIR:    f = L_ref / L where both are defined and > 0 (L_ref from num_ref, den_ref), else 1;
+ *                     field = clamp(f), out = src * field.
+ * MRISR_BIAS_HUM:     f = L / (p50[0] + 0.f) where L is defined and > 0 and count[0] > 0, else 1; field = clamp(f),
+ *                     out = src / field.  p50: one float, count: one int64 (mrisr_f32_volume_masked_percentiles' outputs).
+ * MRISR_BIAS_LOWPASS: out = L, NaN where it is undefined; src and field are not used.
+ * field may be NULL (not written); out may equal src.  Pointers a mode does not use may be NULL.
+ * MRISR_E_ARG: a null pointer the mode needs, an unknown mode, a limit that is not finite or below 1; MRISR_E_SHAPE: n == 0.    */
+int mrisr_f32_volume_bias_apply(const float* src, size_t n, const float* num, const float* den, const float* num_ref,
+                                const float* den_ref, const float* p50, const long long* count, float limit, int mode, float* field,
+                                float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ WINDOW_F32, WINDOW_I16 = 0, 1      # MRISR_WINDOW_*: out_dtype of mrisr_f32_wind
 VOLBLEND_SET, VOLBLEND_ADD, VOLBLEND_FINISH = 0, 1, 2      # MRISR_VOLBLEND_*: mode of mrisr_f32_volume_up2_blend
 MORPH_DILATE, MORPH_ERODE = 0, 1      # MRISR_MORPH_*: op of mrisr_u8_volume_morph
 RESAMPLE_LINEAR, RESAMPLE_CUBIC, RESAMPLE_AREA, RESAMPLE_LANCZOS4 = 1, 2, 3, 4      # MRISR_RESAMPLE_*: method of mrisr_resample_taps
+BIAS_PAIR, BIAS_HUM, BIAS_LOWPASS = 0, 1, 2      # MRISR_BIAS_*: mode of mrisr_f32_volume_bias_apply
 RESAMPLE_NEAREST = 5      # MRISR_RESAMPLE_NEAREST: mrisr_f32_volume_reslice only
 PACK_RING = 256      # MRISR_PACK_RING: OR into transpose_flip for the ring weight layout (csrc/conv_ring.hip)
 PACK_UPADJ = 512     # MRISR_PACK_UPADJ: the W^T image of mrisr_conv_upadj (csrc/conv_upadj.hip)
@@ -179,10 +180,12 @@ SIGNATURES = {
     "mrisr_f32_masked_percentiles_workspace_bytes": (_sz, [_i]),
     "mrisr_f32_volume_masked_percentiles": (_i, [_fp, _vp, _sz, C.POINTER(C.c_double), _i, _fp, _vp, _vp, _vp]),
     "mrisr_f32_volume_piecewise_map": (_i, [_fp, _sz, _fp, _fp, _i, _fp, _vp]),
+    "mrisr_f32_volume_smooth_masked": (_i, [_fp, _vp, _vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _fp, _fp, _fp, _vp]),
+    "mrisr_f32_volume_bias_apply": (_i, [_fp, _sz, _fp, _fp, _fp, _fp, _fp, _vp, _f, _i, _fp, _fp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 318      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 319      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -11,7 +11,7 @@ function that sends its landmarks onto the target's.
 ``masked_percentiles``, ``piecewise_map``, ``match_intensity``   the device path (``csrc/volume_intensity.hip``), equal to the
                         specification bit for bit.  There is no CPU path: CPU tensors raise.
 
-Not built: histogram-exact (full CDF) matching, bias-field correction.
+Not built: histogram-exact (full CDF) matching.
 """
 from __future__ import annotations
 

@@ -53,6 +53,13 @@ of the reference's (``volume_intensity.match_intensity``, Nyul-Udupa; ``csrc/vol
 its own Otsu mask (``volume_eval.foreground_mask``, no closing), whatever ``--mask`` says; the voxels a reslice left at the fill
 value 0 fall below Otsu's threshold and do not move the landmarks.  The landmarks and the voxel counts are logged.  The default,
 ``none``, leaves a run as it was.
+
+``--match_bias pair`` (with ``--input``) handles what a global map cannot: the slowly varying gain across the head (B1 / coil
+sensitivity), strong at 3 T, weak at low field and different in every session.  After the ``--align`` reslice and after
+``--match_intensity``, before any method sees it, every input frame is multiplied by the ratio of two masked Gaussian low-passes
+(``volume_bias.match_bias``, ``--match_bias_sigma_mm``, default 25 mm; ``csrc/volume_bias.hip``): that of the reference frame's mean
+over pairs (``volume_eval.downsample2``, on the input's grid) over its own, inside the intersection of the two Otsu foregrounds
+``--match_intensity`` uses.  The default, ``none``, leaves a run as it was.
 """
 import argparse
 import csv
@@ -69,7 +76,8 @@ if REPO not in sys.path:
 
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
 from mri_superresolution_amd.utils.nifti import downscaled_affine, frames, grid_matrix, mask_frames, read_nifti, write_nifti   # noqa: E402
-from mri_superresolution_amd.volume_eval import evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
+from mri_superresolution_amd.volume_bias import match_bias as match_bias_field, sigmas_for                  # noqa: E402
+from mri_superresolution_amd.volume_eval import downsample2, evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity    # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice, reslice_mask    # noqa: E402
@@ -95,8 +103,14 @@ def load_mask(mask_path, ref, ref_affine=None):
     return out if len(header.shape) == 4 else out * count
 
 
-def check_options(input_path, align, align_interp, align_init, align_mask, match):
+def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0):
     """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
+    if match_bias not in ("none", "pair"):
+        raise ValueError(f"--match_bias is none or pair, got {match_bias!r}")
+    if match_bias != "none" and not input_path:
+        raise ValueError("--match_bias goes with --input")
+    if not (np.isfinite(match_bias_sigma_mm) and match_bias_sigma_mm >= 0):
+        raise ValueError(f"--match_bias_sigma_mm must be finite and not negative, got {match_bias_sigma_mm}")
     if match not in ("none", "landmarks", "range"):
         raise ValueError(f"--match_intensity is none, range or landmarks, got {match!r}")
     if match != "none" and not input_path:
@@ -113,10 +127,29 @@ def check_options(input_path, align, align_interp, align_init, align_mask, match
         raise ValueError("--align_init and --align_mask go with --align rigid")
 
 
+def prepare_input(lr, vol, match="none", match_bias="none", axes=(0, 1, 2), sigmas_vox=None, what="input", reference="its reference"):
+    """What ``--match_intensity`` and ``--match_bias`` do to one input frame ``lr`` next to its reference frame ``vol`` (CUDA
+    tensors) -> the frame every method sees.  ``match`` first, then ``match_bias="pair"`` against ``downsample2(vol, axes)`` - the
+    reference on the input's grid - with ``sigmas_vox`` on that grid.  Both ``"none"``: ``lr`` itself."""
+    if match != "none":
+        lr, found = match_intensity(lr, vol, foreground_mask(lr)[0], foreground_mask(vol)[0], LANDMARKS if match == "landmarks" else RANGE)
+        marks = "  ".join(f"{q:g}%: {a:.6g} -> {b:.6g}" for q, a, b in zip(found.percentiles, found.source_landmarks, found.target_landmarks))
+        logger.info(f"{what} mapped onto the intensity scale of {reference} ({match}): {found.source_count} input and "
+                    f"{found.target_count} reference foreground voxels; landmarks {marks}")
+    if match_bias != "none":
+        want = tuple(2 * d if a in axes else d for a, d in enumerate(lr.shape))
+        if any(w > d for w, d in zip(want, vol.shape)):
+            raise ValueError(f"--match_bias: the input {tuple(lr.shape)} is not half of the reference {tuple(vol.shape)} on the axes {axes}")
+        low_ref = downsample2(vol[:want[0], :want[1], :want[2]].contiguous(), axes)
+        lr = match_bias_field(lr, low_ref, foreground_mask(lr)[0], foreground_mask(low_ref)[0], sigmas_vox, want_field=False)[0]
+        logger.info(f"{what}: bias field matched to that of {reference} (sigmas {tuple(round(float(x), 3) for x in sigmas_vox)} voxels)")
+    return lr
+
+
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
-               match="none"):
+               match="none", match_bias="none", match_bias_sigma_mm=25.0):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -125,8 +158,9 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     to the reference first and resliced once through the estimated transform; ``align_init="global"`` starts that registration
     from a coarse grid of rotations about the masks' centres of mass, ``align_mask="otsu"`` puts the reference's Otsu mask in its
     cost (``volume_register.register_rigid``).  ``match`` (``"landmarks"`` / ``"range"``): every input frame is mapped onto its
-    reference frame's intensity scale before any method sees it (module docstring)."""
-    check_options(input_path, align, align_interp, align_init, align_mask, match)
+    reference frame's intensity scale before any method sees it (module docstring); ``match_bias="pair"``: then its bias field is
+    matched to the reference's (``prepare_input``)."""
+    check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm)
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
     if low is not None and low.ndim != ref.ndim:
@@ -135,9 +169,10 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
         raise ValueError(f"{input_path} has {low.shape[3]} timepoints, {reference_path} has {ref.shape[3]}")
     ref_frames, low_frames = frames(ref), (frames(low) if low is not None else None)
     masks = load_mask(mask, ref, ref_header.affine() if align else None) if mask not in (None, "otsu") else None
+    axes = (0, 1, 2) if isotropic else tuple(a for a in (0, 1, 2) if a != axis)
+    bias_sigmas = sigmas_for(downscaled_affine(ref_header.affine(), axes), match_bias_sigma_mm) if match_bias != "none" else None
     if align:
         # the grid a x2 pass over the doubled axes expects its input on; the crop takes trailing voxels, so the affine stays
-        axes = (0, 1, 2) if isotropic else tuple(a for a in (0, 1, 2) if a != axis)
         crop = tuple(d - d % 2 if a in axes else d for a, d in enumerate(ref.shape[:3]))
         if 0 in crop:
             raise ValueError(f"nothing is left of the reference volume {tuple(ref.shape[:3])} after cropping to even extents")
@@ -175,12 +210,9 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             lr = low_frames[t] if align else torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device)
         if masks is not None:
             m = masks[t] if align else torch.from_numpy(masks[t]).to(device)
-        if match != "none":
-            lr, found = match_intensity(lr, vol, foreground_mask(lr)[0], foreground_mask(vol)[0],
-                                        LANDMARKS if match == "landmarks" else RANGE)
-            marks = "  ".join(f"{q:g}%: {a:.6g} -> {b:.6g}" for q, a, b in zip(found.percentiles, found.source_landmarks, found.target_landmarks))
-            logger.info(f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''} mapped onto the intensity scale of {reference_path} ({match}): "
-                        f"{found.source_count} input and {found.target_count} reference foreground voxels; landmarks {marks}")
+        if lr is not None:
+            lr = prepare_input(lr, vol, match, match_bias, axes, bias_sigmas, f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}",
+                               reference_path)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
                               mask_fill_holes=mask_fill_holes)
@@ -257,7 +289,8 @@ def main(args):
             raise ValueError("--mask_close goes with --mask")
         if args.mask is None and (args.mask_largest or args.mask_fill_holes is not None or args.save_mask):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
-        check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity)
+        check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity, args.match_bias,
+                      args.match_bias_sigma_mm)
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -280,7 +313,7 @@ def main(args):
                                    graph_cache=graphs, mask=args.mask, mask_close=args.mask_close, mask_largest=args.mask_largest,
                                    mask_fill_holes=fill, save_mask=args.save_mask, align=args.align, align_interp=args.align_interp,
                                    align_bins=args.align_bins, align_init=args.align_init, align_mask=args.align_mask,
-                                   match=args.match_intensity)
+                                   match=args.match_intensity, match_bias=args.match_bias, match_bias_sigma_mm=args.match_bias_sigma_mm)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -351,6 +384,10 @@ def parse_args(argv=None):
     p.add_argument("--match_intensity", type=str, choices=["none", "range", "landmarks"], default="none",
                    help="map every --input frame onto its reference frame's intensity scale before any method sees it: the percentiles "
                         "1, 10, ..., 90, 99 (landmarks) or 1 and 99 (range) of the two Otsu foregrounds (needs --input)")
+    p.add_argument("--match_bias", type=str, choices=["none", "pair"], default="none",
+                   help="match every --input frame's bias field to its reference frame's (the ratio of two masked Gaussian low-passes, "
+                        "inside the two Otsu foregrounds), after --align and --match_intensity (needs --input)")
+    p.add_argument("--match_bias_sigma_mm", type=float, default=25.0, help="sigma of --match_bias's low-pass in millimetres")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 
