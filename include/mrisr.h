@@ -739,6 +739,36 @@ int mrisr_f32_volume_bias_apply(const float* src, size_t n, const float* num, co
                                 const float* den_ref, const float* p50, const long long* count, float limit, int mode, float* field,
                                 float* out, void* stream);
 
+/* ---- Rician non-local-means denoising (extension; csrc/volume_denoise.hip): the 3-D non-local-means filter with patch radius 1 and
+ *      the Rician correction on the squared signal, and the Rayleigh estimate of the noise level from the background. ----------- */
+/* out = the filtered DEVICE float32 volume vol (X, Y, Z in C order), bit for bit volume_denoise.denoise_np.  params: DEVICE, 4 floats
+ * (inv_h2, two_sigma2, sigma, beta), of which the first two are read; table: DEVICE, the 4096 floats float32(exp(-(k + 0.5) / 256)).
+ * With c(p) the clamp of every coordinate into the volume, sq(p) = (v[c(p)] - v[c(p + t)])^2, row(p) = (sq(p - e2) + sq(p)) + sq(p + e2),
+ * plane(p) = (row(p - e1) + row(p)) + row(p + e1), d(p) = (plane(p - e0) + plane(p)) + plane(p + e0), every candidate t != 0 with
+ * |t_i| <= radius in ascending (t0, t1, t2) order: x = d(p) * inv_h2; when 0 <= x < 16 (NaN and inf compare false) and p + t lies
+ * inside the volume, w = table[(int)(x * 256)], num = num + w * val[p + t], den = den + w, wmax = max(wmax, w), with val = v * v when
+ * rician, else v; every other candidate adds nothing.  Then wc = wmax > 0 ? wmax : 1, num = num + wc * val[p], den = den + wc,
+ * m = num / den; rician: u = m - two_sigma2, out = u > 0 ? sqrt(u) : 0, else out = m.  Every operation is one rounded float32
+ * operation, never an fma.  A voxel that is not finite is copied through.  One launch on stream, one workgroup per 8 x 16 x 32 tile,
+ * the tile and a halo of radius + 1 in LDS; no host synchronisation (HIP-graph capturable; a radius of 3 or more raises the
+ * kernel's LDS limit on the current device at every call, a host-side attribute).
+ * MRISR_E_ARG: null or misaligned pointer, radius outside 1..5, vol == out; MRISR_E_SHAPE: an extent outside 1..32767.             */
+int mrisr_f32_volume_nlm(const float* vol, int X, int Y, int Z, int radius, int rician, const float* params, const float* table,
+                         float* out, void* stream);
+/* bytes of DEVICE workspace of mrisr_f32_volume_noise_params (any volume size); no initialisation needed, 8-byte aligned.        */
+size_t mrisr_f32_volume_noise_workspace_bytes(void);
+/* params (DEVICE, 4 floats) = (inv_h2, two_sigma2, sigma, beta) and count (DEVICE, one int64) of the DEVICE float32 volume vol (n
+ * voxels).  sigma_given == 0: over the voxels that are finite and whose byte of background (DEVICE uint8, n bytes) is non-zero,
+ * S = the float64 sum of (double)v^2 and count their number, sigma = (float)sqrt(S / (2 count)), 0 when count == 0 (the Rayleigh
+ * estimate); partial sums of at most 1024 workgroups in fixed slots of the workspace, added in slot order by a last launch: the
+ * same bits on every run.  sigma_given > 0: that sigma, count = 0, vol and background are not read (and may be NULL).  Then, in
+ * float32, two_sigma2 = (sigma * sigma) * 2, h2 = (two_sigma2 * beta) * 27, inv_h2 = 1 / h2 (inf for sigma == 0).  Two launches (one
+ * when sigma is given) on stream, no host synchronisation (HIP-graph capturable).
+ * MRISR_E_ARG: a null or misaligned pointer that is needed, beta not finite and positive, sigma_given negative or not finite;
+ * MRISR_E_SHAPE: n == 0 when sigma is to be estimated.                                                                            */
+int mrisr_f32_volume_noise_params(const float* vol, const unsigned char* background, size_t n, float beta, float sigma_given,
+                                  float* params, long long* count, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,10 +182,13 @@ SIGNATURES = {
     "mrisr_f32_volume_piecewise_map": (_i, [_fp, _sz, _fp, _fp, _i, _fp, _vp]),
     "mrisr_f32_volume_smooth_masked": (_i, [_fp, _vp, _vp, _i, _i, _i, _fp, _i, _fp, _i, _fp, _i, _fp, _fp, _fp, _vp]),
     "mrisr_f32_volume_bias_apply": (_i, [_fp, _sz, _fp, _fp, _fp, _fp, _fp, _vp, _f, _i, _fp, _fp, _vp]),
+    "mrisr_f32_volume_nlm": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
+    "mrisr_f32_volume_noise_workspace_bytes": (_sz, []),
+    "mrisr_f32_volume_noise_params": (_i, [_fp, _vp, _sz, _f, _f, _fp, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 319      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 320      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -60,6 +60,13 @@ sensitivity), strong at 3 T, weak at low field and different in every session.  
 (``volume_bias.match_bias``, ``--match_bias_sigma_mm``, default 25 mm; ``csrc/volume_bias.hip``): that of the reference frame's mean
 over pairs (``volume_eval.downsample2``, on the input's grid) over its own, inside the intersection of the two Otsu foregrounds
 ``--match_intensity`` uses.  The default, ``none``, leaves a run as it was.
+
+``--denoise_input nlm`` (with ``--input``) takes the noise out of every input frame first of all, on the frame's own grid and BEFORE
+the ``--align`` reslice - interpolation correlates the noise of neighbouring voxels, and the Rayleigh estimate of sigma needs raw
+air: the Rician non-local-means filter of ``volume_denoise.denoise_volume`` (``csrc/volume_denoise.hip``), sigma estimated per frame
+from the background or given with ``--denoise_sigma``, ``--denoise_beta`` (default 1) scaling the filter's strength,
+``--denoise_radius`` (default 3) its search window.  Sigma and the background count are logged.  The default, ``none``, leaves a
+run as it was.
 """
 import argparse
 import csv
@@ -77,6 +84,7 @@ if REPO not in sys.path:
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
 from mri_superresolution_amd.utils.nifti import downscaled_affine, frames, grid_matrix, mask_frames, read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_bias import match_bias as match_bias_field, sigmas_for                  # noqa: E402
+from mri_superresolution_amd.volume_denoise import denoise_volume                                             # noqa: E402
 from mri_superresolution_amd.volume_eval import downsample2, evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity    # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
@@ -103,8 +111,17 @@ def load_mask(mask_path, ref, ref_affine=None):
     return out if len(header.shape) == 4 else out * count
 
 
-def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0):
+def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0,
+                  denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3):
     """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
+    if denoise_input not in ("none", "nlm"):
+        raise ValueError(f"--denoise_input is none or nlm, got {denoise_input!r}")
+    if denoise_input != "none" and not input_path:
+        raise ValueError("--denoise_input goes with --input")
+    if denoise_sigma is not None and not (np.isfinite(denoise_sigma) and denoise_sigma > 0):
+        raise ValueError(f"--denoise_sigma must be finite and positive, got {denoise_sigma}")
+    if not (np.isfinite(denoise_beta) and denoise_beta > 0) or denoise_radius not in (1, 2, 3, 4, 5):
+        raise ValueError(f"--denoise_beta must be finite and positive and --denoise_radius in 1..5, got {denoise_beta} and {denoise_radius}")
     if match_bias not in ("none", "pair"):
         raise ValueError(f"--match_bias is none or pair, got {match_bias!r}")
     if match_bias != "none" and not input_path:
@@ -125,6 +142,21 @@ def check_options(input_path, align, align_interp, align_init, align_mask, match
         raise ValueError(f"--align_init is header or global and --align_mask none or otsu, got {align_init} and {align_mask}")
     if align != "rigid" and (align_init != "header" or align_mask != "none"):
         raise ValueError("--align_init and --align_mask go with --align rigid")
+
+
+def upload_input(frame, device="cuda", denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, onto=None,
+                 what="input"):
+    """One input frame (a numpy array) -> the CUDA tensor the rest of the run works on: uploaded, with ``denoise_input="nlm"``
+    denoised on its own grid (``volume_denoise.denoise_volume``, sigma estimated from the frame's background unless given), and only
+    then, with ``onto = (matrix, shape, interpolation)``, resliced (``--align``).  ``"none"`` and no ``onto``: the upload alone."""
+    lr = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
+    if denoise_input != "none":
+        lr, noise = denoise_volume(lr, sigma=denoise_sigma, beta=denoise_beta, radius=denoise_radius, return_noise=True)
+        logger.info(f"{what} denoised (nlm, radius {denoise_radius}, beta {denoise_beta:g}): sigma {noise['sigma']:.6g}"
+                    + (f" from {noise['count']} background voxels" if denoise_sigma is None else " (given)"))
+    if onto is not None:
+        lr = reslice(lr, *onto)
+    return lr
 
 
 def prepare_input(lr, vol, match="none", match_bias="none", axes=(0, 1, 2), sigmas_vox=None, what="input", reference="its reference"):
@@ -149,7 +181,8 @@ def prepare_input(lr, vol, match="none", match_bias="none", axes=(0, 1, 2), sigm
 def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, data_range=None, batch_size=16, use_amp=False,
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
-               match="none", match_bias="none", match_bias_sigma_mm=25.0):
+               match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
+               denoise_radius=3):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -159,8 +192,11 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     from a coarse grid of rotations about the masks' centres of mass, ``align_mask="otsu"`` puts the reference's Otsu mask in its
     cost (``volume_register.register_rigid``).  ``match`` (``"landmarks"`` / ``"range"``): every input frame is mapped onto its
     reference frame's intensity scale before any method sees it (module docstring); ``match_bias="pair"``: then its bias field is
-    matched to the reference's (``prepare_input``)."""
-    check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm)
+    matched to the reference's (``prepare_input``).  ``denoise_input="nlm"``: every input frame is denoised on its own grid before
+    anything else happens to it (``upload_input``)."""
+    check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
+                  denoise_sigma, denoise_beta, denoise_radius)
+    noise_options = (denoise_input, denoise_sigma, denoise_beta, denoise_radius)
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
     if low is not None and low.ndim != ref.ndim:
@@ -196,7 +232,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             low_grid = found.world @ low_grid
             del fixed, moving
         m = grid_matrix(low_header.affine(), low_grid)
-        low_frames = [reslice(torch.from_numpy(np.ascontiguousarray(f)).to(device), m, low_shape, align_interp) for f in low_frames]
+        low_frames = [upload_input(f, device, *noise_options, onto=(m, low_shape, align_interp),
+                                   what=f"{input_path}{f'[t={t}]' if len(low_frames) > 1 else ''}") for t, f in enumerate(low_frames)]
         share = float(covered_share(low.shape[:3], m, low_shape, device))
         logger.info(f"{input_path} {tuple(low.shape[:3])} resliced onto the low-resolution grid {low_shape} of {reference_path} "
                     f"({align_interp}); it covers {100.0 * share:.2f} % of that grid.")
@@ -207,7 +244,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
         lr, m = None, mask
         if low_frames is not None:      # with --align the frames are on the device already
-            lr = low_frames[t] if align else torch.from_numpy(np.ascontiguousarray(low_frames[t])).to(device)
+            lr = low_frames[t] if align else upload_input(low_frames[t], device, *noise_options,
+                                                          what=f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}")
         if masks is not None:
             m = masks[t] if align else torch.from_numpy(masks[t]).to(device)
         if lr is not None:
@@ -290,7 +328,7 @@ def main(args):
         if args.mask is None and (args.mask_largest or args.mask_fill_holes is not None or args.save_mask):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
         check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity, args.match_bias,
-                      args.match_bias_sigma_mm)
+                      args.match_bias_sigma_mm, args.denoise_input, args.denoise_sigma, args.denoise_beta, args.denoise_radius)
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -313,7 +351,9 @@ def main(args):
                                    graph_cache=graphs, mask=args.mask, mask_close=args.mask_close, mask_largest=args.mask_largest,
                                    mask_fill_holes=fill, save_mask=args.save_mask, align=args.align, align_interp=args.align_interp,
                                    align_bins=args.align_bins, align_init=args.align_init, align_mask=args.align_mask,
-                                   match=args.match_intensity, match_bias=args.match_bias, match_bias_sigma_mm=args.match_bias_sigma_mm)
+                                   match=args.match_intensity, match_bias=args.match_bias, match_bias_sigma_mm=args.match_bias_sigma_mm,
+                                   denoise_input=args.denoise_input, denoise_sigma=args.denoise_sigma, denoise_beta=args.denoise_beta,
+                                   denoise_radius=args.denoise_radius)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -388,6 +428,12 @@ def parse_args(argv=None):
                    help="match every --input frame's bias field to its reference frame's (the ratio of two masked Gaussian low-passes, "
                         "inside the two Otsu foregrounds), after --align and --match_intensity (needs --input)")
     p.add_argument("--match_bias_sigma_mm", type=float, default=25.0, help="sigma of --match_bias's low-pass in millimetres")
+    p.add_argument("--denoise_input", type=str, choices=["none", "nlm"], default="none",
+                   help="denoise every --input frame on its own grid, before the --align reslice: the Rician non-local-means filter, "
+                        "sigma estimated from the frame's background (needs --input)")
+    p.add_argument("--denoise_sigma", type=float, default=None, help="the noise level of --denoise_input, in intensity units (default: estimated)")
+    p.add_argument("--denoise_beta", type=float, default=1.0, help="strength of --denoise_input: h^2 = 2 beta sigma^2 per patch voxel")
+    p.add_argument("--denoise_radius", type=int, default=3, help="search radius of --denoise_input in voxels, 1..5")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

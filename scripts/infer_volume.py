@@ -19,6 +19,11 @@ along its own slice axis and the three are averaged on the device (``volume.enha
 enhancement (``volume_reslice.reslice``, ``--spacing_interp linear|cubic``): a 1.5 x 1.5 x 5 mm scan with
 ``--spacing 0 0 1.5 --isotropic`` comes out at 0.75 mm in every direction.  The output header is that of the respaced grid
 (``utils.nifti.respaced_grid`` / ``header_for_grid``) after the x2 write.
+
+``--denoise nlm`` takes the noise out of the uploaded volume first of all, before the ``--spacing`` reslice and the windowing: the
+Rician non-local-means filter of ``volume_denoise.denoise_volume`` (``csrc/volume_denoise.hip``), sigma estimated per volume from
+the air around the head or given with ``--denoise_sigma``; ``--denoise_beta`` (default 1) scales the filter's strength,
+``--denoise_radius`` (default 3) is its search radius.  The default, ``none``, leaves a run as it was.
 """
 import argparse
 import logging
@@ -34,6 +39,7 @@ if REPO not in sys.path:
 
 from mri_superresolution_amd.utils.nifti import frames, grid_matrix, header_for_grid, read_nifti, respaced_grid, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume import enhance_volume, enhance_volume_isotropic   # noqa: E402
+from mri_superresolution_amd.volume_denoise import denoise_volume        # noqa: E402
 from mri_superresolution_amd.volume_reslice import reslice               # noqa: E402
 from scripts.infer import find_best_checkpoint, load_model               # noqa: E402
 
@@ -41,9 +47,13 @@ logger = logging.getLogger("infer_volume")
 
 
 def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_amp=False, use_graph=True, output_dtype="float32",
-                   device="cuda", isotropic=False, spacing=None, spacing_interp="linear"):
+                   device="cuda", isotropic=False, spacing=None, spacing_interp="linear", denoise="none", denoise_sigma=None,
+                   denoise_beta=1.0, denoise_radius=3):
     """NIfTI file -> NIfTI file; returns the output array (as written).  ``spacing`` (three voxel sizes in mm, 0 or ``None`` keeps
-    an axis): every volume is resliced to that spacing on the device before it is windowed and enhanced."""
+    an axis): every volume is resliced to that spacing on the device before it is windowed and enhanced.  ``denoise="nlm"``: every
+    volume is denoised before that (``volume_denoise.denoise_volume``; ``denoise_sigma`` None: estimated from its background)."""
+    if denoise not in ("none", "nlm"):
+        raise ValueError(f"--denoise is none or nlm, got {denoise!r}")
     data, header = read_nifti(input_path)
     dtype = {"float32": torch.float32, "int16": torch.int16}[output_dtype]
     in_plane = (0, 1, 2) if isotropic else tuple(a for a in (0, 1, 2) if a != axis)
@@ -64,6 +74,10 @@ def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_am
     outs, graphs = [], {}
     for frame in frames(data):
         vol = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
+        if denoise != "none":
+            vol, noise = denoise_volume(vol, sigma=denoise_sigma, beta=denoise_beta, radius=denoise_radius, return_noise=True)
+            logger.info(f"Denoised (nlm, radius {denoise_radius}, beta {denoise_beta:g}): sigma {noise['sigma']:.6g}"
+                        + (f" from {noise['count']} background voxels" if denoise_sigma is None else " (given)"))
         if regrid is not None:
             vol = reslice(vol, regrid, shape, spacing_interp)
         if isotropic:
@@ -99,7 +113,9 @@ def main(args):
         model = load_model(args.model_type, ckpt, device, base_filters=args.base_filters)
         process_volume(model, args.input, args.output, args.axis, args.batch_size, args.use_amp, not args.no_graph,
                        args.output_dtype, device, isotropic=args.isotropic, spacing=getattr(args, "spacing", None),
-                       spacing_interp=getattr(args, "spacing_interp", "linear"))
+                       spacing_interp=getattr(args, "spacing_interp", "linear"), denoise=getattr(args, "denoise", "none"),
+                       denoise_sigma=getattr(args, "denoise_sigma", None), denoise_beta=getattr(args, "denoise_beta", 1.0),
+                       denoise_radius=getattr(args, "denoise_radius", 3))
         logger.info("Inference completed successfully!")
         return 0
     except Exception as e:
@@ -132,6 +148,13 @@ def parse_args(argv=None):
                    help="(extension) reslice the volume to this voxel size in mm on the device before enhancement; 0 keeps an axis")
     p.add_argument("--spacing_interp", type=str, choices=["linear", "cubic"], default=argparse.SUPPRESS,
                    help="(extension) interpolation of the --spacing reslice (default: linear)")
+    p.add_argument("--denoise", type=str, choices=["none", "nlm"], default=argparse.SUPPRESS,
+                   help="(extension) denoise the uploaded volume before --spacing and the windowing: nlm, the Rician non-local-means "
+                        "filter with sigma from the background (default: none)")
+    p.add_argument("--denoise_sigma", type=float, default=argparse.SUPPRESS,
+                   help="(extension) the noise level of --denoise in intensity units (default: estimated from the air around the head)")
+    p.add_argument("--denoise_beta", type=float, default=argparse.SUPPRESS, help="(extension) strength of --denoise (default: 1)")
+    p.add_argument("--denoise_radius", type=int, default=argparse.SUPPRESS, help="(extension) search radius of --denoise, 1..5 (default: 3)")
     return p.parse_args(argv)
 
 
