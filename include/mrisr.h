@@ -769,6 +769,44 @@ size_t mrisr_f32_volume_noise_workspace_bytes(void);
 int mrisr_f32_volume_noise_params(const float* vol, const unsigned char* background, size_t n, float beta, float sigma_given,
                                   float* params, long long* count, void* workspace, void* stream);
 
+/* ---- Deformable registration (extension; csrc/volume_deform.hip): Thirion's demons, additive update, Gaussian regularisation of
+ *      the field.  A field u is DEVICE float32 (3, X, Y, Z) in C order, in voxels: fixed(x) is compared with moving(x + u(x)).
+ *      The coordinate of voxel (i0, i1, i2) is p_a = (double)i_a + (double)u_a; the inside test -0.5 <= p_a <= n_a - 0.5 (a NaN or
+ *      infinite displacement fails it), the taps, their clamp and the reduction are mrisr_f32_volume_reslice's.  Every operation is
+ *      one rounded operation, never an fma; the specification is mri_superresolution_amd/volume_deform.py. ------------------------- */
+/* bytes of DEVICE workspace of the force and the Jacobian entries (any volume size); no initialisation needed, 8-byte aligned.    */
+size_t mrisr_f32_volume_deform_workspace_bytes(void);
+/* out (X, Y, Z) = moving at x + u(x), MRISR_RESAMPLE_LINEAR or _CUBIC, fill outside; bit for bit volume_deform.warp_np.  One launch.
+ * MRISR_E_ARG: null or misaligned pointer, unknown method, out == moving or u; MRISR_E_SHAPE: an extent below 1, more than
+ * 2^31 - 1 voxels.                                                                                                                  */
+int mrisr_f32_volume_warp(const float* moving, const float* u, int X, int Y, int Z, int method, float fill, float* out, void* stream);
+/* v = u + upd, bit for bit volume_deform.demons_force_np: d = warp(moving, u, LINEAR, fill) - fixed; g = the gradient of fixed
+ * (0.5 (f[i+1] - f[i-1]) inside, the one-sided difference at the two ends, 0 along an axis of extent 1);
+ * den = ((g0 g0 + g1 g1) + g2 g2) + d d; s = d / den where den > 1e-9f, else 0; upd_a = -(s g_a), clamped to [-max_step, max_step]
+ * by comparisons, 0 where the voxel is outside moving or upd_a is not a number.  One launch; nothing but v is written to a volume.
+ * The float64 sum of d^2 over the inside voxels with a finite d and their count leave the launch as per-workgroup partial sums
+ * (each a sum and its accumulated rounding error) in fixed slots of workspace.  stats_row (DEVICE: one double, one int64) given:
+ * a second launch of one wave adds the slots in a fixed order into it.  NULL: the next mrisr_f32_volume_field_smooth that is given
+ * this workspace does so.  The same bits on every run, no floating-point atomics; no host synchronisation (HIP-graph capturable).
+ * MRISR_E_ARG: null or misaligned pointer, max_step negative or not finite, v equal to an input; MRISR_E_SHAPE as above.          */
+int mrisr_f32_volume_demons_force(const float* fixed, const float* moving, const float* u, int X, int Y, int Z, float max_step,
+                                  float fill, float* v, void* workspace, void* stats_row, void* stream);
+/* out = one pass of a Gaussian along axis (0, 1 or 2) over all three components of the field in, bit for bit one pass of
+ * volume_deform.smooth_field_np: acc = 0, then acc = acc + taps[k] * in[clamp(i + k - radius)] for k = 0 .. 2 radius (the border is
+ * replicated).  taps: DEVICE, 2 radius + 1 floats.  One launch, the tile and its halo staged in LDS once per workgroup.  workspace and
+ * stats_row given (both or neither): the first workgroup also finalises the sums a preceding mrisr_f32_volume_demons_force on the
+ * same volume shape left in workspace into stats_row.
+ * MRISR_E_ARG: null or misaligned pointer, unknown axis, in == out, one of workspace / stats_row without the other;
+ * MRISR_E_SHAPE: radius outside 0..16, an extent below 1, more than 2^31 - 1 voxels.                                               */
+int mrisr_f32_volume_field_smooth(const float* in, float* out, int X, int Y, int Z, int axis, const float* taps, int radius,
+                                  const void* workspace, void* stats_row, void* stream);
+/* min_det (DEVICE, one float) = the smallest determinant of I + grad u over the voxels (the gradient rule of the force per component;
+ * det = (J00 (J11 J22 - J12 J21) - J01 (J10 J22 - J12 J20)) + J02 (J10 J21 - J11 J20); +inf when none is a number) and count
+ * (DEVICE, one int64) = the number of voxels with det <= 0; volume_deform.jacobian_stats_np.  Two launches through the fixed slots
+ * of workspace.  MRISR_E_ARG: null or misaligned pointer; MRISR_E_SHAPE as above.                                                  */
+int mrisr_f32_volume_jacobian_stats(const float* u, int X, int Y, int Z, float* min_det, long long* count, void* workspace,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

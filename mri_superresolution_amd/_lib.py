@@ -185,10 +185,15 @@ SIGNATURES = {
     "mrisr_f32_volume_nlm": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
     "mrisr_f32_volume_noise_workspace_bytes": (_sz, []),
     "mrisr_f32_volume_noise_params": (_i, [_fp, _vp, _sz, _f, _f, _fp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_deform_workspace_bytes": (_sz, []),
+    "mrisr_f32_volume_warp": (_i, [_fp, _fp, _i, _i, _i, _i, _f, _fp, _vp]),
+    "mrisr_f32_volume_demons_force": (_i, [_fp, _fp, _fp, _i, _i, _i, _f, _f, _fp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_field_smooth": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _i, _vp, _vp, _vp]),
+    "mrisr_f32_volume_jacobian_stats": (_i, [_fp, _i, _i, _i, _fp, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 320      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 321      # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -1,0 +1,479 @@
+"""Deformable registration of volumes on the device (extension): what is left between two scans of one head
+after the best rigid fit - gradient non-linearity, susceptibility / B0 distortion - is non-rigid.  Thirion's demons with an
+additive update and a Gaussian ("diffusion-like") regularisation of the field, coarse to fine, with fixed iteration counts and no
+line search.  The cost is an intensity difference: standardise the intensities and match the bias first.
+
+A field ``u`` is float32 ``(3, X, Y, Z)`` in voxels of the common grid: ``fixed(x)`` is compared with ``moving(x + u(x))``.
+
+``warp_np``, ``gradient_np``, ``demons_force_np``, ``smooth_field_np``, ``jacobian_stats_np``, ``register_deformable_np``   the
+                      specification: float32, every product, sum, difference and division rounded on its own (no fma), the orders
+                      written in the docstrings.
+``pyramid_shapes``    the shapes of the levels, coarse to fine.
+``warp``, ``demons_force``, ``smooth_field``, ``jacobian_stats``, ``register_deformable``   the device path
+                      (``csrc/volume_deform.hip``), equal to the specification bit for bit (the float64 sum of squared
+                      differences: within one spacing, the same bits on every run).  There is no CPU path: CPU tensors raise.
+                      ``register_deformable`` reads the device once, at its end; its iteration loop - four launches per
+                      iteration - is HIP-graph capturable with a ``DeformWorkspace`` made before the capture.
+
+Not built: diffeomorphic / log-domain demons, composing the field with the rigid matrix into one interpolation, masks in the
+force, a mutual-information force, affine.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .volume_bias import gaussian_taps
+from .volume_eval import downsample2, downsample2_np, upscale2, upscale2_np
+from .volume_intensity import _check_vol
+from .volume_reslice import _check_shape, _taps_np, _weighted_sum_np
+
+MAX_RADIUS = 16
+DEN_MIN = np.float32(1e-9)                 # MRISR_DEFORM_DEN_MIN: below it a voxel has neither a gradient nor a difference
+METHODS = {"linear": L.RESAMPLE_LINEAR, "cubic": L.RESAMPLE_CUBIC}
+MIN_EXTENT = 16                            # pyramid_shapes: an extent below this is not halved
+DEFAULT_ITERATIONS = (40, 20, 10)          # coarse -> fine
+
+
+class DeformResult(NamedTuple):
+    field: object          # (3, X, Y, Z) float32
+    warped: object         # moving at x + field(x)
+    stats: list            # one (sum of d^2, n) row per iteration, coarse level first
+    jacobian: tuple        # (minimum determinant of I + grad field, count of determinants <= 0)
+    schedule: tuple        # ((shape, iterations), ...) coarse -> fine: the rows of stats belong to the levels in this order
+
+
+# ---------------------------------------------------------------- numpy specification
+
+def _check_volume_np(v, what):
+    v = np.asarray(v)
+    if v.dtype != np.float32 or v.ndim != 3 or v.size == 0:
+        raise ValueError(f"{what}: expected a non-empty float32 volume (X,Y,Z), got {v.dtype} {v.shape}")
+    _check_shape(v.shape, f"{what}: the volume's shape")
+    return v
+
+
+def _check_field_np(u, shape, what):
+    u = np.asarray(u)
+    if u.dtype != np.float32 or u.shape != (3,) + tuple(shape):
+        raise ValueError(f"{what}: the field must be float32 of shape {(3,) + tuple(shape)}, got {u.dtype} {u.shape}")
+    return u
+
+
+def _check_method(method):
+    if method not in METHODS:
+        raise ValueError(f"Unknown interpolation method: {method} (linear or cubic)")
+    return method
+
+
+def _check_max_step(max_step) -> np.float32:
+    m = np.float32(max_step)
+    if not (np.isfinite(m) and m >= 0):
+        raise ValueError(f"max_step must be finite and not negative, got {max_step!r}")
+    return m
+
+
+def _coordinates_np(u):
+    """-> (p, inside): ``p_a = float64(i_a) + float64(u_a)`` and the test ``-0.5 <= p_a <= n_a - 0.5`` on all three axes (a NaN or
+    infinite displacement fails it)."""
+    shape = u.shape[1:]
+    p = []
+    inside = np.ones(shape, dtype=bool)
+    with np.errstate(invalid="ignore"):
+        for a, n in enumerate(shape):
+            i = np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)])
+            pa = i + u[a].astype(np.float64)
+            inside &= (pa >= -0.5) & (pa <= n - 0.5)
+            p.append(pa)
+    return p, inside
+
+
+def _warp_np(moving, u, method, fill):
+    p, inside = _coordinates_np(u)
+    out = np.full(moving.shape, np.float32(fill), dtype=np.float32)
+    if inside.any():
+        with np.errstate(all="ignore"):
+            (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
+            rx = []
+            for xa in ix:
+                ry = [_weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
+                rx.append(_weighted_sum_np(wy, ry))
+            out[inside] = _weighted_sum_np(wx, rx)
+    return out, inside
+
+
+def warp_np(moving, u, method: str = "linear", fill: float = 0.0) -> np.ndarray:
+    """``moving`` at ``x + u(x)``, float32.  Coordinate ``p_a = float64(i_a) + float64(u_a)``, one double addition; then
+    ``volume_reslice.reslice_np``'s rules: inside test ``-0.5 <= p_a <= n_a - 0.5`` on all axes, outside -> ``fill`` and nothing
+    is converted to an integer, ``_taps_np``, clamped taps, reduction along z, then y, then x.  A NaN or infinite displacement is
+    outside."""
+    moving = _check_volume_np(moving, "warp_np")
+    u = _check_field_np(u, moving.shape, "warp_np")
+    return _warp_np(moving, u, _check_method(method), fill)[0]
+
+
+def _gradient_axis_np(f, axis):
+    n = f.shape[axis]
+    g = np.zeros(f.shape, dtype=np.float32)
+    if n == 1:
+        return g
+    m, gm = np.moveaxis(f, axis, 0), np.moveaxis(g, axis, 0)
+    with np.errstate(all="ignore"):
+        gm[1:-1] = np.float32(0.5) * (m[2:] - m[:-2])
+        gm[0] = m[1] - m[0]
+        gm[-1] = m[-1] - m[-2]
+    return g
+
+
+def gradient_np(f) -> np.ndarray:
+    """float32 ``(3, X, Y, Z)``: along every axis ``0.5 * (f[i + 1] - f[i - 1])`` inside, the one-sided difference
+    ``f[1] - f[0]`` / ``f[n - 1] - f[n - 2]`` at the two ends, 0 along an axis of extent 1."""
+    f = _check_volume_np(f, "gradient_np")
+    return np.stack([_gradient_axis_np(f, a) for a in range(3)])
+
+
+def demons_force_np(fixed, moving, u, max_step: float = 2.0, fill: float = 0.0):
+    """-> ``(v, stats)``.  ``d = warp_np(moving, u, "linear", fill) - fixed``; ``g = gradient_np(fixed)``;
+    ``g2 = (g0 g0 + g1 g1) + g2 g2``; ``den = g2 + d d``; ``s = d / den`` where ``den > DEN_MIN``, else 0;
+    ``upd_a = -(s g_a)``, clamped to ``[-max_step, max_step]`` by comparisons, 0 where the voxel is outside the moving volume or
+    ``upd_a`` is not a number; ``v_a = u_a + upd_a``.  ``stats = (S, n)``: over the inside voxels with a finite ``d``, ``n`` their
+    count and ``S`` the sum of ``float64(d)^2`` (each square is exact), correctly rounded (``math.fsum``)."""
+    fixed = _check_volume_np(fixed, "demons_force_np")
+    moving = _check_volume_np(moving, "demons_force_np")
+    if fixed.shape != moving.shape:
+        raise ValueError(f"demons_force_np: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
+    u = _check_field_np(u, fixed.shape, "demons_force_np")
+    ms = _check_max_step(max_step)
+    warped, inside = _warp_np(moving, u, "linear", fill)
+    with np.errstate(all="ignore"):
+        d = warped - fixed
+        g = gradient_np(fixed)
+        g2 = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]
+        den = g2 + d * d
+        ok = den > DEN_MIN
+        s = np.where(ok, d / np.where(ok, den, np.float32(1)), np.float32(0)).astype(np.float32)
+        v = np.empty_like(u)
+        for a in range(3):
+            x = -(s * g[a])
+            x = np.where(x > ms, ms, np.where(x < -ms, -ms, x))
+            x = np.where(inside & ~np.isnan(x), x, np.float32(0)).astype(np.float32)
+            v[a] = u[a] + x
+    keep = inside & np.isfinite(d)
+    dd = d[keep].astype(np.float64)
+    return v, (math.fsum(dd * dd), int(keep.sum()))
+
+
+def _check_sigmas(sigmas_vox) -> list:
+    try:
+        s = [float(x) for x in sigmas_vox]
+    except (TypeError, ValueError):
+        raise ValueError(f"three sigmas in voxels are expected, got {sigmas_vox!r}") from None
+    if len(s) != 3:
+        raise ValueError(f"three sigmas in voxels are expected, got {sigmas_vox!r}")
+    taps = [gaussian_taps(x) for x in s]
+    for x, w in zip(s, taps):
+        if (w.size - 1) // 2 > MAX_RADIUS:
+            raise ValueError(f"sigma {x:g} voxels needs a radius of {(w.size - 1) // 2} taps, at most {MAX_RADIUS} are built for a field")
+    return taps
+
+
+def _pass_np(x, w, axis):
+    """One axis of a ``(3, X, Y, Z)`` field (``axis`` 0..2 of the volume): ``acc = 0``, then ``acc = acc + w[k] * x[clamp(i + k - r)]``
+    for k ascending - the border replicated."""
+    r = (w.size - 1) // 2
+    n = x.shape[axis + 1]
+    pad = [(0, 0)] * 4
+    pad[axis + 1] = (r, r)
+    xp = np.pad(x, pad, mode="edge")
+    acc = np.zeros(x.shape, dtype=np.float32)
+    index = [slice(None)] * 4
+    with np.errstate(all="ignore"):
+        for k in range(w.size):
+            index[axis + 1] = slice(k, k + n)
+            acc = acc + w[k] * xp[tuple(index)]
+    return acc
+
+
+def smooth_field_np(v, sigmas_vox) -> np.ndarray:
+    """A separable Gaussian of each component of the field ``v`` over axis 2, then 1, then 0 of the volume: taps
+    ``volume_bias.gaussian_taps``, added in ascending order to a sum that starts at 0, every product and sum float32; the border is
+    replicated (``np.pad(mode="edge")``).  ``ValueError`` for a radius past 16 taps."""
+    v = np.asarray(v)
+    if v.dtype != np.float32 or v.ndim != 4 or v.shape[0] != 3 or v.size == 0:
+        raise ValueError(f"smooth_field_np: expected a non-empty float32 field (3,X,Y,Z), got {v.dtype} {v.shape}")
+    taps = _check_sigmas(sigmas_vox)
+    for axis in (2, 1, 0):
+        v = _pass_np(v, taps[axis], axis)
+    return v
+
+
+def jacobian_stats_np(u):
+    """-> ``(min det, count of det <= 0)`` of ``J = I + grad u``: ``J[a][b] = gradient_np(u_a)[b]``, ``J[a][a] = 1 + J[a][a]``,
+    ``det = (J00 (J11 J22 - J12 J21) - J01 (J10 J22 - J12 J20)) + J02 (J10 J21 - J11 J20)`` - the expansion along the first row, every
+    operation float32.  A determinant that is not a number enters neither; the minimum of none is +inf; ``-0.0`` is returned as 0."""
+    u = np.asarray(u)
+    if u.dtype != np.float32 or u.ndim != 4 or u.shape[0] != 3 or u.size == 0:
+        raise ValueError(f"jacobian_stats_np: expected a non-empty float32 field (3,X,Y,Z), got {u.dtype} {u.shape}")
+    with np.errstate(all="ignore"):
+        J = [list(gradient_np(u[a])) for a in range(3)]
+        for a in range(3):
+            J[a][a] = np.float32(1) + J[a][a]
+        c0 = J[1][1] * J[2][2] - J[1][2] * J[2][1]
+        c1 = J[1][0] * J[2][2] - J[1][2] * J[2][0]
+        c2 = J[1][0] * J[2][1] - J[1][1] * J[2][0]
+        det = (J[0][0] * c0 - J[0][1] * c1) + J[0][2] * c2
+        m = np.where(np.isnan(det), np.float32(np.inf), det).min() + np.float32(0)
+        return float(m), int((det <= 0).sum())
+
+
+def pyramid_shapes(shape, levels: int) -> list:
+    """The shapes of the levels, coarse to fine: ``shape`` is halved while every extent is even and at least 16, at most
+    ``levels - 1`` times."""
+    shape = _check_shape(shape, "shape")
+    if not isinstance(levels, (int, np.integer)) or isinstance(levels, bool) or levels < 1:
+        raise ValueError(f"levels is a positive integer, got {levels!r}")
+    shapes = [shape]
+    while len(shapes) < levels and all(d % 2 == 0 and d >= MIN_EXTENT for d in shapes[0]):
+        shapes.insert(0, tuple(d // 2 for d in shapes[0]))
+    return shapes
+
+
+def _schedule(shape, levels, iterations) -> tuple:
+    """((shape, iterations), ...) coarse -> fine.  ``iterations``: one count for every level, or ``levels`` counts coarse -> fine, of
+    which a shorter pyramid uses the last (finest) ones."""
+    shapes = pyramid_shapes(shape, levels)
+    if isinstance(iterations, (int, np.integer)) and not isinstance(iterations, bool):
+        its = [int(iterations)] * len(shapes)
+    else:
+        its = [int(i) for i in iterations]
+        if len(its) != levels:
+            raise ValueError(f"iterations: one count or one per level ({levels}), coarse to fine, got {iterations!r}")
+        its = its[len(its) - len(shapes):]
+    if any(i < 0 for i in its):
+        raise ValueError(f"iterations must not be negative, got {iterations!r}")
+    return tuple(zip(shapes, its))
+
+
+def _check_pair_np(fixed, moving, what):
+    fixed, moving = _check_volume_np(fixed, what), _check_volume_np(moving, what)
+    if fixed.shape != moving.shape:
+        raise ValueError(f"{what}: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
+    return np.ascontiguousarray(fixed), np.ascontiguousarray(moving)
+
+
+def register_deformable_np(fixed, moving, levels: int = 3, iterations=DEFAULT_ITERATIONS, sigma_vox: float = 1.5, max_step: float = 2.0,
+                           fill: float = 0.0, method: str = "linear") -> DeformResult:
+    """The specification of ``register_deformable``.  The volumes of a level are repeated ``downsample2_np`` of the scans
+    (``pyramid_shapes``); the field starts at zero on the coarsest level; an iteration is
+    ``u = smooth_field_np(demons_force_np(fixed_l, moving_l, u, max_step, fill)[0], (sigma_vox,) * 3)`` (sigma in voxels of the level);
+    the field goes to the next level as ``upscale2_np(u_a, "linear") * 2`` per component; ``warped = warp_np(moving, field, method,
+    fill)`` once at the end.  Identical scans leave the field exactly zero."""
+    fixed, moving = _check_pair_np(fixed, moving, "register_deformable_np")
+    schedule = _schedule(fixed.shape, levels, iterations)
+    sigmas = (float(sigma_vox),) * 3
+    _check_sigmas(sigmas), _check_max_step(max_step), _check_method(method)
+    pyramid = [(fixed, moving)]
+    for _ in schedule[1:]:
+        pyramid.insert(0, tuple(downsample2_np(v) for v in pyramid[0]))
+    u = np.zeros((3,) + schedule[0][0], dtype=np.float32)
+    stats = []
+    for level, ((shape, its), (f, m)) in enumerate(zip(schedule, pyramid)):
+        if level:
+            u = np.stack([upscale2_np(np.ascontiguousarray(u[a]), "linear") * np.float32(2) for a in range(3)])
+        for _ in range(its):
+            v, row = demons_force_np(f, m, u, max_step, fill)
+            u = smooth_field_np(v, sigmas)
+            stats.append(row)
+    return DeformResult(u, warp_np(moving, u, method, fill), stats, jacobian_stats_np(u), schedule)
+
+
+# ---------------------------------------------------------------- device
+
+def _check_volume(vol, what) -> torch.Tensor:
+    vol = _check_vol(vol, what)
+    if vol.dim() != 3:
+        raise ValueError(f"{what}: a volume has three axes, got shape {tuple(vol.shape)}")
+    _check_shape(vol.shape, f"{what}: the volume's shape")
+    return vol
+
+
+def _check_field(u, shape, device, what) -> torch.Tensor:
+    u = _check_vol(u, what)
+    if tuple(u.shape) != (3,) + tuple(shape) or u.device != device:
+        raise ValueError(f"{what}: the field must have shape {(3,) + tuple(shape)} on {device}, got {tuple(u.shape)} on {u.device}")
+    return u
+
+
+def _check_out(out, like, others, what) -> torch.Tensor:
+    if out is None:
+        return torch.empty_like(like)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != like.shape or not out.is_contiguous() \
+            or out.device != like.device or any(out.data_ptr() == o.data_ptr() for o in others):
+        raise ValueError(f"{what}: out must be another contiguous float32 tensor of shape {tuple(like.shape)} on {like.device}")
+    return out
+
+
+def _slots(device) -> torch.Tensor:
+    return torch.empty(int(L.load().mrisr_f32_volume_deform_workspace_bytes()) // 8, dtype=torch.int64, device=device)
+
+
+def warp(moving: torch.Tensor, u: torch.Tensor, method: str = "linear", fill: float = 0.0, out=None) -> torch.Tensor:
+    """moving: contiguous float32 CUDA tensor (X, Y, Z); u: (3, X, Y, Z) -> ``warp_np``, bit for bit.  One launch, no device-to-host
+    read.  ``out``: another tensor like ``moving``."""
+    m = _check_volume(moving, "warp")
+    u = _check_field(u, m.shape, m.device, "warp")
+    _check_method(method)
+    out = _check_out(out, m, (m, u), "warp")
+    L.call("mrisr_f32_volume_warp", m.data_ptr(), u.data_ptr(), *m.shape, METHODS[method], float(fill), out.data_ptr(), L.stream_ptr(),
+           nbytes=20 * m.numel())
+    return out
+
+
+def _force(fixed, moving, u, max_step, fill, v, slots, stats_row):
+    L.call("mrisr_f32_volume_demons_force", fixed.data_ptr(), moving.data_ptr(), u.data_ptr(), *fixed.shape, float(max_step), float(fill),
+           v.data_ptr(), slots.data_ptr(), L.ptr(stats_row), L.stream_ptr(), nbytes=32 * fixed.numel())      # 5 floats read, 3 written
+
+
+def _smooth_pass(src, dst, shape, axis, taps, radius, slots=None, stats_row=None):
+    L.call("mrisr_f32_volume_field_smooth", src.data_ptr(), dst.data_ptr(), *shape, axis, taps.data_ptr(), radius, L.ptr(slots),
+           L.ptr(stats_row), L.stream_ptr(), nbytes=24 * int(np.prod(shape)))
+
+
+def demons_force(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, max_step: float = 2.0, fill: float = 0.0, out=None):
+    """The device path of ``demons_force_np`` -> ``(v, S, n)``: ``v`` bit for bit; ``S`` (0-d float64) within one spacing of the
+    specification's sum and the same bits on every run, ``n`` (0-d int64) equal - both stay on the device.  Two launches (the
+    force; one wave that adds the fixed slots), no device-to-host read.  ``out``: another tensor like ``u``."""
+    f, m = _check_volume(fixed, "demons_force"), _check_volume(moving, "demons_force")
+    if f.shape != m.shape or f.device != m.device:
+        raise ValueError(f"demons_force: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    u = _check_field(u, f.shape, f.device, "demons_force")
+    _check_max_step(max_step)
+    v = _check_out(out, u, (u, f, m), "demons_force")
+    row = torch.empty(2, dtype=torch.int64, device=f.device)
+    _force(f, m, u, max_step, fill, v, _slots(f.device), row)
+    return v, row[:1].view(torch.float64)[0], row[1]
+
+
+def smooth_field(v: torch.Tensor, sigmas_vox, out=None) -> torch.Tensor:
+    """v: contiguous float32 CUDA field (3, X, Y, Z) -> ``smooth_field_np``, bit for bit.  Three launches (axis 2, 1, 0), all three
+    components in each.  ``out``: another tensor like ``v``."""
+    v = _check_vol(v, "smooth_field")
+    if v.dim() != 4 or v.shape[0] != 3:
+        raise ValueError(f"smooth_field: a field is (3, X, Y, Z), got shape {tuple(v.shape)}")
+    shape = _check_shape(v.shape[1:], "smooth_field: the volume's shape")
+    taps = [torch.from_numpy(w).to(v.device) for w in _check_sigmas(sigmas_vox)]
+    out = _check_out(out, v, (v,), "smooth_field")
+    tmp = torch.empty_like(v)
+    for src, dst, axis in ((v, out, 2), (out, tmp, 1), (tmp, out, 0)):
+        _smooth_pass(src, dst, shape, axis, taps[axis], (taps[axis].numel() - 1) // 2)
+    return out
+
+
+def _jacobian(u, shape, min_det, count, slots):
+    L.call("mrisr_f32_volume_jacobian_stats", u.data_ptr(), *shape, min_det.data_ptr(), count.data_ptr(), slots.data_ptr(), L.stream_ptr())
+
+
+def jacobian_stats(u: torch.Tensor):
+    """u: contiguous float32 CUDA field (3, X, Y, Z) -> ``(min det, count of det <= 0)`` of ``jacobian_stats_np`` as a 0-d float32 and a
+    0-d int64 tensor on the device.  Two launches, no device-to-host read."""
+    u = _check_vol(u, "jacobian_stats")
+    if u.dim() != 4 or u.shape[0] != 3:
+        raise ValueError(f"jacobian_stats: a field is (3, X, Y, Z), got shape {tuple(u.shape)}")
+    shape = _check_shape(u.shape[1:], "jacobian_stats: the volume's shape")
+    min_det = torch.empty(1, dtype=torch.float32, device=u.device)
+    count = torch.empty(1, dtype=torch.int64, device=u.device)
+    _jacobian(u, shape, min_det, count, _slots(u.device))
+    return min_det[0], count[0]
+
+
+class DeformWorkspace:
+    """Everything ``register_deformable`` needs besides the two scans, for volumes of ``shape`` and this schedule: the volumes of the
+    coarser levels, the two field buffers (every level's field is a view of their beginning), the taps on the device, the fixed slots
+    of the sums and the stats buffer - one (double, int64) row per iteration and a last row for the Jacobian numbers.  Made before
+    a HIP-graph capture, it serves call after call on one stream."""
+
+    def __init__(self, shape, device, levels=3, iterations=DEFAULT_ITERATIONS, sigma_vox=1.5):
+        self.schedule = _schedule(shape, levels, iterations)
+        self.key = (tuple(self.schedule), float(sigma_vox))
+        w = _check_sigmas((float(sigma_vox),) * 3)[0]
+        self.radius = (w.size - 1) // 2
+        self.taps = torch.from_numpy(w).to(device)
+        n = int(np.prod(self.schedule[-1][0]))
+        self.fields = [torch.empty(3 * n, dtype=torch.float32, device=device) for _ in range(2)]
+        self.volumes = [tuple(torch.empty(s, dtype=torch.float32, device=device) for _ in range(2)) for s, _ in self.schedule[:-1]]
+        self.rows = sum(its for _, its in self.schedule)
+        self.stats = torch.zeros((self.rows + 1, 2), dtype=torch.int64, device=device)
+        self.slots = _slots(device)
+
+    def field(self, which, level) -> torch.Tensor:
+        shape = self.schedule[level][0]
+        return self.fields[which][:3 * int(np.prod(shape))].view(3, *shape)
+
+
+def _iterate(ws, level, fixed, moving, iterations, row, max_step, fill):
+    """``iterations`` iterations on one level, four launches each: the force (field 0 -> field 1), then the passes over axis 2
+    (1 -> 0; its first workgroup adds the force's slots into the stats row), 1 (0 -> 1) and 0 (1 -> 0).  Nothing is allocated."""
+    shape = ws.schedule[level][0]
+    a, b = ws.field(0, level), ws.field(1, level)
+    for it in range(iterations):
+        _force(fixed, moving, a, max_step, fill, b, ws.slots, None)
+        _smooth_pass(b, a, shape, 2, ws.taps, ws.radius, ws.slots, ws.stats[row + it])
+        _smooth_pass(a, b, shape, 1, ws.taps, ws.radius)
+        _smooth_pass(b, a, shape, 0, ws.taps, ws.radius)
+
+
+def register_deformable(fixed: torch.Tensor, moving: torch.Tensor, levels: int = 3, iterations=DEFAULT_ITERATIONS, sigma_vox: float = 1.5,
+                        max_step: float = 2.0, fill: float = 0.0, method: str = "linear", workspace=None, graph: bool = False) -> DeformResult:
+    """The device path of ``register_deformable_np``: ``field`` and ``warped`` (CUDA tensors) bit for bit, ``stats`` and ``jacobian``
+    as there (the sums within one spacing).  The pyramid is ``downsample2`` / ``upscale2``; an iteration is four launches; the one
+    device-to-host read, of the stats rows and the Jacobian numbers, is the last thing done.  ``graph``: the iteration loop of every
+    level is captured into a HIP graph and replayed (after one eager iteration as a warm-up, which loads the code objects) - the
+    same bits as the eager loop."""
+    f, m = _check_volume(fixed, "register_deformable"), _check_volume(moving, "register_deformable")
+    if f.shape != m.shape or f.device != m.device:
+        raise ValueError(f"register_deformable: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    _check_max_step(max_step), _check_method(method)
+    if workspace is None:
+        workspace = DeformWorkspace(f.shape, f.device, levels, iterations, sigma_vox)
+    ws = workspace
+    if not isinstance(ws, DeformWorkspace) or ws.key != (tuple(_schedule(f.shape, levels, iterations)), float(sigma_vox)) \
+            or ws.slots.device != f.device:
+        raise ValueError(f"register_deformable: the workspace must be a DeformWorkspace for volumes of {tuple(f.shape)}, this schedule "
+                         f"and sigma on {f.device}")
+    pyramid = [(f, m)]
+    for pair in reversed(ws.volumes):
+        for dst, src in zip(pair, pyramid[0]):
+            dst.copy_(downsample2(src))
+        pyramid.insert(0, pair)
+    ws.field(0, 0).zero_()
+    if graph and ws.rows:
+        _iterate(ws, 0, *pyramid[0], 1, 0, max_step, fill)
+        ws.field(0, 0).zero_()
+    row = 0
+    for level, ((shape, its), (fl, ml)) in enumerate(zip(ws.schedule, pyramid)):
+        if level:
+            coarse = ws.field(0, level - 1)
+            up = [upscale2(coarse[a], "linear") for a in range(3)]      # all three before the finer field overwrites the coarse one
+            for a in range(3):
+                torch.mul(up[a], 2.0, out=ws.field(0, level)[a])
+        if graph and its:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                _iterate(ws, level, fl, ml, its, row, max_step, fill)
+            g.replay()
+        else:
+            _iterate(ws, level, fl, ml, its, row, max_step, fill)
+        row += its
+    field = ws.field(0, len(ws.schedule) - 1).clone()
+    warped = warp(m, field, method, fill)
+    last = ws.stats[ws.rows]
+    _jacobian(field, f.shape, last[:1].view(torch.float32), last[1:], ws.slots)
+    host = ws.stats.cpu().numpy()                                       # the one device-to-host read
+    stats = [(float(s), int(n)) for s, n in zip(host[:ws.rows, 0].copy().view(np.float64), host[:ws.rows, 1])]
+    jacobian = (float(host[ws.rows, :1].copy().view(np.float32)[0]), int(host[ws.rows, 1]))
+    return DeformResult(field, warped, stats, jacobian, ws.schedule)

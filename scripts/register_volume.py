@@ -13,6 +13,15 @@ estimated transform (``--interp linear|cubic``, voxels outside the moving scan a
 ``utils.nifti.header_for_grid`` of the moving scan's header.  ``--save_transform`` writes the 4 x 4 fixed world -> moving world
 matrix as text (``numpy.loadtxt`` reads it back).  A 4-D file is registered on its frame 0 and the transform is applied to every
 frame.  Exit code 0 / 1 (error logged), as ``scripts/infer_volume.py``.
+
+``--nonrigid demons`` adds a deformable stage for what a rigid transform leaves between two scanners (gradient non-linearity,
+susceptibility distortion): after the rigid stage and its one reslice, a displacement field on the fixed grid is estimated against
+the fixed scan (``volume_deform.register_deformable``: ``csrc/volume_deform.hip``, Thirion's demons, ``--nonrigid_levels``,
+``--nonrigid_iterations`` coarse to fine, ``--nonrigid_sigma`` and ``--nonrigid_max_step`` in voxels) and the resliced scan is
+warped through it (``--interp``): the output is then interpolated twice.  The force is an intensity difference, so both scans should
+be on one intensity scale (``scripts/evaluate_volume.py --match_intensity`` / ``--match_bias`` do that for an evaluation).
+``--save_field`` writes the field as a 4-D float32 NIfTI of three frames (voxels of the fixed grid) under the fixed grid's header.
+The default, ``none``, leaves the script as it was.
 """
 import argparse
 import logging
@@ -27,6 +36,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd.utils.nifti import frames as frames_of, header_for_grid, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.volume_deform import DEFAULT_ITERATIONS, register_deformable, warp      # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                             # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice                      # noqa: E402
 
@@ -47,11 +57,43 @@ def describe_coarse(result):
             f"{p[1]:.4f}, {p[2]:.4f}) mm, r = ({p[3]:.4f}, {p[4]:.4f}, {p[5]:.4f}) degrees, NMI {entry['best']:.6f}")
 
 
+def describe_nonrigid(result):
+    """One line per level: the mean squared difference at its first and last iteration; then the Jacobian numbers."""
+    lines, row = [], 0
+    for shape, its in result.schedule:
+        if its:
+            (s0, n0), (s1, n1) = result.stats[row], result.stats[row + its - 1]
+            lines.append(f"level {'x'.join(map(str, shape))}: mean squared difference {s0 / max(n0, 1):.6g} -> {s1 / max(n1, 1):.6g} "
+                         f"in {its} iterations")
+        row += its
+    return lines
+
+
+def nonrigid_stage(fixed0, outs, interp, fill, levels, iterations, sigma, max_step):
+    """The field of frame 0 against the fixed scan, applied to every resliced frame -> (warped frames, DeformResult)."""
+    if isinstance(iterations, (list, tuple)) and len(iterations) == 1:
+        iterations = int(iterations[0])
+    result = register_deformable(fixed0, outs[0], levels=levels, iterations=iterations, sigma_vox=sigma, max_step=max_step, fill=fill,
+                                 method=interp)
+    for line in describe_nonrigid(result):
+        logger.info(f"Non-rigid stage, {line}")
+    min_det, folded = result.jacobian
+    logger.info(f"Non-rigid stage: minimum Jacobian determinant {min_det:.4f}, {folded} voxel(s) with a determinant that is not positive")
+    if folded:
+        logger.warning(f"The field folds at {folded} voxel(s): raise --nonrigid_sigma (now {sigma:g}) for a smoother field.")
+    return [result.warped] + [warp(o, result.field, interp, fill) for o in outs[1:]], result
+
+
 def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64, save_transform=None, fill=0.0, device="cuda",
-                  init="header", init_limit=40.0, init_step=20.0, mask="none"):
+                  init="header", init_limit=40.0, init_step=20.0, mask="none", nonrigid="none", nonrigid_levels=3,
+                  nonrigid_iterations=DEFAULT_ITERATIONS, nonrigid_sigma=1.5, nonrigid_max_step=2.0, save_field=None):
     """NIfTI files -> the moving scan on the fixed scan's grid (written and returned), and the ``RigidResult``."""
     if mask not in ("none", "otsu"):
         raise ValueError(f"--mask must be none or otsu, got {mask}")
+    if nonrigid not in ("none", "demons"):
+        raise ValueError(f"--nonrigid must be none or demons, got {nonrigid}")
+    if save_field and nonrigid == "none":
+        raise ValueError("--save_field goes with --nonrigid demons")
     fixed, fixed_header = read_nifti(fixed_path)
     moving, moving_header = read_nifti(moving_path)
     frames = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)).to(device) for f in frames_of(moving)]
@@ -65,6 +107,17 @@ def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64
     logger.info(f"Registered {moving_path} to {fixed_path}: {describe(result)}")
     outs = [reslice(f, result.matrix, shape, interp, fill) for f in frames]
     share = covered_share(moving.shape[:3], result.matrix, shape, device)
+    if nonrigid == "demons":
+        outs, deformed = nonrigid_stage(fixed0, outs, interp, fill, nonrigid_levels, nonrigid_iterations, nonrigid_sigma, nonrigid_max_step)
+        if save_field:
+            os.makedirs(os.path.dirname(os.path.abspath(save_field)), exist_ok=True)
+            field = np.ascontiguousarray(np.moveaxis(deformed.field.cpu().numpy(), 0, 3))
+            field_header = header_for_grid(fixed_header, shape, fixed_affine)
+            dim = list(field_header.get("dim"))
+            dim[0], dim[4] = 4, 3                                       # three frames: the components along the grid's axes
+            field_header.set("dim", dim)
+            write_nifti(save_field, field, field_header)
+            logger.info(f"Field {tuple(field.shape)} (voxels of the fixed grid) saved to {save_field}")
     data = outs[0].cpu().numpy() if moving.ndim == 3 else np.stack([o.cpu().numpy() for o in outs], axis=3)
     logger.info(f"{100.0 * (1.0 - float(share)):.2f} % of the output voxels fell outside the moving scan (set to {fill:g}).")
     os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
@@ -85,7 +138,8 @@ def main(args):
         device = torch.device("cuda")
         logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
         register_file(args.fixed, args.moving, args.output, args.interp, args.bins, args.save_transform, args.fill, device, args.init,
-                      args.init_limit, args.init_step, args.mask)
+                      args.init_limit, args.init_step, args.mask, args.nonrigid, args.nonrigid_levels, args.nonrigid_iterations,
+                      args.nonrigid_sigma, args.nonrigid_max_step, args.save_field)
         return 0
     except Exception as e:
         logger.error(f"Error during registration: {e}")
@@ -108,6 +162,17 @@ def parse_args(argv=None):
                    help="otsu: only the samples inside the fixed scan's Otsu foreground mask enter the cost")
     p.add_argument("--save_transform", type=str, default=None, help="write the 4 x 4 fixed world -> moving world matrix as text")
     p.add_argument("--fill", type=float, default=0.0, help="value of the output voxels whose centre lies outside the moving scan")
+    p.add_argument("--nonrigid", type=str, choices=["none", "demons"], default="none",
+                   help="demons: after the rigid stage and its reslice, estimate a displacement field against the fixed scan (Thirion's "
+                        "demons, an intensity-difference force: bring both scans onto one intensity scale first) and write the warped "
+                        "scan instead; the output is then interpolated twice")
+    p.add_argument("--nonrigid_levels", type=int, default=3, help="--nonrigid demons: levels of the pyramid (halved while every extent is even and at least 16)")
+    p.add_argument("--nonrigid_iterations", type=int, nargs="+", default=list(DEFAULT_ITERATIONS),
+                   help="--nonrigid demons: iterations per level, coarse to fine (one count per level, or one for all)")
+    p.add_argument("--nonrigid_sigma", type=float, default=1.5, help="--nonrigid demons: sigma of the field's Gaussian in voxels of a level (at most 5.33)")
+    p.add_argument("--nonrigid_max_step", type=float, default=2.0, help="--nonrigid demons: bound of one iteration's update in voxels")
+    p.add_argument("--save_field", type=str, default=None,
+                   help="--nonrigid demons: write the field as a 4-D float32 NIfTI of three frames (voxels of the fixed grid)")
     p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
     return p.parse_args(argv)
 

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Times one demons iteration (the force and the three smoothing passes, csrc/volume_deform.hip) on a volume of --size^3 at
+--sigma, against the same iteration written with torch (grid_sample, conv1d with replicated borders), and the force kernel's achieved
+bytes/s against a device-to-device copy of the same number of bytes measured in the same run.  Not run by bench.py.
+
+    python tools/deform_bench.py --size 256 --sigma 1.5 --iters 50
+
+Times are device events around --iters back-to-back iterations after --warmup; the algorithmic bytes of the force are 5 floats
+read and 3 written per voxel (fixed, moving - once, its taps come from cache - and the three components in, three out).  One JSON
+line at the end.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+from mri_superresolution_amd import volume_deform as D                       # noqa: E402
+from mri_superresolution_amd.volume_bias import gaussian_taps                # noqa: E402
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(iters):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) / iters      # ms
+
+
+def torch_iteration(fixed, moving, u, taps, max_step):
+    """The same rule with torch operators (its own roundings): grid_sample for the gather, slicing for the gradient, conv1d per axis."""
+    X, Y, Z = fixed.shape
+    idx = torch.stack(torch.meshgrid(*(torch.arange(n, device=u.device, dtype=torch.float32) for n in (X, Y, Z)), indexing="ij"))
+    p = idx + u
+    grid = torch.stack([2 * (p[2] + 0.5) / Z - 1, 2 * (p[1] + 0.5) / Y - 1, 2 * (p[0] + 0.5) / X - 1], dim=-1)[None]
+    warped = F.grid_sample(moving[None, None], grid, mode="bilinear", padding_mode="border", align_corners=False)[0, 0]
+    d = warped - fixed
+    g = torch.stack(torch.gradient(fixed))
+    den = (g * g).sum(0) + d * d
+    s = torch.where(den > 1e-9, d / den, torch.zeros_like(d))
+    v = u + (-(s * g)).clamp(-max_step, max_step)
+    r = (taps.numel() - 1) // 2
+    for axis in (3, 2, 1):
+        x = v.movedim(axis, -1).reshape(-1, 1, v.shape[axis])
+        x = F.conv1d(F.pad(x, (r, r), mode="replicate"), taps.view(1, 1, -1))
+        v = x.reshape(*v.movedim(axis, -1).shape).movedim(-1, axis)
+    return v
+
+
+def main(args):
+    if not torch.cuda.is_available():
+        raise SystemExit("this tool measures on an MI355X: no GPU found")
+    n = args.size
+    rng = np.random.default_rng(0)
+    x = np.linspace(-1, 1, n, dtype=np.float32)
+    base = 600 * np.exp(-2 * (x[:, None, None] ** 2 + x[None, :, None] ** 2 + x[None, None, :] ** 2)).astype(np.float32)
+    fixed = torch.from_numpy(base + rng.normal(0, 5, base.shape).astype(np.float32)).cuda()
+    moving = torch.roll(fixed, (1, -1, 1), (0, 1, 2)).contiguous()
+    u = torch.from_numpy(rng.uniform(-1.5, 1.5, (3, n, n, n)).astype(np.float32)).cuda()
+    ws = D.DeformWorkspace(fixed.shape, fixed.device, levels=1, iterations=1, sigma_vox=args.sigma)
+    a, b = ws.field(0, 0), ws.field(1, 0)
+
+    def iteration():
+        if args.reset_field:
+            a.copy_(u)
+        D._iterate(ws, 0, fixed, moving, 1, 0, 2.0, 0.0)
+
+    def force_only():
+        D._force(fixed, moving, a, 2.0, 0.0, b, ws.slots, None)
+
+    a.copy_(u)
+    nbytes = 32 * fixed.numel()
+    src, dst = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda"), torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
+    t_iter = timed(iteration, args.iters, args.warmup)
+    a.copy_(u)
+    t_force = timed(force_only, args.iters, args.warmup)
+    t_copy = timed(lambda: dst.copy_(src), args.iters, args.warmup)      # nbytes / 2 read and nbytes / 2 written
+    taps = torch.from_numpy(gaussian_taps(args.sigma)).cuda()
+    with torch.no_grad():
+        t_torch = timed(lambda: torch_iteration(fixed, moving, u, taps, 2.0), max(args.iters // 5, 2), 2)
+    result = {"size": n, "sigma": args.sigma, "iteration_ms": round(t_iter, 4), "force_ms": round(t_force, 4),
+              "torch_iteration_ms": round(t_torch, 4), "speedup_over_torch": round(t_torch / t_iter, 2),
+              "force_GBps": round(nbytes / t_force / 1e6, 1), "copy_same_bytes_ms": round(t_copy, 4),
+              "copy_GBps": round(nbytes / t_copy / 1e6, 1), "force_share_of_copy_rate": round(t_copy / t_force, 3)}
+    print(json.dumps(result))
+    return 0
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Time one demons iteration against torch and the force kernel against a device copy")
+    p.add_argument("--size", type=int, default=256)
+    p.add_argument("--sigma", type=float, default=1.5)
+    p.add_argument("--iters", type=int, default=50)
+    p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--reset_field", action="store_true", help="copy the random field back in before every iteration (adds a copy to the time)")
+    return p.parse_args(argv)
+
+
+if __name__ == "__main__":
+    sys.exit(main(parse_args()))
