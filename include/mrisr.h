@@ -806,6 +806,28 @@ int mrisr_f32_volume_field_smooth(const float* in, float* out, int X, int Y, int
  * of workspace.  MRISR_E_ARG: null or misaligned pointer; MRISR_E_SHAPE as above.                                                  */
 int mrisr_f32_volume_jacobian_stats(const float* u, int X, int Y, int Z, float* min_det, long long* count, void* workspace,
                                     void* stream);
+/* Diffeomorphic demons: the update is scaled, turned into a small diffeomorphism by repeated squaring and composed with the field.
+ * out = v + (u at x + v(x)), all DEVICE float32 (3, X, Y, Z); bit for bit volume_deform.compose_np: p_a = (double)i_a + (double)v_a,
+ * clamped into [0, n_a - 1] by comparisons (a field continues constantly past the faces; an infinite displacement lands on a face),
+ * the linear taps and the reduction of mrisr_f32_volume_reslice once per voxel for all three components of u, then one float32 add.
+ * A voxel with a displacement in v that is not a number gets NaN in all three components; nothing of it is converted to an integer.
+ * warp(warp(m, u), v) samples m at x + out(x), up to interpolation.  One launch.  u and v may be one buffer (squaring).
+ * MRISR_E_ARG: null or misaligned pointer, out == u or v; MRISR_E_SHAPE: an extent below 1, more than 2^31 - 1 voxels.            */
+int mrisr_f32_volume_field_compose(const float* u, const float* v, int X, int Y, int Z, float* out, void* stream);
+/* w = upd * scale, one rounded float32 product (scale = 2^-K: exact), upd the update of mrisr_f32_volume_demons_force, which this
+ * entry shares its kernel, its workspace slots and its stats_row with; bit for bit volume_deform.demons_update_np.
+ * MRISR_E_ARG: as there, and scale not finite and positive; MRISR_E_SHAPE as there.                                                */
+int mrisr_f32_volume_demons_update(const float* fixed, const float* moving, const float* u, int X, int Y, int Z, float max_step,
+                                   float fill, float scale, float* w, void* workspace, void* stats_row, void* stream);
+/* out (X, Y, Z) = moving (SX, SY, SZ) at M (x + u(x)): ONE interpolation through a field on the fixed grid and the 3 x 4 matrix
+ * m12 (HOST, row-major doubles, fixed index -> moving index: the matrix of mrisr_f32_volume_reslice).  q_a = (double)i_a +
+ * (double)u_a; p_a = ((m[a][0] q_0 + m[a][1] q_1) + m[a][2] q_2) + m[a][3]; then the inside test on moving's extents, the taps and
+ * the reduction of mrisr_f32_volume_reslice, MRISR_RESAMPLE_LINEAR or _CUBIC; bit for bit volume_deform.warp_matrix_np (that is
+ * mrisr_f32_volume_reslice for a zero field and mrisr_f32_volume_warp for the identity matrix).  One launch, the matrix by value.
+ * MRISR_E_ARG: null or misaligned pointer, unknown method, a matrix entry that is not finite, out == moving or u;
+ * MRISR_E_SHAPE: an extent below 1 or more than 2^31 - 1 voxels on either grid.                                                    */
+int mrisr_f32_volume_warp_matrix(const float* moving, int SX, int SY, int SZ, const float* u, int X, int Y, int Z, const double* m12,
+                                 int method, float fill, float* out, void* stream);
 
 #ifdef __cplusplus
 }

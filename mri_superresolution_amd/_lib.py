@@ -190,10 +190,13 @@ SIGNATURES = {
     "mrisr_f32_volume_demons_force": (_i, [_fp, _fp, _fp, _i, _i, _i, _f, _f, _fp, _vp, _vp, _vp]),
     "mrisr_f32_volume_field_smooth": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _i, _vp, _vp, _vp]),
     "mrisr_f32_volume_jacobian_stats": (_i, [_fp, _i, _i, _i, _fp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_field_compose": (_i, [_fp, _fp, _i, _i, _i, _fp, _vp]),
+    "mrisr_f32_volume_demons_update": (_i, [_fp, _fp, _fp, _i, _i, _i, _f, _f, _f, _fp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_warp_matrix": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, _f, _fp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 321      # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 322     # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -1,7 +1,8 @@
 // Deformable registration of volumes on the device (gfx950; extension): Thirion's demons with an additive
-// update and a Gaussian regularisation of the field.  The specification is volume_deform.warp_np / demons_force_np /
-// smooth_field_np / jacobian_stats_np; every kernel here is bit-equal to it.  Compiled with -ffp-contract=off (build.py): every
-// product, sum, difference and division is rounded on its own, never an fma.
+// update and a Gaussian regularisation of the field, and its diffeomorphic variant.  The specification is volume_deform.warp_np /
+// demons_force_np / smooth_field_np / jacobian_stats_np / compose_np / demons_update_np / warp_matrix_np; every kernel here is
+// bit-equal to it.  Compiled with -ffp-contract=off (build.py): every product, sum, difference and division is rounded on its own,
+// never an fma.
 //
 // A volume is (X, Y, Z) in C order, Z fastest; a field u is (3, X, Y, Z) float32 in voxels: fixed(x) is compared with
 // moving(x + u(x)).  The coordinate of a voxel is p_a = (double)i_a + (double)u_a, the inside test, the taps and the reduction
@@ -19,6 +20,14 @@
 //                              the smoothing pass that follows, or a launch of one wave when the caller wants the row at once -
 //                              so nothing is handed between workgroups inside a launch and there is no floating-point atomic:
 //                              the same bits on every run.
+//   f32_volume_demons_update   the same kernel under a template flag, writing w = upd * scale (scale = 2^-K) instead of u + upd: the
+//                              update of the diffeomorphic variant, which is squared K times and composed with the field.
+//   f32_volume_field_compose   out = v + (u at x + v(x)), compose_np: one thread per voxel on the warp kernel's bricks; the three
+//                              coordinates - clamped into the grid by comparisons, a field continues constantly past its faces -
+//                              and the eight taps once per voxel for all three components: 3 coalesced loads of v, 24 gathered
+//                              loads of u, 3 stores.  u and v may be one buffer (squaring).
+//   f32_volume_warp_matrix     moving at M (x + u(x)), warp_matrix_np: the warp kernel with the 3 x 4 matrix of the reslice by value
+//                              between the field and the inside test - one interpolation instead of a reslice and a warp.
 //   f32_volume_field_smooth    one pass along one axis, all three components (they are the slowest axis of the field: the z and y
 //                              passes see a volume of 3 X slabs, the x pass three slabs with columns of Y Z).  A workgroup stages
 //                              its tile plus the halo in LDS once, the index of a staged element clamped into the axis (the border
@@ -92,14 +101,10 @@ __device__ __forceinline__ bool field_coordinate(const float* __restrict__ u, si
     return inside;
 }
 
-template <int METHOD>
-__device__ __forceinline__ float gather(const float* __restrict__ src, int X, int Y, int Z, const double* p) {
-    constexpr int N = METHOD == kLinear ? 2 : 4;
-    int ix[N], iy[N], iz[N];
-    float wx[N], wy[N], wz[N];
-    axis_taps<METHOD>(p[0], X, ix, wx);
-    axis_taps<METHOD>(p[1], Y, iy, wy);
-    axis_taps<METHOD>(p[2], Z, iz, wz);
+// the taps of the three axes reduced along z, then y, then x
+template <int N>
+__device__ __forceinline__ float gather_at(const float* __restrict__ src, int Y, int Z, const int* ix, const int* iy, const int* iz,
+                                           const float* wx, const float* wy, const float* wz) {
     float rx[N];
 #pragma unroll
     for (int a = 0; a < N; ++a) {
@@ -115,6 +120,17 @@ __device__ __forceinline__ float gather(const float* __restrict__ src, int X, in
         rx[a] = weighted_sum<N>(wy, ry);
     }
     return weighted_sum<N>(wx, rx);
+}
+
+template <int METHOD>
+__device__ __forceinline__ float gather(const float* __restrict__ src, int X, int Y, int Z, const double* p) {
+    constexpr int N = METHOD == kLinear ? 2 : 4;
+    int ix[N], iy[N], iz[N];
+    float wx[N], wy[N], wz[N];
+    axis_taps<METHOD>(p[0], X, ix, wx);
+    axis_taps<METHOD>(p[1], Y, iy, wy);
+    axis_taps<METHOD>(p[2], Z, iz, wz);
+    return gather_at<N>(src, Y, Z, ix, iy, iz, wx, wy, wz);
 }
 
 // gradient_np along one axis: i the index on it, n its extent, stride its distance in elements
@@ -137,10 +153,69 @@ __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ mov
     out[idx] = inside ? gather<METHOD>(moving, X, Y, Z, p) : fill;
 }
 
-__global__ __launch_bounds__(256) void demons_force_kernel(const float* __restrict__ fixed, const float* __restrict__ moving,
-                                                           const float* __restrict__ u, int X, int Y, int Z, float max_step, float fill,
-                                                           float* __restrict__ v, unsigned nbricks, unsigned nby, unsigned nbz,
-                                                           DeformSlot* __restrict__ slots) {
+struct Matrix34 {
+    double m[3][4];
+};
+
+// moving (SX, SY, SZ) at M (x + u(x)): the coordinate under the field, then grid_coordinate's order, then the inside test of the source
+template <int METHOD>
+__global__ __launch_bounds__(256) void warp_matrix_kernel(const float* __restrict__ moving, int SX, int SY, int SZ,
+                                                          const float* __restrict__ u, int X, int Y, int Z, Matrix34 g, float fill,
+                                                          float* __restrict__ out, unsigned nby, unsigned nbz) {
+    int i, j, k;
+    if (!brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k)) return;
+    const size_t n = (size_t)X * Y * Z, idx = ((size_t)i * Y + j) * Z + k;
+    const int at[3] = {i, j, k}, ext[3] = {SX, SY, SZ};
+    double q[3], p[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q[a] = __dadd_rn((double)at[a], (double)u[a * n + idx]);
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        p[a] = grid_coordinate(g.m[a], q[0], q[1], q[2]);
+        inside = inside && p[a] >= -0.5 && p[a] <= (double)ext[a] - 0.5;      // NaN compares false
+    }
+    out[idx] = inside ? gather<METHOD>(moving, SX, SY, SZ, p) : fill;
+}
+
+// out = v + (u at x + v(x)): the three coordinates, clamped into the grid by comparisons (the field continues constantly past the
+// faces), and the eight taps are computed once and serve all three components; a coordinate that is not a number makes all three NaN
+__global__ __launch_bounds__(256) void compose_kernel(const float* __restrict__ u, const float* __restrict__ v, int X, int Y, int Z,
+                                                      float* __restrict__ out, unsigned nby, unsigned nbz) {
+    int i, j, k;
+    if (!brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k)) return;
+    const size_t n = (size_t)X * Y * Z, idx = ((size_t)i * Y + j) * Z + k;
+    const int at[3] = {i, j, k}, ext[3] = {X, Y, Z};
+    float va[3];
+    double p[3];
+    bool number = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        va[a] = v[a * n + idx];
+        const double q = __dadd_rn((double)at[a], (double)va[a]), last = (double)(ext[a] - 1);
+        p[a] = q < 0.0 ? 0.0 : (q > last ? last : q);      // NaN fails both and stays
+        number = number && p[a] == p[a];
+    }
+    if (!number) {                                           // nothing of it is converted to an integer
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[a * n + idx] = __uint_as_float(0x7fc00000u);
+        return;
+    }
+    int ix[2], iy[2], iz[2];
+    float wx[2], wy[2], wz[2];
+    axis_taps<kLinear>(p[0], X, ix, wx);
+    axis_taps<kLinear>(p[1], Y, iy, wy);
+    axis_taps<kLinear>(p[2], Z, iz, wz);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[a * n + idx] = __fadd_rn(va[a], gather_at<2>(u + a * n, Y, Z, ix, iy, iz, wx, wy, wz));
+}
+
+// UPDATE: w = upd * scale (mrisr_f32_volume_demons_update); else v = u + upd (mrisr_f32_volume_demons_force, scale unused)
+template <bool UPDATE>
+__global__ __launch_bounds__(256) void demons_kernel(const float* __restrict__ fixed, const float* __restrict__ moving,
+                                                     const float* __restrict__ u, int X, int Y, int Z, float max_step, float fill,
+                                                     float scale, float* __restrict__ v, unsigned nbricks, unsigned nby, unsigned nbz,
+                                                     DeformSlot* __restrict__ slots) {
     __shared__ DeformSlot part[4];
     const size_t n = (size_t)X * Y * Z;
     PairSum acc = {0.0, 0.0, 0};
@@ -167,7 +242,7 @@ __global__ __launch_bounds__(256) void demons_force_kernel(const float* __restri
             if (isfinite(d)) acc.add((double)d * (double)d, 0.0, 1);      // the square of a float is exact in double
         }
 #pragma unroll
-        for (int a = 0; a < 3; ++a) v[a * n + idx] = __fadd_rn(ua[a], upd[a]);
+        for (int a = 0; a < 3; ++a) v[a * n + idx] = UPDATE ? __fmul_rn(upd[a], scale) : __fadd_rn(ua[a], upd[a]);
     }
     acc.wave_reduce();
     const int wave = threadIdx.x >> 6;
@@ -366,25 +441,70 @@ extern "C" int mrisr_f32_volume_warp(const float* moving, const float* u, int X,
     return MRISR_OK;
 }
 
-extern "C" int mrisr_f32_volume_demons_force(const float* fixed, const float* moving, const float* u, int X, int Y, int Z, float max_step,
-                                             float fill, float* v, void* workspace, void* stats_row, void* stream) {
-    if (!fixed || !moving || !u || !v || !workspace) MRISR_FAIL(MRISR_E_ARG, "f32_volume_demons_force: null pointer");
-    if (!(max_step >= 0.f) || !isfinite(max_step))
-        MRISR_FAIL(MRISR_E_ARG, "f32_volume_demons_force: max_step %g (finite, not negative)", (double)max_step);
+// the force and the update-only force: one set of checks, one kernel
+template <bool UPDATE>
+static int launch_demons(const char* name, const float* fixed, const float* moving, const float* u, int X, int Y, int Z, float max_step,
+                         float fill, float scale, float* v, void* workspace, void* stats_row, void* stream) {
+    if (!fixed || !moving || !u || !v || !workspace) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (!(max_step >= 0.f) || !isfinite(max_step)) MRISR_FAIL(MRISR_E_ARG, "%s: max_step %g (finite, not negative)", name, (double)max_step);
+    if (!(scale > 0.f) || !isfinite(scale)) MRISR_FAIL(MRISR_E_ARG, "%s: scale %g (finite, positive)", name, (double)scale);
     BrickGrid g;
-    if (const int rc = check_field_volume("f32_volume_demons_force", X, Y, Z, &g)) return rc;
+    if (const int rc = check_field_volume(name, X, Y, Z, &g)) return rc;
     if (!aligned_to(fixed, 4) || !aligned_to(moving, 4) || !aligned_to(u, 4) || !aligned_to(v, 4) || !aligned_to(workspace, 8) ||
         !aligned_to(stats_row, 8))
-        MRISR_FAIL(MRISR_E_ARG, "f32_volume_demons_force: misaligned pointer");
-    if (v == u || v == fixed || v == moving) MRISR_FAIL(MRISR_E_ARG, "f32_volume_demons_force: v must be a buffer of its own");
+        MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer", name);
+    if (v == u || v == fixed || v == moving) MRISR_FAIL(MRISR_E_ARG, "%s: %s must be a buffer of its own", name, UPDATE ? "w" : "v");
     hipStream_t s = (hipStream_t)stream;
     DeformSlot* slots = (DeformSlot*)workspace;
-    demons_force_kernel<<<g.nslots, 256, 0, s>>>(fixed, moving, u, X, Y, Z, max_step, fill, v, g.nbricks, g.nby, g.nbz, slots);
-    MRISR_CHECK_LAUNCH("f32_volume_demons_force");
+    demons_kernel<UPDATE><<<g.nslots, 256, 0, s>>>(fixed, moving, u, X, Y, Z, max_step, fill, scale, v, g.nbricks, g.nby, g.nbz, slots);
+    MRISR_CHECK_LAUNCH(name);
     if (stats_row) {
         force_stats_kernel<<<1, 64, 0, s>>>(slots, g.nslots, (StatsRow*)stats_row);
-        MRISR_CHECK_LAUNCH("f32_volume_demons_force (stats)");
+        MRISR_CHECK_LAUNCH(name);
     }
+    return MRISR_OK;
+}
+
+extern "C" int mrisr_f32_volume_demons_force(const float* fixed, const float* moving, const float* u, int X, int Y, int Z, float max_step,
+                                             float fill, float* v, void* workspace, void* stats_row, void* stream) {
+    return launch_demons<false>("f32_volume_demons_force", fixed, moving, u, X, Y, Z, max_step, fill, 1.f, v, workspace, stats_row, stream);
+}
+
+extern "C" int mrisr_f32_volume_demons_update(const float* fixed, const float* moving, const float* u, int X, int Y, int Z, float max_step,
+                                              float fill, float scale, float* w, void* workspace, void* stats_row, void* stream) {
+    return launch_demons<true>("f32_volume_demons_update", fixed, moving, u, X, Y, Z, max_step, fill, scale, w, workspace, stats_row, stream);
+}
+
+extern "C" int mrisr_f32_volume_field_compose(const float* u, const float* v, int X, int Y, int Z, float* out, void* stream) {
+    if (!u || !v || !out) MRISR_FAIL(MRISR_E_ARG, "f32_volume_field_compose: null pointer");
+    BrickGrid g;
+    if (const int rc = check_field_volume("f32_volume_field_compose", X, Y, Z, &g)) return rc;
+    if (!aligned_to(u, 4) || !aligned_to(v, 4) || !aligned_to(out, 4)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_field_compose: misaligned pointer");
+    if (out == u || out == v) MRISR_FAIL(MRISR_E_ARG, "f32_volume_field_compose: out must be a buffer of its own (u and v may be one)");
+    compose_kernel<<<g.nbricks, 256, 0, (hipStream_t)stream>>>(u, v, X, Y, Z, out, g.nby, g.nbz);
+    MRISR_CHECK_LAUNCH("f32_volume_field_compose");
+    return MRISR_OK;
+}
+
+extern "C" int mrisr_f32_volume_warp_matrix(const float* moving, int SX, int SY, int SZ, const float* u, int X, int Y, int Z,
+                                            const double* m12, int method, float fill, float* out, void* stream) {
+    if (!moving || !u || !m12 || !out) MRISR_FAIL(MRISR_E_ARG, "f32_volume_warp_matrix: null pointer");
+    if (method != kLinear && method != kCubic)
+        MRISR_FAIL(MRISR_E_ARG, "f32_volume_warp_matrix: method %d (MRISR_RESAMPLE_LINEAR or _CUBIC)", method);
+    Matrix34 m;
+    for (int e = 0; e < 12; ++e) {
+        if (!isfinite(m12[e])) MRISR_FAIL(MRISR_E_ARG, "f32_volume_warp_matrix: matrix entry [%d][%d] is not finite", e / 4, e % 4);
+        m.m[e / 4][e % 4] = m12[e];
+    }
+    BrickGrid source, g;
+    if (const int rc = check_field_volume("f32_volume_warp_matrix (moving)", SX, SY, SZ, &source)) return rc;
+    if (const int rc = check_field_volume("f32_volume_warp_matrix", X, Y, Z, &g)) return rc;
+    if (!aligned_to(moving, 4) || !aligned_to(u, 4) || !aligned_to(out, 4)) MRISR_FAIL(MRISR_E_ARG, "f32_volume_warp_matrix: misaligned pointer");
+    if (out == moving || out == u) MRISR_FAIL(MRISR_E_ARG, "f32_volume_warp_matrix: out must be a buffer of its own");
+    hipStream_t s = (hipStream_t)stream;
+    if (method == kLinear) warp_matrix_kernel<kLinear><<<g.nbricks, 256, 0, s>>>(moving, SX, SY, SZ, u, X, Y, Z, m, fill, out, g.nby, g.nbz);
+    else warp_matrix_kernel<kCubic><<<g.nbricks, 256, 0, s>>>(moving, SX, SY, SZ, u, X, Y, Z, m, fill, out, g.nby, g.nbz);
+    MRISR_CHECK_LAUNCH("f32_volume_warp_matrix");
     return MRISR_OK;
 }
 

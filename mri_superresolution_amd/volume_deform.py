@@ -8,15 +8,21 @@ A field ``u`` is float32 ``(3, X, Y, Z)`` in voxels of the common grid: ``fixed(
 ``warp_np``, ``gradient_np``, ``demons_force_np``, ``smooth_field_np``, ``jacobian_stats_np``, ``register_deformable_np``   the
                       specification: float32, every product, sum, difference and division rounded on its own (no fma), the orders
                       written in the docstrings.
+``compose_np``, ``demons_update_np``, ``exp_field_np``, ``register_diffeomorphic_np``   the specification of the diffeomorphic
+                      variant (Vercauteren): the update is scaled by ``2^-K``, squared ``K`` times into a small diffeomorphism
+                      (``compose_np(w, w)``) and COMPOSED with the field, ``u = smooth(compose(u, exp(upd)))``, not added - an additive
+                      field may fold, a composition of diffeomorphisms does not (up to the smoothing and the interpolation).
+``warp_matrix_np``    one interpolation through a grid matrix and a field: ``moving`` at ``M (x + u(x))``.
 ``pyramid_shapes``    the shapes of the levels, coarse to fine.
 ``warp``, ``demons_force``, ``smooth_field``, ``jacobian_stats``, ``register_deformable``   the device path
                       (``csrc/volume_deform.hip``), equal to the specification bit for bit (the float64 sum of squared
                       differences: within one spacing, the same bits on every run).  There is no CPU path: CPU tensors raise.
                       ``register_deformable`` reads the device once, at its end; its iteration loop - four launches per
                       iteration - is HIP-graph capturable with a ``DeformWorkspace`` made before the capture.
+``compose``, ``demons_update``, ``exp_field``, ``warp_matrix``, ``register_diffeomorphic``   the device path of the second group, under
+                      the same rules; an iteration of ``register_diffeomorphic`` is ``5 + exp_steps`` launches (``DiffeoWorkspace``).
 
-Not built: diffeomorphic / log-domain demons, composing the field with the rigid matrix into one interpolation, masks in the
-force, a mutual-information force, affine.
+Not built: log-domain demons with a stored velocity, an inverse field, masks in the force, a mutual-information force, affine.
 """
 from __future__ import annotations
 
@@ -30,7 +36,7 @@ from . import _lib as L
 from .volume_bias import gaussian_taps
 from .volume_eval import downsample2, downsample2_np, upscale2, upscale2_np
 from .volume_intensity import _check_vol
-from .volume_reslice import _check_shape, _taps_np, _weighted_sum_np
+from .volume_reslice import _check_matrix, _check_shape, _matrix_arg, _taps_np, _weighted_sum_np
 
 MAX_RADIUS = 16
 DEN_MIN = np.float32(1e-9)                 # MRISR_DEFORM_DEN_MIN: below it a voxel has neither a gradient nor a difference
@@ -136,17 +142,14 @@ def gradient_np(f) -> np.ndarray:
     return np.stack([_gradient_axis_np(f, a) for a in range(3)])
 
 
-def demons_force_np(fixed, moving, u, max_step: float = 2.0, fill: float = 0.0):
-    """-> ``(v, stats)``.  ``d = warp_np(moving, u, "linear", fill) - fixed``; ``g = gradient_np(fixed)``;
-    ``g2 = (g0 g0 + g1 g1) + g2 g2``; ``den = g2 + d d``; ``s = d / den`` where ``den > DEN_MIN``, else 0;
-    ``upd_a = -(s g_a)``, clamped to ``[-max_step, max_step]`` by comparisons, 0 where the voxel is outside the moving volume or
-    ``upd_a`` is not a number; ``v_a = u_a + upd_a``.  ``stats = (S, n)``: over the inside voxels with a finite ``d``, ``n`` their
-    count and ``S`` the sum of ``float64(d)^2`` (each square is exact), correctly rounded (``math.fsum``)."""
-    fixed = _check_volume_np(fixed, "demons_force_np")
-    moving = _check_volume_np(moving, "demons_force_np")
+def _demons_update_np(fixed, moving, u, max_step, fill, what):
+    """-> ``(u, upd, stats)``: the checked field, the three cleaned update components and the (sum of d^2, count) row, as
+    ``demons_force_np`` states them."""
+    fixed = _check_volume_np(fixed, what)
+    moving = _check_volume_np(moving, what)
     if fixed.shape != moving.shape:
-        raise ValueError(f"demons_force_np: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
-    u = _check_field_np(u, fixed.shape, "demons_force_np")
+        raise ValueError(f"{what}: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
+    u = _check_field_np(u, fixed.shape, what)
     ms = _check_max_step(max_step)
     warped, inside = _warp_np(moving, u, "linear", fill)
     with np.errstate(all="ignore"):
@@ -156,15 +159,139 @@ def demons_force_np(fixed, moving, u, max_step: float = 2.0, fill: float = 0.0):
         den = g2 + d * d
         ok = den > DEN_MIN
         s = np.where(ok, d / np.where(ok, den, np.float32(1)), np.float32(0)).astype(np.float32)
-        v = np.empty_like(u)
+        upd = []
         for a in range(3):
             x = -(s * g[a])
             x = np.where(x > ms, ms, np.where(x < -ms, -ms, x))
-            x = np.where(inside & ~np.isnan(x), x, np.float32(0)).astype(np.float32)
-            v[a] = u[a] + x
+            upd.append(np.where(inside & ~np.isnan(x), x, np.float32(0)).astype(np.float32))
     keep = inside & np.isfinite(d)
     dd = d[keep].astype(np.float64)
-    return v, (math.fsum(dd * dd), int(keep.sum()))
+    return u, upd, (math.fsum(dd * dd), int(keep.sum()))
+
+
+def demons_force_np(fixed, moving, u, max_step: float = 2.0, fill: float = 0.0):
+    """-> ``(v, stats)``.  ``d = warp_np(moving, u, "linear", fill) - fixed``; ``g = gradient_np(fixed)``;
+    ``g2 = (g0 g0 + g1 g1) + g2 g2``; ``den = g2 + d d``; ``s = d / den`` where ``den > DEN_MIN``, else 0;
+    ``upd_a = -(s g_a)``, clamped to ``[-max_step, max_step]`` by comparisons, 0 where the voxel is outside the moving volume or
+    ``upd_a`` is not a number; ``v_a = u_a + upd_a``.  ``stats = (S, n)``: over the inside voxels with a finite ``d``, ``n`` their
+    count and ``S`` the sum of ``float64(d)^2`` (each square is exact), correctly rounded (``math.fsum``)."""
+    u, upd, stats = _demons_update_np(fixed, moving, u, max_step, fill, "demons_force_np")
+    v = np.empty_like(u)
+    with np.errstate(all="ignore"):
+        for a in range(3):
+            v[a] = u[a] + upd[a]
+    return v, stats
+
+
+def _check_scale(scale) -> np.float32:
+    s = np.float32(scale)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f"scale must be finite and positive, got {scale!r}")
+    return s
+
+
+def demons_update_np(fixed, moving, u, max_step: float = 2.0, fill: float = 0.0, scale: float = 1.0):
+    """-> ``(w, stats)``: ``upd_a`` and ``stats`` exactly as in ``demons_force_np`` (same operations, same order), then
+    ``w_a = upd_a * float32(scale)``, one rounded float32 product - exact for the ``2^-K`` the exponential passes - instead of
+    ``u_a + upd_a``.  The field ``u`` only says where ``moving`` is read."""
+    sc = _check_scale(scale)
+    u, upd, stats = _demons_update_np(fixed, moving, u, max_step, fill, "demons_update_np")
+    with np.errstate(all="ignore"):
+        return np.stack([x * sc for x in upd]), stats
+
+
+def _check_field4_np(u, what):
+    u = np.asarray(u)
+    if u.dtype != np.float32 or u.ndim != 4 or u.shape[0] != 3 or u.size == 0:
+        raise ValueError(f"{what}: expected a non-empty float32 field (3,X,Y,Z), got {u.dtype} {u.shape}")
+    _check_shape(u.shape[1:], f"{what}: the volume's shape")
+    return u
+
+
+def compose_np(u, v) -> np.ndarray:
+    """``v_a + U_a``, float32 ``(3, X, Y, Z)``: ``U_a`` is ``u_a`` interpolated linearly at ``p = float64(i) + float64(v)`` (the coordinate
+    of ``warp_np``), so that ``warp(warp(m, u), v)`` samples ``m`` at ``x + compose_np(u, v)(x)``, up to interpolation.  Each ``p_a``
+    is clamped into ``[0, n_a - 1]`` by comparisons, ``p < 0 -> 0``, ``p > n_a - 1 -> n_a - 1``: a displacement field continues
+    constantly past the faces (a zero fill would pull the field to zero at the border).  Then ``_taps_np`` / ``_weighted_sum_np``
+    along z, then y, then x - the taps once for all three components - and one float32 add.
+
+    An infinite displacement in ``v`` is clamped like any other, onto a face; the sum ``v_a + U_a`` is then infinite in that
+    component.  A displacement that is not a number fails both comparisons and stays: such a voxel gets NaN in ALL THREE components
+    (where it points is unknown), and nothing of it is converted to an integer."""
+    u, v = _check_field4_np(u, "compose_np"), _check_field4_np(v, "compose_np")
+    if u.shape != v.shape:
+        raise ValueError(f"compose_np: the fields must share a grid, got shapes {u.shape} and {v.shape}")
+    shape = u.shape[1:]
+    p, number = [], np.ones(shape, dtype=bool)
+    with np.errstate(invalid="ignore"):
+        for a, n in enumerate(shape):
+            i = np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)])
+            pa = i + v[a].astype(np.float64)
+            pa = np.where(pa < 0.0, 0.0, np.where(pa > n - 1.0, n - 1.0, pa))
+            number &= ~np.isnan(pa)
+            p.append(pa)
+    out = np.full(u.shape, np.float32(np.nan), dtype=np.float32)
+    if number.any():
+        with np.errstate(all="ignore"):
+            (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa[number], n, "linear") for pa, n in zip(p, shape))
+            for a in range(3):
+                rx = []
+                for xa in ix:
+                    ry = [_weighted_sum_np(wz, [u[a][xa, yb, zc] for zc in iz]) for yb in iy]
+                    rx.append(_weighted_sum_np(wy, ry))
+                out[a][number] = v[a][number] + _weighted_sum_np(wx, rx)
+    return out
+
+
+MAX_EXP_STEPS = 8
+
+
+def _check_exp_steps(steps) -> int:
+    if not isinstance(steps, (int, np.integer)) or isinstance(steps, bool) or not 0 <= steps <= MAX_EXP_STEPS:
+        raise ValueError(f"exp_steps is an integer in 0..{MAX_EXP_STEPS}, got {steps!r}")
+    return int(steps)
+
+
+def exp_field_np(w, steps: int) -> np.ndarray:
+    """The exponential of the velocity field ``w`` by scaling and squaring: ``w = w * float32(2^-steps)``, then ``steps`` times
+    ``w = compose_np(w, w)``.  ``steps`` in 0..8; 0 returns ``w``."""
+    w = _check_field4_np(w, "exp_field_np")
+    steps = _check_exp_steps(steps)
+    with np.errstate(all="ignore"):
+        w = w * np.float32(2.0 ** -steps)
+    for _ in range(steps):
+        w = compose_np(w, w)
+    return w
+
+
+def warp_matrix_np(moving, m, u, method: str = "linear", fill: float = 0.0) -> np.ndarray:
+    """``moving`` (a float32 volume of any shape) at ``M (x + u(x))``, on the grid of the field ``u`` (3, X, Y, Z): ONE interpolation
+    through a field and the ``(3, 4)`` float64 matrix ``m``, fixed index -> moving index (the matrix ``reslice`` takes).
+    ``q_a = float64(i_a) + float64(u_a)``; ``p_a = ((m[a,0] q_0 + m[a,1] q_1) + m[a,2] q_2) + m[a,3]`` in float64, the order of
+    ``source_coordinates_np``; then ``reslice_np``'s inside test (on ``moving``'s extents), taps and reduction.  Bit for bit
+    ``reslice_np`` for a zero field and ``warp_np`` for the identity matrix.  A NaN or infinite displacement is outside."""
+    moving = _check_volume_np(moving, "warp_matrix_np")
+    m = _check_matrix(m)
+    u = _check_field4_np(u, "warp_matrix_np")
+    _check_method(method)
+    shape = u.shape[1:]
+    with np.errstate(invalid="ignore"):
+        q = [np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)]) + u[a].astype(np.float64)
+             for a, n in enumerate(shape)]
+        p = [((m[a, 0] * q[0] + m[a, 1] * q[1]) + m[a, 2] * q[2]) + m[a, 3] for a in range(3)]
+        inside = np.ones(shape, dtype=bool)
+        for a in range(3):
+            inside &= (p[a] >= -0.5) & (p[a] <= moving.shape[a] - 0.5)
+    out = np.full(shape, np.float32(fill), dtype=np.float32)
+    if inside.any():
+        with np.errstate(all="ignore"):
+            (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
+            rx = []
+            for xa in ix:
+                ry = [_weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
+                rx.append(_weighted_sum_np(wy, ry))
+            out[inside] = _weighted_sum_np(wx, rx)
+    return out
 
 
 def _check_sigmas(sigmas_vox) -> list:
@@ -287,6 +414,34 @@ def register_deformable_np(fixed, moving, levels: int = 3, iterations=DEFAULT_IT
         for _ in range(its):
             v, row = demons_force_np(f, m, u, max_step, fill)
             u = smooth_field_np(v, sigmas)
+            stats.append(row)
+    return DeformResult(u, warp_np(moving, u, method, fill), stats, jacobian_stats_np(u), schedule)
+
+
+def register_diffeomorphic_np(fixed, moving, levels: int = 3, iterations=DEFAULT_ITERATIONS, sigma_vox: float = 1.5, max_step: float = 2.0,
+                              fill: float = 0.0, method: str = "linear", exp_steps: int = 2) -> DeformResult:
+    """The specification of ``register_diffeomorphic``: ``register_deformable_np`` with the iteration
+    ``w = demons_update_np(fixed_l, moving_l, u, max_step, fill, 2^-exp_steps)[0]``; ``exp_steps`` times ``w = compose_np(w, w)``;
+    ``u = smooth_field_np(compose_np(u, w), (sigma_vox,) * 3)``.  Thirion's update is at most half a voxel, so with the default
+    ``exp_steps = 2`` the sub-steps are at most an eighth.  Identical scans leave the field exactly zero."""
+    fixed, moving = _check_pair_np(fixed, moving, "register_diffeomorphic_np")
+    schedule = _schedule(fixed.shape, levels, iterations)
+    sigmas = (float(sigma_vox),) * 3
+    _check_sigmas(sigmas), _check_max_step(max_step), _check_method(method)
+    scale = np.float32(2.0 ** -_check_exp_steps(exp_steps))
+    pyramid = [(fixed, moving)]
+    for _ in schedule[1:]:
+        pyramid.insert(0, tuple(downsample2_np(v) for v in pyramid[0]))
+    u = np.zeros((3,) + schedule[0][0], dtype=np.float32)
+    stats = []
+    for level, ((shape, its), (f, m)) in enumerate(zip(schedule, pyramid)):
+        if level:
+            u = np.stack([upscale2_np(np.ascontiguousarray(u[a]), "linear") * np.float32(2) for a in range(3)])
+        for _ in range(its):
+            w, row = demons_update_np(f, m, u, max_step, fill, scale)
+            for _ in range(exp_steps):
+                w = compose_np(w, w)
+            u = smooth_field_np(compose_np(u, w), sigmas)
             stats.append(row)
     return DeformResult(u, warp_np(moving, u, method, fill), stats, jacobian_stats_np(u), schedule)
 
@@ -433,16 +588,24 @@ def register_deformable(fixed: torch.Tensor, moving: torch.Tensor, levels: int =
     device-to-host read, of the stats rows and the Jacobian numbers, is the last thing done.  ``graph``: the iteration loop of every
     level is captured into a HIP graph and replayed (after one eager iteration as a warm-up, which loads the code objects) - the
     same bits as the eager loop."""
-    f, m = _check_volume(fixed, "register_deformable"), _check_volume(moving, "register_deformable")
+    return _register(fixed, moving, levels, iterations, sigma_vox, max_step, fill, method, workspace, graph, "register_deformable",
+                     DeformWorkspace, (), _iterate)
+
+
+def _register(fixed, moving, levels, iterations, sigma_vox, max_step, fill, method, workspace, graph, what, ws_type, ws_extra, iterate):
+    """The frame of ``register_deformable`` and ``register_diffeomorphic``: the pyramid, the hand-over between levels, the (captured)
+    loop ``iterate`` of every level, the final warp and the one read.  ``ws_type(shape, device, levels, iterations, sigma_vox,
+    *ws_extra)`` is the workspace it needs."""
+    f, m = _check_volume(fixed, what), _check_volume(moving, what)
     if f.shape != m.shape or f.device != m.device:
-        raise ValueError(f"register_deformable: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+        raise ValueError(f"{what}: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
     _check_max_step(max_step), _check_method(method)
     if workspace is None:
-        workspace = DeformWorkspace(f.shape, f.device, levels, iterations, sigma_vox)
+        workspace = ws_type(f.shape, f.device, levels, iterations, sigma_vox, *ws_extra)
     ws = workspace
-    if not isinstance(ws, DeformWorkspace) or ws.key != (tuple(_schedule(f.shape, levels, iterations)), float(sigma_vox)) \
+    if not isinstance(ws, ws_type) or ws.key != (tuple(_schedule(f.shape, levels, iterations)), float(sigma_vox)) + tuple(ws_extra) \
             or ws.slots.device != f.device:
-        raise ValueError(f"register_deformable: the workspace must be a DeformWorkspace for volumes of {tuple(f.shape)}, this schedule "
+        raise ValueError(f"{what}: the workspace must be a {ws_type.__name__} for volumes of {tuple(f.shape)}, this schedule "
                          f"and sigma on {f.device}")
     pyramid = [(f, m)]
     for pair in reversed(ws.volumes):
@@ -451,7 +614,7 @@ def register_deformable(fixed: torch.Tensor, moving: torch.Tensor, levels: int =
         pyramid.insert(0, pair)
     ws.field(0, 0).zero_()
     if graph and ws.rows:
-        _iterate(ws, 0, *pyramid[0], 1, 0, max_step, fill)
+        iterate(ws, 0, *pyramid[0], 1, 0, max_step, fill)
         ws.field(0, 0).zero_()
     row = 0
     for level, ((shape, its), (fl, ml)) in enumerate(zip(ws.schedule, pyramid)):
@@ -464,10 +627,10 @@ def register_deformable(fixed: torch.Tensor, moving: torch.Tensor, levels: int =
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                _iterate(ws, level, fl, ml, its, row, max_step, fill)
+                iterate(ws, level, fl, ml, its, row, max_step, fill)
             g.replay()
         else:
-            _iterate(ws, level, fl, ml, its, row, max_step, fill)
+            iterate(ws, level, fl, ml, its, row, max_step, fill)
         row += its
     field = ws.field(0, len(ws.schedule) - 1).clone()
     warped = warp(m, field, method, fill)
@@ -477,3 +640,122 @@ def register_deformable(fixed: torch.Tensor, moving: torch.Tensor, levels: int =
     stats = [(float(s), int(n)) for s, n in zip(host[:ws.rows, 0].copy().view(np.float64), host[:ws.rows, 1])]
     jacobian = (float(host[ws.rows, :1].copy().view(np.float32)[0]), int(host[ws.rows, 1]))
     return DeformResult(field, warped, stats, jacobian, ws.schedule)
+
+
+# ---------------------------------------------------------------- device: the diffeomorphic variant
+
+def _check_field4(u, what) -> torch.Tensor:
+    u = _check_vol(u, what)
+    if u.dim() != 4 or u.shape[0] != 3:
+        raise ValueError(f"{what}: a field is (3, X, Y, Z), got shape {tuple(u.shape)}")
+    _check_shape(u.shape[1:], f"{what}: the volume's shape")
+    return u
+
+
+def _compose(u, v, out, shape):
+    L.call("mrisr_f32_volume_field_compose", u.data_ptr(), v.data_ptr(), *shape, out.data_ptr(), L.stream_ptr(),
+           nbytes=36 * int(np.prod(shape)))                                                                   # 6 floats read, 3 written
+
+
+def _update(fixed, moving, u, max_step, fill, scale, w, slots, stats_row):
+    L.call("mrisr_f32_volume_demons_update", fixed.data_ptr(), moving.data_ptr(), u.data_ptr(), *fixed.shape, float(max_step), float(fill),
+           float(scale), w.data_ptr(), slots.data_ptr(), L.ptr(stats_row), L.stream_ptr(), nbytes=32 * fixed.numel())
+
+
+def compose(u: torch.Tensor, v: torch.Tensor, out=None) -> torch.Tensor:
+    """u, v: contiguous float32 CUDA fields (3, X, Y, Z) -> ``compose_np(u, v)``, bit for bit.  One launch: the coordinates and the
+    eight taps of a voxel once for all three components.  ``u`` and ``v`` may be one tensor (squaring); ``out``: another tensor."""
+    u = _check_field4(u, "compose")
+    v = _check_field(v, u.shape[1:], u.device, "compose")
+    out = _check_out(out, u, (u, v), "compose")
+    _compose(u, v, out, tuple(u.shape[1:]))
+    return out
+
+
+def demons_update(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, max_step: float = 2.0, fill: float = 0.0, scale: float = 1.0,
+                  out=None):
+    """The device path of ``demons_update_np`` -> ``(w, S, n)`` as ``demons_force`` returns them: the same kernel, writing
+    ``upd * scale``.  ``out``: another tensor like ``u``."""
+    f, m = _check_volume(fixed, "demons_update"), _check_volume(moving, "demons_update")
+    if f.shape != m.shape or f.device != m.device:
+        raise ValueError(f"demons_update: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    u = _check_field(u, f.shape, f.device, "demons_update")
+    _check_max_step(max_step)
+    scale = _check_scale(scale)
+    w = _check_out(out, u, (u, f, m), "demons_update")
+    row = torch.empty(2, dtype=torch.int64, device=f.device)
+    _update(f, m, u, max_step, fill, scale, w, _slots(f.device), row)
+    return w, row[:1].view(torch.float64)[0], row[1]
+
+
+def exp_field(w: torch.Tensor, steps: int, out=None) -> torch.Tensor:
+    """w: contiguous float32 CUDA field (3, X, Y, Z) -> ``exp_field_np(w, steps)``, bit for bit: the product with ``2^-steps``, then
+    ``steps`` launches of ``compose`` between two buffers.  ``steps`` is a host integer: nothing is read from the device."""
+    w = _check_field4(w, "exp_field")
+    steps = _check_exp_steps(steps)
+    out = _check_out(out, w, (w,), "exp_field")
+    shape = tuple(w.shape[1:])
+    other = torch.empty_like(w) if steps else None
+    src = out if steps % 2 == 0 else other           # the last of the squarings lands in out
+    torch.mul(w, 2.0 ** -steps, out=src)
+    for _ in range(steps):
+        dst = other if src is out else out
+        _compose(src, src, dst, shape)
+        src = dst
+    return out
+
+
+def warp_matrix(moving: torch.Tensor, m, u: torch.Tensor, method: str = "linear", fill: float = 0.0, out=None) -> torch.Tensor:
+    """moving: contiguous float32 CUDA volume of any shape; m: (3, 4) matrix (host, float64), index on the field's grid -> index in
+    ``moving``; u: (3, X, Y, Z) -> ``warp_matrix_np``, bit for bit: the (X, Y, Z) volume ``moving`` at ``M (x + u(x))``, one
+    interpolation, one launch, the matrix by value (no upload, no synchronisation)."""
+    mv = _check_volume(moving, "warp_matrix")
+    u = _check_field4(u, "warp_matrix")
+    if u.device != mv.device:
+        raise ValueError(f"warp_matrix: the field must lie on {mv.device}, got {u.device}")
+    _check_method(method)
+    out = _check_out(out, u[0], (mv, u), "warp_matrix")
+    L.call("mrisr_f32_volume_warp_matrix", mv.data_ptr(), *mv.shape, u.data_ptr(), *u.shape[1:], _matrix_arg(m), METHODS[method], float(fill),
+           out.data_ptr(), L.stream_ptr(), nbytes=4 * (mv.numel() + 4 * out.numel()))
+    return out
+
+
+class DiffeoWorkspace(DeformWorkspace):
+    """``DeformWorkspace`` for ``register_diffeomorphic``: two more field buffers, for the update and its squarings."""
+
+    def __init__(self, shape, device, levels=3, iterations=DEFAULT_ITERATIONS, sigma_vox=1.5, exp_steps=2):
+        self.exp_steps = _check_exp_steps(exp_steps)
+        super().__init__(shape, device, levels, iterations, sigma_vox)
+        self.key = self.key + (self.exp_steps,)
+        self.fields += [torch.empty_like(self.fields[0]) for _ in range(2 if self.exp_steps else 1)]
+
+
+def _iterate_diffeo(ws, level, fixed, moving, iterations, row, max_step, fill):
+    """``iterations`` iterations on one level, ``5 + exp_steps`` launches each: the scaled update (field 0 -> 2), its squarings
+    (2 -> 3 -> 2 ...), the composition with the field (0 and the last of those -> 1), then the passes over axis 2 (1 -> 0; its first
+    workgroup adds the update's slots into the stats row), 1 (0 -> 1) and 0 (1 -> 0).  Nothing is allocated."""
+    shape = ws.schedule[level][0]
+    a, b = ws.field(0, level), ws.field(1, level)
+    scale = 2.0 ** -ws.exp_steps
+    for it in range(iterations):
+        w = ws.field(2, level)
+        _update(fixed, moving, a, max_step, fill, scale, w, ws.slots, None)
+        for _ in range(ws.exp_steps):
+            sq = ws.field(3, level) if w.data_ptr() == ws.fields[2].data_ptr() else ws.field(2, level)
+            _compose(w, w, sq, shape)
+            w = sq
+        _compose(a, w, b, shape)
+        _smooth_pass(b, a, shape, 2, ws.taps, ws.radius, ws.slots, ws.stats[row + it])
+        _smooth_pass(a, b, shape, 1, ws.taps, ws.radius)
+        _smooth_pass(b, a, shape, 0, ws.taps, ws.radius)
+
+
+def register_diffeomorphic(fixed: torch.Tensor, moving: torch.Tensor, levels: int = 3, iterations=DEFAULT_ITERATIONS, sigma_vox: float = 1.5,
+                           max_step: float = 2.0, fill: float = 0.0, method: str = "linear", exp_steps: int = 2, workspace=None,
+                           graph: bool = False) -> DeformResult:
+    """The device path of ``register_diffeomorphic_np``, under the rules of ``register_deformable``: ``field`` and ``warped`` bit for
+    bit, the sums within one spacing, one device-to-host read at the end; an iteration is ``5 + exp_steps`` launches; ``graph``
+    captures the loop of every level.  ``workspace``: a ``DiffeoWorkspace`` of this schedule, sigma and ``exp_steps``."""
+    exp_steps = _check_exp_steps(exp_steps)
+    return _register(fixed, moving, levels, iterations, sigma_vox, max_step, fill, method, workspace, graph, "register_diffeomorphic",
+                     DiffeoWorkspace, (exp_steps,), _iterate_diffeo)

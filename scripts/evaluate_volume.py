@@ -73,7 +73,9 @@ run as it was.
 every input frame is warped onto ``downsample2`` of its reference frame (the input's grid, or the grid ``--align`` implies) through a
 displacement field estimated by Thirion's demons (``volume_deform.register_deformable``; ``csrc/volume_deform.hip``) with
 ``--align_interp``: the frame is then interpolated twice.  The force is an intensity difference, so a run without
-``--match_intensity`` is warned about.  The default, ``none``, leaves a run as it was.
+``--match_intensity`` is warned about.  ``--deform_input diffeomorphic`` estimates the field by diffeomorphic demons instead
+(``volume_deform.register_diffeomorphic``, ``--deform_exp_steps`` squarings of an update's exponential): the update is composed with
+the field, not added, so the warped frame is not that of a folded field.  The default, ``none``, leaves a run as it was.
 """
 import argparse
 import csv
@@ -91,7 +93,7 @@ if REPO not in sys.path:
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
 from mri_superresolution_amd.utils.nifti import downscaled_affine, frames, grid_matrix, mask_frames, read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_bias import match_bias as match_bias_field, sigmas_for                  # noqa: E402
-from mri_superresolution_amd.volume_deform import register_deformable                     # noqa: E402
+from mri_superresolution_amd.volume_deform import MAX_EXP_STEPS, register_deformable, register_diffeomorphic      # noqa: E402
 from mri_superresolution_amd.volume_denoise import denoise_volume                                             # noqa: E402
 from mri_superresolution_amd.volume_eval import downsample2, evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity    # noqa: E402
@@ -120,10 +122,12 @@ def load_mask(mask_path, ref, ref_affine=None):
 
 
 def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0,
-                  denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, deform_input="none"):
+                  denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, deform_input="none", deform_exp_steps=2):
     """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
-    if deform_input not in ("none", "demons"):
-        raise ValueError(f"--deform_input is none or demons, got {deform_input!r}")
+    if deform_input not in ("none", "demons", "diffeomorphic"):
+        raise ValueError(f"--deform_input is none, demons or diffeomorphic, got {deform_input!r}")
+    if isinstance(deform_exp_steps, bool) or not isinstance(deform_exp_steps, int) or not 0 <= deform_exp_steps <= MAX_EXP_STEPS:
+        raise ValueError(f"--deform_exp_steps must be an integer in 0..{MAX_EXP_STEPS}, got {deform_exp_steps}")
     if deform_input != "none" and not input_path:
         raise ValueError("--deform_input goes with --input")
     if denoise_input not in ("none", "nlm"):
@@ -180,12 +184,13 @@ def low_reference(lr, vol, axes, option):
 
 
 def prepare_input(lr, vol, match="none", match_bias="none", axes=(0, 1, 2), sigmas_vox=None, what="input", reference="its reference",
-                  deform="none", deform_interp="linear"):
+                  deform="none", deform_interp="linear", deform_exp_steps=2):
     """What ``--match_intensity``, ``--match_bias`` and ``--deform_input`` do to one input frame ``lr`` next to its reference frame
     ``vol`` (CUDA tensors) -> the frame every method sees.  ``match`` first, then ``match_bias="pair"`` against
     ``downsample2(vol, axes)`` - the reference on the input's grid - with ``sigmas_vox`` on that grid, then ``deform="demons"``: a
     displacement field against that same low reference (``volume_deform.register_deformable``), the frame warped through it with
-    ``deform_interp``.  All ``"none"``: ``lr`` itself."""
+    ``deform_interp``; ``deform="diffeomorphic"``: the field of ``volume_deform.register_diffeomorphic`` with ``deform_exp_steps``.
+    All ``"none"``: ``lr`` itself."""
     if match != "none":
         lr, found = match_intensity(lr, vol, foreground_mask(lr)[0], foreground_mask(vol)[0], LANDMARKS if match == "landmarks" else RANGE)
         marks = "  ".join(f"{q:g}%: {a:.6g} -> {b:.6g}" for q, a, b in zip(found.percentiles, found.source_landmarks, found.target_landmarks))
@@ -199,9 +204,12 @@ def prepare_input(lr, vol, match="none", match_bias="none", axes=(0, 1, 2), sigm
         if match == "none":
             logger.warning("--deform_input without --match_intensity: the demons force is an intensity difference, and the two scans "
                            "are not on one intensity scale.")
-        found = register_deformable(low_reference(lr, vol, axes, "--deform_input"), lr, method=deform_interp)
+        if deform == "diffeomorphic":
+            found = register_diffeomorphic(low_reference(lr, vol, axes, "--deform_input"), lr, method=deform_interp, exp_steps=deform_exp_steps)
+        else:
+            found = register_deformable(low_reference(lr, vol, axes, "--deform_input"), lr, method=deform_interp)
         first, last = found.stats[0], found.stats[-1]
-        logger.info(f"{what} warped onto {reference} (demons, {deform_interp}): mean squared difference {first[0] / max(first[1], 1):.6g} -> "
+        logger.info(f"{what} warped onto {reference} ({deform}, {deform_interp}): mean squared difference {first[0] / max(first[1], 1):.6g} -> "
                     f"{last[0] / max(last[1], 1):.6g} over {len(found.stats)} iterations on {len(found.schedule)} level(s); minimum Jacobian "
                     f"determinant {found.jacobian[0]:.4f}, {found.jacobian[1]} voxel(s) not positive")
         lr = found.warped
@@ -212,7 +220,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
                match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
-               denoise_radius=3, deform_input="none"):
+               denoise_radius=3, deform_input="none", deform_exp_steps=2):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -224,9 +232,9 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     reference frame's intensity scale before any method sees it (module docstring); ``match_bias="pair"``: then its bias field is
     matched to the reference's (``prepare_input``).  ``denoise_input="nlm"``: every input frame is denoised on its own grid before
     anything else happens to it (``upload_input``).  ``deform_input="demons"``: after all of that every input frame is warped onto its
-    reference frame on the input's grid (``prepare_input``)."""
+    reference frame on the input's grid (``prepare_input``); ``"diffeomorphic"`` with ``deform_exp_steps`` likewise."""
     check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
-                  denoise_sigma, denoise_beta, denoise_radius, deform_input)
+                  denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps)
     noise_options = (denoise_input, denoise_sigma, denoise_beta, denoise_radius)
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
@@ -281,7 +289,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             m = masks[t] if align else torch.from_numpy(masks[t]).to(device)
         if lr is not None:
             lr = prepare_input(lr, vol, match, match_bias, axes, bias_sigmas, f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}",
-                               reference_path, deform_input, align_interp)
+                               reference_path, deform_input, align_interp, deform_exp_steps)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
                               mask_fill_holes=mask_fill_holes)
@@ -360,7 +368,7 @@ def main(args):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
         check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity, args.match_bias,
                       args.match_bias_sigma_mm, args.denoise_input, args.denoise_sigma, args.denoise_beta, args.denoise_radius,
-                      args.deform_input)
+                      args.deform_input, args.deform_exp_steps)
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -385,7 +393,8 @@ def main(args):
                                    align_bins=args.align_bins, align_init=args.align_init, align_mask=args.align_mask,
                                    match=args.match_intensity, match_bias=args.match_bias, match_bias_sigma_mm=args.match_bias_sigma_mm,
                                    denoise_input=args.denoise_input, denoise_sigma=args.denoise_sigma, denoise_beta=args.denoise_beta,
-                                   denoise_radius=args.denoise_radius, deform_input=args.deform_input)
+                                   denoise_radius=args.denoise_radius, deform_input=args.deform_input,
+                                   deform_exp_steps=args.deform_exp_steps)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -466,11 +475,13 @@ def parse_args(argv=None):
     p.add_argument("--denoise_sigma", type=float, default=None, help="the noise level of --denoise_input, in intensity units (default: estimated)")
     p.add_argument("--denoise_beta", type=float, default=1.0, help="strength of --denoise_input: h^2 = 2 beta sigma^2 per patch voxel")
     p.add_argument("--denoise_radius", type=int, default=3, help="search radius of --denoise_input in voxels, 1..5")
-    p.add_argument("--deform_input", type=str, choices=["none", "demons"], default="none",
+    p.add_argument("--deform_input", type=str, choices=["none", "demons", "diffeomorphic"], default="none",
                    help="demons: warp every input frame onto its reference frame on the input's grid (downsample2 of the reference, or "
                         "the grid --align implies) by a demons displacement field, after the --align reslice, --match_intensity and "
                         "--match_bias; warped with --align_interp, so the frame is then interpolated twice (needs --input; an "
-                        "intensity-difference force: use --match_intensity)")
+                        "intensity-difference force: use --match_intensity); diffeomorphic: the same with the update composed with the "
+                        "field through its exponential, not added - a field that does not fold")
+    p.add_argument("--deform_exp_steps", type=int, default=2, help="--deform_input diffeomorphic: squarings of an update's exponential, 0..8")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

@@ -22,6 +22,13 @@ warped through it (``--interp``): the output is then interpolated twice.  The fo
 be on one intensity scale (``scripts/evaluate_volume.py --match_intensity`` / ``--match_bias`` do that for an evaluation).
 ``--save_field`` writes the field as a 4-D float32 NIfTI of three frames (voxels of the fixed grid) under the fixed grid's header.
 The default, ``none``, leaves the script as it was.
+
+``--nonrigid diffeomorphic`` estimates the field by diffeomorphic demons instead (``volume_deform.register_diffeomorphic``): the
+update of an iteration is turned into a small diffeomorphism by ``--nonrigid_exp_steps`` squarings and composed with the field, not
+added to it, so the field does not fold where the additive one does.  ``--nonrigid_resample once`` (with either method) writes every
+frame as ONE interpolation of the original moving frame through the rigid matrix and the field
+(``volume_deform.warp_matrix``: the frame at ``M (x + u(x))``), not as a warp of the resliced frame; the field itself is still
+estimated on the resliced frame 0.  The default, ``twice``, writes the bytes it wrote before.
 """
 import argparse
 import logging
@@ -36,7 +43,8 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd.utils.nifti import frames as frames_of, header_for_grid, read_nifti, write_nifti      # noqa: E402
-from mri_superresolution_amd.volume_deform import DEFAULT_ITERATIONS, register_deformable, warp      # noqa: E402
+from mri_superresolution_amd.volume_deform import DEFAULT_ITERATIONS, MAX_EXP_STEPS, register_deformable, warp      # noqa: E402
+from mri_superresolution_amd.volume_deform import register_diffeomorphic, warp_matrix      # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                             # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice                      # noqa: E402
 
@@ -69,31 +77,53 @@ def describe_nonrigid(result):
     return lines
 
 
-def nonrigid_stage(fixed0, outs, interp, fill, levels, iterations, sigma, max_step):
-    """The field of frame 0 against the fixed scan, applied to every resliced frame -> (warped frames, DeformResult)."""
+def check_options(nonrigid="none", nonrigid_exp_steps=2, nonrigid_resample="twice", save_field=None):
+    """The rules of the non-rigid options, stated once; ``register_file`` applies them before it reads a file."""
+    if nonrigid not in ("none", "demons", "diffeomorphic"):
+        raise ValueError(f"--nonrigid must be none, demons or diffeomorphic, got {nonrigid}")
+    if save_field and nonrigid == "none":
+        raise ValueError("--save_field goes with --nonrigid demons or diffeomorphic")
+    if nonrigid_resample not in ("twice", "once"):
+        raise ValueError(f"--nonrigid_resample must be twice or once, got {nonrigid_resample}")
+    if nonrigid_resample == "once" and nonrigid == "none":
+        raise ValueError("--nonrigid_resample once goes with --nonrigid demons or diffeomorphic: without a field the rigid stage "
+                         "already interpolates once")
+    if isinstance(nonrigid_exp_steps, bool) or not isinstance(nonrigid_exp_steps, int) or not 0 <= nonrigid_exp_steps <= MAX_EXP_STEPS:
+        raise ValueError(f"--nonrigid_exp_steps must be an integer in 0..{MAX_EXP_STEPS}, got {nonrigid_exp_steps}")
+
+
+def nonrigid_stage(fixed0, outs, interp, fill, levels, iterations, sigma, max_step, nonrigid="demons", exp_steps=2, once=None):
+    """The field of frame 0 against the fixed scan, applied to every resliced frame -> (warped frames, DeformResult).  ``once =
+    (original frames, matrix)``: every output frame is instead one interpolation of its original frame through matrix and field."""
     if isinstance(iterations, (list, tuple)) and len(iterations) == 1:
         iterations = int(iterations[0])
-    result = register_deformable(fixed0, outs[0], levels=levels, iterations=iterations, sigma_vox=sigma, max_step=max_step, fill=fill,
-                                 method=interp)
+    if nonrigid == "diffeomorphic":
+        result = register_diffeomorphic(fixed0, outs[0], levels=levels, iterations=iterations, sigma_vox=sigma, max_step=max_step,
+                                        fill=fill, method=interp, exp_steps=exp_steps)
+    else:
+        result = register_deformable(fixed0, outs[0], levels=levels, iterations=iterations, sigma_vox=sigma, max_step=max_step, fill=fill,
+                                     method=interp)
     for line in describe_nonrigid(result):
         logger.info(f"Non-rigid stage, {line}")
     min_det, folded = result.jacobian
     logger.info(f"Non-rigid stage: minimum Jacobian determinant {min_det:.4f}, {folded} voxel(s) with a determinant that is not positive")
     if folded:
         logger.warning(f"The field folds at {folded} voxel(s): raise --nonrigid_sigma (now {sigma:g}) for a smoother field.")
+    if once is not None:
+        frames, matrix = once
+        logger.info(f"Non-rigid stage: every frame is interpolated once, through the rigid matrix and the field ({interp}).")
+        return [warp_matrix(f, matrix, result.field, interp, fill) for f in frames], result
     return [result.warped] + [warp(o, result.field, interp, fill) for o in outs[1:]], result
 
 
 def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64, save_transform=None, fill=0.0, device="cuda",
                   init="header", init_limit=40.0, init_step=20.0, mask="none", nonrigid="none", nonrigid_levels=3,
-                  nonrigid_iterations=DEFAULT_ITERATIONS, nonrigid_sigma=1.5, nonrigid_max_step=2.0, save_field=None):
+                  nonrigid_iterations=DEFAULT_ITERATIONS, nonrigid_sigma=1.5, nonrigid_max_step=2.0, save_field=None, nonrigid_exp_steps=2,
+                  nonrigid_resample="twice"):
     """NIfTI files -> the moving scan on the fixed scan's grid (written and returned), and the ``RigidResult``."""
     if mask not in ("none", "otsu"):
         raise ValueError(f"--mask must be none or otsu, got {mask}")
-    if nonrigid not in ("none", "demons"):
-        raise ValueError(f"--nonrigid must be none or demons, got {nonrigid}")
-    if save_field and nonrigid == "none":
-        raise ValueError("--save_field goes with --nonrigid demons")
+    check_options(nonrigid, nonrigid_exp_steps, nonrigid_resample, save_field)
     fixed, fixed_header = read_nifti(fixed_path)
     moving, moving_header = read_nifti(moving_path)
     frames = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)).to(device) for f in frames_of(moving)]
@@ -107,8 +137,9 @@ def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64
     logger.info(f"Registered {moving_path} to {fixed_path}: {describe(result)}")
     outs = [reslice(f, result.matrix, shape, interp, fill) for f in frames]
     share = covered_share(moving.shape[:3], result.matrix, shape, device)
-    if nonrigid == "demons":
-        outs, deformed = nonrigid_stage(fixed0, outs, interp, fill, nonrigid_levels, nonrigid_iterations, nonrigid_sigma, nonrigid_max_step)
+    if nonrigid != "none":
+        outs, deformed = nonrigid_stage(fixed0, outs, interp, fill, nonrigid_levels, nonrigid_iterations, nonrigid_sigma, nonrigid_max_step,
+                                        nonrigid, nonrigid_exp_steps, (frames, result.matrix) if nonrigid_resample == "once" else None)
         if save_field:
             os.makedirs(os.path.dirname(os.path.abspath(save_field)), exist_ok=True)
             field = np.ascontiguousarray(np.moveaxis(deformed.field.cpu().numpy(), 0, 3))
@@ -139,7 +170,7 @@ def main(args):
         logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
         register_file(args.fixed, args.moving, args.output, args.interp, args.bins, args.save_transform, args.fill, device, args.init,
                       args.init_limit, args.init_step, args.mask, args.nonrigid, args.nonrigid_levels, args.nonrigid_iterations,
-                      args.nonrigid_sigma, args.nonrigid_max_step, args.save_field)
+                      args.nonrigid_sigma, args.nonrigid_max_step, args.save_field, args.nonrigid_exp_steps, args.nonrigid_resample)
         return 0
     except Exception as e:
         logger.error(f"Error during registration: {e}")
@@ -162,10 +193,16 @@ def parse_args(argv=None):
                    help="otsu: only the samples inside the fixed scan's Otsu foreground mask enter the cost")
     p.add_argument("--save_transform", type=str, default=None, help="write the 4 x 4 fixed world -> moving world matrix as text")
     p.add_argument("--fill", type=float, default=0.0, help="value of the output voxels whose centre lies outside the moving scan")
-    p.add_argument("--nonrigid", type=str, choices=["none", "demons"], default="none",
+    p.add_argument("--nonrigid", type=str, choices=["none", "demons", "diffeomorphic"], default="none",
                    help="demons: after the rigid stage and its reslice, estimate a displacement field against the fixed scan (Thirion's "
                         "demons, an intensity-difference force: bring both scans onto one intensity scale first) and write the warped "
-                        "scan instead; the output is then interpolated twice")
+                        "scan instead; the output is then interpolated twice unless --nonrigid_resample once; diffeomorphic: the same "
+                        "with the update composed with the field through its exponential, not added: a field that does not fold")
+    p.add_argument("--nonrigid_exp_steps", type=int, default=2,
+                   help="--nonrigid diffeomorphic: squarings of the exponential of one update (0..8; the update is scaled by 2^-N first)")
+    p.add_argument("--nonrigid_resample", type=str, choices=["twice", "once"], default="twice",
+                   help="twice: warp the resliced scan (as before); once: write every frame as ONE interpolation of the original moving "
+                        "frame through the rigid matrix and the field (needs --nonrigid demons or diffeomorphic)")
     p.add_argument("--nonrigid_levels", type=int, default=3, help="--nonrigid demons: levels of the pyramid (halved while every extent is even and at least 16)")
     p.add_argument("--nonrigid_iterations", type=int, nargs="+", default=list(DEFAULT_ITERATIONS),
                    help="--nonrigid demons: iterations per level, coarse to fine (one count per level, or one for all)")

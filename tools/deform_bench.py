@@ -8,6 +8,13 @@ bytes/s against a device-to-device copy of the same number of bytes measured in 
 Times are device events around --iters back-to-back iterations after --warmup; the algorithmic bytes of the force are 5 floats
 read and 3 written per voxel (fixed, moving - once, its taps come from cache - and the three components in, three out).  One JSON
 line at the end.
+
+    python tools/deform_bench.py --diffeomorphic --exp_steps 2 --rounds 5
+
+adds the diffeomorphic iteration (the scaled update, --exp_steps squarings, the composition with the field and the three smoothing
+passes: 5 + exp_steps launches) next to the additive one - timed in alternating order, --rounds times each, the median reported with
+the smallest and largest - and the compose kernel's achieved bytes/s against a device copy of its algorithmic bytes: 6 floats read
+(the three components of both fields once, the 24 taps come from cache) and 3 written per voxel.
 """
 import argparse
 import json
@@ -59,6 +66,39 @@ def torch_iteration(fixed, moving, u, taps, max_step):
     return v
 
 
+def diffeomorphic(args, fixed, moving, u, additive_iteration):
+    """The diffeomorphic iteration against the additive one (alternating) and the compose kernel against a copy of its bytes."""
+    ws = D.DiffeoWorkspace(fixed.shape, fixed.device, levels=1, iterations=1, sigma_vox=args.sigma, exp_steps=args.exp_steps)
+    a, b, w = ws.field(0, 0), ws.field(1, 0), ws.field(2, 0)
+    a.copy_(u)
+    shape = tuple(fixed.shape)
+
+    def iteration():
+        D._iterate_diffeo(ws, 0, fixed, moving, 1, 0, 2.0, 0.0)
+
+    t_add, t_dif = [], []
+    for _ in range(args.rounds):
+        t_add.append(timed(additive_iteration, args.iters, args.warmup))
+        t_dif.append(timed(iteration, args.iters, args.warmup))
+    a.copy_(u)
+    w.copy_(u).mul_(0.125)                           # sub-steps of the size the loop composes
+    nbytes = 36 * fixed.numel()
+    src, dst = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda"), torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
+    t_comp, t_sq, t_copy = [], [], []
+    for _ in range(args.rounds):
+        t_comp.append(timed(lambda: D._compose(a, w, b, shape), args.iters, args.warmup))
+        t_sq.append(timed(lambda: D._compose(w, w, b, shape), args.iters, args.warmup))
+        t_copy.append(timed(lambda: dst.copy_(src), args.iters, args.warmup))
+    med = lambda t: float(np.median(t))              # noqa: E731
+    return {"exp_steps": args.exp_steps, "rounds": args.rounds,
+            "additive_iteration_ms": [round(f(t_add), 4) for f in (med, min, max)],
+            "diffeomorphic_iteration_ms": [round(f(t_dif), 4) for f in (med, min, max)],
+            "diffeomorphic_over_additive": round(med(t_dif) / med(t_add), 3),
+            "compose_ms": [round(f(t_comp), 4) for f in (med, min, max)], "square_ms": round(med(t_sq), 4),
+            "compose_GBps": round(nbytes / med(t_comp) / 1e6, 1), "compose_copy_same_bytes_ms": round(med(t_copy), 4),
+            "compose_share_of_copy_rate": round(med(t_copy) / med(t_comp), 3)}
+
+
 def main(args):
     if not torch.cuda.is_available():
         raise SystemExit("this tool measures on an MI355X: no GPU found")
@@ -90,10 +130,11 @@ def main(args):
     taps = torch.from_numpy(gaussian_taps(args.sigma)).cuda()
     with torch.no_grad():
         t_torch = timed(lambda: torch_iteration(fixed, moving, u, taps, 2.0), max(args.iters // 5, 2), 2)
+    extra = diffeomorphic(args, fixed, moving, u, iteration) if args.diffeomorphic else {}
     result = {"size": n, "sigma": args.sigma, "iteration_ms": round(t_iter, 4), "force_ms": round(t_force, 4),
               "torch_iteration_ms": round(t_torch, 4), "speedup_over_torch": round(t_torch / t_iter, 2),
               "force_GBps": round(nbytes / t_force / 1e6, 1), "copy_same_bytes_ms": round(t_copy, 4),
-              "copy_GBps": round(nbytes / t_copy / 1e6, 1), "force_share_of_copy_rate": round(t_copy / t_force, 3)}
+              "copy_GBps": round(nbytes / t_copy / 1e6, 1), "force_share_of_copy_rate": round(t_copy / t_force, 3), **extra}
     print(json.dumps(result))
     return 0
 
@@ -104,6 +145,9 @@ def parse_args(argv=None):
     p.add_argument("--sigma", type=float, default=1.5)
     p.add_argument("--iters", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--diffeomorphic", action="store_true", help="also time the diffeomorphic iteration and the compose kernel")
+    p.add_argument("--exp_steps", type=int, default=2, help="--diffeomorphic: squarings of the exponential")
+    p.add_argument("--rounds", type=int, default=5, help="--diffeomorphic: alternating repetitions of every timing")
     p.add_argument("--reset_field", action="store_true", help="copy the random field back in before every iteration (adds a copy to the time)")
     return p.parse_args(argv)
 
