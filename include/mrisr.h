@@ -829,6 +829,40 @@ int mrisr_f32_volume_demons_update(const float* fixed, const float* moving, cons
 int mrisr_f32_volume_warp_matrix(const float* moving, int SX, int SY, int SZ, const float* u, int X, int Y, int Z, const double* m12,
                                  int method, float fill, float* out, void* stream);
 
+/* ---- Tissue classification and label overlap (extension; csrc/volume_tissue.hip): a K-class Gaussian mixture on a 256-bin
+ *      quantisation of the foreground with a Potts prior over the 6 face neighbours, minimised by iterated conditional modes in a
+ *      checkerboard order, and the confusion matrix of two label volumes.  A label volume is DEVICE uint8 (X, Y, Z) in C order: 0
+ *      outside the mask, 1..K inside, K in 2..6.  All arithmetic on voxels is integer except the bin of a voxel; the class
+ *      parameters and the cost table are the host's (mri_superresolution_amd/volume_tissue.py, the specification).  Counters are
+ *      DEVICE 64-bit words that the entries ACCUMULATE into: the caller clears them.  One launch each, no host synchronisation. -- */
+/* q_out[i] = the bin 0..255 of the DEVICE float32 vol[i], i < n, between range2 = (lo, hi) (DEVICE, 2 floats): scale = 256.f /
+ * (hi - lo), q = clip((int)((v - lo) * scale), 0, 255), every operation one rounded float32 operation, the conversion truncating;
+ * bit for bit volume_tissue.quantise_np.  hi == lo, or a width or a scale that is not finite (NaN bounds: an empty mask): every q is
+ * 0 and bit 0 of flags[0] is set.  hist256[b] += the voxels with q == b whose byte of mask (DEVICE uint8, n bytes) is non-zero.
+ * labels_out (optional, DEVICE uint8, n bytes) = 1 where mask is non-zero, else 0: the seed of mrisr_u8_volume_icm_half.  16-byte
+ * reads of vol and word accesses of the byte volumes where vol lies on 16 bytes and the others on 4, the scalar form otherwise.
+ * MRISR_E_ARG: a null or misaligned pointer, two of mask / q_out / labels_out the same; MRISR_E_SHAPE: n outside 1..2^32 - 1.    */
+int mrisr_f32_volume_quantise(const float* vol, const unsigned char* mask, size_t n, const float* range2, unsigned char* q_out,
+                              unsigned char* labels_out, unsigned long long* hist256, unsigned long long* flags, void* stream);
+/* joint[(l - 1) * 256 + b] += the voxels i < n with labels[i] == l in 1..K and q[i] == b (label 0 and labels above K are skipped);
+ * volume_tissue.joint_hist_np.  MRISR_E_ARG: null or misaligned pointer, K outside 2..6; MRISR_E_SHAPE as above.                 */
+int mrisr_u8_volume_joint_hist(const unsigned char* q, const unsigned char* labels, size_t n, int K, unsigned long long* joint,
+                               void* stream);
+/* One half-sweep in place, bit for bit volume_tissue.icm_half_np: every voxel with a non-zero label and (x + y + z) & 1 == colour
+ * takes the class k + 1 of the smallest cost[k * 256 + q] + beta_q * d_k in int32, ties to the smallest k; d_k = the number of its 6
+ * face neighbours inside the volume with a non-zero label other than k + 1.  cost: DEVICE int32[K * 256], entries in 0..2^30;
+ * beta_q in 0..16 * 2^16.  changed[0] += the labels that changed.  Voxels of the other colour and voxels with label 0 are not
+ * written with another value.  Word loads and stores where Z % 4 == 0 and q and labels lie on 4 bytes, bytes otherwise.
+ * MRISR_E_ARG: null or misaligned pointer, q == labels, K, beta_q or colour out of range; MRISR_E_SHAPE: an extent outside
+ * 1..32767.                                                                                                                      */
+int mrisr_u8_volume_icm_half(const unsigned char* q, unsigned char* labels, int X, int Y, int Z, int K, const int* cost, int beta_q,
+                             int colour, unsigned long long* changed, void* stream);
+/* conf[a[i] * (K + 1) + b[i]] += 1 for every i < n whose byte of mask is non-zero (mask NULL: every i) with both labels in 0..K;
+ * a voxel with a label above K adds to conf[(K + 1)^2] instead and is not tallied: conf has (K + 1)^2 + 1 words.
+ * volume_tissue.confusion_np.  MRISR_E_ARG: null or misaligned pointer, K outside 2..6; MRISR_E_SHAPE as above.                   */
+int mrisr_u8_volume_confusion(const unsigned char* a, const unsigned char* b, const unsigned char* mask, size_t n, int K,
+                              unsigned long long* conf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

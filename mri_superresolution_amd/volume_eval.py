@@ -588,16 +588,17 @@ class VolumeScores(OrderedDict):
     (the uint8 CUDA tensor every method was scored with), ``mask_count`` (its voxel count, 0-d float64 CUDA tensor) and
     ``mask_stats`` (``foreground_mask``'s (4,) float64 CUDA tensor lo, hi, t*, count for ``"otsu"``); all three ``None`` otherwise.
     ``mask_cleanup``: the (3,) float64 CUDA tensor [components found, kept size, voxels filled] of the mask's clean-up (NaN for a
-    step that is off), ``None`` when neither ``mask_largest`` nor ``mask_fill_holes`` is on."""
+    step that is off), ``None`` when neither ``mask_largest`` nor ``mask_fill_holes`` is on.  ``tissue_dice``: ``{method: (K,) float64
+    numpy array}`` with ``evaluate_volume(tissue_dice=K)``, else ``None``."""
 
     def __init__(self):
         super().__init__()
-        self.mask = self.mask_count = self.mask_stats = self.mask_cleanup = None
+        self.mask = self.mask_count = self.mask_stats = self.mask_cleanup = self.tissue_dice = None
 
 
 def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic: bool = False, axis: int = 2, val_range: float = None,
                     batch_size: int = 16, use_amp: bool = False, use_graph: bool = True, graph_cache: dict = None, mask=None,
-                    mask_close: int = 0, mask_largest: bool = False, mask_fill_holes=None) -> "VolumeScores":
+                    mask_close: int = 0, mask_largest: bool = False, mask_fill_holes=None, tissue_dice: int = 0) -> "VolumeScores":
     """Scores the U-Net and the interpolation baselines against the ground truth ``ref`` (float32 CUDA volume).
 
     The doubled axes are all three with ``isotropic``, else the two in-plane axes of the slices across ``axis``.  ``lr=None``
@@ -614,7 +615,12 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     volume, row 1 the foreground - and the returned ``VolumeScores`` carries ``.mask``, ``.mask_count`` and ``.mask_stats``.
     Without one nothing changes.  ``mask_largest`` / ``mask_fill_holes`` (``"3d"`` or an axis 0..2) clean the mask after the closing,
     ``"otsu"`` and a given tensor alike (``foreground_mask``'s ``largest`` / ``fill_holes``); ``.mask_cleanup`` then holds what they
-    found.  Both need a mask."""
+    found.  Both need a mask.
+
+    ``tissue_dice`` K in 2..6 (0: off; needs a mask): the reference and every method's output are segmented into K tissue classes
+    inside the mask (``volume_tissue.segment_tissue``, the reference once) and ``.tissue_dice`` is ``{method: (K,) float64 numpy array}``,
+    the Dice overlap of the method's classes with the reference's.  A last method ``reference`` - the reference scored against itself,
+    Dice 1 for every class it has - is then added as the check of the whole path."""
     # the checks that need no data come first, the device check after them
     if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or ref.dim() != 3 or ref.numel() == 0:
         raise ValueError(f"expected a non-empty float32 volume (X,Y,Z), got {getattr(ref, 'dtype', type(ref))} "
@@ -625,6 +631,11 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
         raise ValueError(f"batch_size must be positive, got {batch_size}")
     if val_range is not None and not val_range > 0:
         raise ValueError(f"val_range must be positive, got {val_range}")
+    if tissue_dice != 0:
+        from .volume_tissue import TissueWorkspace, _check_classes, dice, label_confusion, segment_tissue
+        _check_classes(tissue_dice)
+        if mask is None:
+            raise ValueError("tissue_dice needs a mask")
     if mask is None:
         if mask_close != 0:
             raise ValueError("mask_close needs a mask")
@@ -680,13 +691,26 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
             closed = binary_close(_check_mask(mask, ref.shape, "evaluate_volume"), mask_close)
             score["mask"], results.mask_cleanup = _clean_mask(closed, bool(mask_largest), fill)
         results.mask = score["mask"]
+    if tissue_dice:
+        tissue_ws = TissueWorkspace(ref.shape, tissue_dice, ref.device)
+        ref_labels = segment_tissue(ref, score["mask"], tissue_dice, workspace=tissue_ws).labels.clone()
+        results.tissue_dice = {}
+
+    def scored(method, out):
+        results[method] = volume_metrics(out, ref, val_range, **score)
+        if tissue_dice:
+            labels = segment_tissue(out.contiguous(), score["mask"], tissue_dice, workspace=tissue_ws).labels
+            results.tissue_dice[method] = dice(label_confusion(labels, ref_labels, score["mask"], tissue_dice))
+
     if isotropic:
-        results["unet"] = volume_metrics(enhance_volume_isotropic(model, lr, **common), ref, val_range, **score)
-        results["unet_axis2_linear"] = volume_metrics(enhance_volume_isotropic(model, lr, planes=(2,), **common), ref, val_range, **score)
+        scored("unet", enhance_volume_isotropic(model, lr, **common))
+        scored("unet_axis2_linear", enhance_volume_isotropic(model, lr, planes=(2,), **common))
     else:
-        results["unet"] = volume_metrics(enhance_volume(model, lr, axis=axis, **common), ref, val_range, **score)
+        scored("unet", enhance_volume(model, lr, axis=axis, **common))
     for method in ("linear", "cubic"):
-        results[method] = volume_metrics(upscale2(lr, method, axes), ref, val_range, **score)
+        scored(method, upscale2(lr, method, axes))
+    if tissue_dice:
+        scored("reference", ref)
     if mask is not None:
         results.mask_count = results["unet"].mask_count
     return results

@@ -76,6 +76,13 @@ displacement field estimated by Thirion's demons (``volume_deform.register_defor
 ``--match_intensity`` is warned about.  ``--deform_input diffeomorphic`` estimates the field by diffeomorphic demons instead
 (``volume_deform.register_diffeomorphic``, ``--deform_exp_steps`` squarings of an update's exponential): the update is composed with
 the field, not added, so the warped frame is not that of a folded field.  The default, ``none``, leaves a run as it was.
+
+``--tissue_dice K`` (2..6, with ``--mask``) asks what SSIM and PSNR answer only indirectly - whether a method keeps the anatomy: the
+reference and every method's output are segmented into K tissue classes inside the mask (``volume_tissue.segment_tissue``: a Gaussian
+mixture on 256 bins with a Potts prior, iterated conditional modes; ``csrc/volume_tissue.hip``), the reference once, and the Dice
+overlap per class, class 1 the darkest, is appended to the foreground tables and as the columns ``dice_1 ... dice_K`` to the CSV
+(empty in the rows of the whole volume).  A last row ``reference`` - the reference against itself, Dice 1 - checks the path.  The
+default, 0, leaves a run as it was.
 """
 import argparse
 import csv
@@ -106,6 +113,11 @@ CSV_COLUMNS_MASKED = ["scan", "region", "method", "ssim", "psnr", "mse", "rmse",
 REGIONS = ("whole", "foreground")
 
 
+def dice_columns(classes):
+    """The columns ``--tissue_dice K`` appends."""
+    return [f"dice_{k}" for k in range(1, classes + 1)]
+
+
 def load_mask(mask_path, ref, ref_affine=None):
     """-> one uint8 frame per timepoint of the reference (``utils.nifti.mask_frames``).  ``ref_affine`` (``--align``): the mask may
     lie on any grid and is resliced onto the reference's through the two affines with ``nearest``, on the device; the frames are
@@ -122,8 +134,13 @@ def load_mask(mask_path, ref, ref_affine=None):
 
 
 def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0,
-                  denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, deform_input="none", deform_exp_steps=2):
+                  denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, deform_input="none", deform_exp_steps=2,
+                  tissue_dice=0, mask=None):
     """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
+    if isinstance(tissue_dice, bool) or not isinstance(tissue_dice, int) or not (tissue_dice == 0 or 2 <= tissue_dice <= 6):
+        raise ValueError(f"--tissue_dice is 0 (off) or a number of classes in 2..6, got {tissue_dice}")
+    if tissue_dice and mask is None:
+        raise ValueError("--tissue_dice goes with --mask")
     if deform_input not in ("none", "demons", "diffeomorphic"):
         raise ValueError(f"--deform_input is none, demons or diffeomorphic, got {deform_input!r}")
     if isinstance(deform_exp_steps, bool) or not isinstance(deform_exp_steps, int) or not 0 <= deform_exp_steps <= MAX_EXP_STEPS:
@@ -220,7 +237,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
                match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
-               denoise_radius=3, deform_input="none", deform_exp_steps=2):
+               denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -232,9 +249,11 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     reference frame's intensity scale before any method sees it (module docstring); ``match_bias="pair"``: then its bias field is
     matched to the reference's (``prepare_input``).  ``denoise_input="nlm"``: every input frame is denoised on its own grid before
     anything else happens to it (``upload_input``).  ``deform_input="demons"``: after all of that every input frame is warped onto its
-    reference frame on the input's grid (``prepare_input``); ``"diffeomorphic"`` with ``deform_exp_steps`` likewise."""
+    reference frame on the input's grid (``prepare_input``); ``"diffeomorphic"`` with ``deform_exp_steps`` likewise.
+    ``tissue_dice`` K (needs ``mask``): the rows of the foreground carry ``dice_1 ... dice_K``, the Dice overlap of the method's tissue
+    classes with the reference's (``""`` in the rows of the whole volume), and a last method ``reference`` is scored."""
     check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
-                  denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps)
+                  denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask)
     noise_options = (denoise_input, denoise_sigma, denoise_beta, denoise_radius)
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
@@ -292,7 +311,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                                reference_path, deform_input, align_interp, deform_exp_steps)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
-                              mask_fill_holes=mask_fill_holes)
+                              mask_fill_holes=mask_fill_holes, tissue_dice=tissue_dice)
         scan = name if len(ref_frames) == 1 else f"{name}[t={t}]"
         if mask is None:
             values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
@@ -315,6 +334,9 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                 vals = down[10 * i + 5 * r:10 * i + 5 * r + 5]
                 rows.append({"scan": scan, "region": region, "method": method, **extra,
                              **dict(zip(METRIC_COLUMNS, (float(v) for v in vals)))})
+                if tissue_dice:
+                    overlap = res.tissue_dice[method]
+                    rows[-1].update({c: float(overlap[k]) if region == "foreground" else "" for k, c in enumerate(dice_columns(tissue_dice))})
     if save_mask:
         data = saved[0] if ref.ndim == 3 else np.stack(saved, axis=3)
         header = ref_header.copy()                              # the reference's, with the extents left after the crop
@@ -326,16 +348,20 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     return rows
 
 
-def format_table(title, rows):
-    lines = [title, f"{'method':18s} {'SSIM':>8s} {'PSNR':>8s} {'MSE':>12s} {'RMSE':>10s} {'MAE':>10s}"]
+def format_table(title, rows, dice=()):
+    """``dice``: the columns of ``--tissue_dice`` to append (the foreground tables)."""
+    lines = [title, f"{'method':18s} {'SSIM':>8s} {'PSNR':>8s} {'MSE':>12s} {'RMSE':>10s} {'MAE':>10s}" + "".join(f" {c:>8s}" for c in dice)]
     for r in rows:
-        lines.append(f"{r['method']:18s} {r['ssim']:8.4f} {r['psnr']:8.3f} {r['mse']:12.6g} {r['rmse']:10.6g} {r['mae']:10.6g}")
+        lines.append(f"{r['method']:18s} {r['ssim']:8.4f} {r['psnr']:8.3f} {r['mse']:12.6g} {r['rmse']:10.6g} {r['mae']:10.6g}"
+                     + "".join(f" {r[c]:8.4f}" for c in dice))
     return "\n".join(lines)
 
 
-def mean_rows(rows):
+def mean_rows(rows, dice=()):
+    """``dice``: the columns of ``--tissue_dice``, averaged like the metrics where the rows carry numbers (the foreground)."""
     methods = list(dict.fromkeys(r["method"] for r in rows))
-    return [{"scan": "mean", "method": m, **{k: float(np.mean([r[k] for r in rows if r["method"] == m])) for k in METRIC_COLUMNS}}
+    columns = list(METRIC_COLUMNS) + [c for c in dice if rows and rows[0][c] != ""]
+    return [{"scan": "mean", "method": m, **{c: "" for c in dice}, **{k: float(np.mean([r[k] for r in rows if r["method"] == m])) for k in columns}}
             for m in methods]
 
 
@@ -368,7 +394,7 @@ def main(args):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
         check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity, args.match_bias,
                       args.match_bias_sigma_mm, args.denoise_input, args.denoise_sigma, args.denoise_beta, args.denoise_radius,
-                      args.deform_input, args.deform_exp_steps)
+                      args.deform_input, args.deform_exp_steps, args.tissue_dice, args.mask)
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -385,6 +411,8 @@ def main(args):
         fill = args.mask_fill_holes if args.mask_fill_holes in (None, "3d") else int(args.mask_fill_holes)
         rows, graphs = [], {}
         regions = REGIONS if args.mask else (None,)
+        dice = dice_columns(args.tissue_dice)
+        shown = {"foreground": dice}                     # the tables of the whole volume stay as they are
         for path in args.reference:
             scan_rows = score_scan(model, path, input_path=args.input, isotropic=args.isotropic, axis=args.axis, data_range=args.data_range,
                                    batch_size=args.batch_size, use_amp=args.use_amp, use_graph=not args.no_graph, device=device,
@@ -394,24 +422,24 @@ def main(args):
                                    match=args.match_intensity, match_bias=args.match_bias, match_bias_sigma_mm=args.match_bias_sigma_mm,
                                    denoise_input=args.denoise_input, denoise_sigma=args.denoise_sigma, denoise_beta=args.denoise_beta,
                                    denoise_radius=args.denoise_radius, deform_input=args.deform_input,
-                                   deform_exp_steps=args.deform_exp_steps)
+                                   deform_exp_steps=args.deform_exp_steps, tissue_dice=args.tissue_dice)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
-                    print(format_table(foreground_title(part) if region == "foreground" else scan, part))
+                    print(format_table(foreground_title(part) if region == "foreground" else scan, part, shown.get(region, ())))
             rows += scan_rows
         means = []
         for region in regions:
             part = [r for r in rows if r.get("region") == region]
             title = f"mean over {len(set(r['scan'] for r in part))} scan(s)"
-            mean = mean_rows(part)
+            mean = mean_rows(part, dice)
             if region is not None:
                 mean = [{**r, "region": region} for r in mean]
-            print(format_table(f"foreground, {title}" if region == "foreground" else title, mean))
+            print(format_table(f"foreground, {title}" if region == "foreground" else title, mean, shown.get(region, ())))
             means += mean
         if args.output_csv:
             os.makedirs(os.path.dirname(os.path.abspath(args.output_csv)), exist_ok=True)
-            columns = CSV_COLUMNS_MASKED if args.mask else CSV_COLUMNS
+            columns = (CSV_COLUMNS_MASKED if args.mask else CSV_COLUMNS) + dice
             with open(args.output_csv, "w", newline="") as f:
                 wr = csv.DictWriter(f, fieldnames=columns)
                 wr.writeheader()
@@ -482,6 +510,9 @@ def parse_args(argv=None):
                         "intensity-difference force: use --match_intensity); diffeomorphic: the same with the update composed with the "
                         "field through its exponential, not added - a field that does not fold")
     p.add_argument("--deform_exp_steps", type=int, default=2, help="--deform_input diffeomorphic: squarings of an update's exponential, 0..8")
+    p.add_argument("--tissue_dice", type=int, default=0,
+                   help="segment the reference and every method's output into this many tissue classes (2..6) inside the mask and append "
+                        "the Dice overlap per class, dice_1 ... dice_K (needs --mask; 0: off)")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 
