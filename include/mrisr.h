@@ -863,6 +863,38 @@ int mrisr_u8_volume_icm_half(const unsigned char* q, unsigned char* labels, int 
 int mrisr_u8_volume_confusion(const unsigned char* a, const unsigned char* b, const unsigned char* mask, size_t n, int K,
                               unsigned long long* conf, void* stream);
 
+/* ---- Surface distances between label volumes (extension; csrc/volume_surface.hip): the boundary of a label volume, the exact
+ *      squared Euclidean distance transform of a voxel set with anisotropic voxel sizes, and the gather of one surface's distances
+ *      to another.  Volumes are DEVICE, (X, Y, Z) in C order; the specification is mri_superresolution_amd/volume_surface.py and
+ *      every entry is bit-equal to it.  No host synchronisation, no floating-point atomics. ---------------------------------- */
+/* out[v] = labels[v] where labels[v] != 0 and one of the 6 face neighbours differs, else 0 (volume_surface.boundary_np).
+ * background = 1: a neighbour differs if it lies outside the volume or carries another label, 0 included; background = 0: only if
+ * it lies inside the volume and carries another non-zero label.  above (optional, DEVICE 64-bit word, ACCUMULATED: the caller clears
+ * it) += the voxels with a label above classes (1..255).  One launch.  MRISR_E_ARG: null or misaligned pointer, labels == out,
+ * background or classes out of range; MRISR_E_SHAPE: an extent outside 1..32767.                                                 */
+int mrisr_u8_volume_label_boundary(const unsigned char* labels, int X, int Y, int Z, int background, int classes, unsigned char* out,
+                                   unsigned long long* above, void* stream);
+/* out = the squared distance of every voxel to the nearest site, float32, bit for bit volume_surface.edt_sq_np: a voxel is a site
+ * if sites[v] == value (value 0: if sites[v] != 0); g = 0 at the sites and +inf elsewhere, then along axis 2 (weight wz), 1 (wy), 0
+ * (wx):  g'[i] = min_j fl32(g[j] + fl32(w * fl32((i - j)^2))).  The weights are the squared voxel sizes, finite and positive.  No
+ * site: every voxel is +inf.  Three launches, in place in out, no scratch volume.  Every axis is at most 1024 (a line is staged in
+ * LDS).  passes = 7 is the transform; any other mask of the axes (bit a: the pass along axis a; 1..7) makes those passes alone, for
+ * measurement: the pass along axis 2 forms out from sites, the two others work on out as it is.  full_scan = 1 visits every
+ * candidate of a line (the form to measure against); 0 ends a walk once no candidate further out can be smaller: the same bits.
+ * MRISR_E_ARG: null or misaligned pointer, value outside 0..255, a weight that is not finite and positive, passes outside 1..7,
+ * full_scan not 0 or 1; MRISR_E_SHAPE: an extent outside 1..1024.                                                                 */
+int mrisr_u8_volume_edt_sq(const unsigned char* sites, int X, int Y, int Z, int value, float wx, float wy, float wz, float* out,
+                           int passes, int full_scan, void* stream);
+/* bytes of DEVICE workspace of mrisr_f32_volume_surface_gather (any volume size); no initialisation needed, 8-byte aligned.     */
+size_t mrisr_f32_volume_surface_workspace_bytes(void);
+/* For i < n: where query[i] == value (1..255), dist[i] = sqrtf(d2[i]) correctly rounded and sel[i] = 1; elsewhere both are 0.
+ * result (DEVICE, 3 words of 8 bytes, overwritten): [0] the count of selected voxels (int64), [1] the float64 sum of their finite
+ * distances, [2] their maximum as a float32 in the low 4 bytes (the high 4 are 0).  Per-workgroup partial results go to fixed slots
+ * of ws and a second launch adds them in ascending order: the same bits on every run.  MRISR_E_ARG: null or misaligned pointer,
+ * dist == d2, sel == query, value out of range; MRISR_E_SHAPE: n outside 1..2^32 - 1.                                             */
+int mrisr_f32_volume_surface_gather(const float* d2, const unsigned char* query, int value, size_t n, float* dist, unsigned char* sel,
+                                    void* ws, unsigned long long* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

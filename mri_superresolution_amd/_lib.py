@@ -197,10 +197,14 @@ SIGNATURES = {
     "mrisr_u8_volume_joint_hist": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
     "mrisr_u8_volume_icm_half": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "mrisr_u8_volume_confusion": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp]),
+    "mrisr_u8_volume_label_boundary": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mrisr_u8_volume_edt_sq": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _fp, _i, _i, _vp]),
+    "mrisr_f32_volume_surface_workspace_bytes": (_sz, []),
+    "mrisr_f32_volume_surface_gather": (_i, [_fp, _vp, _i, _sz, _fp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 323     # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 324    # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -589,16 +589,18 @@ class VolumeScores(OrderedDict):
     ``mask_stats`` (``foreground_mask``'s (4,) float64 CUDA tensor lo, hi, t*, count for ``"otsu"``); all three ``None`` otherwise.
     ``mask_cleanup``: the (3,) float64 CUDA tensor [components found, kept size, voxels filled] of the mask's clean-up (NaN for a
     step that is off), ``None`` when neither ``mask_largest`` nor ``mask_fill_holes`` is on.  ``tissue_dice``: ``{method: (K,) float64
-    numpy array}`` with ``evaluate_volume(tissue_dice=K)``, else ``None``."""
+    numpy array}`` with ``evaluate_volume(tissue_dice=K)``, else ``None``.  ``tissue_surface``: ``{method: volume_surface.SurfaceDistances}`` with
+    ``evaluate_volume(tissue_surface=True)``, else ``None``."""
 
     def __init__(self):
         super().__init__()
-        self.mask = self.mask_count = self.mask_stats = self.mask_cleanup = self.tissue_dice = None
+        self.mask = self.mask_count = self.mask_stats = self.mask_cleanup = self.tissue_dice = self.tissue_surface = None
 
 
 def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic: bool = False, axis: int = 2, val_range: float = None,
                     batch_size: int = 16, use_amp: bool = False, use_graph: bool = True, graph_cache: dict = None, mask=None,
-                    mask_close: int = 0, mask_largest: bool = False, mask_fill_holes=None, tissue_dice: int = 0) -> "VolumeScores":
+                    mask_close: int = 0, mask_largest: bool = False, mask_fill_holes=None, tissue_dice: int = 0, tissue_surface: bool = False,
+                    spacing=None) -> "VolumeScores":
     """Scores the U-Net and the interpolation baselines against the ground truth ``ref`` (float32 CUDA volume).
 
     The doubled axes are all three with ``isotropic``, else the two in-plane axes of the slices across ``axis``.  ``lr=None``
@@ -620,7 +622,11 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     ``tissue_dice`` K in 2..6 (0: off; needs a mask): the reference and every method's output are segmented into K tissue classes
     inside the mask (``volume_tissue.segment_tissue``, the reference once) and ``.tissue_dice`` is ``{method: (K,) float64 numpy array}``,
     the Dice overlap of the method's classes with the reference's.  A last method ``reference`` - the reference scored against itself,
-    Dice 1 for every class it has - is then added as the check of the whole path."""
+    Dice 1 for every class it has - is then added as the check of the whole path.
+
+    ``tissue_surface`` (needs ``tissue_dice``): ``.tissue_surface`` is ``{method: SurfaceDistances}``, the surface distances per class
+    between the tissue interfaces of the label volumes already made for Dice (``volume_surface.surface_distances`` with
+    ``background=False``: the mask's outer rim is the same on both sides), in the unit of ``spacing``, the three voxel sizes (None: 1)."""
     # the checks that need no data come first, the device check after them
     if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or ref.dim() != 3 or ref.numel() == 0:
         raise ValueError(f"expected a non-empty float32 volume (X,Y,Z), got {getattr(ref, 'dtype', type(ref))} "
@@ -636,6 +642,14 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
         _check_classes(tissue_dice)
         if mask is None:
             raise ValueError("tissue_dice needs a mask")
+    if tissue_surface:
+        from .volume_surface import SurfaceWorkspace, _check_spacing, surface_distances
+        if not tissue_dice:
+            raise ValueError("tissue_surface needs tissue_dice")
+        spacing = (1.0, 1.0, 1.0) if spacing is None else spacing
+        _check_spacing(spacing)
+    elif spacing is not None:
+        raise ValueError("spacing needs tissue_surface")
     if mask is None:
         if mask_close != 0:
             raise ValueError("mask_close needs a mask")
@@ -695,12 +709,17 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
         tissue_ws = TissueWorkspace(ref.shape, tissue_dice, ref.device)
         ref_labels = segment_tissue(ref, score["mask"], tissue_dice, workspace=tissue_ws).labels.clone()
         results.tissue_dice = {}
+    if tissue_surface:
+        surface_ws = SurfaceWorkspace(ref.shape, tissue_dice, ref.device)
+        results.tissue_surface = {}
 
     def scored(method, out):
         results[method] = volume_metrics(out, ref, val_range, **score)
         if tissue_dice:
             labels = segment_tissue(out.contiguous(), score["mask"], tissue_dice, workspace=tissue_ws).labels
             results.tissue_dice[method] = dice(label_confusion(labels, ref_labels, score["mask"], tissue_dice))
+            if tissue_surface:
+                results.tissue_surface[method] = surface_distances(labels, ref_labels, tissue_dice, spacing, False, surface_ws)
 
     if isotropic:
         scored("unet", enhance_volume_isotropic(model, lr, **common))

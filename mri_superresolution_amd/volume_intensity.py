@@ -169,11 +169,12 @@ def percentiles_workspace(nq: int, device) -> torch.Tensor:
     return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
 
 
-def masked_percentiles(vol: torch.Tensor, mask=None, percentiles=LANDMARKS, workspace=None):
+def masked_percentiles(vol: torch.Tensor, mask=None, percentiles=LANDMARKS, workspace=None, out=None):
     """vol: contiguous float32 CUDA tensor; mask: a uint8 or bool CUDA tensor of its shape (non-zero = counted) or None -> (float32
     CUDA tensor (L,), int64 CUDA tensor (1,)): the landmarks and the count of ``landmarks_np``, equal by value.  One quantile alone
     is allowed here.  The ranks are derived on the device from the device-side count: 9 launches, no host read, no synchronisation
-    (HIP-graph capturable when ``workspace`` - ``percentiles_workspace`` - is allocated before the capture)."""
+    (HIP-graph capturable when ``workspace`` - ``percentiles_workspace`` - is allocated before the capture).  ``out``: the pair of
+    result tensors to write into (contiguous, on the volume's device: float32 (L,) and int64 (1,)), so that nothing is allocated."""
     v = _check_vol(vol, "masked_percentiles")
     q = _check_percentiles(percentiles, least=1)
     m = None if mask is None else _check_mask(mask, v, "masked_percentiles")
@@ -184,8 +185,13 @@ def masked_percentiles(vol: torch.Tensor, mask=None, percentiles=LANDMARKS, work
     if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.is_contiguous() and ws.numel() * ws.element_size() >= need
             and ws.data_ptr() % 16 == 0):
         raise ValueError(f"the workspace must be a contiguous 16-byte aligned CUDA tensor of at least {need} bytes")
-    out = torch.empty(len(q), dtype=torch.float32, device=v.device)
-    count = torch.empty(1, dtype=torch.int64, device=v.device)
+    if out is None:
+        out, count = torch.empty(len(q), dtype=torch.float32, device=v.device), torch.empty(1, dtype=torch.int64, device=v.device)
+    else:
+        out, count = out
+        for t, dtype, n in ((out, torch.float32, len(q)), (count, torch.int64, 1)):
+            if not (isinstance(t, torch.Tensor) and t.device == v.device and t.dtype == dtype and tuple(t.shape) == (n,) and t.is_contiguous()):
+                raise ValueError(f"out is a pair of contiguous tensors on {v.device}: float32 ({len(q)},) and int64 (1,)")
     L.call("mrisr_f32_volume_masked_percentiles", v.data_ptr(), L.ptr(m), v.numel(), (L.C.c_double * len(q))(*q), len(q), out.data_ptr(),
            count.data_ptr(), ws.data_ptr(), L.stream_ptr())
     return out, count

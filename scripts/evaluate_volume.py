@@ -83,6 +83,13 @@ mixture on 256 bins with a Potts prior, iterated conditional modes; ``csrc/volum
 overlap per class, class 1 the darkest, is appended to the foreground tables and as the columns ``dice_1 ... dice_K`` to the CSV
 (empty in the rows of the whole volume).  A last row ``reference`` - the reference against itself, Dice 1 - checks the path.  The
 default, 0, leaves a run as it was.
+
+``--tissue_surface`` (with ``--tissue_dice K``) adds how far the boundaries between the tissue classes have moved, in millimetres: the
+average symmetric surface distance and the 95th-percentile Hausdorff distance per class between the method's and the reference's
+tissue interfaces (``volume_surface.surface_distances`` with ``background=False``: an exact Euclidean distance transform with the
+voxel sizes of the reference's header; ``csrc/volume_surface.hip``), as the columns ``assd_1 ... assd_K, hd95_1 ... hd95_K`` after the
+Dice columns (empty in the rows of the whole volume, 0 in the row ``reference``, NaN for a class without an interface).  Without the
+switch a run is as it was.
 """
 import argparse
 import csv
@@ -118,6 +125,16 @@ def dice_columns(classes):
     return [f"dice_{k}" for k in range(1, classes + 1)]
 
 
+def surface_columns(classes):
+    """The columns ``--tissue_surface`` appends after those of ``--tissue_dice K``."""
+    return [f"{name}_{k}" for name in ("assd", "hd95") for k in range(1, classes + 1)]
+
+
+def voxel_sizes(affine):
+    """The voxel sizes along the three array axes in world units: the lengths of the affine's columns."""
+    return tuple(float(x) for x in np.linalg.norm(np.asarray(affine, dtype=np.float64)[:3, :3], axis=0))
+
+
 def load_mask(mask_path, ref, ref_affine=None):
     """-> one uint8 frame per timepoint of the reference (``utils.nifti.mask_frames``).  ``ref_affine`` (``--align``): the mask may
     lie on any grid and is resliced onto the reference's through the two affines with ``nearest``, on the device; the frames are
@@ -135,12 +152,14 @@ def load_mask(mask_path, ref, ref_affine=None):
 
 def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0,
                   denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, deform_input="none", deform_exp_steps=2,
-                  tissue_dice=0, mask=None):
+                  tissue_dice=0, mask=None, tissue_surface=False):
     """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
     if isinstance(tissue_dice, bool) or not isinstance(tissue_dice, int) or not (tissue_dice == 0 or 2 <= tissue_dice <= 6):
         raise ValueError(f"--tissue_dice is 0 (off) or a number of classes in 2..6, got {tissue_dice}")
     if tissue_dice and mask is None:
         raise ValueError("--tissue_dice goes with --mask")
+    if tissue_surface and not tissue_dice:
+        raise ValueError("--tissue_surface goes with --tissue_dice")
     if deform_input not in ("none", "demons", "diffeomorphic"):
         raise ValueError(f"--deform_input is none, demons or diffeomorphic, got {deform_input!r}")
     if isinstance(deform_exp_steps, bool) or not isinstance(deform_exp_steps, int) or not 0 <= deform_exp_steps <= MAX_EXP_STEPS:
@@ -237,7 +256,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
                match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
-               denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0):
+               denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0, tissue_surface=False):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -251,9 +270,10 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     anything else happens to it (``upload_input``).  ``deform_input="demons"``: after all of that every input frame is warped onto its
     reference frame on the input's grid (``prepare_input``); ``"diffeomorphic"`` with ``deform_exp_steps`` likewise.
     ``tissue_dice`` K (needs ``mask``): the rows of the foreground carry ``dice_1 ... dice_K``, the Dice overlap of the method's tissue
-    classes with the reference's (``""`` in the rows of the whole volume), and a last method ``reference`` is scored."""
+    classes with the reference's (``""`` in the rows of the whole volume), and a last method ``reference`` is scored.
+    ``tissue_surface`` (needs ``tissue_dice``): those rows also carry ``surface_columns(K)``, in the world units of the reference's header."""
     check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
-                  denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask)
+                  denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask, tissue_surface)
     noise_options = (denoise_input, denoise_sigma, denoise_beta, denoise_radius)
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
@@ -311,7 +331,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                                reference_path, deform_input, align_interp, deform_exp_steps)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
-                              mask_fill_holes=mask_fill_holes, tissue_dice=tissue_dice)
+                              mask_fill_holes=mask_fill_holes, tissue_dice=tissue_dice, tissue_surface=tissue_surface,
+                              spacing=voxel_sizes(ref_header.affine()) if tissue_surface else None)
         scan = name if len(ref_frames) == 1 else f"{name}[t={t}]"
         if mask is None:
             values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
@@ -337,6 +358,10 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                 if tissue_dice:
                     overlap = res.tissue_dice[method]
                     rows[-1].update({c: float(overlap[k]) if region == "foreground" else "" for k, c in enumerate(dice_columns(tissue_dice))})
+                if tissue_surface:
+                    found = res.tissue_surface[method]
+                    values = [float(x) for x in found.assd] + [float(x) for x in found.hd95]
+                    rows[-1].update({c: v if region == "foreground" else "" for c, v in zip(surface_columns(tissue_dice), values)})
     if save_mask:
         data = saved[0] if ref.ndim == 3 else np.stack(saved, axis=3)
         header = ref_header.copy()                              # the reference's, with the extents left after the crop
@@ -349,7 +374,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
 
 
 def format_table(title, rows, dice=()):
-    """``dice``: the columns of ``--tissue_dice`` to append (the foreground tables)."""
+    """``dice``: the columns of ``--tissue_dice`` and ``--tissue_surface`` to append (the foreground tables)."""
     lines = [title, f"{'method':18s} {'SSIM':>8s} {'PSNR':>8s} {'MSE':>12s} {'RMSE':>10s} {'MAE':>10s}" + "".join(f" {c:>8s}" for c in dice)]
     for r in rows:
         lines.append(f"{r['method']:18s} {r['ssim']:8.4f} {r['psnr']:8.3f} {r['mse']:12.6g} {r['rmse']:10.6g} {r['mae']:10.6g}"
@@ -358,7 +383,7 @@ def format_table(title, rows, dice=()):
 
 
 def mean_rows(rows, dice=()):
-    """``dice``: the columns of ``--tissue_dice``, averaged like the metrics where the rows carry numbers (the foreground)."""
+    """``dice``: the columns of ``--tissue_dice`` and ``--tissue_surface``, averaged like the metrics where the rows carry numbers (the foreground)."""
     methods = list(dict.fromkeys(r["method"] for r in rows))
     columns = list(METRIC_COLUMNS) + [c for c in dice if rows and rows[0][c] != ""]
     return [{"scan": "mean", "method": m, **{c: "" for c in dice}, **{k: float(np.mean([r[k] for r in rows if r["method"] == m])) for k in columns}}
@@ -394,7 +419,7 @@ def main(args):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
         check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity, args.match_bias,
                       args.match_bias_sigma_mm, args.denoise_input, args.denoise_sigma, args.denoise_beta, args.denoise_radius,
-                      args.deform_input, args.deform_exp_steps, args.tissue_dice, args.mask)
+                      args.deform_input, args.deform_exp_steps, args.tissue_dice, args.mask, args.tissue_surface)
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -411,7 +436,7 @@ def main(args):
         fill = args.mask_fill_holes if args.mask_fill_holes in (None, "3d") else int(args.mask_fill_holes)
         rows, graphs = [], {}
         regions = REGIONS if args.mask else (None,)
-        dice = dice_columns(args.tissue_dice)
+        dice = dice_columns(args.tissue_dice) + (surface_columns(args.tissue_dice) if args.tissue_surface else [])
         shown = {"foreground": dice}                     # the tables of the whole volume stay as they are
         for path in args.reference:
             scan_rows = score_scan(model, path, input_path=args.input, isotropic=args.isotropic, axis=args.axis, data_range=args.data_range,
@@ -422,7 +447,8 @@ def main(args):
                                    match=args.match_intensity, match_bias=args.match_bias, match_bias_sigma_mm=args.match_bias_sigma_mm,
                                    denoise_input=args.denoise_input, denoise_sigma=args.denoise_sigma, denoise_beta=args.denoise_beta,
                                    denoise_radius=args.denoise_radius, deform_input=args.deform_input,
-                                   deform_exp_steps=args.deform_exp_steps, tissue_dice=args.tissue_dice)
+                                   deform_exp_steps=args.deform_exp_steps, tissue_dice=args.tissue_dice,
+                                   tissue_surface=args.tissue_surface)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -513,6 +539,9 @@ def parse_args(argv=None):
     p.add_argument("--tissue_dice", type=int, default=0,
                    help="segment the reference and every method's output into this many tissue classes (2..6) inside the mask and append "
                         "the Dice overlap per class, dice_1 ... dice_K (needs --mask; 0: off)")
+    p.add_argument("--tissue_surface", action="store_true",
+                   help="append the surface distances per class between every method's and the reference's tissue interfaces in mm: "
+                        "assd_1 ... assd_K, hd95_1 ... hd95_K (needs --tissue_dice)")
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 

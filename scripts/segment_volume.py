@@ -12,7 +12,8 @@ minimised by at most ``--iterations`` sweeps of iterated conditional modes (``vo
 wired as there; ``--mask PATH`` reads it from a NIfTI-1 file of the input's spatial shape (non-zero = inside; a 3-D mask serves every
 timepoint).  The labels are written as uint8 under the input's header, 0 outside the mask, a 4-D file timepoint by timepoint; the
 class means, the voxel counts and the sweeps are logged per frame.  ``--compare`` prints the Dice overlap per class with another
-label file of the same shape, inside the mask.  Exit code 0 / 1 (error logged), as ``scripts/reslice_volume.py``.
+label file of the same shape, inside the mask, and the surface distances per class between the two label volumes in the world units
+of the input's header: ASSD, HD95 and HD (``volume_surface.surface_distances``).  Exit code 0 / 1 (error logged), as ``scripts/reslice_volume.py``.
 """
 import argparse
 import logging
@@ -29,7 +30,8 @@ if REPO not in sys.path:
 from mri_superresolution_amd.utils.nifti import frames, read_nifti, write_nifti      # noqa: E402
 from mri_superresolution_amd.volume_eval import foreground_mask                      # noqa: E402
 from mri_superresolution_amd.volume_tissue import TissueWorkspace, dice, label_confusion, segment_tissue      # noqa: E402
-from scripts.evaluate_volume import load_mask                                        # noqa: E402
+from mri_superresolution_amd.volume_surface import SurfaceWorkspace, surface_distances                      # noqa: E402
+from scripts.evaluate_volume import load_mask, voxel_sizes                                        # noqa: E402
 
 logger = logging.getLogger("segment_volume")
 
@@ -51,6 +53,7 @@ def segment_file(input_path, output_path, classes=3, beta=1.0, iterations=20, ma
         if not np.array_equal(other, np.clip(np.rint(other), 0, 255)):
             raise ValueError(f"{compare} does not hold labels 0..255")
     ws = TissueWorkspace(data.shape[:3], classes, device)
+    surface_ws = SurfaceWorkspace(data.shape[:3], classes, device) if compare is not None else None
     outs, overlaps = [], []
     for t, frame in enumerate(frames(data)):
         vol = torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(device)
@@ -64,6 +67,9 @@ def segment_file(input_path, output_path, classes=3, beta=1.0, iterations=20, ma
             theirs = torch.from_numpy(np.ascontiguousarray(frames(other)[t]).astype(np.uint8)).to(device)
             overlaps.append(dice(label_confusion(found.labels, theirs, m, classes)))
             print(f"{what} Dice against {compare}: " + "  ".join(f"class {k + 1} {d:.6f}" for k, d in enumerate(overlaps[-1])))
+            far = surface_distances(found.labels, theirs, classes, voxel_sizes(header.affine()), workspace=surface_ws)
+            for name, values in (("ASSD", far.assd), ("HD95", far.hd95), ("HD", far.hd)):
+                print(f"{what} {name} against {compare}: " + "  ".join(f"class {k + 1} {d:.6f}" for k, d in enumerate(values)))
         outs.append(found.labels.cpu().numpy())
     result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
     os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
