@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(os.path.dirname(HERE), "build", "mrisr")
 LIB = os.path.join(HERE, "libmrisr.so")
-SOURCES = ["api.cpp", "conv_fwd.hip", "conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_pack.hip", "conv_ring.hip", "conv_pc.hip", "conv1x1.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_upadj.hip", "norm.hip", "head_stem.hip", "loss.hip", "optim.hip", "vgg.hip", "image.hip", "evalops.hip", "lowfield.hip", "percentile.hip", "resample.hip", "volume_blend.hip", "volume_eval.hip", "volume_label.hip", "volume_mask.hip", "volume_metrics.hip", "volume_reslice.hip", "volume_register.hip", "volume_intensity.hip", "volume_bias.hip", "volume_denoise.hip", "volume_deform.hip", "volume_tissue.hip", "volume_surface.hip"]
+SOURCES = ["api.cpp", "conv_fwd.hip", "conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_pack.hip", "conv_ring.hip", "conv_pc.hip", "conv1x1.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_upadj.hip", "norm.hip", "norm_bwd.hip", "norm_bwd_onepass.hip", "norm_bwd_shuffle.hip", "head_stem.hip", "loss.hip", "optim.hip", "vgg.hip", "image.hip", "evalops.hip", "lowfield.hip", "percentile.hip", "resample.hip", "volume_blend.hip", "volume_eval.hip", "volume_label.hip", "volume_mask.hip", "volume_metrics.hip", "volume_reslice.hip", "volume_register.hip", "volume_intensity.hip", "volume_bias.hip", "volume_denoise.hip", "volume_deform.hip", "volume_tissue.hip", "volume_surface.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # conv_igemm_*.hip (the classic forward kernel) and conv_pack.hip (the packers, once in one file with it): no SLP

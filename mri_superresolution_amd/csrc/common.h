@@ -202,3 +202,34 @@ __device__ __forceinline__ unsigned noise_key(unsigned long long seed) {
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ---------------------------------------------------------------- host-side launch helpers
+// f(tag) with  typename decltype(tag)::type  = the storage type of `dtype`; false (and no call) for a dtype that is not
+// among the ones served.  with_dtype16: the entries that take 16-bit storage only.
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> static inline bool with_dtype16(int dtype, F&& f) {
+    if (dtype == MRISR_BF16) f(TypeTag<bf16_t>{});
+    else if (dtype == MRISR_F16) f(TypeTag<f16_t>{});
+    else return false;
+    return true;
+}
+template <typename F> static inline bool with_dtype(int dtype, F&& f) {
+    if (with_dtype16(dtype, f)) return true;
+    if (dtype != MRISR_F32) return false;
+    f(TypeTag<float>{});
+    return true;
+}
+
+// Blocking of the element-wise kernels whose block is (item range, image, channel slice of 256 16-byte vectors) and whose
+// thread is (item lane, channel vector): 256 / nvec lanes, each taking `per_lane` items (pixels, windows, groups) of a
+// full block.  The lane count follows the widest slice; an image smaller than one block is covered by one block.
+struct PixelBlocks {
+    int per_block;      // items per block: the kernel's pix_per_block
+    dim3 grid;
+};
+static inline PixelBlocks pixel_blocks(int items, int N, int C, int vec, int per_lane) {
+    const int nslice = ceil_div(C / vec, 256), nvec = nslice > 1 ? 256 : C / vec, lanes = 256 / nvec;
+    int per_block = lanes * per_lane;
+    if (per_block > items) per_block = ceil_div(items, lanes) * lanes;
+    return PixelBlocks{per_block, dim3(ceil_div(items, per_block), N, nslice)};
+}

@@ -334,7 +334,7 @@ extern "C" int mrisr_head_forward(int dtype, const void* x, const float* scale, 
 // Thread = (pixel lane, 16-byte channel vector): a wave reads / writes whole pixel rows (C*sizeof(T) contiguous
 // bytes per pixel), so x is fetched once and da is written in full lines (a thread-per-pixel loop over channel
 // vectors re-fetched every line C/VEC times: 1.2 GB read for a 268 MB tensor).
-// (The network's own one-channel head does not come through here in training: norm.hip's GroupNorm-backward passes form
+// (The network's own one-channel head does not come through here in training: norm_bwd.hip's GroupNorm-backward passes form
 // dz * w on the fly.  This is the stand-alone form, and the one the engine uses for out_channels > 1.)
 template <typename T, int K>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ x, const float* __restrict__ scale,

@@ -501,7 +501,7 @@ class UNetEngine:
 
             def onepass():
                 # plain consumers of the node's own geometry (or a 2x2-pooled node on even dims): ONE launch that reads x and the
-                # consumer gradients once and keeps them in registers across an in-kernel image barrier (csrc/norm.hip:
+                # consumer gradients once and keeps them in registers across an in-kernel image barrier (csrc/norm_bwd_onepass.hip:
                 # act_bwd_onepass_kernel / act_bwd_onepass_window_kernel)
                 arrive = red[SL * N * Cn * 2 + 256:SL * N * Cn * 2 + 256 + narr]
                 f = L.GnBwdFin(*gn, None, None, None, count, 1.0, GN_GROUPS)
@@ -552,7 +552,7 @@ class UNetEngine:
             def blend_pair():
                 # the two branches of the alpha blend, reached at the pixel-shuffled one: each has one consumer, and it is the same
                 # tensor (final_conv.0's dain), so both nodes go through the two passes TOGETHER and each pass reads that tensor once
-                # (csrc/norm.hip: act_bwd_blend_reduce_kernel / act_bwd_blend_apply_kernel).  The plain branch's dx waits in blend_dx
+                # (csrc/norm_bwd_shuffle.hip: act_bwd_blend_reduce_kernel / act_bwd_blend_apply_kernel).  The plain branch's dx waits in blend_dx
                 # for that node's own node_backward call.  None = not this case: the per-node launches below
                 sib = self._blend_sibling.get(n)
                 if sib is None or not (fused_ps and blend_branch) or sib.shuffled or sib.C != Cn or (c0.C_total, c0.c_off) != (Cn, 0):

@@ -1,4 +1,4 @@
-"""GroupNorm(8, C) + LeakyReLU(0.2) backward (csrc/norm.hip): a float64 specification with derived error bounds, inputs
+"""GroupNorm(8, C) + LeakyReLU(0.2) backward (csrc/norm_bwd*.hip): a float64 specification with derived error bounds, inputs
 under which the mean terms of the backward are as large as the direct term, and a float32 restatement of the kernels'
 arithmetic with switchable defects ("mutants").  Helper module of test_norm_bwd_host.py and test_gpu_norm_bwd.py.
 

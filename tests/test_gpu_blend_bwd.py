@@ -1,4 +1,4 @@
-"""csrc/norm.hip: the GroupNorm + LeakyReLU backward of the two alpha-blend branches in ONE pair of launches
+"""csrc/norm_bwd_shuffle.hip: the GroupNorm + LeakyReLU backward of the two alpha-blend branches in ONE pair of launches
 (mrisr_act_bwd_blend_reduce / mrisr_act_bwd_blend_apply: the shared gradient of the blended tensor is read once per pass),
 against a float64 CPU restatement and against the four launches it replaces (mrisr_act_bwd_reduce twice,
 mrisr_act_bwd_apply_fused_unshuffle, mrisr_act_bwd_apply_fused).  Weights as the engine registers them

@@ -599,7 +599,7 @@ def test_act_backward(dt, mode):
 @pytest.mark.parametrize("dt", [L.BF16, L.F16])
 @pytest.mark.parametrize("case", ["one_block", "many_blocks", "two_consumers", "tail_block", "wide", "pool", "pool+skip", "pool_tail"])
 def test_act_backward_onepass(dt, case):
-    """mrisr_act_bwd_onepass (csrc/norm.hip: act_bwd_onepass_kernel, in-kernel image barrier): GroupNorm + LeakyReLU backward
+    """mrisr_act_bwd_onepass (csrc/norm_bwd_onepass.hip: act_bwd_onepass_kernel, in-kernel image barrier): GroupNorm + LeakyReLU backward
     of a node with plain consumers of its own geometry in ONE launch, against autograd of F.group_norm + F.leaky_relu
     (unet_model.py:30-31) and against the two-pass kernels on the same operands.  many_blocks: 64 blocks per image, 6 images
     (the barrier is crossed by many blocks on different XCDs); two_consumers: skip concat window (c_off) + a second plain

@@ -1,4 +1,4 @@
-"""csrc/norm.hip: every launch sequence of the GroupNorm + LeakyReLU backward against the float64 specification of normbwdutil
+"""csrc/norm_bwd*.hip: every launch sequence of the GroupNorm + LeakyReLU backward against the float64 specification of normbwdutil
 under its DERIVED bounds (store rounding, float32 evaluation, float32 summation - see that module's docstring), on inputs under
 which the mean terms x B + C are as large as g A: upstream gradients of non-zero mean that follow xhat, gamma of mixed sign and
 exactly zero, 2x2 windows with tied maxima, and pre exactly zero.  test_norm_bwd_host.py proves on the same inputs that a
