@@ -376,15 +376,16 @@ int mrisr_feature_loss(int dtype, const void* a, const void* b, size_t n, int ki
                        void* da, int relu_gate, void* stream);
 
 /* ---- optimiser: torch.optim.Adam with L2-coupled weight decay (scripts/train.py:186) ------- */
-/* grad_scale multiplies g first (1/world_size after a sum all-reduce).                        */
-int mrisr_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1,
-                    float beta2, float eps, float weight_decay, int step, float grad_scale,
+/* grad_scale multiplies g first (1/world_size after a sum all-reduce).  beta1, beta2 are doubles: the kernels use
+ * (float)beta and (float)(1 - beta), as torch does on fp32 tensors (1 - (float)0.999 would be 1.3e-5 off 0.001).      */
+int mrisr_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, double beta1,
+                    double beta2, float eps, float weight_decay, int step, float grad_scale,
                     void* stream);
 /* The same update under torch.amp.GradScaler's device-side contract (fp16 autocast, scripts/train.py:303-311):
  * gradients are multiplied by grad_mul / *loss_scale_device, the update is skipped when *found_inf_device != 0, and
  * the bias-correction step count *step_device (int32 on the device, starts at 0) advances only when the update ran.
  * loss_scale_device / found_inf_device may be NULL (= 1 / never).  No host read-back.                              */
-int mrisr_adam_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+int mrisr_adam_step_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, double beta1, double beta2,
                         float eps, float weight_decay, int* step_device, float grad_mul,
                         const float* loss_scale_device, const float* found_inf_device, void* stream);
 

@@ -136,8 +136,8 @@ SIGNATURES = {
     "mrisr_maxpool2_forward": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mrisr_maxpool2_backward": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mrisr_feature_loss": (_i, [_i, _vp, _vp, _sz, _i, _dp, _fp, _vp, _i, _vp]),
-    "mrisr_adam_step": (_i, [_fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _i, _f, _vp]),
-    "mrisr_adam_step_amp": (_i, [_fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _vp, _f, _fp, _fp, _vp]),
+    "mrisr_adam_step": (_i, [_fp, _fp, _fp, _fp, _sz, _f, _d, _d, _f, _f, _i, _f, _vp]),
+    "mrisr_adam_step_amp": (_i, [_fp, _fp, _fp, _fp, _sz, _f, _d, _d, _f, _f, _vp, _f, _fp, _fp, _vp]),
     "mrisr_u8_histogram": (_i, [_vp, _sz, _i, _vp, _vp]),
     "mrisr_u8_percentile_normalise": (_i, [_vp, _vp, _sz, _i, _d, _d, _fp, _fp, _vp]),
     "mrisr_f32_to_u8": (_i, [_fp, _vp, _sz, _vp]),
@@ -204,7 +204,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 324    # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 325    # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():
