@@ -820,6 +820,18 @@ int mrisr_f32_volume_field_compose(const float* u, const float* v, int X, int Y,
  * MRISR_E_ARG: as there, and scale not finite and positive; MRISR_E_SHAPE as there.                                                */
 int mrisr_f32_volume_demons_update(const float* fixed, const float* moving, const float* u, int X, int Y, int Z, float max_step,
                                    float fill, float scale, float* w, void* workspace, void* stats_row, void* stream);
+/* Demons across contrasts (csrc/volume_lcc.hip): the locally normalised correlation force, bit for bit volume_deform.lcc_force_np
+ * (update 0: v = u + upd) and lcc_update_np (update 1: v = upd * scale).  warped is mrisr_f32_volume_warp(moving, u, LINEAR) with a
+ * NaN fill; a voxel is valid where fixed and warped are finite.  Window sums of 1, F, M, F F, M M, F M in float64 over the cube of
+ * radius voxels either side (clipped to the grid, invalid voxels left out), separable along axis 2, 1, 0, ascending, each sum
+ * starting at +0.0; mF = sF / n, mM = sM / n, A = sFM - mM sF, B = sFF - mF sF, C = sMM - mM sM; d = (M - mM)(B / A) - (F - mF) and
+ * w = min(A A / (B C), 1), both rounded to float32, 0 unless the voxel is valid, n >= 2, B > 0, C > 0, A != 0 and both are finite;
+ * then the rule of mrisr_f32_volume_demons_force with s = (d / den) w.  One launch; workspace and stats_row as there: the row is
+ * (the sum of (double)w over the voxels that passed, their count).  The same bits on every run, no floating-point atomics, no host
+ * synchronisation.  MRISR_E_ARG: null or misaligned pointer, max_step or scale out of range, update not 0 or 1, v equal to an input;
+ * MRISR_E_SHAPE: radius outside 1..4, an extent below 1, more than 2^31 - 1 voxels.                                                */
+int mrisr_f32_volume_lcc_force(const float* fixed, const float* warped, const float* u, int X, int Y, int Z, int radius, float max_step,
+                               float scale, int update, float* v, void* workspace, void* stats_row, void* stream);
 /* out (X, Y, Z) = moving (SX, SY, SZ) at M (x + u(x)): ONE interpolation through a field on the fixed grid and the 3 x 4 matrix
  * m12 (HOST, row-major doubles, fixed index -> moving index: the matrix of mrisr_f32_volume_reslice).  q_a = (double)i_a +
  * (double)u_a; p_a = ((m[a][0] q_0 + m[a][1] q_1) + m[a][2] q_2) + m[a][3]; then the inside test on moving's extents, the taps and

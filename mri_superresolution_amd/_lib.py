@@ -193,6 +193,7 @@ SIGNATURES = {
     "mrisr_f32_volume_field_compose": (_i, [_fp, _fp, _i, _i, _i, _fp, _vp]),
     "mrisr_f32_volume_demons_update": (_i, [_fp, _fp, _fp, _i, _i, _i, _f, _f, _f, _fp, _vp, _vp, _vp]),
     "mrisr_f32_volume_warp_matrix": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, _f, _fp, _vp]),
+    "mrisr_f32_volume_lcc_force": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _f, _f, _i, _fp, _vp, _vp, _vp]),
     "mrisr_f32_volume_quantise": (_i, [_fp, _vp, _sz, _fp, _vp, _vp, _vp, _vp, _vp]),
     "mrisr_u8_volume_joint_hist": (_i, [_vp, _vp, _sz, _i, _vp, _vp]),
     "mrisr_u8_volume_icm_half": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
@@ -204,7 +205,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 325    # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 326    # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

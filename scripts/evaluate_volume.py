@@ -73,7 +73,9 @@ run as it was.
 every input frame is warped onto ``downsample2`` of its reference frame (the input's grid, or the grid ``--align`` implies) through a
 displacement field estimated by Thirion's demons (``volume_deform.register_deformable``; ``csrc/volume_deform.hip``) with
 ``--align_interp``: the frame is then interpolated twice.  The force is an intensity difference, so a run without
-``--match_intensity`` is warned about.  ``--deform_input diffeomorphic`` estimates the field by diffeomorphic demons instead
+``--match_intensity`` is warned about.  ``--deform_force lcc`` (``--deform_lcc_radius``) takes the force across contrasts instead
+(``volume_deform.lcc_force``; ``csrc/volume_lcc.hip``): every window of the scans gets its own affine intensity relation, so neither a
+common intensity scale nor that warning is needed, and the log reports ``1 - mean rho^2``.  ``--deform_input diffeomorphic`` estimates the field by diffeomorphic demons instead
 (``volume_deform.register_diffeomorphic``, ``--deform_exp_steps`` squarings of an update's exponential): the update is composed with
 the field, not added, so the warped frame is not that of a folded field.  The default, ``none``, leaves a run as it was.
 
@@ -107,7 +109,7 @@ if REPO not in sys.path:
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
 from mri_superresolution_amd.utils.nifti import downscaled_affine, frames, grid_matrix, mask_frames, read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_bias import match_bias as match_bias_field, sigmas_for                  # noqa: E402
-from mri_superresolution_amd.volume_deform import MAX_EXP_STEPS, register_deformable, register_diffeomorphic      # noqa: E402
+from mri_superresolution_amd.volume_deform import MAX_EXP_STEPS, MAX_LCC_RADIUS, register_deformable, register_diffeomorphic      # noqa: E402
 from mri_superresolution_amd.volume_denoise import denoise_volume                                             # noqa: E402
 from mri_superresolution_amd.volume_eval import downsample2, evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity    # noqa: E402
@@ -152,7 +154,7 @@ def load_mask(mask_path, ref, ref_affine=None):
 
 def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0,
                   denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, deform_input="none", deform_exp_steps=2,
-                  tissue_dice=0, mask=None, tissue_surface=False):
+                  tissue_dice=0, mask=None, tissue_surface=False, deform_force="ssd", deform_lcc_radius=2):
     """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
     if isinstance(tissue_dice, bool) or not isinstance(tissue_dice, int) or not (tissue_dice == 0 or 2 <= tissue_dice <= 6):
         raise ValueError(f"--tissue_dice is 0 (off) or a number of classes in 2..6, got {tissue_dice}")
@@ -166,6 +168,12 @@ def check_options(input_path, align, align_interp, align_init, align_mask, match
         raise ValueError(f"--deform_exp_steps must be an integer in 0..{MAX_EXP_STEPS}, got {deform_exp_steps}")
     if deform_input != "none" and not input_path:
         raise ValueError("--deform_input goes with --input")
+    if deform_force not in ("ssd", "lcc"):
+        raise ValueError(f"--deform_force is ssd or lcc, got {deform_force!r}")
+    if deform_force == "lcc" and deform_input == "none":
+        raise ValueError("--deform_force lcc goes with --deform_input demons or diffeomorphic")
+    if isinstance(deform_lcc_radius, bool) or not isinstance(deform_lcc_radius, int) or not 1 <= deform_lcc_radius <= MAX_LCC_RADIUS:
+        raise ValueError(f"--deform_lcc_radius must be an integer in 1..{MAX_LCC_RADIUS}, got {deform_lcc_radius}")
     if denoise_input not in ("none", "nlm"):
         raise ValueError(f"--denoise_input is none or nlm, got {denoise_input!r}")
     if denoise_input != "none" and not input_path:
@@ -220,13 +228,14 @@ def low_reference(lr, vol, axes, option):
 
 
 def prepare_input(lr, vol, match="none", match_bias="none", axes=(0, 1, 2), sigmas_vox=None, what="input", reference="its reference",
-                  deform="none", deform_interp="linear", deform_exp_steps=2):
+                  deform="none", deform_interp="linear", deform_exp_steps=2, deform_force="ssd", deform_lcc_radius=2):
     """What ``--match_intensity``, ``--match_bias`` and ``--deform_input`` do to one input frame ``lr`` next to its reference frame
     ``vol`` (CUDA tensors) -> the frame every method sees.  ``match`` first, then ``match_bias="pair"`` against
     ``downsample2(vol, axes)`` - the reference on the input's grid - with ``sigmas_vox`` on that grid, then ``deform="demons"``: a
     displacement field against that same low reference (``volume_deform.register_deformable``), the frame warped through it with
     ``deform_interp``; ``deform="diffeomorphic"``: the field of ``volume_deform.register_diffeomorphic`` with ``deform_exp_steps``.
-    All ``"none"``: ``lr`` itself."""
+    ``deform_force="lcc"``: either registration with the force across contrasts (``volume_deform.lcc_force_np``, windows of
+    ``deform_lcc_radius`` voxels either side), which needs no common intensity scale.  All ``"none"``: ``lr`` itself."""
     if match != "none":
         lr, found = match_intensity(lr, vol, foreground_mask(lr)[0], foreground_mask(vol)[0], LANDMARKS if match == "landmarks" else RANGE)
         marks = "  ".join(f"{q:g}%: {a:.6g} -> {b:.6g}" for q, a, b in zip(found.percentiles, found.source_landmarks, found.target_landmarks))
@@ -237,16 +246,21 @@ def prepare_input(lr, vol, match="none", match_bias="none", axes=(0, 1, 2), sigm
         lr = match_bias_field(lr, low_ref, foreground_mask(lr)[0], foreground_mask(low_ref)[0], sigmas_vox, want_field=False)[0]
         logger.info(f"{what}: bias field matched to that of {reference} (sigmas {tuple(round(float(x), 3) for x in sigmas_vox)} voxels)")
     if deform != "none":
-        if match == "none":
+        chosen = dict(force=deform_force, lcc_radius=deform_lcc_radius) if deform_force != "ssd" else {}
+        if match == "none" and deform_force != "lcc":
             logger.warning("--deform_input without --match_intensity: the demons force is an intensity difference, and the two scans "
                            "are not on one intensity scale.")
         if deform == "diffeomorphic":
-            found = register_diffeomorphic(low_reference(lr, vol, axes, "--deform_input"), lr, method=deform_interp, exp_steps=deform_exp_steps)
+            found = register_diffeomorphic(low_reference(lr, vol, axes, "--deform_input"), lr, method=deform_interp, exp_steps=deform_exp_steps,
+                                           **chosen)
         else:
-            found = register_deformable(low_reference(lr, vol, axes, "--deform_input"), lr, method=deform_interp)
+            found = register_deformable(low_reference(lr, vol, axes, "--deform_input"), lr, method=deform_interp, **chosen)
         first, last = found.stats[0], found.stats[-1]
-        logger.info(f"{what} warped onto {reference} ({deform}, {deform_interp}): mean squared difference {first[0] / max(first[1], 1):.6g} -> "
-                    f"{last[0] / max(last[1], 1):.6g} over {len(found.stats)} iterations on {len(found.schedule)} level(s); minimum Jacobian "
+        if deform_force == "lcc":
+            cost = f"1 - mean rho^2 {1.0 - first[0] / max(first[1], 1):.6g} -> {1.0 - last[0] / max(last[1], 1):.6g}"
+        else:
+            cost = f"mean squared difference {first[0] / max(first[1], 1):.6g} -> {last[0] / max(last[1], 1):.6g}"
+        logger.info(f"{what} warped onto {reference} ({deform}, {deform_interp}): {cost} over {len(found.stats)} iterations on {len(found.schedule)} level(s); minimum Jacobian "
                     f"determinant {found.jacobian[0]:.4f}, {found.jacobian[1]} voxel(s) not positive")
         lr = found.warped
     return lr
@@ -256,7 +270,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                use_graph=True, device="cuda", graph_cache=None, mask=None, mask_close=0, mask_largest=False, mask_fill_holes=None,
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
                match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
-               denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0, tissue_surface=False):
+               denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0, tissue_surface=False, deform_force="ssd",
+               deform_lcc_radius=2):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -268,12 +283,14 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     reference frame's intensity scale before any method sees it (module docstring); ``match_bias="pair"``: then its bias field is
     matched to the reference's (``prepare_input``).  ``denoise_input="nlm"``: every input frame is denoised on its own grid before
     anything else happens to it (``upload_input``).  ``deform_input="demons"``: after all of that every input frame is warped onto its
-    reference frame on the input's grid (``prepare_input``); ``"diffeomorphic"`` with ``deform_exp_steps`` likewise.
+    reference frame on the input's grid (``prepare_input``); ``"diffeomorphic"`` with ``deform_exp_steps`` likewise;
+    ``deform_force="lcc"`` with ``deform_lcc_radius``: the force across contrasts in either.
     ``tissue_dice`` K (needs ``mask``): the rows of the foreground carry ``dice_1 ... dice_K``, the Dice overlap of the method's tissue
     classes with the reference's (``""`` in the rows of the whole volume), and a last method ``reference`` is scored.
     ``tissue_surface`` (needs ``tissue_dice``): those rows also carry ``surface_columns(K)``, in the world units of the reference's header."""
     check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
-                  denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask, tissue_surface)
+                  denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask, tissue_surface,
+                  deform_force, deform_lcc_radius)
     noise_options = (denoise_input, denoise_sigma, denoise_beta, denoise_radius)
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
@@ -328,7 +345,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             m = masks[t] if align else torch.from_numpy(masks[t]).to(device)
         if lr is not None:
             lr = prepare_input(lr, vol, match, match_bias, axes, bias_sigmas, f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}",
-                               reference_path, deform_input, align_interp, deform_exp_steps)
+                               reference_path, deform_input, align_interp, deform_exp_steps, deform_force, deform_lcc_radius)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
                               mask_fill_holes=mask_fill_holes, tissue_dice=tissue_dice, tissue_surface=tissue_surface,
@@ -419,7 +436,8 @@ def main(args):
             raise ValueError("--mask_largest, --mask_fill_holes and --save_mask go with --mask")
         check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity, args.match_bias,
                       args.match_bias_sigma_mm, args.denoise_input, args.denoise_sigma, args.denoise_beta, args.denoise_radius,
-                      args.deform_input, args.deform_exp_steps, args.tissue_dice, args.mask, args.tissue_surface)
+                      args.deform_input, args.deform_exp_steps, args.tissue_dice, args.mask, args.tissue_surface, args.deform_force,
+                      args.deform_lcc_radius)
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -447,7 +465,8 @@ def main(args):
                                    match=args.match_intensity, match_bias=args.match_bias, match_bias_sigma_mm=args.match_bias_sigma_mm,
                                    denoise_input=args.denoise_input, denoise_sigma=args.denoise_sigma, denoise_beta=args.denoise_beta,
                                    denoise_radius=args.denoise_radius, deform_input=args.deform_input,
-                                   deform_exp_steps=args.deform_exp_steps, tissue_dice=args.tissue_dice,
+                                   deform_exp_steps=args.deform_exp_steps, deform_force=args.deform_force,
+                                   deform_lcc_radius=args.deform_lcc_radius, tissue_dice=args.tissue_dice,
                                    tissue_surface=args.tissue_surface)
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
@@ -536,6 +555,10 @@ def parse_args(argv=None):
                         "intensity-difference force: use --match_intensity); diffeomorphic: the same with the update composed with the "
                         "field through its exponential, not added - a field that does not fold")
     p.add_argument("--deform_exp_steps", type=int, default=2, help="--deform_input diffeomorphic: squarings of an update's exponential, 0..8")
+    p.add_argument("--deform_force", type=str, choices=["ssd", "lcc"], default="ssd",
+                   help="the force of --deform_input.  ssd: the intensity difference (use --match_intensity); lcc: a locally normalised "
+                        "correlation force for an input of another contrast than its reference - no common intensity scale is needed")
+    p.add_argument("--deform_lcc_radius", type=int, default=2, help="--deform_force lcc: the window is this many voxels either side (1..4)")
     p.add_argument("--tissue_dice", type=int, default=0,
                    help="segment the reference and every method's output into this many tissue classes (2..6) inside the mask and append "
                         "the Dice overlap per class, dice_1 ... dice_K (needs --mask; 0: off)")
