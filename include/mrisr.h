@@ -908,6 +908,30 @@ size_t mrisr_f32_volume_surface_workspace_bytes(void);
 int mrisr_f32_volume_surface_gather(const float* d2, const unsigned char* query, int value, size_t n, float* dist, unsigned char* sel,
                                     void* ws, unsigned long long* result, void* stream);
 
+/* ---- Edge sharpness across tissue interfaces (extension; csrc/volume_edge.hip): the sides of an interface, the signed distance to
+ *      it and the edge-spread function of a volume across up to five interfaces in one pass.  Arrays are DEVICE, flattened volumes
+ *      of n voxels; the specification is mri_superresolution_amd/volume_sharpness.py.  No host synchronisation, no atomics. ---- */
+/* out[i] = 0 where labels[i] == 0, 1 where 0 < labels[i] <= k, 2 where labels[i] > k (volume_sharpness.interface_sides_np); out is a
+ * buffer of its own.  One launch.  MRISR_E_ARG: null pointer, k outside 1..254; MRISR_E_SHAPE: n outside 1..2^32 - 1.                        */
+int mrisr_u8_volume_interface_sides(const unsigned char* labels, size_t n, int k, unsigned char* out, void* stream);
+/* out[i] = +sqrtf(da2[i]) where sides[i] == 2, -sqrtf(db2[i]) where sides[i] == 1, NaN elsewhere, the roots correctly rounded
+ * (volume_sharpness.signed_distance_np: da2 and db2 are mrisr_u8_volume_edt_sq of sides with the values 1 and 2); an infinity stays
+ * one.  out is a buffer of its own.  One launch.  MRISR_E_ARG: null or misaligned pointer; MRISR_E_SHAPE as above.                       */
+int mrisr_f32_volume_signed_distance(const unsigned char* sides, const float* da2, const float* db2, size_t n, float* out, void* stream);
+/* bytes of DEVICE workspace of mrisr_f32_volume_edge_profile for this many interfaces (1..5) and bins (2..64), any volume size; no
+ * initialisation needed, 8-byte aligned.  0 for a count out of range.                                                              */
+size_t mrisr_f32_volume_edge_workspace_bytes(int interfaces, int bins);
+/* The edge-spread functions of vol (n voxels) across the interfaces whose signed distances are sdist[j * n + i], j < interfaces
+ * (volume_sharpness.edge_profile_np): voxel i enters bin b = floor(fl32(fl32(s + radius) / bin_width)) of interface j when s is
+ * finite, 0 <= b < bins and vol[i] is finite.  result (DEVICE, interfaces x bins x 4 words of 8 bytes, overwritten): per bin the
+ * count (int64) and the float64 sums of v, s and v * v.  The counts are exact; the sums are added in an order that depends on n
+ * alone - a wave owns a fixed set of voxels, lanes of one bin are added in a fixed tree, per-workgroup results go to fixed slots of
+ * ws and a second launch adds them in slot order - the same bits on every run.  vol is read at most once, sdist once, no volume
+ * is written.  Two launches.  MRISR_E_ARG: null or misaligned pointer, interfaces outside 1..5, bins outside 2..64, radius or
+ * bin_width not finite and positive; MRISR_E_SHAPE: n outside 1..2^32 - 1.                                                          */
+int mrisr_f32_volume_edge_profile(const float* vol, const float* sdist, int interfaces, size_t n, float radius, float bin_width, int bins,
+                                  void* ws, unsigned long long* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

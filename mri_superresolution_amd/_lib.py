@@ -202,10 +202,14 @@ SIGNATURES = {
     "mrisr_u8_volume_edt_sq": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _fp, _i, _i, _vp]),
     "mrisr_f32_volume_surface_workspace_bytes": (_sz, []),
     "mrisr_f32_volume_surface_gather": (_i, [_fp, _vp, _i, _sz, _fp, _vp, _vp, _vp, _vp]),
+    "mrisr_u8_volume_interface_sides": (_i, [_vp, _sz, _i, _vp, _vp]),
+    "mrisr_f32_volume_signed_distance": (_i, [_vp, _fp, _fp, _sz, _fp, _vp]),
+    "mrisr_f32_volume_edge_workspace_bytes": (_sz, [_i, _i]),
+    "mrisr_f32_volume_edge_profile": (_i, [_fp, _fp, _i, _sz, _f, _f, _i, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 326    # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 327    # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -590,17 +590,19 @@ class VolumeScores(OrderedDict):
     ``mask_cleanup``: the (3,) float64 CUDA tensor [components found, kept size, voxels filled] of the mask's clean-up (NaN for a
     step that is off), ``None`` when neither ``mask_largest`` nor ``mask_fill_holes`` is on.  ``tissue_dice``: ``{method: (K,) float64
     numpy array}`` with ``evaluate_volume(tissue_dice=K)``, else ``None``.  ``tissue_surface``: ``{method: volume_surface.SurfaceDistances}`` with
-    ``evaluate_volume(tissue_surface=True)``, else ``None``."""
+    ``evaluate_volume(tissue_surface=True)``, else ``None``.  ``tissue_edges``: ``{method: volume_sharpness.EdgeSharpness}`` with
+    ``evaluate_volume(tissue_edges=True)``, else ``None``."""
 
     def __init__(self):
         super().__init__()
         self.mask = self.mask_count = self.mask_stats = self.mask_cleanup = self.tissue_dice = self.tissue_surface = None
+        self.tissue_edges = None
 
 
 def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic: bool = False, axis: int = 2, val_range: float = None,
                     batch_size: int = 16, use_amp: bool = False, use_graph: bool = True, graph_cache: dict = None, mask=None,
                     mask_close: int = 0, mask_largest: bool = False, mask_fill_holes=None, tissue_dice: int = 0, tissue_surface: bool = False,
-                    spacing=None) -> "VolumeScores":
+                    spacing=None, tissue_edges: bool = False, edge_radius: float = 4.0, edge_bin: float = 0.5) -> "VolumeScores":
     """Scores the U-Net and the interpolation baselines against the ground truth ``ref`` (float32 CUDA volume).
 
     The doubled axes are all three with ``isotropic``, else the two in-plane axes of the slices across ``axis``.  ``lr=None``
@@ -626,7 +628,12 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
 
     ``tissue_surface`` (needs ``tissue_dice``): ``.tissue_surface`` is ``{method: SurfaceDistances}``, the surface distances per class
     between the tissue interfaces of the label volumes already made for Dice (``volume_surface.surface_distances`` with
-    ``background=False``: the mask's outer rim is the same on both sides), in the unit of ``spacing``, the three voxel sizes (None: 1)."""
+    ``background=False``: the mask's outer rim is the same on both sides), in the unit of ``spacing``, the three voxel sizes (None: 1).
+
+    ``tissue_edges`` (needs ``tissue_dice``): ``.tissue_edges`` is ``{method: EdgeSharpness}``, the 10 % - 90 % width and the contrast of
+    every method's output across the ``tissue_dice - 1`` interfaces between the tissue classes of the REFERENCE's label volume
+    (``volume_sharpness``): the signed distances to them are taken once, with ``spacing``, and each output and the ``reference`` row get
+    one ``edge_profile`` pass with ``edge_radius`` and ``edge_bin`` in the unit of ``spacing``."""
     # the checks that need no data come first, the device check after them
     if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or ref.dim() != 3 or ref.numel() == 0:
         raise ValueError(f"expected a non-empty float32 volume (X,Y,Z), got {getattr(ref, 'dtype', type(ref))} "
@@ -648,7 +655,15 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
             raise ValueError("tissue_surface needs tissue_dice")
         spacing = (1.0, 1.0, 1.0) if spacing is None else spacing
         _check_spacing(spacing)
-    elif spacing is not None:
+    if tissue_edges:
+        from .volume_sharpness import EdgeWorkspace, _check_bins, edge_sharpness, signed_distances
+        from .volume_surface import _check_spacing
+        if not tissue_dice:
+            raise ValueError("tissue_edges needs tissue_dice")
+        spacing = (1.0, 1.0, 1.0) if spacing is None else spacing
+        _check_spacing(spacing)
+        edge_bins = _check_bins(edge_radius, edge_bin)[2]
+    if spacing is not None and not (tissue_surface or tissue_edges):
         raise ValueError("spacing needs tissue_surface")
     if mask is None:
         if mask_close != 0:
@@ -712,6 +727,10 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     if tissue_surface:
         surface_ws = SurfaceWorkspace(ref.shape, tissue_dice, ref.device)
         results.tissue_surface = {}
+    if tissue_edges:
+        edge_ws = EdgeWorkspace(tissue_dice - 1, edge_bins, ref.device)
+        ref_sdist = signed_distances(ref_labels, tissue_dice, spacing)
+        results.tissue_edges = {}
 
     def scored(method, out):
         results[method] = volume_metrics(out, ref, val_range, **score)
@@ -720,6 +739,9 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
             results.tissue_dice[method] = dice(label_confusion(labels, ref_labels, score["mask"], tissue_dice))
             if tissue_surface:
                 results.tissue_surface[method] = surface_distances(labels, ref_labels, tissue_dice, spacing, False, surface_ws)
+            if tissue_edges:
+                results.tissue_edges[method] = edge_sharpness(out.contiguous(), radius=edge_radius, bin_width=edge_bin, workspace=edge_ws,
+                                                              sdist=ref_sdist)
 
     if isotropic:
         scored("unet", enhance_volume_isotropic(model, lr, **common))

@@ -15,8 +15,9 @@ result.  With unit weights every value is an exact integer (an axis is at most 1
 Device path: ``surface_distances`` makes 2 launches for the two boundaries and, per class and direction, 3 for the transform, 2 for
 the gather and the 9 of ``masked_percentiles``; one download of ``(8 K + 1) * 8`` bytes at the end covers all classes.
 
-Not built: a signed distance map, morphology by a radius in mm, distances to an atlas surface, a linear-time (lower-envelope)
-transform, axes longer than 1024 voxels, a 2-D form for ``scripts/evaluate.py``.
+Not built: morphology by a radius in mm, distances to an atlas surface, a linear-time (lower-envelope)
+transform, axes longer than 1024 voxels, a 2-D form for ``scripts/evaluate.py``.  The signed distance to a tissue interface is
+``volume_sharpness.signed_distance``.
 """
 from __future__ import annotations
 

@@ -13,7 +13,9 @@ wired as there; ``--mask PATH`` reads it from a NIfTI-1 file of the input's spat
 timepoint).  The labels are written as uint8 under the input's header, 0 outside the mask, a 4-D file timepoint by timepoint; the
 class means, the voxel counts and the sweeps are logged per frame.  ``--compare`` prints the Dice overlap per class with another
 label file of the same shape, inside the mask, and the surface distances per class between the two label volumes in the world units
-of the input's header: ASSD, HD95 and HD (``volume_surface.surface_distances``).  Exit code 0 / 1 (error logged), as ``scripts/reslice_volume.py``.
+of the input's header: ASSD, HD95 and HD (``volume_surface.surface_distances``).  ``--edges SCAN`` prints, per interface between the classes just written,
+the 10 % - 90 % width in those units and the contrast of ``SCAN``'s edge across it (``volume_sharpness.edge_sharpness``; ``SCAN`` has the
+input's shape).  Exit code 0 / 1 (error logged), as ``scripts/reslice_volume.py``.
 """
 import argparse
 import logging
@@ -31,13 +33,14 @@ from mri_superresolution_amd.utils.nifti import frames, read_nifti, write_nifti 
 from mri_superresolution_amd.volume_eval import foreground_mask                      # noqa: E402
 from mri_superresolution_amd.volume_tissue import TissueWorkspace, dice, label_confusion, segment_tissue      # noqa: E402
 from mri_superresolution_amd.volume_surface import SurfaceWorkspace, surface_distances                      # noqa: E402
+from mri_superresolution_amd.volume_sharpness import edge_sharpness                                         # noqa: E402
 from scripts.evaluate_volume import load_mask, voxel_sizes                                        # noqa: E402
 
 logger = logging.getLogger("segment_volume")
 
 
 def segment_file(input_path, output_path, classes=3, beta=1.0, iterations=20, mask="otsu", mask_close=0, mask_largest=False,
-                 mask_fill_holes=None, compare=None, device="cuda"):
+                 mask_fill_holes=None, compare=None, device="cuda", edges=None):
     """NIfTI file -> uint8 NIfTI label file; returns (the label array as written, the Dice per frame against ``compare`` or None)."""
     data, header = read_nifti(input_path)
     if mask != "otsu" and (mask_close != 0 or mask_largest or mask_fill_holes is not None):
@@ -52,6 +55,11 @@ def segment_file(input_path, output_path, classes=3, beta=1.0, iterations=20, ma
             raise ValueError(f"{compare} has the shape {tuple(other.shape)}, {input_path} {tuple(data.shape)}")
         if not np.array_equal(other, np.clip(np.rint(other), 0, 255)):
             raise ValueError(f"{compare} does not hold labels 0..255")
+    scan = None
+    if edges is not None:
+        scan = read_nifti(edges)[0]
+        if scan.shape != data.shape:
+            raise ValueError(f"{edges} has the shape {tuple(scan.shape)}, {input_path} {tuple(data.shape)}")
     ws = TissueWorkspace(data.shape[:3], classes, device)
     surface_ws = SurfaceWorkspace(data.shape[:3], classes, device) if compare is not None else None
     outs, overlaps = [], []
@@ -70,6 +78,11 @@ def segment_file(input_path, output_path, classes=3, beta=1.0, iterations=20, ma
             far = surface_distances(found.labels, theirs, classes, voxel_sizes(header.affine()), workspace=surface_ws)
             for name, values in (("ASSD", far.assd), ("HD95", far.hd95), ("HD", far.hd)):
                 print(f"{what} {name} against {compare}: " + "  ".join(f"class {k + 1} {d:.6f}" for k, d in enumerate(values)))
+        if scan is not None:
+            theirs = torch.from_numpy(np.ascontiguousarray(frames(scan)[t], dtype=np.float32)).to(device)
+            sharp = edge_sharpness(theirs, found.labels, classes, voxel_sizes(header.affine()))
+            for name, values in (("edge width", sharp.width), ("edge contrast", sharp.contrast)):
+                print(f"{what} {name} of {edges}: " + "  ".join(f"interface {k + 1} {d:.6f}" for k, d in enumerate(values)))
         outs.append(found.labels.cpu().numpy())
     result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
     os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
@@ -87,7 +100,7 @@ def main(args):
         logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
         fill = args.mask_fill_holes if args.mask_fill_holes in (None, "3d") else int(args.mask_fill_holes)
         segment_file(args.input, args.output, args.classes, args.beta, args.iterations, args.mask, args.mask_close, args.mask_largest, fill,
-                     args.compare, device)
+                     args.compare, device, args.edges)
         return 0
     except Exception as e:
         logger.error(f"Error during segmentation: {e}")
@@ -109,6 +122,8 @@ def parse_args(argv=None):
     p.add_argument("--mask_fill_holes", type=str, choices=["3d", "0", "1", "2"], default=None,
                    help="fill the holes of the Otsu mask: those of the volume (3d) or of every plane across this axis")
     p.add_argument("--compare", type=str, default=None, help="print the Dice overlap per class with this label file (same shape)")
+    p.add_argument("--edges", type=str, default=None,
+                   help="print the 10 %% - 90 %% edge width and the contrast of this scan (same shape) across every interface of the labels")
     p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
     return p.parse_args(argv)
 
