@@ -932,6 +932,50 @@ size_t mrisr_f32_volume_edge_workspace_bytes(int interfaces, int bins);
 int mrisr_f32_volume_edge_profile(const float* vol, const float* sdist, int interfaces, size_t n, float radius, float bin_width, int bins,
                                   void* ws, unsigned long long* result, void* stream);
 
+/* ---- Reconstruction from orthogonal thick-slice stacks (extension; csrc/volume_stacks.hip): iterative back-projection
+ *      (Irani-Peleg) of up to MRISR_STACKS_MAX stacks into one estimate x (DEVICE float32 (X, Y, Z), C order).  Both directions are
+ *      gathers under the rules of mrisr_f32_volume_reslice, MRISR_RESAMPLE_LINEAR: the coordinate
+ *      p_a = ((m[a][0] q_0 + m[a][1] q_1) + m[a][2] q_2) + m[a][3] in double, the inside test -0.5 <= p_a <= n_a - 0.5, clamped
+ *      taps, reduction along z, y, x.  Every operation is one rounded operation, never an fma; the specification is
+ *      mri_superresolution_amd/volume_stacks.py.  No host synchronisation (HIP-graph capturable), no floating-point atomics. ---- */
+#define MRISR_STACKS_MAX 8
+#define MRISR_STACK_SAMPLES_MAX 16
+/* one stack as the update sees it: data DEVICE float32 (nx, ny, nz); m (row-major 3 x 4) maps an OUTPUT voxel index to the
+ * continuous index in the stack                                                                                                 */
+typedef struct mrisr_stack_view {
+    const float* data;
+    int32_t nx, ny, nz, reserved_;
+    double m[12];
+} mrisr_stack_view;
+/* bytes of DEVICE workspace for K stacks (1..8; 0 otherwise): K regions of equal size, region k for the residual launch of stack
+ * k; no initialisation needed, 8-byte aligned.                                                                                  */
+size_t mrisr_f32_volume_stack_workspace_bytes(int K);
+/* r (SX, SY, SZ) = y - the stack simulated from x, bit for bit volume_stacks.stack_residual_np.  m12 (HOST): stack index -> output
+ * index.  For t = 0 .. T - 1: q = (i, j, k) in double with q[slice_axis] = (double)i_s + offsets[t] (HOST doubles, one rounded
+ * add); p = m q; a sample inside x adds fl(weights[t] * gather) to acc and weights[t] to wsum (HOST floats; float32 sums from +0),
+ * one outside adds nothing.  r = fl(y - fl(acc / wsum)) where wsum >= 0.5f, else +0.  One launch, one thread per stack voxel.
+ * The float64 sum of r^2 over the voxels that passed the wsum test and their count leave the launch in the fixed slots of
+ * workspace (ONE region of mrisr_f32_volume_stack_workspace_bytes), as mrisr_f32_volume_demons_force leaves its sums.  stats_row
+ * (DEVICE: one double, one int64) given: a second launch of one wave adds the slots into it.  NULL: the next
+ * mrisr_f32_volume_stack_update does so.  The same bits on every run.
+ * MRISR_E_ARG: null or misaligned pointer, T outside 1..16, slice_axis outside 0..2, a matrix entry, offset or weight that is
+ * not finite, r equal to x or y; MRISR_E_SHAPE: an extent below 1 or more than 2^31 - 1 voxels on either grid.                   */
+int mrisr_f32_volume_stack_residual(const float* x, int X, int Y, int Z, const float* y, int SX, int SY, int SZ, const double* m12,
+                                    int slice_axis, const double* offsets, const float* weights, int T, float* r, void* workspace,
+                                    void* stats_row, void* stream);
+/* out = x + step * (the mean over the covering stacks of their gathers), bit for bit volume_stacks.stack_update_np: for k = 0 ..
+ * K - 1 (views: HOST array), p = views[k].m (i, j, k); inside stack k: sum = fl(sum + gather of views[k].data), cnt += 1.
+ * out = fl(x + fl(step * fl(sum / (float)cnt))) where cnt > 0, then lo where use_clamp and that is below lo; out = x where
+ * cnt == 0.  out may be x (every voxel is read once and written once by its own thread).  cover (DEVICE uint8 (X, Y, Z)) given:
+ * cover = cnt.  ONE launch for all stacks, the views by value.  workspace (all K regions) and stats_rows (DEVICE, K rows of one
+ * double, one int64) given, both or neither: the first wave also adds the slots the K preceding residual launches left, row k
+ * from region k - an iteration is K + 1 launches.
+ * MRISR_E_ARG: null or misaligned pointer, K outside 1..8, step or (with use_clamp) lo not finite, use_clamp not 0 / 1, a matrix
+ * entry that is not finite, out or cover equal to a stack, cover equal to x or out, one of workspace / stats_rows without the
+ * other; MRISR_E_SHAPE: an extent below 1 or more than 2^31 - 1 voxels on any grid.                                             */
+int mrisr_f32_volume_stack_update(const float* x, int X, int Y, int Z, const mrisr_stack_view* views, int K, float step, int use_clamp,
+                                  float lo, float* out, unsigned char* cover, const void* workspace, void* stats_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,11 @@ class Consumer(C.Structure):
                 ("head_dw", _fp), ("head_db", _fp)]
 
 
+class StackView(C.Structure):
+    _fields_ = [("data", _fp), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("reserved_", C.c_int32),
+                ("m", C.c_double * 12)]
+
+
 # every symbol include/mrisr.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "mrisr_last_error": (C.c_char_p, []),
@@ -206,10 +211,14 @@ SIGNATURES = {
     "mrisr_f32_volume_signed_distance": (_i, [_vp, _fp, _fp, _sz, _fp, _vp]),
     "mrisr_f32_volume_edge_workspace_bytes": (_sz, [_i, _i]),
     "mrisr_f32_volume_edge_profile": (_i, [_fp, _fp, _i, _sz, _f, _f, _i, _vp, _vp, _vp]),
+    "mrisr_f32_volume_stack_workspace_bytes": (_sz, [_i]),
+    "mrisr_f32_volume_stack_residual": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
+                                             C.POINTER(C.c_float), _i, _fp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_stack_update": (_i, [_fp, _i, _i, _i, C.POINTER(StackView), _i, _f, _i, _f, _fp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 327    # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 328   # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -1,0 +1,221 @@
+// Super-resolution reconstruction from orthogonal thick-slice stacks by iterative back-projection on the device (gfx950; extension,
+// DESIGN.md section 7).
+//
+// Restates stack_residual_np / stack_update_np of mri_superresolution_amd/volume_stacks.py operation by operation and is tested bit
+// for bit against them (compiled with -ffp-contract=off).  A volume is (X, Y, Z) in C order, Z fastest.  Both directions are gathers
+// through the taps of volume_taps.h - the coordinate rule, the inside test, the clamp and the reduction of csrc/volume_reslice.hip:
+//
+//   f32_volume_stack_residual   one launch per stack, one thread per STACK voxel: the T samples of its slice profile lie on a line
+//                               along the slice axis; each sample inside the estimate adds w_t times the linear gather of the
+//                               estimate to acc and w_t to wsum (float32, t ascending); r = y - acc / wsum where wsum >= 0.5, else +0.
+//                               The float64 sum of r^2 and the count of such voxels leave the launch as in
+//                               mrisr_f32_volume_demons_force: a thread's (sum, rounding error) pair, the waves and the workgroup in
+//                               a fixed order, one slot per workgroup (volume_deform.h), added by one wave of a LATER launch.
+//   f32_volume_stack_update     ONE launch for all stacks, one thread per OUTPUT voxel: for k ascending, the linear gather of r_k
+//                               where the voxel lies inside stack k; x' = x + step * (sum / cnt) where cnt > 0, clamped from below
+//                               there.  The views (pointer, extents, matrix) travel by value in the kernel arguments.  Its first
+//                               wave adds the slots the K residual launches left: an iteration is K + 1 launches.
+//
+// Both kernels walk the 2 x 2 x 64 bricks of the reslice and warp kernels, z fastest.  Nothing is uploaded and nothing synchronises
+// (HIP-graph capturable); no floating-point atomics: the same bits on every run.
+#include "volume_deform.h"
+#include "volume_taps.h"
+
+constexpr int kMaxStacks = MRISR_STACKS_MAX, kMaxSamples = MRISR_STACK_SAMPLES_MAX;
+
+struct StackMatrix {
+    double m[3][4];
+};
+struct StackProfile {
+    double offset[kMaxSamples];
+    float weight[kMaxSamples];
+};
+struct StackViews {
+    const float* data[kMaxStacks];
+    int n[kMaxStacks][3];
+    int nslots[kMaxStacks];
+    double m[kMaxStacks][3][4];
+};
+
+// voxel of thread tid in brick b (bricks numbered along z, then y, then x)
+__device__ __forceinline__ bool stack_brick_voxel(unsigned b, unsigned nby, unsigned nbz, int X, int Y, int Z, int& i, int& j, int& k) {
+    const unsigned bz = b % nbz, rest = b / nbz, by = rest % nby, bx = rest / nby;
+    const int tid = threadIdx.x;
+    k = (int)bz * kBZ + tid % kBZ, j = (int)by * kBY + tid / kBZ % kBY, i = (int)bx * kBX + tid / (kBZ * kBY);
+    return i < X && j < Y && k < Z;
+}
+
+// the linear gather of src (X, Y, Z) at p, inside [-0.5, n - 0.5] on every axis: the taps reduced along z, then y, then x
+__device__ __forceinline__ float linear_gather(const float* __restrict__ src, int X, int Y, int Z, const double* p) {
+    int ix[2], iy[2], iz[2];
+    float wx[2], wy[2], wz[2];
+    axis_taps<kLinear>(p[0], X, ix, wx);
+    axis_taps<kLinear>(p[1], Y, iy, wy);
+    axis_taps<kLinear>(p[2], Z, iz, wz);
+    float rx[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        float ry[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const float* row = src + ((size_t)ix[a] * Y + iy[b]) * Z;
+            const float v[2] = {row[iz[0]], row[iz[1]]};
+            ry[b] = weighted_sum<2>(wz, v);
+        }
+        rx[a] = weighted_sum<2>(wy, ry);
+    }
+    return weighted_sum<2>(wx, rx);
+}
+
+// p = m q and the inside test of a volume of extents n
+__device__ __forceinline__ bool stack_coordinate(const double (*m)[4], double q0, double q1, double q2, int n0, int n1, int n2, double* p) {
+    const int n[3] = {n0, n1, n2};
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        p[a] = grid_coordinate(m[a], q0, q1, q2);
+        inside = inside && p[a] >= -0.5 && p[a] <= (double)n[a] - 0.5;      // NaN compares false
+    }
+    return inside;
+}
+
+// at most kSlots workgroups walk the bricks of the STACK with a stride of the grid
+__global__ __launch_bounds__(256) void stack_residual_kernel(const float* __restrict__ x, int X, int Y, int Z, const float* __restrict__ y,
+                                                             int SX, int SY, int SZ, StackMatrix g, int axis, StackProfile pr, int T,
+                                                             float* __restrict__ r, unsigned nbricks, unsigned nby, unsigned nbz,
+                                                             DeformSlot* __restrict__ slots) {
+    __shared__ DeformSlot part[4];
+    PairSum sq = {0.0, 0.0, 0};
+    for (unsigned b = blockIdx.x; b < nbricks; b += gridDim.x) {
+        int i, j, k;
+        if (!stack_brick_voxel(b, nby, nbz, SX, SY, SZ, i, j, k)) continue;
+        const size_t idx = ((size_t)i * SY + j) * SZ + k;
+        const double di = (double)i, dj = (double)j, dk = (double)k;
+        const double along = axis == 0 ? di : (axis == 1 ? dj : dk);
+        float acc = 0.f, wsum = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const double s = __dadd_rn(along, pr.offset[t]);
+            double p[3];
+            if (!stack_coordinate(g.m, axis == 0 ? s : di, axis == 1 ? s : dj, axis == 2 ? s : dk, X, Y, Z, p)) continue;
+            const float w = pr.weight[t];
+            acc = __fadd_rn(acc, __fmul_rn(w, linear_gather(x, X, Y, Z, p)));
+            wsum = __fadd_rn(wsum, w);
+        }
+        float res = 0.f;
+        if (wsum >= 0.5f) {
+            res = __fsub_rn(y[idx], __fdiv_rn(acc, wsum));
+            sq.add((double)res * (double)res, 0.0, 1);      // the square of a float is exact in double
+        }
+        r[idx] = res;
+    }
+    block_sum_to_slot(sq, part, &slots[blockIdx.x]);
+}
+
+// one brick per workgroup; x is read once and out written once at the thread's own voxel, so out may be x
+__global__ __launch_bounds__(256) void stack_update_kernel(const float* x, float* out, unsigned char* __restrict__ cover, int X, int Y,
+                                                           int Z, StackViews v, int K, float step, int use_clamp, float lo, unsigned nby,
+                                                           unsigned nbz, const DeformSlot* __restrict__ slots, StatsRow* __restrict__ rows) {
+    if (rows && blockIdx.x == 0 && threadIdx.x < 64)
+        for (int s = 0; s < K; ++s) finalize_force(slots + (size_t)s * kSlots, v.nslots[s], rows + s);
+    int i, j, k;
+    if (!stack_brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k)) return;
+    const size_t idx = ((size_t)i * Y + j) * Z + k;
+    const double di = (double)i, dj = (double)j, dk = (double)k;
+    float sum = 0.f;
+    int cnt = 0;
+#pragma unroll 1
+    for (int s = 0; s < K; ++s) {
+        double p[3];
+        if (!stack_coordinate(v.m[s], di, dj, dk, v.n[s][0], v.n[s][1], v.n[s][2], p)) continue;
+        sum = __fadd_rn(sum, linear_gather(v.data[s], v.n[s][0], v.n[s][1], v.n[s][2], p));
+        ++cnt;
+    }
+    float xv = x[idx];
+    if (cnt > 0) {
+        xv = __fadd_rn(xv, __fmul_rn(step, __fdiv_rn(sum, (float)cnt)));
+        if (use_clamp && xv < lo) xv = lo;                  // a NaN stays
+    }
+    out[idx] = xv;
+    if (cover) cover[idx] = (unsigned char)cnt;
+}
+
+static int check_matrix(const char* name, const double* m12, double (*m)[4]) {
+    for (int e = 0; e < 12; ++e) {
+        if (!isfinite(m12[e])) MRISR_FAIL(MRISR_E_ARG, "%s: matrix entry [%d][%d] is not finite", name, e / 4, e % 4);
+        m[e / 4][e % 4] = m12[e];
+    }
+    return MRISR_OK;
+}
+
+extern "C" size_t mrisr_f32_volume_stack_workspace_bytes(int K) {
+    return K >= 1 && K <= kMaxStacks ? (size_t)K * kSlots * sizeof(DeformSlot) : 0;
+}
+
+extern "C" int mrisr_f32_volume_stack_residual(const float* x, int X, int Y, int Z, const float* y, int SX, int SY, int SZ, const double* m12,
+                                               int slice_axis, const double* offsets, const float* weights, int T, float* r, void* workspace,
+                                               void* stats_row, void* stream) {
+    const char* name = "f32_volume_stack_residual";
+    if (!x || !y || !m12 || !offsets || !weights || !r || !workspace) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (T < 1 || T > kMaxSamples) MRISR_FAIL(MRISR_E_ARG, "%s: %d profile samples (1..%d)", name, T, kMaxSamples);
+    if (slice_axis < 0 || slice_axis > 2) MRISR_FAIL(MRISR_E_ARG, "%s: slice axis %d (0..2)", name, slice_axis);
+    StackMatrix g;
+    if (const int rc = check_matrix(name, m12, g.m)) return rc;
+    StackProfile pr = {};
+    for (int t = 0; t < T; ++t) {
+        if (!isfinite(offsets[t]) || !isfinite(weights[t])) MRISR_FAIL(MRISR_E_ARG, "%s: profile sample %d is not finite", name, t);
+        pr.offset[t] = offsets[t];
+        pr.weight[t] = weights[t];
+    }
+    BrickGrid out_grid, grid;
+    if (const int rc = check_field_volume(name, X, Y, Z, &out_grid)) return rc;
+    if (const int rc = check_field_volume(name, SX, SY, SZ, &grid)) return rc;
+    if (!aligned_to(x, 4) || !aligned_to(y, 4) || !aligned_to(r, 4) || !aligned_to(workspace, 8) || !aligned_to(stats_row, 8))
+        MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer", name);
+    if (r == x || r == y) MRISR_FAIL(MRISR_E_ARG, "%s: r must be a buffer of its own", name);
+    hipStream_t st = (hipStream_t)stream;
+    DeformSlot* slots = (DeformSlot*)workspace;
+    stack_residual_kernel<<<grid.nslots, 256, 0, st>>>(x, X, Y, Z, y, SX, SY, SZ, g, slice_axis, pr, T, r, grid.nbricks, grid.nby, grid.nbz,
+                                                        slots);
+    MRISR_CHECK_LAUNCH(name);
+    if (stats_row) {
+        force_stats_kernel<<<1, 64, 0, st>>>(slots, grid.nslots, (StatsRow*)stats_row);
+        MRISR_CHECK_LAUNCH(name);
+    }
+    return MRISR_OK;
+}
+
+extern "C" int mrisr_f32_volume_stack_update(const float* x, int X, int Y, int Z, const mrisr_stack_view* views, int K, float step,
+                                             int use_clamp, float lo, float* out, unsigned char* cover, const void* workspace,
+                                             void* stats_rows, void* stream) {
+    const char* name = "f32_volume_stack_update";
+    if (!x || !views || !out) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (K < 1 || K > kMaxStacks) MRISR_FAIL(MRISR_E_ARG, "%s: %d stacks (1..%d)", name, K, kMaxStacks);
+    if (!isfinite(step)) MRISR_FAIL(MRISR_E_ARG, "%s: step %g is not finite", name, (double)step);
+    if (use_clamp != 0 && use_clamp != 1) MRISR_FAIL(MRISR_E_ARG, "%s: use_clamp %d (0 or 1)", name, use_clamp);
+    if (use_clamp && !isfinite(lo)) MRISR_FAIL(MRISR_E_ARG, "%s: the lower clamp %g is not finite", name, (double)lo);
+    if ((workspace == nullptr) != (stats_rows == nullptr)) MRISR_FAIL(MRISR_E_ARG, "%s: workspace and stats_rows go together", name);
+    BrickGrid grid;
+    if (const int rc = check_field_volume(name, X, Y, Z, &grid)) return rc;
+    if (!aligned_to(x, 4) || !aligned_to(out, 4) || !aligned_to(workspace, 8) || !aligned_to(stats_rows, 8))
+        MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer", name);
+    StackViews v = {};
+    for (int s = 0; s < K; ++s) {
+        const mrisr_stack_view& in = views[s];
+        if (!in.data) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: null pointer", name, s);
+        if (!aligned_to(in.data, 4)) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: misaligned pointer", name, s);
+        if (in.data == out || (const void*)in.data == (const void*)cover)
+            MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: out and cover must be buffers of their own", name, s);
+        if (const int rc = check_matrix(name, in.m, v.m[s])) return rc;
+        BrickGrid sg;
+        if (const int rc = check_field_volume(name, in.nx, in.ny, in.nz, &sg)) return rc;
+        v.data[s] = in.data;
+        v.n[s][0] = in.nx, v.n[s][1] = in.ny, v.n[s][2] = in.nz;
+        v.nslots[s] = sg.nslots;
+    }
+    if ((const void*)cover == (const void*)x || (const void*)cover == (const void*)out)
+        MRISR_FAIL(MRISR_E_ARG, "%s: cover must be a buffer of its own", name);
+    stack_update_kernel<<<grid.nbricks, 256, 0, (hipStream_t)stream>>>(x, out, cover, X, Y, Z, v, K, step, use_clamp, lo, grid.nby, grid.nbz,
+                                                                        (const DeformSlot*)workspace, (StatsRow*)stats_rows);
+    MRISR_CHECK_LAUNCH(name);
+    return MRISR_OK;
+}
