@@ -975,6 +975,20 @@ int mrisr_f32_volume_stack_residual(const float* x, int X, int Y, int Z, const f
  * other; MRISR_E_SHAPE: an extent below 1 or more than 2^31 - 1 voxels on any grid.                                             */
 int mrisr_f32_volume_stack_update(const float* x, int X, int Y, int Z, const mrisr_stack_view* views, int K, float step, int use_clamp,
                                   float lo, float* out, unsigned char* cover, const void* workspace, void* stats_rows, void* stream);
+/* mrisr_f32_volume_stack_update with the Huber prior on the six face neighbours, bit for bit volume_stacks.stack_update_np with
+ * reg_lambda > 0.  For a voxel c with cnt > 0 and m = fl(sum / (float)cnt): reg = +0; for a = 0, 1, 2 and side = -1, +1, the
+ * neighbour n = c + side e_a inside the grid with cover_in[n] != 0: d = fl(x[n] - x[c]), psi = d clipped to [-delta, delta] (a NaN
+ * stays), reg = fl(reg + fl(coeffs[a] * psi)); out = fl(x + fl(step * fl(m + fl(lambda * reg)))), then the clamp.  A neighbour
+ * outside the grid or with cover_in == 0 is skipped; out = x where cnt == 0.  cover_in (DEVICE uint8 (X, Y, Z), required): the
+ * coverage counts of these same views, as mrisr_f32_volume_stack_update writes them to cover.  coeffs: HOST, three floats.  delta
+ * may be +inf (the quadratic prior).  All neighbours are read from x, so out must differ from x.  ONE launch for all stacks: a
+ * workgroup stages its 8 x 8 x 32 tile of x with a halo of one in LDS; cover, workspace and stats_rows as in the plain update.
+ * MRISR_E_ARG: as the plain update, and: coeffs or cover_in null, out equal to x, cover_in equal to x or out, cover equal to
+ * cover_in, lambda not finite or negative, delta NaN or <= 0, a coefficient not finite or <= 0, the stability bound
+ * step * lambda * (c_0 + c_1 + c_2) <= 0.5 (in double) broken; MRISR_E_SHAPE as the plain update.                                */
+int mrisr_f32_volume_stack_update_reg(const float* x, int X, int Y, int Z, const mrisr_stack_view* views, int K, float step, int use_clamp,
+                                      float lo, float lambda, float delta, const float* coeffs, const unsigned char* cover_in, float* out,
+                                      unsigned char* cover, const void* workspace, void* stats_rows, void* stream);
 
 #ifdef __cplusplus
 }

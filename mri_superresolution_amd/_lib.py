@@ -215,10 +215,12 @@ SIGNATURES = {
     "mrisr_f32_volume_stack_residual": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
                                              C.POINTER(C.c_float), _i, _fp, _vp, _vp, _vp]),
     "mrisr_f32_volume_stack_update": (_i, [_fp, _i, _i, _i, C.POINTER(StackView), _i, _f, _i, _f, _fp, _vp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_stack_update_reg": (_i, [_fp, _i, _i, _i, C.POINTER(StackView), _i, _f, _i, _f, _f, _f, C.POINTER(C.c_float), _vp,
+                                               _fp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 328   # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 329   # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

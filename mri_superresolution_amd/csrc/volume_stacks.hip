@@ -15,9 +15,16 @@
 //                               where the voxel lies inside stack k; x' = x + step * (sum / cnt) where cnt > 0, clamped from below
 //                               there.  The views (pointer, extents, matrix) travel by value in the kernel arguments.  Its first
 //                               wave adds the slots the K residual launches left: an iteration is K + 1 launches.
+//   f32_volume_stack_update_reg the same update with the Huber prior of stack_update_np (reg_lambda > 0): the mean of the residuals
+//                               plus lambda times the sum, over the covered face neighbours, of c_a times the difference to the
+//                               neighbour clipped at +-delta.  Still ONE launch; the neighbours are read from the estimate before
+//                               the update (Jacobi), so out is a buffer of its own.  A workgroup owns an 8 x 8 x 32 tile, a thread
+//                               the 8 voxels along x at its (y, z); the tile of x with a halo of one (10 x 10 x 34: 1.66 staged
+//                               elements per voxel, 16.6 KB with the flags) and, per staged voxel, whether it lies in the grid and
+//                               a stack covers it, are staged in LDS once.  The gathers are those of the plain kernel.
 //
-// Both kernels walk the 2 x 2 x 64 bricks of the reslice and warp kernels, z fastest.  Nothing is uploaded and nothing synchronises
-// (HIP-graph capturable); no floating-point atomics: the same bits on every run.
+// The first two kernels walk the 2 x 2 x 64 bricks of the reslice and warp kernels, z fastest.  Nothing is uploaded and nothing
+// synchronises (HIP-graph capturable); no floating-point atomics: the same bits on every run.
 #include "volume_deform.h"
 #include "volume_taps.h"
 
@@ -139,6 +146,85 @@ __global__ __launch_bounds__(256) void stack_update_kernel(const float* x, float
     if (cover) cover[idx] = (unsigned char)cnt;
 }
 
+// the tile of the regularised update and its staged image (a halo of one on every side)
+constexpr int kRX = 8, kRY = 8, kRZ = 32;
+constexpr int kHX = kRX + 2, kHY = kRY + 2, kHZ = kRZ + 2, kHalo = kHX * kHY * kHZ;
+
+struct StackPrior {
+    float lambda, delta, c[3];
+};
+
+// one tile per workgroup (tiles numbered along z, then y, then x); thread t owns the voxels (0..7, t / 32, t % 32) of the tile
+__global__ __launch_bounds__(256) void stack_update_reg_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                               const unsigned char* __restrict__ cover_in, unsigned char* __restrict__ cover,
+                                                               int X, int Y, int Z, StackViews v, int K, float step, int use_clamp, float lo,
+                                                               StackPrior pr, unsigned nty, unsigned ntz, const DeformSlot* __restrict__ slots,
+                                                               StatsRow* __restrict__ rows) {
+    __shared__ float sx[kHalo];
+    __shared__ unsigned char sok[kHalo];                    // 1: inside the grid and covered by a stack
+    if (rows && blockIdx.x == 0 && threadIdx.x < 64)
+        for (int s = 0; s < K; ++s) finalize_force(slots + (size_t)s * kSlots, v.nslots[s], rows + s);
+    const unsigned tz = blockIdx.x % ntz, rest = blockIdx.x / ntz, ty = rest % nty, tx = rest / nty;
+    const int x0 = (int)tx * kRX, y0 = (int)ty * kRY, z0 = (int)tz * kRZ;
+    for (int e = threadIdx.x; e < kHalo; e += 256) {
+        const int hz = e % kHZ, hy = e / kHZ % kHY, hx = e / (kHZ * kHY);
+        const int i = x0 + hx - 1, j = y0 + hy - 1, k = z0 + hz - 1;
+        // only face neighbours are read: the edges and corners of the halo are not fetched
+        const int faces = (hx == 0 || hx == kHX - 1) + (hy == 0 || hy == kHY - 1) + (hz == 0 || hz == kHZ - 1);
+        float val = 0.f;
+        unsigned char ok = 0;
+        if (faces <= 1 && i >= 0 && i < X && j >= 0 && j < Y && k >= 0 && k < Z) {
+            const size_t idx = ((size_t)i * Y + j) * Z + k;
+            val = x[idx];
+            ok = cover_in[idx] != 0;
+        }
+        sx[e] = val;
+        sok[e] = ok;
+    }
+    __syncthreads();
+    const int lz = threadIdx.x % kRZ, ly = threadIdx.x / kRZ;
+    const int j = y0 + ly, k = z0 + lz;
+    if (j >= Y || k >= Z) return;
+    const double dj = (double)j, dk = (double)k;
+    constexpr int kStride[3] = {kHY * kHZ, kHZ, 1};
+#pragma unroll 1
+    for (int lx = 0; lx < kRX && x0 + lx < X; ++lx) {
+        const int i = x0 + lx;
+        const size_t idx = ((size_t)i * Y + j) * Z + k;
+        const double di = (double)i;
+        float sum = 0.f;
+        int cnt = 0;
+#pragma unroll 1
+        for (int s = 0; s < K; ++s) {
+            double p[3];
+            if (!stack_coordinate(v.m[s], di, dj, dk, v.n[s][0], v.n[s][1], v.n[s][2], p)) continue;
+            sum = __fadd_rn(sum, linear_gather(v.data[s], v.n[s][0], v.n[s][1], v.n[s][2], p));
+            ++cnt;
+        }
+        const int h = ((lx + 1) * kHY + ly + 1) * kHZ + lz + 1;
+        float xv = sx[h];
+        if (cnt > 0) {
+            float reg = 0.f;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+#pragma unroll
+                for (int side = -1; side <= 1; side += 2) {
+                    const int n = h + side * kStride[a];
+                    if (!sok[n]) continue;
+                    const float d = __fsub_rn(sx[n], xv);
+                    const float psi = d > pr.delta ? pr.delta : (d < -pr.delta ? -pr.delta : d);      // a NaN stays
+                    reg = __fadd_rn(reg, __fmul_rn(pr.c[a], psi));
+                }
+            }
+            const float m = __fdiv_rn(sum, (float)cnt);
+            xv = __fadd_rn(xv, __fmul_rn(step, __fadd_rn(m, __fmul_rn(pr.lambda, reg))));
+            if (use_clamp && xv < lo) xv = lo;              // a NaN stays
+        }
+        out[idx] = xv;
+        if (cover) cover[idx] = (unsigned char)cnt;
+    }
+}
+
 static int check_matrix(const char* name, const double* m12, double (*m)[4]) {
     for (int e = 0; e < 12; ++e) {
         if (!isfinite(m12[e])) MRISR_FAIL(MRISR_E_ARG, "%s: matrix entry [%d][%d] is not finite", name, e / 4, e % 4);
@@ -216,6 +302,56 @@ extern "C" int mrisr_f32_volume_stack_update(const float* x, int X, int Y, int Z
         MRISR_FAIL(MRISR_E_ARG, "%s: cover must be a buffer of its own", name);
     stack_update_kernel<<<grid.nbricks, 256, 0, (hipStream_t)stream>>>(x, out, cover, X, Y, Z, v, K, step, use_clamp, lo, grid.nby, grid.nbz,
                                                                         (const DeformSlot*)workspace, (StatsRow*)stats_rows);
+    MRISR_CHECK_LAUNCH(name);
+    return MRISR_OK;
+}
+
+extern "C" int mrisr_f32_volume_stack_update_reg(const float* x, int X, int Y, int Z, const mrisr_stack_view* views, int K, float step,
+                                                 int use_clamp, float lo, float lambda, float delta, const float* coeffs,
+                                                 const unsigned char* cover_in, float* out, unsigned char* cover, const void* workspace,
+                                                 void* stats_rows, void* stream) {
+    const char* name = "f32_volume_stack_update_reg";
+    if (!x || !views || !out || !coeffs || !cover_in) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (K < 1 || K > kMaxStacks) MRISR_FAIL(MRISR_E_ARG, "%s: %d stacks (1..%d)", name, K, kMaxStacks);
+    if (!isfinite(step)) MRISR_FAIL(MRISR_E_ARG, "%s: step %g is not finite", name, (double)step);
+    if (use_clamp != 0 && use_clamp != 1) MRISR_FAIL(MRISR_E_ARG, "%s: use_clamp %d (0 or 1)", name, use_clamp);
+    if (use_clamp && !isfinite(lo)) MRISR_FAIL(MRISR_E_ARG, "%s: the lower clamp %g is not finite", name, (double)lo);
+    if (!isfinite(lambda) || lambda < 0.f) MRISR_FAIL(MRISR_E_ARG, "%s: lambda %g (finite, not negative)", name, (double)lambda);
+    if (!(delta > 0.f)) MRISR_FAIL(MRISR_E_ARG, "%s: delta %g (positive, may be infinite)", name, (double)delta);
+    StackPrior pr = {lambda, delta, {coeffs[0], coeffs[1], coeffs[2]}};
+    for (int a = 0; a < 3; ++a)
+        if (!isfinite(pr.c[a]) || !(pr.c[a] > 0.f)) MRISR_FAIL(MRISR_E_ARG, "%s: coefficient %d is %g (finite, positive)", name, a, (double)pr.c[a]);
+    const double bound = (double)step * (double)lambda * (((double)pr.c[0] + (double)pr.c[1]) + (double)pr.c[2]);
+    if (!(bound <= 0.5))
+        MRISR_FAIL(MRISR_E_ARG, "%s: step * lambda * (c_0 + c_1 + c_2) = %g breaks the stability bound <= 0.5", name, bound);
+    if ((workspace == nullptr) != (stats_rows == nullptr)) MRISR_FAIL(MRISR_E_ARG, "%s: workspace and stats_rows go together", name);
+    BrickGrid grid;
+    if (const int rc = check_field_volume(name, X, Y, Z, &grid)) return rc;
+    if (!aligned_to(x, 4) || !aligned_to(out, 4) || !aligned_to(workspace, 8) || !aligned_to(stats_rows, 8))
+        MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer", name);
+    if (out == x) MRISR_FAIL(MRISR_E_ARG, "%s: out must differ from x (the neighbours are read before the update)", name);
+    StackViews v = {};
+    for (int s = 0; s < K; ++s) {
+        const mrisr_stack_view& in = views[s];
+        if (!in.data) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: null pointer", name, s);
+        if (!aligned_to(in.data, 4)) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: misaligned pointer", name, s);
+        if (in.data == out || (const void*)in.data == (const void*)cover)
+            MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: out and cover must be buffers of their own", name, s);
+        if (const int rc = check_matrix(name, in.m, v.m[s])) return rc;
+        BrickGrid sg;
+        if (const int rc = check_field_volume(name, in.nx, in.ny, in.nz, &sg)) return rc;
+        v.data[s] = in.data;
+        v.n[s][0] = in.nx, v.n[s][1] = in.ny, v.n[s][2] = in.nz;
+        v.nslots[s] = sg.nslots;
+    }
+    if ((const void*)cover_in == (const void*)x || (const void*)cover_in == (const void*)out)
+        MRISR_FAIL(MRISR_E_ARG, "%s: cover_in must be a buffer of its own", name);
+    if (cover && ((const void*)cover == (const void*)x || (const void*)cover == (const void*)out || cover == cover_in))
+        MRISR_FAIL(MRISR_E_ARG, "%s: cover must be a buffer of its own", name);
+    // at most ceil(2^31 / 2048) tiles plus the remainder tiles of every row: far inside unsigned
+    const unsigned ntx = ceil_div(X, kRX), nty = ceil_div(Y, kRY), ntz = ceil_div(Z, kRZ);
+    stack_update_reg_kernel<<<ntx * nty * ntz, 256, 0, (hipStream_t)stream>>>(x, out, cover_in, cover, X, Y, Z, v, K, step, use_clamp, lo, pr, nty,
+                                                                              ntz, (const DeformSlot*)workspace, (StatsRow*)stats_rows);
     MRISR_CHECK_LAUNCH(name);
     return MRISR_OK;
 }

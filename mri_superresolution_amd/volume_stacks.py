@@ -10,6 +10,7 @@ to ``M_k`` (stack index -> output index) and ``N_k`` (output index -> stack inde
 
 ``slice_profile``, ``default_profile_samples``, ``default_slice_axis``, ``default_output_grid``, ``stack_geometry``   the host side.
 ``simulate_stack_np``   the forward model alone: a stack from a volume (the tests make their stacks with it).
+``regulariser_coeffs``   the weights of the regulariser's neighbour differences from the output grid's voxel sizes.
 ``stack_residual_np``, ``stack_update_np``, ``combine_stacks_np``   the specification: float32, every product, sum, difference and
                       division rounded on its own (no fma), the orders written in the docstrings.
 ``stack_residual``, ``stack_update``, ``combine_stacks``   the device path (``csrc/volume_stacks.hip``), equal to the specification
@@ -20,13 +21,25 @@ to ``M_k`` (stack index -> output index) and ``N_k`` (output index -> stack inde
 Quality (the specification on the CPU, ``tests/stackutil.py``: a 32 x 36 x 40 phantom, three orthogonal stacks, box profile, 10
 iterations, no noise): the RMSE against the truth over the initial estimate's is 0.0196, 0.0707 and 0.1058 at thickness factors 2, 3
 and 4, falling at every iteration (the stacks are made with this forward model on grids that share the output's voxel edges, the
-most favourable case).  With noise of sigma 20 the error is lowest after 2 iterations (0.54 of the initial estimate's), is 0.63,
-0.66 and 0.62 at iteration 5 and rises slowly afterwards (semi-convergence: there is no regulariser); stop early on noisy data.
-Speed on an MI355X (``tools/stacks_bench.py``, 2026-10-20, 256^3 output, three 256 x 256 x 64 stacks, T = 4): 0.46 ms an iteration
-- 0.071 ms a residual launch, 0.19 ms the update - against 9.8 ms with torch's ``affine_grid`` + ``grid_sample``.
+most favourable case).  With noise of sigma 20 the plain iteration is best after 2 iterations (0.54 of the initial estimate's), is
+0.63, 0.66 and 0.62 at iteration 5 and 0.72, 0.79 and 0.76 at iteration 20 (semi-convergence); at sigma 40 it is above 1.19 from
+iteration 10 on - worse than the initial estimate.
 
-Not built: a regulariser (TV or Laplacian); slice-to-volume motion correction within a stack; an exact adjoint (scatter)
-back-projection; intensity or bias matching between stacks inside the loop; more than 8 stacks.
+The regulariser (``reg_lambda``, ``reg_delta``, ``reg_coeffs`` of ``stack_update_np``, ``combine_stacks_np``, ``stack_update`` and
+``combine_stacks``; default off) ends that: a Huber prior on the six face neighbours, ``x' = x + step (m + lambda sum_n c_a
+clip(x[n] - x[c], -delta, delta))`` over the covered neighbours inside the grid, read before the update (Jacobi).  With lambda =
+0.03 and delta = inf the ratio at sigma 20 is 0.578, 0.591 and 0.566 at iteration 10 and 0.579, 0.592 and 0.568 at iteration 20
+(sigma 40: 0.89, 0.94, 0.93 at iteration 20): it settles and can be run to convergence - on noisy data use ``--regularise`` rather
+than stopping early.  The prior costs detail on clean stacks (0.33, 0.31, 0.30 at iteration 10 against 0.02, 0.07, 0.11); the clip
+gives most of it back (lambda = 0.05: 0.158, 0.160, 0.173 with delta = 30 against 0.508, 0.466, 0.439 with delta = inf).  The full
+table is in the README.
+
+Speed on an MI355X (``tools/stacks_bench.py --regularise``, 2026-10-20, 256^3 output, three 256 x 256 x 64 stacks, T = 4): 0.44 ms
+an iteration - 0.071 ms a residual launch, 0.19 ms the update - against 9.7 ms with torch's ``affine_grid`` + ``grid_sample``;
+regularised 0.50 ms an iteration, 0.23 ms the update launch (1.23 times the plain one), against 10.1 ms with torch.
+
+Not built: a 26-neighbour or true total-variation prior; an automatic choice of lambda; slice-to-volume motion correction within a
+stack; an exact adjoint (scatter) back-projection; intensity or bias matching between stacks inside the loop; more than 8 stacks.
 """
 from __future__ import annotations
 
@@ -218,6 +231,53 @@ def _check_stack_count(n, what):
         raise ValueError(f"{what}: 1..{MAX_STACKS} stacks are combined, got {n}")
 
 
+def regulariser_coeffs(affine_out) -> np.ndarray:
+    """(3,) float32: ``(h_min / h_a)^2`` of the output grid's voxel sizes ``h``, computed in float64 and rounded once - the weights of
+    the regulariser's neighbour differences along the three axes; an isotropic grid gives ``(1, 1, 1)``."""
+    h = voxel_sizes(affine_out)
+    if not (np.isfinite(h).all() and (h > 0).all()):
+        raise ValueError(f"the voxel sizes {h.tolist()} mm must be finite and positive")
+    return ((h.min() / h) ** 2).astype(np.float32)
+
+
+def _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs):
+    """-> ``(lambda, delta, coeffs)`` in float32 (coeffs: (3,), None gives ones); ``ValueError`` for what the rule cannot take."""
+    with np.errstate(all="ignore"):
+        lam, delta = np.float32(reg_lambda), np.float32(reg_delta)
+    if not (np.isfinite(lam) and lam >= 0):
+        raise ValueError(f"reg_lambda must be finite and not negative, got {reg_lambda!r}")
+    if not delta > 0:                                                # a NaN compares false
+        raise ValueError(f"reg_delta must be positive (inf: the quadratic prior), got {reg_delta!r}")
+    if reg_coeffs is None:
+        c = np.ones(3, dtype=np.float32)
+    else:
+        with np.errstate(all="ignore"):
+            c = np.asarray(reg_coeffs, dtype=np.float32)
+        if c.shape != (3,) or not (np.isfinite(c).all() and (c > 0).all()):
+            raise ValueError(f"reg_coeffs are three finite positive numbers, got {reg_coeffs!r}")
+    bound = float(step) * float(lam) * ((float(c[0]) + float(c[1])) + float(c[2]))
+    if not bound <= 0.5:
+        raise ValueError(f"step * reg_lambda * (c_0 + c_1 + c_2) = {bound:.6g} breaks the stability bound <= 0.5 of the explicit "
+                         f"diffusion step (unit coefficients, step 1: reg_lambda <= 1/6)")
+    return lam, delta, np.ascontiguousarray(c)
+
+
+def _regulariser_np(x, cnt, delta, coeffs):
+    """``reg`` of ``stack_update_np`` for every voxel, float32: axes ascending, the lower neighbour before the upper one."""
+    reg = np.zeros(x.shape, dtype=np.float32)
+    covered = cnt > 0
+    for a in range(3):
+        for side in (-1, 1):
+            here = [slice(None)] * 3
+            there = [slice(None)] * 3
+            here[a], there[a] = (slice(1, None), slice(None, -1)) if side < 0 else (slice(None, -1), slice(1, None))
+            here, there = tuple(here), tuple(there)
+            d = x[there] - x[here]
+            psi = np.where(d > delta, delta, np.where(d < -delta, -delta, d))      # a NaN falls through and stays
+            reg[here] = np.where(covered[there], reg[here] + coeffs[a] * psi, reg[here])
+    return reg
+
+
 def _index_axes(shape):
     return [np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)]) for a, n in enumerate(shape)]
 
@@ -286,18 +346,29 @@ def stack_residual_np(x, y, geometry: StackGeometry):
     return r, (math.fsum(r64 * r64), int(ok.sum()))
 
 
-def stack_update_np(x, residuals, geometries, step: float = 1.0, clamp=0.0):
+def stack_update_np(x, residuals, geometries, step: float = 1.0, clamp=0.0, reg_lambda: float = 0.0, reg_delta: float = math.inf,
+                    reg_coeffs=None):
     """-> ``(x', cnt)``.  For every output voxel and ``k`` ascending: ``p = N_k (i, j, k)`` (the coordinate rule above); inside
     stack ``k``: ``sum = sum + g`` with ``g`` the linear gather of ``residuals[k]`` (border replicated) and ``cnt += 1``.
     ``x' = x + step * (sum / float32(cnt))`` where ``cnt > 0``, every operation rounded to float32, then ``clamp`` where that is
     below ``clamp`` (None: no clamp; a NaN stays); ``x' = x`` where no stack covers the voxel - neither stepped nor clamped.
-    ``cnt`` is uint8."""
+    ``cnt`` is uint8.
+
+    ``reg_lambda > 0`` adds a Huber prior on the six face neighbours.  With ``m = sum / float32(cnt)``, at a voxel ``c`` with
+    ``cnt > 0``: ``reg = +0``; for ``a`` in 0, 1, 2 and ``side`` in -1, +1, the neighbour ``n = c + side e_a`` - skipped when it lies
+    outside the grid or no stack covers it (``cnt[n] == 0``: it holds the fill, not anatomy) - adds ``d = x[n] - x[c]``,
+    ``psi = delta if d > delta else (-delta if d < -delta else d)`` (a NaN stays), ``reg = reg + c_a * psi``; then
+    ``x' = x + step * (m + reg_lambda * reg)``, every operation one rounded float32 operation, and the clamp.  All neighbours are
+    read from ``x`` before the update (Jacobi).  ``reg_delta = inf`` is the quadratic prior; ``reg_coeffs`` (None: ones) are the
+    ``c_a``, ``regulariser_coeffs`` of the output grid.  ``step * reg_lambda * (c_0 + c_1 + c_2) <= 0.5`` must hold (the limit of
+    an explicit diffusion step).  ``reg_lambda = 0`` is the rule above, the same operations as without the keywords."""
     x = _check_volume_np(x, "stack_update_np")
     residuals, geometries = list(residuals), list(geometries)
     _check_stack_count(len(residuals), "stack_update_np")
     if len(geometries) != len(residuals):
         raise ValueError(f"stack_update_np: {len(residuals)} stacks and {len(geometries)} geometries")
     step, lo = _check_step(step), _check_clamp(clamp)
+    lam, delta, coeffs = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
     q = _index_axes(x.shape)
     total, cnt = np.zeros(x.shape, dtype=np.float32), np.zeros(x.shape, dtype=np.uint8)
     with np.errstate(all="ignore"):
@@ -309,7 +380,10 @@ def stack_update_np(x, residuals, geometries, step: float = 1.0, clamp=0.0):
                 cnt[inside] += 1
         out = x.copy()
         hit = cnt > 0
-        new = x[hit] + step * (total[hit] / cnt[hit].astype(np.float32))
+        if lam > 0:
+            new = x[hit] + step * (total[hit] / cnt[hit].astype(np.float32) + lam * _regulariser_np(x, cnt, delta, coeffs)[hit])
+        else:
+            new = x[hit] + step * (total[hit] / cnt[hit].astype(np.float32))
         if lo is not None:
             new = np.where(new < lo, lo, new)
         out[hit] = new
@@ -323,17 +397,19 @@ def _rms_table(sums, counts):
 
 
 def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_ITERATIONS, step: float = 1.0, clamp=0.0, fill: float = 0.0,
-                      on_iteration=None) -> StackResult:
+                      on_iteration=None, reg_lambda: float = 0.0, reg_delta: float = math.inf, reg_coeffs=None) -> StackResult:
     """The specification of ``combine_stacks``.  The initial estimate is ``stack_update_np`` of a volume of ``fill`` with ``step = 1``
     and the stacks themselves in place of the residuals: the mean, over the stacks that cover a voxel, of their linear reslices; a
     voxel no stack covers is ``fill`` to the end.  Then ``iterations`` times: ``r_k = stack_residual_np(x, y_k, g_k)`` for every
     stack, ``x = stack_update_np(x, r, g, step, clamp)``.  ``on_iteration(it, x)`` is called with the initial estimate (``it = 0``)
-    and after every update."""
+    and after every update.  ``reg_lambda``, ``reg_delta``, ``reg_coeffs``: the regulariser of ``stack_update_np``, in the updates of
+    the iterations alone - the initial estimate is never regularised."""
     stacks, geometries = [_check_volume_np(y, "combine_stacks_np") for y in stacks], list(geometries)
     _check_stack_count(len(stacks), "combine_stacks_np")
     if len(geometries) != len(stacks):
         raise ValueError(f"combine_stacks_np: {len(stacks)} stacks and {len(geometries)} geometries")
     shape_out, iterations = _check_shape(shape_out, "shape_out"), _check_iterations(iterations)
+    _check_regulariser(_check_step(step), reg_lambda, reg_delta, reg_coeffs)
     x, cnt = stack_update_np(np.full(shape_out, np.float32(fill), dtype=np.float32), stacks, geometries, 1.0, clamp)
     initial = x.copy()
     if on_iteration is not None:
@@ -344,7 +420,7 @@ def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_I
         for k, (y, g) in enumerate(zip(stacks, geometries)):
             r, (sums[it, k], counts[it, k]) = stack_residual_np(x, y, g)
             res.append(r)
-        x = stack_update_np(x, res, geometries, step, clamp)[0]
+        x = stack_update_np(x, res, geometries, step, clamp, reg_lambda, reg_delta, reg_coeffs)[0]
         if on_iteration is not None:
             on_iteration(it + 1, x)
     return StackResult(x, initial, _rms_table(sums, counts), counts, np.bincount(cnt.reshape(-1), minlength=len(stacks) + 1).astype(np.int64))
@@ -390,6 +466,14 @@ def _update(x, volumes, geometries, step, lo, out, cover, slots, stats_rows):
            L.stream_ptr(), nbytes=4 * (2 * x.numel() + sum(v.numel() for v in volumes)))
 
 
+def _update_reg(x, volumes, geometries, step, lo, reg, coverage, out, cover, slots, stats_rows):
+    lam, delta, coeffs = reg
+    L.call("mrisr_f32_volume_stack_update_reg", x.data_ptr(), *x.shape, _views_arg(volumes, geometries), len(volumes), float(step),
+           int(lo is not None), 0.0 if lo is None else float(lo), float(lam), float(delta), (L.C.c_float * 3)(*coeffs.tolist()),
+           coverage.data_ptr(), out.data_ptr(), L.ptr(cover), L.ptr(slots), L.ptr(stats_rows), L.stream_ptr(),
+           nbytes=4 * (2 * x.numel() + sum(v.numel() for v in volumes)) + x.numel())
+
+
 def stack_residual(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, out=None):
     """The device path of ``stack_residual_np`` -> ``(r, S, n)``: ``r`` bit for bit; ``S`` (0-d float64) within one spacing of the
     specification's sum and the same bits on every run, ``n`` (0-d int64) equal - both stay on the device.  Two launches (the
@@ -415,15 +499,31 @@ def _check_stacks(volumes, geometries, device, what):
     return volumes, [_check_geometry(g, f"{what}: stack {k}") for k, g in enumerate(geometries)]
 
 
-def stack_update(x: torch.Tensor, residuals, geometries, step: float = 1.0, clamp=0.0, out=None, cover: bool = False):
+def stack_update(x: torch.Tensor, residuals, geometries, step: float = 1.0, clamp=0.0, out=None, cover: bool = False,
+                 reg_lambda: float = 0.0, reg_delta: float = math.inf, reg_coeffs=None, coverage=None):
     """The device path of ``stack_update_np`` -> ``(x', cnt)``, bit for bit; ``cnt`` (uint8) only with ``cover=True``, else None.
-    ONE launch for all the stacks, no device-to-host read.  ``out``: a tensor like ``x`` - ``x`` itself updates in place."""
+    ONE launch for all the stacks, no device-to-host read.  ``out``: a tensor like ``x`` - ``x`` itself updates in place.
+    ``reg_lambda > 0``: the regularised kernel, which reads the neighbours of a voxel - ``out`` must not be ``x`` - and the coverage
+    counts of these stacks: ``coverage`` (uint8, like ``x``; ``cnt`` of an earlier call) is taken as given, None costs one launch of
+    the plain kernel into scratch."""
     x = _check_tensor(x, (torch.float32,), "stack_update")
     volumes, geometries = _check_stacks(residuals, geometries, x.device, "stack_update")
     step, lo = _check_step(step), _check_clamp(clamp)
+    reg = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
+    if coverage is not None and (not isinstance(coverage, torch.Tensor) or coverage.dtype != torch.uint8 or coverage.shape != x.shape
+                                 or coverage.device != x.device or not coverage.is_contiguous()):
+        raise ValueError(f"stack_update: coverage must be a contiguous uint8 tensor of shape {tuple(x.shape)} on {x.device}")
+    if reg[0] > 0 and isinstance(out, torch.Tensor) and out.data_ptr() == x.data_ptr():
+        raise ValueError("stack_update: with reg_lambda > 0 the neighbours are read before the update: out must be another tensor than x")
     out = x if out is x else _check_out(out, x, volumes, "stack_update")
     cnt = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if cover else None
-    _update(x, volumes, geometries, step, lo, out, cnt, None, None)
+    if reg[0] > 0:
+        if coverage is None:
+            coverage = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+            _update(x, volumes, geometries, 1.0, None, torch.empty_like(x), coverage, None, None)
+        _update_reg(x, volumes, geometries, step, lo, reg, coverage, out, cnt, None, None)
+    else:
+        _update(x, volumes, geometries, step, lo, out, cnt, None, None)
     return out, cnt
 
 
@@ -431,15 +531,17 @@ class StackWorkspace:
     """Everything ``combine_stacks`` needs besides the stacks, for this output shape, these stack shapes and this iteration count:
     the estimate, one residual volume per stack, the coverage counts, the fixed slots of the sums (one region per stack) and the
     stats buffer - one (double, int64) row per iteration and stack.  Made before a HIP-graph capture, it serves call after call on
-    one stream."""
+    one stream.  ``regularised``: it also holds a second estimate - the regularised update reads the neighbours of a voxel and cannot
+    run in place, so the iterations alternate between the two."""
 
-    def __init__(self, shape_out, stack_shapes, device, iterations: int = DEFAULT_ITERATIONS):
+    def __init__(self, shape_out, stack_shapes, device, iterations: int = DEFAULT_ITERATIONS, regularised: bool = False):
         self.shape_out = _check_shape(shape_out, "shape_out")
         self.stack_shapes = tuple(_check_shape(s, "stack shape") for s in stack_shapes)
         _check_stack_count(len(self.stack_shapes), "StackWorkspace")
         self.iterations = _check_iterations(iterations)
         self.key = (self.shape_out, self.stack_shapes, self.iterations)
         self.x = torch.empty(self.shape_out, dtype=torch.float32, device=device)
+        self.x2 = torch.empty_like(self.x) if regularised else None
         self.residuals = [torch.empty(s, dtype=torch.float32, device=device) for s in self.stack_shapes]
         self.cover = torch.empty(self.shape_out, dtype=torch.uint8, device=device)
         self.slots = _slots(device, len(self.stack_shapes))
@@ -449,51 +551,64 @@ class StackWorkspace:
         return self.slots.data_ptr() + k * _region_bytes()
 
 
-def _iterate(ws, stacks, geometries, first, count, step, lo):
+def _iterate(ws, stacks, geometries, first, count, step, lo, reg=None):
     """``count`` iterations from row ``first``, ``K + 1`` launches each: the residual of every stack against the estimate, then the
-    update in place, whose first wave adds the residuals' slots into the iteration's stats rows.  Nothing is allocated."""
+    update in place, whose first wave adds the residuals' slots into the iteration's stats rows.  Nothing is allocated.  ``reg``
+    (``_check_regulariser``): the regularised update, from ``ws.x`` into ``ws.x2`` in the even iterations and back in the odd ones,
+    with the coverage counts in ``ws.cover``."""
     for it in range(first, first + count):
+        x, out = (ws.x, ws.x) if reg is None else ((ws.x, ws.x2) if it % 2 == 0 else (ws.x2, ws.x))
         for k, (y, g) in enumerate(zip(stacks, geometries)):
-            _residual(ws.x, y, g, ws.residuals[k], ws.region(k), None)
-        _update(ws.x, ws.residuals, geometries, step, lo, ws.x, None, ws.slots, ws.stats[it])
+            _residual(x, y, g, ws.residuals[k], ws.region(k), None)
+        if reg is None:
+            _update(x, ws.residuals, geometries, step, lo, out, None, ws.slots, ws.stats[it])
+        else:
+            _update_reg(x, ws.residuals, geometries, step, lo, reg, ws.cover, out, None, ws.slots, ws.stats[it])
 
 
 def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITERATIONS, step: float = 1.0, clamp=0.0, fill: float = 0.0,
-                   workspace=None, graph: bool = False, check: bool = False) -> StackResult:
+                   workspace=None, graph: bool = False, check: bool = False, reg_lambda: float = 0.0, reg_delta: float = math.inf,
+                   reg_coeffs=None) -> StackResult:
     """The device path of ``combine_stacks_np``: ``volume`` and ``initial`` (CUDA tensors) bit for bit, ``counts`` and ``coverage``
     equal, ``rms`` from sums within one spacing.  An iteration is ``K + 1`` launches; the one device-to-host read - the stats rows
     and the coverage counts - is the last thing done.  ``graph``: the iteration loop is captured into a HIP graph and replayed
     (after one eager iteration as a warm-up, which loads the code objects) - the same bits as the eager loop.  ``workspace``: a
     ``StackWorkspace`` of these shapes and this iteration count.  ``check``: a volume that is not finite everywhere raises - the
-    flag travels in the same read."""
+    flag travels in the same read.  ``reg_lambda``, ``reg_delta``, ``reg_coeffs``: the regulariser of ``stack_update_np``; with
+    ``reg_lambda > 0`` the iterations run the regularised kernel between the two estimates of a ``StackWorkspace(...,
+    regularised=True)`` - still ``K + 1`` launches and one read; with 0 the kernels and the bits are those without the keywords."""
     if not stacks:
         raise ValueError(f"combine_stacks: 1..{MAX_STACKS} stacks are combined, got 0")
     first = _check_tensor(list(stacks)[0], (torch.float32,), "combine_stacks: stack 0")
     stacks, geometries = _check_stacks(stacks, geometries, first.device, "combine_stacks")
     shape_out, iterations = _check_shape(shape_out, "shape_out"), _check_iterations(iterations)
     step, lo = _check_step(step), _check_clamp(clamp)
+    reg = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
+    reg = reg if reg[0] > 0 else None
     if workspace is None:
-        workspace = StackWorkspace(shape_out, [y.shape for y in stacks], first.device, iterations)
+        workspace = StackWorkspace(shape_out, [y.shape for y in stacks], first.device, iterations, regularised=reg is not None)
     ws = workspace
     if not isinstance(ws, StackWorkspace) or ws.key != (shape_out, tuple(tuple(y.shape) for y in stacks), iterations) \
             or ws.x.device != first.device:
         raise ValueError(f"combine_stacks: the workspace must be a StackWorkspace for an output of {shape_out}, these stack shapes and "
                          f"{iterations} iterations on {first.device}")
+    if reg is not None and ws.x2 is None:
+        raise ValueError("combine_stacks: reg_lambda > 0 needs a workspace with the second estimate: StackWorkspace(..., regularised=True)")
     K = len(stacks)
     ws.x.fill_(float(fill))
     _update(ws.x, stacks, geometries, 1.0, lo, ws.x, ws.cover, None, None)
     initial = ws.x.clone()
     if graph and iterations:
-        _iterate(ws, stacks, geometries, 0, 1, step, lo)
+        _iterate(ws, stacks, geometries, 0, 1, step, lo, reg)
         ws.x.copy_(initial)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            _iterate(ws, stacks, geometries, 0, iterations, step, lo)
+            _iterate(ws, stacks, geometries, 0, iterations, step, lo, reg)
         g.replay()
     else:
-        _iterate(ws, stacks, geometries, 0, iterations, step, lo)
-    volume = ws.x.clone()
+        _iterate(ws, stacks, geometries, 0, iterations, step, lo, reg)
+    volume = (ws.x2 if reg is not None and iterations % 2 else ws.x).clone()       # the estimate an odd count of regularised updates left
     tail = [torch.stack([(ws.cover == c).sum() for c in range(K + 1)])]
     if check:
         tail.append(torch.isfinite(volume).all().to(torch.int64).reshape(1))

@@ -13,7 +13,11 @@ a sample per output voxel over the profile) describe the slices.  ``--register r
 first (``volume_register.register_rigid``) and folds the transform into that stack's matrices: the patient moves between
 acquisitions.  Per iteration and stack the RMS of the residual is logged, and the share of the output voxels covered by 0, 1, ...,
 K stacks.  ``--no_clamp`` lets the estimate go below 0; ``--fill`` is the value of the voxels no stack covers; ``--save_initial``
-writes the initial estimate (the mean of the stacks' linear reslices).  4-D inputs must agree in their frame count and are combined
+writes the initial estimate (the mean of the stacks' linear reslices).  ``--regularise LAMBDA`` (default 0: none) adds the Huber
+prior of ``volume_stacks.stack_update_np`` on the six face neighbours to every update - on noisy stacks the plain iteration is past
+its best after two or three updates, with the prior it settles and can be run to convergence; ``--regularise_delta D`` (default inf:
+the quadratic prior) clips the neighbour differences at ``D`` intensity units, which keeps tissue steps and fine detail; the
+coefficients are ``volume_stacks.regulariser_coeffs`` of the output grid.  4-D inputs must agree in their frame count and are combined
 frame by frame.  The output is float32 under ``utils.nifti.header_for_grid`` of the first input's header.  Exit code 0 / 1 (error
 logged), as ``scripts/infer_volume.py``.
 """
@@ -44,11 +48,13 @@ def per_stack(values, count, name, default):
     return list(values) * (count if len(values) == 1 else 1)
 
 
-def check_options(inputs, iterations=S.DEFAULT_ITERATIONS, step=1.0, slice_axis=None, thickness_mm=None, profile_samples=None, spacing=None):
+def check_options(inputs, iterations=S.DEFAULT_ITERATIONS, step=1.0, slice_axis=None, thickness_mm=None, profile_samples=None, spacing=None,
+                  regularise=0.0, regularise_delta=float("inf")):
     """The checks that need no file: raises ``ValueError`` before anything is read."""
     if not 1 <= len(inputs) <= S.MAX_STACKS:
         raise ValueError(f"1..{S.MAX_STACKS} stacks are combined, got {len(inputs)}")
     S._check_iterations(iterations), S._check_step(step)
+    S._check_regulariser(0.0, regularise, regularise_delta, None)      # the stability bound needs the grid's coefficients: combine_stacks checks it
     axes = [None if a == "auto" else int(a) for a in per_stack(slice_axis, len(inputs), "slice_axis", "auto")]
     if any(a is not None and a not in (0, 1, 2) for a in axes):
         raise ValueError(f"--slice_axis is auto, 0, 1 or 2, got {slice_axis}")
@@ -63,9 +69,10 @@ def check_options(inputs, iterations=S.DEFAULT_ITERATIONS, step=1.0, slice_axis=
 
 
 def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEFAULT_ITERATIONS, step=1.0, profile="box", thickness_mm=None,
-                  slice_axis=None, profile_samples=None, register="none", clamp=0.0, fill=0.0, save_initial=None, device="cuda"):
+                  slice_axis=None, profile_samples=None, register="none", clamp=0.0, fill=0.0, save_initial=None, device="cuda",
+                  regularise=0.0, regularise_delta=float("inf")):
     """NIfTI stacks -> one NIfTI volume; returns the output array (as written)."""
-    axes, thickness = check_options(inputs, iterations, step, slice_axis, thickness_mm, profile_samples, spacing)
+    axes, thickness = check_options(inputs, iterations, step, slice_axis, thickness_mm, profile_samples, spacing, regularise, regularise_delta)
     scans = [read_nifti(p) for p in inputs]
     per_scan = [[np.ascontiguousarray(f, dtype=np.float32) for f in frames(d)] for d, _ in scans]
     if len({len(f) for f in per_scan}) != 1 or len({d.ndim for d, _ in scans}) != 1:
@@ -88,11 +95,15 @@ def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEF
     for k, g in enumerate(geometries):
         logger.info(f"stack {k}: {shapes[k]} voxels of {np.round(S.voxel_sizes(affines[k]), 3).tolist()} mm, slice axis {g.slice_axis}, "
                     f"{g.offsets.size} {profile} profile samples over {g.offsets[-1] - g.offsets[0]:.3f} slices")
-    ws = S.StackWorkspace(shape_out, shapes, device, iterations)
+    coeffs = S.regulariser_coeffs(affine_out) if regularise > 0 else None
+    if regularise > 0:
+        logger.info(f"regulariser: lambda {regularise:g}, delta {regularise_delta:g}, coefficients {[round(float(c), 6) for c in coeffs]} "
+                    f"(output voxels of {np.round(S.voxel_sizes(affine_out), 3).tolist()} mm)")
+    ws = S.StackWorkspace(shape_out, shapes, device, iterations, regularised=regularise > 0)
     outs, initials = [], []
     for t in range(len(per_scan[0])):
         r = S.combine_stacks([torch.from_numpy(f[t]).to(device) for f in per_scan], geometries, shape_out, iterations, step, clamp, fill,
-                             workspace=ws, check=True)
+                             workspace=ws, check=True, reg_lambda=regularise, reg_delta=regularise_delta, reg_coeffs=coeffs)
         for it in range(iterations):
             logger.info(f"frame {t} iteration {it + 1}: residual RMS per stack {[round(float(v), 4) for v in r.rms[it]]}")
         shares = r.coverage / float(r.coverage.sum())
@@ -115,13 +126,15 @@ def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEF
 def main(args):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     try:
-        check_options(args.inputs, args.iterations, args.step, args.slice_axis, args.thickness_mm, args.profile_samples, args.spacing)
+        check_options(args.inputs, args.iterations, args.step, args.slice_axis, args.thickness_mm, args.profile_samples, args.spacing,
+                      args.regularise, args.regularise_delta)
         if args.cpu or not torch.cuda.is_available():
             raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
         device = torch.device("cuda")
         logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
         combine_files(args.inputs, args.output, args.spacing, args.like, args.iterations, args.step, args.profile, args.thickness_mm,
-                      args.slice_axis, args.profile_samples, args.register, None if args.no_clamp else 0.0, args.fill, args.save_initial, device)
+                      args.slice_axis, args.profile_samples, args.register, None if args.no_clamp else 0.0, args.fill, args.save_initial, device,
+                      args.regularise, args.regularise_delta)
         return 0
     except Exception as e:
         logger.error(f"Error during the reconstruction: {e}")
@@ -145,6 +158,9 @@ def parse_args(argv=None):
     p.add_argument("--no_clamp", action="store_true", help="do not clamp the estimate at 0")
     p.add_argument("--fill", type=float, default=0.0, help="value of the output voxels no stack covers")
     p.add_argument("--save_initial", type=str, default=None, help="write the initial estimate (the mean of the linear reslices)")
+    p.add_argument("--regularise", type=float, default=0.0, metavar="LAMBDA", help="weight of the Huber prior on the six face neighbours (default 0: none); "
+                   "step * LAMBDA * (sum of the coefficients) <= 0.5")
+    p.add_argument("--regularise_delta", type=float, default=float("inf"), metavar="D", help="clip the neighbour differences at D (default inf: quadratic prior)")
     p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
     return p.parse_args(argv)
 

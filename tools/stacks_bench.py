@@ -15,6 +15,15 @@ the smallest and the largest:
               their mean, the difference; then K sampled residuals, their mean, the step and the clamp;
   copy        device-to-device copies that move each kernel's algorithmic bytes (every tensor read or written once).
 
+With --regularise the same run also times, alternating with the plain ones in every round:
+
+  update_reg     the regularised update launch alone (``mrisr_f32_volume_stack_update_reg``: lambda 0.03, delta 60, unit coefficients,
+                 the coverage counts of the stacks), from one estimate into the other;
+  iteration_reg  the regularised iteration (``volume_stacks._iterate`` on a ``StackWorkspace(..., regularised=True)``), an even and
+                 an odd one in turn: half the time of the pair is reported;
+  torch_reg      the torch iteration with the same prior written with shifted slices (replicated faces: a difference of 0), ``clamp``
+                 for the clip.
+
 One JSON line at the end.
 """
 import argparse
@@ -64,7 +73,18 @@ def theta(m, src_shape, dst_shape):
     return torch.from_numpy((flip @ full @ flip)[:3]).float().unsqueeze(0).cuda()
 
 
-def torch_iteration(x, stacks, geometries, step):
+def torch_prior(x, delta):
+    """The sum over the six face neighbours of the clipped differences (unit coefficients, every voxel covered)."""
+    reg = torch.zeros_like(x)
+    for a in range(3):
+        lo, hi = x.narrow(a, 0, x.shape[a] - 1), x.narrow(a, 1, x.shape[a] - 1)
+        d = (hi - lo).clamp_(-delta, delta)
+        reg.narrow(a, 0, x.shape[a] - 1).add_(d)
+        reg.narrow(a, 1, x.shape[a] - 1).sub_(d)
+    return reg
+
+
+def torch_iteration(x, stacks, geometries, step, lam=0.0, delta=float("inf")):
     res = []
     for y, g in zip(stacks, geometries):
         acc = torch.zeros_like(y)
@@ -78,6 +98,8 @@ def torch_iteration(x, stacks, geometries, step):
     for r, g in zip(res, geometries):
         grid = F.affine_grid(theta(g.from_output, r.shape, x.shape), (1, 1) + tuple(x.shape), align_corners=False)
         total = total + F.grid_sample(r[None, None], grid, mode="bilinear", padding_mode="border", align_corners=False)[0, 0]
+    if lam > 0:
+        return (x + step * (total / len(res) + lam * torch_prior(x, delta))).clamp_(min=0)
     return (x + step * (total / len(res))).clamp_(min=0)
 
 
@@ -95,7 +117,7 @@ def main(args):
         affine[axis, 3] = 0.5 * (n / ns - 1.0)
         geometries.append(S.stack_geometry(affine, np.eye(4), axis, "box", samples=T))
         stacks.append(torch.from_numpy(rng.uniform(0, 900, shape).astype(np.float32)).cuda())
-    ws = S.StackWorkspace(out_shape, [y.shape for y in stacks], "cuda", 1)
+    ws = S.StackWorkspace(out_shape, [y.shape for y in stacks], "cuda", 2, regularised=args.regularise)
     ws.x.copy_(torch.from_numpy(rng.uniform(0, 900, out_shape).astype(np.float32)))
     x0 = ws.x.clone()
     voxels, sv = n ** 3, n * n * ns
@@ -103,13 +125,27 @@ def main(args):
     buf = torch.empty(max(res_bytes, upd_bytes) // 2, dtype=torch.uint8, device="cuda")
     dst = torch.empty_like(buf)
     t = {k: [] for k in ("iteration", "residual", "update", "torch", "copy_residual", "copy_update")}
+    lo = np.float32(0)
+    if args.regularise:
+        t.update({k: [] for k in ("iteration_reg", "update_reg", "torch_reg")})
+        lam, delta = 0.03, 60.0
+        reg = S._check_regulariser(1.0, lam, delta, None)
+        S._update(ws.x, stacks, geometries, 1.0, lo, ws.x2, ws.cover, None, None)      # the coverage counts: geometry only
+        ws.x.copy_(x0)
     for _ in range(args.rounds):
+        if args.regularise:
+            t["iteration_reg"].append(0.5 * timed(lambda: S._iterate(ws, stacks, geometries, 0, 2, 1.0, lo, reg), args.iters, args.warmup))
+            ws.x.copy_(x0)
         t["iteration"].append(timed(lambda: S._iterate(ws, stacks, geometries, 0, 1, 1.0, np.float32(0)), args.iters, args.warmup))
         per = [timed(lambda k=k: S._residual(ws.x, stacks[k], geometries[k], ws.residuals[k], ws.region(k), None), args.iters, args.warmup)
                for k in range(3)]
         t["residual"].append(float(np.median(per)))
         t["update"].append(timed(lambda: S._update(ws.x, ws.residuals, geometries, 1.0, np.float32(0), ws.x, None, None, None), args.iters,
                                  args.warmup))
+        if args.regularise:
+            t["update_reg"].append(timed(lambda: S._update_reg(ws.x, ws.residuals, geometries, 1.0, lo, reg, ws.cover, ws.x2, None, None, None),
+                                         args.iters, args.warmup))
+            t["torch_reg"].append(timed(lambda: torch_iteration(x0, stacks, geometries, 1.0, lam, delta), args.torch_iters, 1))
         t["torch"].append(timed(lambda: torch_iteration(x0, stacks, geometries, 1.0), args.torch_iters, 1))
         t["copy_residual"].append(timed(lambda: dst[:res_bytes // 2].copy_(buf[:res_bytes // 2]), args.iters, args.warmup))
         t["copy_update"].append(timed(lambda: dst[:upd_bytes // 2].copy_(buf[:upd_bytes // 2]), args.iters, args.warmup))
@@ -126,6 +162,15 @@ def main(args):
               "update_share_of_copy_rate": round(med["copy_update"] / med["update"], 3),
               "iteration_share_of_copy_rate": round((3 * med["copy_residual"] + med["copy_update"]) / med["iteration"], 3),
               "largest_difference_from_torch": diff}
+    if args.regularise:
+        ws.x.copy_(x0)
+        S._iterate(ws, stacks, geometries, 0, 1, 1.0, lo, reg)
+        result.update({"reg_lambda": lam, "reg_delta": delta, "iteration_reg_ms": stats(t["iteration_reg"]),
+                       "update_reg_ms": stats(t["update_reg"]), "torch_reg_iteration_ms": stats(t["torch_reg"]),
+                       "update_reg_over_update": round(med["update_reg"] / med["update"], 3),
+                       "iteration_reg_over_iteration": round(med["iteration_reg"] / med["iteration"], 3),
+                       "reg_speedup_over_torch": round(med["torch_reg"] / med["iteration_reg"], 2),
+                       "largest_reg_difference_from_torch": float((ws.x2 - torch_iteration(x0, stacks, geometries, 1.0, lam, delta)).abs().max())})
     print(json.dumps(result))
     return 0
 
@@ -139,6 +184,7 @@ def parse_args(argv=None):
     p.add_argument("--torch_iters", type=int, default=3)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--rounds", type=int, default=5, help="alternating repetitions of every timing")
+    p.add_argument("--regularise", action="store_true", help="also time the regularised update launch and iteration, alternating with the plain ones")
     return p.parse_args(argv)
 
 
