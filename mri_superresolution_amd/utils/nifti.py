@@ -221,7 +221,7 @@ def downscaled_affine(affine: np.ndarray, axes: Sequence[int]) -> np.ndarray:
     return out
 
 
-def _check_affine(affine, what) -> np.ndarray:
+def check_affine(affine, what) -> np.ndarray:
     a = np.asarray(affine, dtype=np.float64)
     if a.shape != (4, 4):
         raise ValueError(f"{what} must be a 4 x 4 index -> world affine, got shape {a.shape}")
@@ -232,7 +232,7 @@ def grid_matrix(src_affine: np.ndarray, dst_affine: np.ndarray) -> np.ndarray:
     """(3, 4) float64: the first three rows of ``inv(src_affine) @ dst_affine`` (``np.linalg.solve``) - a voxel index of the
     destination grid -> the continuous voxel index of the source grid.  A singular or non-finite ``src_affine`` (or a non-finite
     ``dst_affine``) is a ``ValueError``."""
-    src, dst = _check_affine(src_affine, "src_affine"), _check_affine(dst_affine, "dst_affine")
+    src, dst = check_affine(src_affine, "src_affine"), check_affine(dst_affine, "dst_affine")
     if not np.isfinite(src).all() or not np.isfinite(dst).all():
         raise ValueError("grid_matrix: an affine has an entry that is not finite")
     try:
@@ -251,7 +251,7 @@ def respaced_grid(affine: np.ndarray, shape: Sequence[int], spacing: Sequence[fl
     ``n' = max(1, ceil(n s / s' - 1e-6))``, ``col' = col s' / s``; translation ``t' = t - sum(col) / 2 + sum(col') / 2``: the
     corner of the first cell stays where it was in world space.  Halving the spacing of two or three axes gives
     ``upscaled_affine`` and the doubled shape."""
-    src = _check_affine(affine, "affine")
+    src = check_affine(affine, "affine")
     shape = tuple(int(d) for d in shape)
     if len(shape) != 3 or any(d < 1 for d in shape) or len(tuple(spacing)) != 3:
         raise ValueError(f"respaced_grid takes three positive extents and three spacings, got {shape} and {tuple(spacing)}")
@@ -273,7 +273,7 @@ def header_for_grid(header: NiftiHeader, shape: Sequence[int], affine: np.ndarra
     column norms of ``affine``, ``srow_*`` its rows, ``sform_code`` kept when positive (else 1) and ``qform_code = 0`` - a
     general affine has no quaternion form, the sform alone then defines the grid.  ``dim[0]``, ``dim[4]``, the byte order and
     everything else are kept; ``write_nifti(path, data, that_header)`` takes it as it is."""
-    aff = _check_affine(affine, "affine")
+    aff = check_affine(affine, "affine")
     shape = tuple(int(d) for d in shape)
     if len(shape) != 3 or any(not 1 <= d <= 32767 for d in shape) or not np.isfinite(aff).all():
         raise ValueError(f"header_for_grid takes three extents in 1..32767 and a finite affine, got {shape}")

@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .volume_intensity import _check_mask, _check_mask_np, _check_vol, _check_vol_np, _landmarks_np
+from ._volume_args import cuda_tensor, mask_np, mask_tensor, three_sigmas, volume_np
+from .volume_intensity import masked_landmarks_np
 
 MAX_RADIUS = 128
 DEN_MIN = np.float32(1e-3)
@@ -61,13 +62,7 @@ def sigmas_for(affine, sigma_mm: float) -> tuple:
 
 
 def _check_sigmas(sigmas_vox) -> list:
-    try:
-        s = [float(x) for x in sigmas_vox]
-    except (TypeError, ValueError):
-        raise ValueError(f"three sigmas in voxels are expected, got {sigmas_vox!r}") from None
-    if len(s) != 3:
-        raise ValueError(f"three sigmas in voxels are expected, got {sigmas_vox!r}")
-    return [gaussian_taps(x) for x in s]
+    return [gaussian_taps(x) for x in three_sigmas(sigmas_vox)]
 
 
 def _check_limit(limit):
@@ -80,10 +75,8 @@ def _check_limit(limit):
 # ---------------------------------------------------------------- numpy specification
 
 def _check_pair_np(vol, mask, what):
-    vol = _check_vol_np(vol, what)
-    if vol.ndim != 3:
-        raise ValueError(f"{what}: a volume has three axes, got shape {vol.shape}")
-    return vol, _check_mask_np(mask, vol.shape, what)
+    vol = volume_np(vol, what)
+    return vol, mask_np(mask, vol.shape, what)
 
 
 def _pass_np(x, w, axis):
@@ -155,7 +148,7 @@ def correct_bias_np(vol, mask, sigmas_vox, limit=4.0):
     taps = _check_sigmas(sigmas_vox)
     lo, hi = _check_limit(limit)
     low = lowpass_np(*_smooth_np(vol, (mask != 0) & ~np.isnan(vol), taps))
-    p50, count = _landmarks_np(low, mask, (50.0,))
+    p50, count = masked_landmarks_np(low, mask, (50.0,))
     with np.errstate(all="ignore"):
         ok = (low > 0) & (count > 0)
         field = np.where(ok, low / (p50[0] + np.float32(0)), np.float32(1)).astype(np.float32)      # + 0: -0.0 and +0.0 are one median
@@ -190,10 +183,8 @@ class BiasWorkspace:
 
 
 def _check_pair(vol, mask, what):
-    vol = _check_vol(vol, what)
-    if vol.dim() != 3:
-        raise ValueError(f"{what}: a volume has three axes, got shape {tuple(vol.shape)}")
-    return vol, _check_mask(mask, vol, what)
+    vol = cuda_tensor(vol, (torch.float32,), what, ndim=3)
+    return vol, mask_tensor(mask, vol.shape, what)
 
 
 def _workspace(workspace, vol, sigmas_vox, what):

@@ -49,10 +49,10 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._volume_args import check_matrix, check_shape, cuda_tensor, matrix_arg, out_like, three_sigmas, volume_np
 from .volume_bias import gaussian_taps
 from .volume_eval import downsample2, downsample2_np, upscale2, upscale2_np
-from .volume_intensity import _check_vol
-from .volume_reslice import _check_matrix, _check_shape, _matrix_arg, _taps_np, _weighted_sum_np
+from .volume_reslice import taps_np, weighted_sum_np
 
 MAX_RADIUS = 16
 DEN_MIN = np.float32(1e-9)                 # MRISR_DEFORM_DEN_MIN: below it a voxel has neither a gradient nor a difference
@@ -74,11 +74,7 @@ class DeformResult(NamedTuple):
 # ---------------------------------------------------------------- numpy specification
 
 def _check_volume_np(v, what):
-    v = np.asarray(v)
-    if v.dtype != np.float32 or v.ndim != 3 or v.size == 0:
-        raise ValueError(f"{what}: expected a non-empty float32 volume (X,Y,Z), got {v.dtype} {v.shape}")
-    _check_shape(v.shape, f"{what}: the volume's shape")
-    return v
+    return volume_np(v, what, limit=True)
 
 
 def _check_field_np(u, shape, what):
@@ -121,19 +117,19 @@ def _warp_np(moving, u, method, fill):
     out = np.full(moving.shape, np.float32(fill), dtype=np.float32)
     if inside.any():
         with np.errstate(all="ignore"):
-            (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
+            (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
             rx = []
             for xa in ix:
-                ry = [_weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
-                rx.append(_weighted_sum_np(wy, ry))
-            out[inside] = _weighted_sum_np(wx, rx)
+                ry = [weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
+                rx.append(weighted_sum_np(wy, ry))
+            out[inside] = weighted_sum_np(wx, rx)
     return out, inside
 
 
 def warp_np(moving, u, method: str = "linear", fill: float = 0.0) -> np.ndarray:
     """``moving`` at ``x + u(x)``, float32.  Coordinate ``p_a = float64(i_a) + float64(u_a)``, one double addition; then
     ``volume_reslice.reslice_np``'s rules: inside test ``-0.5 <= p_a <= n_a - 0.5`` on all axes, outside -> ``fill`` and nothing
-    is converted to an integer, ``_taps_np``, clamped taps, reduction along z, then y, then x.  A NaN or infinite displacement is
+    is converted to an integer, ``taps_np``, clamped taps, reduction along z, then y, then x.  A NaN or infinite displacement is
     outside."""
     moving = _check_volume_np(moving, "warp_np")
     u = _check_field_np(u, moving.shape, "warp_np")
@@ -324,7 +320,7 @@ def _check_field4_np(u, what):
     u = np.asarray(u)
     if u.dtype != np.float32 or u.ndim != 4 or u.shape[0] != 3 or u.size == 0:
         raise ValueError(f"{what}: expected a non-empty float32 field (3,X,Y,Z), got {u.dtype} {u.shape}")
-    _check_shape(u.shape[1:], f"{what}: the volume's shape")
+    check_shape(u.shape[1:], f"{what}: the volume's shape")
     return u
 
 
@@ -332,7 +328,7 @@ def compose_np(u, v) -> np.ndarray:
     """``v_a + U_a``, float32 ``(3, X, Y, Z)``: ``U_a`` is ``u_a`` interpolated linearly at ``p = float64(i) + float64(v)`` (the coordinate
     of ``warp_np``), so that ``warp(warp(m, u), v)`` samples ``m`` at ``x + compose_np(u, v)(x)``, up to interpolation.  Each ``p_a``
     is clamped into ``[0, n_a - 1]`` by comparisons, ``p < 0 -> 0``, ``p > n_a - 1 -> n_a - 1``: a displacement field continues
-    constantly past the faces (a zero fill would pull the field to zero at the border).  Then ``_taps_np`` / ``_weighted_sum_np``
+    constantly past the faces (a zero fill would pull the field to zero at the border).  Then ``taps_np`` / ``weighted_sum_np``
     along z, then y, then x - the taps once for all three components - and one float32 add.
 
     An infinite displacement in ``v`` is clamped like any other, onto a face; the sum ``v_a + U_a`` is then infinite in that
@@ -353,13 +349,13 @@ def compose_np(u, v) -> np.ndarray:
     out = np.full(u.shape, np.float32(np.nan), dtype=np.float32)
     if number.any():
         with np.errstate(all="ignore"):
-            (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa[number], n, "linear") for pa, n in zip(p, shape))
+            (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[number], n, "linear") for pa, n in zip(p, shape))
             for a in range(3):
                 rx = []
                 for xa in ix:
-                    ry = [_weighted_sum_np(wz, [u[a][xa, yb, zc] for zc in iz]) for yb in iy]
-                    rx.append(_weighted_sum_np(wy, ry))
-                out[a][number] = v[a][number] + _weighted_sum_np(wx, rx)
+                    ry = [weighted_sum_np(wz, [u[a][xa, yb, zc] for zc in iz]) for yb in iy]
+                    rx.append(weighted_sum_np(wy, ry))
+                out[a][number] = v[a][number] + weighted_sum_np(wx, rx)
     return out
 
 
@@ -391,7 +387,7 @@ def warp_matrix_np(moving, m, u, method: str = "linear", fill: float = 0.0) -> n
     ``source_coordinates_np``; then ``reslice_np``'s inside test (on ``moving``'s extents), taps and reduction.  Bit for bit
     ``reslice_np`` for a zero field and ``warp_np`` for the identity matrix.  A NaN or infinite displacement is outside."""
     moving = _check_volume_np(moving, "warp_matrix_np")
-    m = _check_matrix(m)
+    m = check_matrix(m)
     u = _check_field4_np(u, "warp_matrix_np")
     _check_method(method)
     shape = u.shape[1:]
@@ -405,22 +401,17 @@ def warp_matrix_np(moving, m, u, method: str = "linear", fill: float = 0.0) -> n
     out = np.full(shape, np.float32(fill), dtype=np.float32)
     if inside.any():
         with np.errstate(all="ignore"):
-            (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
+            (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
             rx = []
             for xa in ix:
-                ry = [_weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
-                rx.append(_weighted_sum_np(wy, ry))
-            out[inside] = _weighted_sum_np(wx, rx)
+                ry = [weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
+                rx.append(weighted_sum_np(wy, ry))
+            out[inside] = weighted_sum_np(wx, rx)
     return out
 
 
 def _check_sigmas(sigmas_vox) -> list:
-    try:
-        s = [float(x) for x in sigmas_vox]
-    except (TypeError, ValueError):
-        raise ValueError(f"three sigmas in voxels are expected, got {sigmas_vox!r}") from None
-    if len(s) != 3:
-        raise ValueError(f"three sigmas in voxels are expected, got {sigmas_vox!r}")
+    s = three_sigmas(sigmas_vox)
     taps = [gaussian_taps(x) for x in s]
     for x, w in zip(s, taps):
         if (w.size - 1) // 2 > MAX_RADIUS:
@@ -480,7 +471,7 @@ def jacobian_stats_np(u):
 def pyramid_shapes(shape, levels: int) -> list:
     """The shapes of the levels, coarse to fine: ``shape`` is halved while every extent is even and at least 16, at most
     ``levels - 1`` times."""
-    shape = _check_shape(shape, "shape")
+    shape = check_shape(shape, "shape")
     if not isinstance(levels, (int, np.integer)) or isinstance(levels, bool) or levels < 1:
         raise ValueError(f"levels is a positive integer, got {levels!r}")
     shapes = [shape]
@@ -574,27 +565,14 @@ def register_diffeomorphic_np(fixed, moving, levels: int = 3, iterations=DEFAULT
 # ---------------------------------------------------------------- device
 
 def _check_volume(vol, what) -> torch.Tensor:
-    vol = _check_vol(vol, what)
-    if vol.dim() != 3:
-        raise ValueError(f"{what}: a volume has three axes, got shape {tuple(vol.shape)}")
-    _check_shape(vol.shape, f"{what}: the volume's shape")
-    return vol
+    return cuda_tensor(vol, (torch.float32,), what, ndim=3, limit=True)
 
 
 def _check_field(u, shape, device, what) -> torch.Tensor:
-    u = _check_vol(u, what)
+    u = cuda_tensor(u, (torch.float32,), what)
     if tuple(u.shape) != (3,) + tuple(shape) or u.device != device:
         raise ValueError(f"{what}: the field must have shape {(3,) + tuple(shape)} on {device}, got {tuple(u.shape)} on {u.device}")
     return u
-
-
-def _check_out(out, like, others, what) -> torch.Tensor:
-    if out is None:
-        return torch.empty_like(like)
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != like.shape or not out.is_contiguous() \
-            or out.device != like.device or any(out.data_ptr() == o.data_ptr() for o in others):
-        raise ValueError(f"{what}: out must be another contiguous float32 tensor of shape {tuple(like.shape)} on {like.device}")
-    return out
 
 
 def _slots(device) -> torch.Tensor:
@@ -607,7 +585,7 @@ def warp(moving: torch.Tensor, u: torch.Tensor, method: str = "linear", fill: fl
     m = _check_volume(moving, "warp")
     u = _check_field(u, m.shape, m.device, "warp")
     _check_method(method)
-    out = _check_out(out, m, (m, u), "warp")
+    out = out_like(out, m, (m, u), "warp")
     L.call("mrisr_f32_volume_warp", m.data_ptr(), u.data_ptr(), *m.shape, METHODS[method], float(fill), out.data_ptr(), L.stream_ptr(),
            nbytes=20 * m.numel())
     return out
@@ -641,7 +619,7 @@ def demons_force(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, max
         raise ValueError(f"demons_force: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
     u = _check_field(u, f.shape, f.device, "demons_force")
     _check_max_step(max_step)
-    v = _check_out(out, u, (u, f, m), "demons_force")
+    v = out_like(out, u, (u, f, m), "demons_force")
     row = torch.empty(2, dtype=torch.int64, device=f.device)
     _force(f, m, u, max_step, fill, v, _slots(f.device), row)
     return v, row[:1].view(torch.float64)[0], row[1]
@@ -650,12 +628,12 @@ def demons_force(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, max
 def smooth_field(v: torch.Tensor, sigmas_vox, out=None) -> torch.Tensor:
     """v: contiguous float32 CUDA field (3, X, Y, Z) -> ``smooth_field_np``, bit for bit.  Three launches (axis 2, 1, 0), all three
     components in each.  ``out``: another tensor like ``v``."""
-    v = _check_vol(v, "smooth_field")
+    v = cuda_tensor(v, (torch.float32,), "smooth_field")
     if v.dim() != 4 or v.shape[0] != 3:
         raise ValueError(f"smooth_field: a field is (3, X, Y, Z), got shape {tuple(v.shape)}")
-    shape = _check_shape(v.shape[1:], "smooth_field: the volume's shape")
+    shape = check_shape(v.shape[1:], "smooth_field: the volume's shape")
     taps = [torch.from_numpy(w).to(v.device) for w in _check_sigmas(sigmas_vox)]
-    out = _check_out(out, v, (v,), "smooth_field")
+    out = out_like(out, v, (v,), "smooth_field")
     tmp = torch.empty_like(v)
     for src, dst, axis in ((v, out, 2), (out, tmp, 1), (tmp, out, 0)):
         _smooth_pass(src, dst, shape, axis, taps[axis], (taps[axis].numel() - 1) // 2)
@@ -669,10 +647,10 @@ def _jacobian(u, shape, min_det, count, slots):
 def jacobian_stats(u: torch.Tensor):
     """u: contiguous float32 CUDA field (3, X, Y, Z) -> ``(min det, count of det <= 0)`` of ``jacobian_stats_np`` as a 0-d float32 and a
     0-d int64 tensor on the device.  Two launches, no device-to-host read."""
-    u = _check_vol(u, "jacobian_stats")
+    u = cuda_tensor(u, (torch.float32,), "jacobian_stats")
     if u.dim() != 4 or u.shape[0] != 3:
         raise ValueError(f"jacobian_stats: a field is (3, X, Y, Z), got shape {tuple(u.shape)}")
-    shape = _check_shape(u.shape[1:], "jacobian_stats: the volume's shape")
+    shape = check_shape(u.shape[1:], "jacobian_stats: the volume's shape")
     min_det = torch.empty(1, dtype=torch.float32, device=u.device)
     count = torch.empty(1, dtype=torch.int64, device=u.device)
     _jacobian(u, shape, min_det, count, _slots(u.device))
@@ -796,10 +774,10 @@ def _register(fixed, moving, levels, iterations, sigma_vox, max_step, fill, meth
 # ---------------------------------------------------------------- device: the diffeomorphic variant
 
 def _check_field4(u, what) -> torch.Tensor:
-    u = _check_vol(u, what)
+    u = cuda_tensor(u, (torch.float32,), what)
     if u.dim() != 4 or u.shape[0] != 3:
         raise ValueError(f"{what}: a field is (3, X, Y, Z), got shape {tuple(u.shape)}")
-    _check_shape(u.shape[1:], f"{what}: the volume's shape")
+    check_shape(u.shape[1:], f"{what}: the volume's shape")
     return u
 
 
@@ -818,7 +796,7 @@ def compose(u: torch.Tensor, v: torch.Tensor, out=None) -> torch.Tensor:
     eight taps of a voxel once for all three components.  ``u`` and ``v`` may be one tensor (squaring); ``out``: another tensor."""
     u = _check_field4(u, "compose")
     v = _check_field(v, u.shape[1:], u.device, "compose")
-    out = _check_out(out, u, (u, v), "compose")
+    out = out_like(out, u, (u, v), "compose")
     _compose(u, v, out, tuple(u.shape[1:]))
     return out
 
@@ -833,7 +811,7 @@ def demons_update(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, ma
     u = _check_field(u, f.shape, f.device, "demons_update")
     _check_max_step(max_step)
     scale = _check_scale(scale)
-    w = _check_out(out, u, (u, f, m), "demons_update")
+    w = out_like(out, u, (u, f, m), "demons_update")
     row = torch.empty(2, dtype=torch.int64, device=f.device)
     _update(f, m, u, max_step, fill, scale, w, _slots(f.device), row)
     return w, row[:1].view(torch.float64)[0], row[1]
@@ -846,7 +824,7 @@ def _lcc_entry(what, fixed, moving, u, radius, max_step, scale, update, out):
     u = _check_field(u, f.shape, f.device, what)
     radius = _check_lcc_radius(radius)
     _check_max_step(max_step)
-    v = _check_out(out, u, (u, f, m), what)
+    v = out_like(out, u, (u, f, m), what)
     row = torch.empty(2, dtype=torch.int64, device=f.device)
     _lcc(f, m, u, radius, max_step, scale, update, torch.empty_like(f), v, _slots(f.device), row)
     return v, row[:1].view(torch.float64)[0], row[1]
@@ -870,7 +848,7 @@ def exp_field(w: torch.Tensor, steps: int, out=None) -> torch.Tensor:
     ``steps`` launches of ``compose`` between two buffers.  ``steps`` is a host integer: nothing is read from the device."""
     w = _check_field4(w, "exp_field")
     steps = _check_exp_steps(steps)
-    out = _check_out(out, w, (w,), "exp_field")
+    out = out_like(out, w, (w,), "exp_field")
     shape = tuple(w.shape[1:])
     other = torch.empty_like(w) if steps else None
     src = out if steps % 2 == 0 else other           # the last of the squarings lands in out
@@ -891,8 +869,8 @@ def warp_matrix(moving: torch.Tensor, m, u: torch.Tensor, method: str = "linear"
     if u.device != mv.device:
         raise ValueError(f"warp_matrix: the field must lie on {mv.device}, got {u.device}")
     _check_method(method)
-    out = _check_out(out, u[0], (mv, u), "warp_matrix")
-    L.call("mrisr_f32_volume_warp_matrix", mv.data_ptr(), *mv.shape, u.data_ptr(), *u.shape[1:], _matrix_arg(m), METHODS[method], float(fill),
+    out = out_like(out, u[0], (mv, u), "warp_matrix")
+    L.call("mrisr_f32_volume_warp_matrix", mv.data_ptr(), *mv.shape, u.data_ptr(), *u.shape[1:], matrix_arg(m), METHODS[method], float(fill),
            out.data_ptr(), L.stream_ptr(), nbytes=4 * (mv.numel() + 4 * out.numel()))
     return out
 

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._volume_args import cuda_tensor, mask_np, mask_tensor, out_like, volume_np
 from .volume_eval import binary_dilate, dilate_np, foreground_mask, foreground_mask_np
-from .volume_intensity import _check_mask, _check_mask_np, _check_vol, _check_vol_np
 
 MAX_RADIUS = 5
 TABLE_SIZE = 4096
@@ -50,10 +50,7 @@ def _check_beta(beta) -> float:
 
 
 def _check_volume_np(v, what):
-    v = _check_vol_np(v, what)
-    if v.ndim != 3:
-        raise ValueError(f"{what}: a volume has three axes, got shape {v.shape}")
-    return np.ascontiguousarray(v)
+    return np.ascontiguousarray(volume_np(v, what))
 
 
 def offsets(radius: int):
@@ -170,7 +167,7 @@ def estimate_sigma_np(v, background):
     ``n`` their count, ``sigma = float32(sqrt(S / (2 n)))`` - the maximum-likelihood estimate of a Rayleigh distribution, the
     magnitude of pure complex Gaussian noise.  ``n == 0``: sigma 0."""
     v = _check_volume_np(v, "estimate_sigma_np")
-    keep = (_check_mask_np(background, v.shape, "estimate_sigma_np") != 0) & np.isfinite(v)
+    keep = (mask_np(background, v.shape, "estimate_sigma_np") != 0) & np.isfinite(v)
     n = int(keep.sum())
     if n == 0:
         return np.float32(0), 0
@@ -203,10 +200,7 @@ def _table(device) -> torch.Tensor:
 
 
 def _check_volume(vol, what) -> torch.Tensor:
-    vol = _check_vol(vol, what)
-    if vol.dim() != 3:
-        raise ValueError(f"{what}: a volume has three axes, got shape {tuple(vol.shape)}")
-    return vol
+    return cuda_tensor(vol, (torch.float32,), what, ndim=3)
 
 
 def _check_params(params, device, what) -> torch.Tensor:
@@ -228,11 +222,7 @@ def denoise(vol: torch.Tensor, params: torch.Tensor, radius=3, rician=True, out=
     v = _check_volume(vol, "denoise")
     radius = _check_radius(radius)
     p = _check_params(params, v.device, "denoise")
-    if out is None:
-        out = torch.empty_like(v)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != v.shape or not out.is_contiguous() \
-            or out.device != v.device or out.data_ptr() == v.data_ptr():
-        raise ValueError(f"denoise: out must be another contiguous float32 tensor of shape {tuple(v.shape)} on {v.device}")
+    out = out_like(out, v, (v,), "denoise")
     L.call("mrisr_f32_volume_nlm", v.data_ptr(), *v.shape, radius, int(bool(rician)), p.data_ptr(), _table(v.device).data_ptr(),
            out.data_ptr(), L.stream_ptr(), nbytes=8 * v.numel())
     return out
@@ -252,7 +242,7 @@ def estimate_noise(vol: torch.Tensor, background: torch.Tensor, beta=1.0, params
             raise ValueError(f"sigma must be finite and positive, got {sigma!r}")
         bg = None
     else:
-        bg = _check_mask(background, v, "estimate_noise")
+        bg = mask_tensor(background, v.shape, "estimate_noise")
     params = torch.empty(4, dtype=torch.float32, device=v.device) if params is None else _check_params(params, v.device, "estimate_noise")
     count = torch.empty(1, dtype=torch.int64, device=v.device)
     ws = torch.empty(int(L.load().mrisr_f32_volume_noise_workspace_bytes()) // 8, dtype=torch.int64, device=v.device)

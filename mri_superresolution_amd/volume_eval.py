@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._volume_args import check_classes, check_spacing, volume_np
 from .utils.evalops import METRIC_COLUMNS
 from .utils.imageops import _need_cuda
 from .utils.losses import _check_window
@@ -48,17 +49,10 @@ def _axes_mask(axes) -> int:
 
 # ---------------------------------------------------------------- numpy specifications
 
-def _check_np(v, what):
-    v = np.asarray(v)
-    if v.dtype != np.float32 or v.ndim != 3 or v.size == 0:
-        raise ValueError(f"{what}: expected a non-empty float32 volume (X,Y,Z), got {v.dtype} {v.shape}")
-    return v
-
-
 def downsample2_np(v: np.ndarray, axes=(0, 1, 2)) -> np.ndarray:
     """Mean over pairs along ``axes``: for the axes in ascending order ``v = v[even] + v[odd]`` (float32), then one product with
     ``0.5 ** len(axes)`` (exact).  An odd extent on one of the axes is a ``ValueError``."""
-    v = _check_np(v, "downsample2_np")
+    v = volume_np(v, "downsample2_np")
     mask = _axes_mask(axes)
     axes = [a for a in (0, 1, 2) if mask >> a & 1]
     for a in axes:
@@ -87,7 +81,7 @@ def upscale2_np(v: np.ndarray, method: str, axes=(0, 1, 2)) -> np.ndarray:
     """Doubles ``axes`` in ascending order, each pass on the float32 result of the one before, border replicated.  ``"linear"``
     is ``volume._up2_np`` (``0.75 e[i] + 0.25 e[i -+ 1]``); ``"cubic"`` is Keys with A = -0.75: ``u[2i]`` from taps
     ``i-2 .. i+1`` with ``CUBIC_WEIGHTS``, ``u[2i+1]`` from taps ``i-1 .. i+2`` with the mirrored weights."""
-    v = _check_np(v, "upscale2_np")
+    v = volume_np(v, "upscale2_np")
     if method not in METHODS:
         raise ValueError(f"Unknown interpolation method: {method}")
     mask = _axes_mask(axes)
@@ -163,7 +157,7 @@ def otsu_bins_np(v: np.ndarray):
     """-> (lo, hi, bins): the extrema of the float32 volume and the histogram bin 0..255 of every voxel (int32), in float32 one
     rounded operation at a time: ``scale = 256 / (hi - lo)``, ``bin = min(255, int((v - lo) * scale))`` (truncated).  ``bins`` is
     ``None`` for a degenerate range: ``hi == lo``, or ``hi - lo`` or ``scale`` not finite in float32."""
-    v = _check_np(v, "otsu_bins_np")
+    v = volume_np(v, "otsu_bins_np")
     f32 = np.float32
     lo, hi = f32(v.min()), f32(v.max())
     with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
@@ -645,24 +639,23 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     if val_range is not None and not val_range > 0:
         raise ValueError(f"val_range must be positive, got {val_range}")
     if tissue_dice != 0:
-        from .volume_tissue import TissueWorkspace, _check_classes, dice, label_confusion, segment_tissue
-        _check_classes(tissue_dice)
+        from .volume_tissue import TissueWorkspace, dice, label_confusion, segment_tissue
+        check_classes(tissue_dice)
         if mask is None:
             raise ValueError("tissue_dice needs a mask")
     if tissue_surface:
-        from .volume_surface import SurfaceWorkspace, _check_spacing, surface_distances
+        from .volume_surface import SurfaceWorkspace, surface_distances
         if not tissue_dice:
             raise ValueError("tissue_surface needs tissue_dice")
         spacing = (1.0, 1.0, 1.0) if spacing is None else spacing
-        _check_spacing(spacing)
+        check_spacing(spacing)
     if tissue_edges:
-        from .volume_sharpness import EdgeWorkspace, _check_bins, edge_sharpness, signed_distances
-        from .volume_surface import _check_spacing
+        from .volume_sharpness import EdgeWorkspace, check_bins, edge_sharpness, signed_distances
         if not tissue_dice:
             raise ValueError("tissue_edges needs tissue_dice")
         spacing = (1.0, 1.0, 1.0) if spacing is None else spacing
-        _check_spacing(spacing)
-        edge_bins = _check_bins(edge_radius, edge_bin)[2]
+        check_spacing(spacing)
+        edge_bins = check_bins(edge_radius, edge_bin)[2]
     if spacing is not None and not (tissue_surface or tissue_edges):
         raise ValueError("spacing needs tissue_surface")
     if mask is None:

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._volume_args import cuda_tensor, mask_np, mask_tensor, volume_np
 from .utils.imageops import np_percentile_f32
 
 logger = logging.getLogger(__name__)
@@ -53,24 +54,11 @@ def _check_percentiles(percentiles, least=2) -> tuple:
 
 # ---------------------------------------------------------------- numpy specification
 
-def _check_vol_np(vol, what):
-    vol = np.asarray(vol)
-    if vol.dtype != np.float32 or vol.size == 0:
-        raise ValueError(f"{what}: expected a non-empty float32 array, got {vol.dtype} {vol.shape}")
-    return vol
-
-
-def _check_mask_np(mask, shape, what):
-    mask = np.asarray(mask)
-    if mask.dtype not in (np.uint8, np.bool_) or mask.shape != tuple(shape):
-        raise ValueError(f"{what}: the mask must be a uint8 or bool array of shape {tuple(shape)}, got {mask.dtype} {mask.shape}")
-    return mask
-
-
-def _landmarks_np(vol, mask, q):
+def masked_landmarks_np(vol, mask, q):
+    """``landmarks_np`` for a checked ``vol`` and any number of percentiles ``q``."""
     keep = ~np.isnan(vol)
     if mask is not None:
-        keep &= _check_mask_np(mask, vol.shape, "landmarks_np") != 0
+        keep &= mask_np(mask, vol.shape, "landmarks_np") != 0
     s = np.sort(vol[keep].ravel())
     n = int(s.size)
     if n == 0:
@@ -82,7 +70,7 @@ def landmarks_np(vol, mask=None, percentiles=LANDMARKS):
     """-> (float32 (L,), int count): ``np.percentile(values, q)`` for every ``q`` of ``percentiles`` over
     ``values = vol[(mask != 0) & ~isnan(vol)]`` (``mask`` None: every voxel), ``count`` their number.  numpy's float32 path for a
     SCALAR ``q``, as ``utils.imageops.np_percentile_f32`` states it.  ``count == 0``: NaNs."""
-    return _landmarks_np(_check_vol_np(vol, "landmarks_np"), mask, _check_percentiles(percentiles))
+    return masked_landmarks_np(volume_np(vol, "landmarks_np", ndim=None), mask, _check_percentiles(percentiles))
 
 
 def _check_landmarks_np(lm, what):
@@ -98,7 +86,7 @@ def piecewise_map_np(vol, src_landmarks, dst_landmarks) -> np.ndarray:
     ``w = s[i+1] - s[i]``, ``slope = 0 if w == 0 else (d[i+1] - d[i]) / w``, ``out = d[i] + (v - s[i]) * slope`` - float32, every
     operation rounded on its own.  Below ``s[0]`` and above ``s[L-1]`` the first and the last segment extend linearly: Nyul-Udupa's
     rule, no clamp.  A NaN voxel gives NaN; NaN landmarks give NaN everywhere."""
-    vol = _check_vol_np(vol, "piecewise_map_np")
+    vol = volume_np(vol, "piecewise_map_np", ndim=None)
     s, d = _check_landmarks_np(src_landmarks, "src_landmarks"), _check_landmarks_np(dst_landmarks, "dst_landmarks")
     if s.shape != d.shape:
         raise ValueError(f"as many source as target landmarks are expected, got {s.size} and {d.size}")
@@ -125,31 +113,14 @@ def match_intensity_np(source, target, source_mask=None, target_mask=None, perce
     landmarks_np(target, target_mask))``.  ``ValueError`` when either side has no voxel to count or the source's landmarks are all
     equal (a constant foreground)."""
     q = _check_percentiles(percentiles)
-    source, target = _check_vol_np(source, "match_intensity_np"), _check_vol_np(target, "match_intensity_np")
-    sl, sc = _landmarks_np(source, source_mask, q)
-    tl, tc = _landmarks_np(target, target_mask, q)
+    source, target = volume_np(source, "match_intensity_np", ndim=None), volume_np(target, "match_intensity_np", ndim=None)
+    sl, sc = masked_landmarks_np(source, source_mask, q)
+    tl, tc = masked_landmarks_np(target, target_mask, q)
     found = _check_match(q, sl, tl, sc, tc)
     return piecewise_map_np(source, sl, tl), found
 
 
 # ---------------------------------------------------------------- device
-
-def _check_vol(vol, what) -> torch.Tensor:
-    if not isinstance(vol, torch.Tensor) or not vol.is_cuda:
-        raise ValueError(f"{what} runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA tensor")
-    if vol.dtype != torch.float32 or vol.numel() == 0 or not vol.is_contiguous():
-        raise ValueError(f"{what}: expected a non-empty contiguous float32 tensor, got {vol.dtype} {tuple(vol.shape)}")
-    return vol
-
-
-def _check_mask(mask, vol, what) -> torch.Tensor:
-    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-        raise ValueError(f"{what} runs on an MI355X through libmrisr.so only (no CPU fallback): the mask must be a CUDA tensor")
-    if mask.dtype not in (torch.uint8, torch.bool) or mask.shape != vol.shape or not mask.is_contiguous():
-        raise ValueError(f"{what}: the mask must be a contiguous uint8 or bool tensor of shape {tuple(vol.shape)}, got {mask.dtype} "
-                         f"{tuple(mask.shape)}")
-    return mask.view(torch.uint8)
-
 
 def _check_landmarks(lm, n, what) -> torch.Tensor:
     if not isinstance(lm, torch.Tensor) or not lm.is_cuda:
@@ -175,9 +146,9 @@ def masked_percentiles(vol: torch.Tensor, mask=None, percentiles=LANDMARKS, work
     is allowed here.  The ranks are derived on the device from the device-side count: 9 launches, no host read, no synchronisation
     (HIP-graph capturable when ``workspace`` - ``percentiles_workspace`` - is allocated before the capture).  ``out``: the pair of
     result tensors to write into (contiguous, on the volume's device: float32 (L,) and int64 (1,)), so that nothing is allocated."""
-    v = _check_vol(vol, "masked_percentiles")
+    v = cuda_tensor(vol, (torch.float32,), "masked_percentiles")
     q = _check_percentiles(percentiles, least=1)
-    m = None if mask is None else _check_mask(mask, v, "masked_percentiles")
+    m = None if mask is None else mask_tensor(mask, v.shape, "masked_percentiles")
     if v.numel() > 0xffffffff:
         raise ValueError(f"masked_percentiles: at most 2^32 - 1 voxels, got {v.numel()}")
     ws = percentiles_workspace(len(q), v.device) if workspace is None else workspace
@@ -200,12 +171,12 @@ def masked_percentiles(vol: torch.Tensor, mask=None, percentiles=LANDMARKS, work
 def piecewise_map(vol: torch.Tensor, src_landmarks: torch.Tensor, dst_landmarks: torch.Tensor, out=None) -> torch.Tensor:
     """vol: contiguous float32 CUDA tensor; the landmarks: float32 CUDA tensors (L,), L in 2..16 -> the float32 CUDA tensor of
     ``piecewise_map_np``, bit for bit.  ``out``: such a tensor to overwrite; it may be ``vol`` itself.  One launch."""
-    v = _check_vol(vol, "piecewise_map")
+    v = cuda_tensor(vol, (torch.float32,), "piecewise_map")
     s = _check_landmarks(src_landmarks, None, "src_landmarks")
     d = _check_landmarks(dst_landmarks, s.numel(), "dst_landmarks")
     if out is None:
         out = torch.empty_like(v)
-    elif _check_vol(out, "piecewise_map").shape != v.shape:
+    elif cuda_tensor(out, (torch.float32,), "piecewise_map").shape != v.shape:
         raise ValueError(f"out must have the shape {tuple(v.shape)}, got {tuple(out.shape)}")
     L.call("mrisr_f32_volume_piecewise_map", v.data_ptr(), v.numel(), s.data_ptr(), d.data_ptr(), s.numel(), out.data_ptr(), L.stream_ptr(),
            nbytes=8 * v.numel())
@@ -217,7 +188,7 @@ def match_intensity(source: torch.Tensor, target: torch.Tensor, source_mask=None
     values), both bit-equal to the specification's.  Exactly ONE device-to-host read: both landmark vectors and both counts in one
     tensor, for the two checks (a count of 0, a constant foreground) and for logging."""
     q = _check_percentiles(percentiles)
-    src, tgt = _check_vol(source, "match_intensity"), _check_vol(target, "match_intensity")
+    src, tgt = cuda_tensor(source, (torch.float32,), "match_intensity"), cuda_tensor(target, (torch.float32,), "match_intensity")
     ws = percentiles_workspace(len(q), src.device)
     sl, sc = masked_percentiles(src, source_mask, q, ws)
     tl, tc = masked_percentiles(tgt, target_mask, q, ws)

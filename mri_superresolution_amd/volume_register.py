@@ -28,8 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .utils.nifti import _check_affine, grid_matrix
-from .volume_reslice import _check_matrix, _check_tensor, reslice_np, source_coordinates_np
+from .utils.nifti import check_affine, grid_matrix
+from ._volume_args import NO_CPU, check_matrix, cuda_tensor, u8_np
+from .volume_reslice import reslice_np, source_coordinates_np
 
 logger = logging.getLogger(__name__)
 
@@ -83,16 +84,9 @@ def bin_np(v: np.ndarray, lo32, scale, bins: int) -> np.ndarray:
 
 def strided_matrix(m, stride: int) -> np.ndarray:
     """``m`` with its first three columns times ``stride`` (exact for a power of two): sample index -> moving voxel index."""
-    ms = _check_matrix(m).copy()
+    ms = check_matrix(m).copy()
     ms[:, :3] *= float(stride)
-    return _check_matrix(ms)
-
-
-def _check_mask_np(mask, shape, what):
-    mask = np.asarray(mask)
-    if mask.dtype not in (np.uint8, np.bool_) or mask.shape != tuple(shape):
-        raise ValueError(f"{what} must be a uint8 or bool volume of shape {tuple(shape)}, got {mask.dtype} {mask.shape}")
-    return mask
+    return check_matrix(ms)
 
 
 def joint_histogram_np(fixed, moving, m, bins, stride, fixed_range, moving_range, fixed_mask=None) -> np.ndarray:
@@ -113,7 +107,7 @@ def joint_histogram_np(fixed, moving, m, bins, stride, fixed_range, moving_range
     _, inside = source_coordinates_np(ms, fs.shape, moving.shape)
     ok = inside & ~np.isnan(fs) & ~np.isnan(mv)
     if fixed_mask is not None:
-        ok &= _check_mask_np(fixed_mask, fixed.shape, "fixed_mask")[::stride, ::stride, ::stride] != 0
+        ok &= u8_np(fixed_mask, fixed.shape, "fixed_mask")[::stride, ::stride, ::stride] != 0
     cell = bin_np(fs[ok], flo, fscale, bins) * bins + bin_np(mv[ok], mlo, mscale, bins)
     return np.bincount(cell, minlength=bins * bins).astype(np.int64).reshape(bins, bins)
 
@@ -140,7 +134,7 @@ def nmi_np(H, min_count=0):
 
 def volume_centre(fixed_affine, shape) -> np.ndarray:
     """(3,) world position of the fixed volume's centre voxel coordinate ``(n - 1) / 2``."""
-    a = _check_affine(fixed_affine, "fixed_affine")
+    a = check_affine(fixed_affine, "fixed_affine")
     return a[:3, :3] @ ((np.asarray(shape[:3], dtype=np.float64) - 1) / 2) + a[:3, 3]
 
 
@@ -172,13 +166,13 @@ def rigid_world(p, centre) -> np.ndarray:
 def candidate_matrix(p, fixed_affine, moving_affine, centre) -> np.ndarray:
     """(3, 4): the first three rows of ``inv(A_mov) W(p) A_fix``, solved as ``grid_matrix`` solves it; ``p = 0`` gives
     ``grid_matrix(A_mov, A_fix)`` to the last bit."""
-    return grid_matrix(moving_affine, rigid_world(p, centre) @ _check_affine(fixed_affine, "fixed_affine"))
+    return grid_matrix(moving_affine, rigid_world(p, centre) @ check_affine(fixed_affine, "fixed_affine"))
 
 
 def corner_displacement(world_a, world_b, fixed_affine, shape) -> float:
     """The worst distance in mm, over the eight corner voxels of the fixed volume, between their images under two fixed world ->
     moving world matrices."""
-    a = _check_affine(fixed_affine, "fixed_affine")
+    a = check_affine(fixed_affine, "fixed_affine")
     n = np.asarray(shape[:3], dtype=np.float64) - 1
     corners = np.array([[i, j, k, 1.0] for i in (0.0, n[0]) for j in (0.0, n[1]) for k in (0.0, n[2])]).T
     world = a @ corners
@@ -231,7 +225,7 @@ def compass_search(cost_batch, p0, levels, max_iterations=MAX_ITERATIONS):
 
 def voxel_size(fixed_affine) -> float:
     """The mean column norm of the affine's 3 x 3 block (mm)."""
-    a = _check_affine(fixed_affine, "fixed_affine")
+    a = check_affine(fixed_affine, "fixed_affine")
     return float(np.mean(np.linalg.norm(a[:3, :3], axis=0)))
 
 
@@ -275,7 +269,7 @@ def mask_centre_world(moments, affine) -> np.ndarray:
         raise ValueError(f"the moments of a mask are four integers (N, sum i, sum j, sum k), got {mo.dtype} {mo.shape}")
     if int(mo[0]) <= 0:
         raise ValueError("the mask is empty: it has no centre of mass")
-    a = _check_affine(affine, "affine")
+    a = check_affine(affine, "affine")
     return a[:3, :3] @ (mo[1:].astype(np.float64) / float(mo[0])) + a[:3, 3]
 
 
@@ -329,7 +323,7 @@ def _prepare(fixed_shape, fixed_affine, moving_affine, bins, levels, p0, init="h
         raise ValueError(f"bins must be one of {BINS}, got {bins}")
     if init not in ("header", "global"):
         raise ValueError(f"init must be 'header' or 'global', got {init!r}")
-    fa, ma = _check_affine(fixed_affine, "fixed_affine"), _check_affine(moving_affine, "moving_affine")
+    fa, ma = check_affine(fixed_affine, "fixed_affine"), check_affine(moving_affine, "moving_affine")
     grid = None
     if init == "global":
         if p0 is not None:
@@ -369,7 +363,7 @@ def register_rigid_np(fixed, fixed_affine, moving, moving_affine, bins=64, level
     if fixed_mask is None and (mask_cost or grid is not None):
         fixed_mask = foreground_mask_np(fixed)
     if fixed_mask is not None:
-        fixed_mask = _check_mask_np(fixed_mask, fixed.shape, "fixed_mask")
+        fixed_mask = u8_np(fixed_mask, fixed.shape, "fixed_mask")
     cost_mask = fixed_mask if mask_cost else None
 
     def min_count(stride):
@@ -382,7 +376,7 @@ def register_rigid_np(fixed, fixed_affine, moving, moving_affine, bins=64, level
                        min_count(stride))[0] for p in ps]
     coarse = None
     if grid is not None:
-        moving_mask = foreground_mask_np(moving) if moving_mask is None else _check_mask_np(moving_mask, moving.shape, "moving_mask")
+        moving_mask = foreground_mask_np(moving) if moving_mask is None else u8_np(moving_mask, moving.shape, "moving_mask")
         cf, cm = mask_centre_world(mask_moments_np(fixed_mask), fa), mask_centre_world(mask_moments_np(moving_mask), ma)
         p0, _, coarse = coarse_start(cost_batch, cf, cm, centre, grid, effective_stride(fixed.shape, COARSE_STRIDE))
     return _result(compass_search(cost_batch, p0, levels), fa, ma, centre, coarse)
@@ -399,11 +393,14 @@ def _matrices_arg(ms):
     return ms.shape[0], (L.C.c_double * (12 * ms.shape[0]))(*ms.reshape(-1).tolist())
 
 
+def _check_tensor(t, what):
+    return cuda_tensor(t, (torch.float32,), what, ndim=3, limit=True)
+
+
 def _check_mask_tensor(mask, shape, what):
-    m = _check_tensor(mask, (torch.uint8,), what)
-    if shape is not None and tuple(m.shape) != tuple(shape):
-        raise ValueError(f"{what}: the mask must have its volume's shape {tuple(shape)}, got {tuple(m.shape)}")
-    return m
+    """uint8 alone (no bool); two steps, so that the extent limit is checked before the shape, as it always was."""
+    m = cuda_tensor(mask, (torch.uint8,), what, name="the mask", ndim=3, limit=True)
+    return m if shape is None else cuda_tensor(m, (torch.uint8,), what, name="the mask", shape=shape)
 
 
 def joint_histogram(fixed: torch.Tensor, moving: torch.Tensor, ms, bins, stride, fixed_range, moving_range, fixed_mask=None,
@@ -412,7 +409,7 @@ def joint_histogram(fixed: torch.Tensor, moving: torch.Tensor, ms, bins, stride,
     tensor (K, bins, bins), equal to ``joint_histogram_np`` of every matrix.  ``fixed_mask``: a contiguous uint8 CUDA tensor of the
     fixed shape (the masked entry; ``None``: the unmasked one).  ``out``: such a tensor to overwrite.  A memset and one launch, no
     host synchronisation."""
-    f, mv = _check_tensor(fixed, (torch.float32,), "joint_histogram"), _check_tensor(moving, (torch.float32,), "joint_histogram")
+    f, mv = _check_tensor(fixed, "joint_histogram"), _check_tensor(moving, "joint_histogram")
     _check_bins_stride(bins, stride)
     _check_range(fixed_range, bins, "fixed_range")
     _check_range(moving_range, bins, "moving_range")
@@ -436,7 +433,7 @@ def nmi(hist: torch.Tensor, min_count=0):
     """hist: contiguous int64 CUDA tensor (K, bins, bins) or (bins, bins) -> (values float64 (K,), counts int64 (K,)), CUDA tensors,
     by ``nmi_np``'s rules.  One launch, no host synchronisation."""
     if not isinstance(hist, torch.Tensor) or not hist.is_cuda:
-        raise ValueError("nmi runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA tensor")
+        raise ValueError(f"nmi {NO_CPU}: expected a CUDA tensor")
     h = hist[None] if hist.dim() == 2 else hist
     if h.dtype != torch.int64 or h.dim() != 3 or h.shape[1] != h.shape[2] or h.shape[1] not in BINS or not h.is_contiguous() \
             or not 1 <= h.shape[0] <= MAX_CANDIDATES or int(min_count) < 0:
@@ -476,7 +473,7 @@ def register_rigid(fixed: torch.Tensor, fixed_affine, moving: torch.Tensor, movi
     values tensor that is read once - the ``coarse`` entry of the trace has ``host_reads == 1`` too.  ``mask_cost=True``: the masked
     histogram entry everywhere; the masked sample counts behind ``min_count`` are read once, before the search."""
     from .volume_eval import foreground_mask
-    f, mv = _check_tensor(fixed, (torch.float32,), "register_rigid"), _check_tensor(moving, (torch.float32,), "register_rigid")
+    f, mv = _check_tensor(fixed, "register_rigid"), _check_tensor(moving, "register_rigid")
     fa, ma, levels, p0, centre, grid = _prepare(f.shape, fixed_affine, moving_affine, bins, levels, p0, init, init_limit, init_step)
     franges, mranges = volume_range(f), volume_range(mv)
     if fixed_mask is None and (mask_cost or grid is not None):

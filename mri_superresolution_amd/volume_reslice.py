@@ -20,34 +20,18 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._volume_args import MAX_VOXELS, check_matrix, check_shape, cuda_tensor, matrix_arg, volume_np      # noqa: F401  (MAX_VOXELS: this module's documented limit)
 from .utils.nifti import grid_matrix
 
 METHODS = {"nearest": L.RESAMPLE_NEAREST, "linear": L.RESAMPLE_LINEAR, "cubic": L.RESAMPLE_CUBIC}
-MAX_VOXELS = 2 ** 31 - 1
 
 
 # ---------------------------------------------------------------- numpy specification
 
-def _check_matrix(m) -> np.ndarray:
-    m = np.asarray(m, dtype=np.float64)
-    if m.shape != (3, 4) or not np.isfinite(m).all():
-        raise ValueError(f"the grid matrix must be (3, 4) and finite, got shape {m.shape}: {m.tolist()}")
-    return np.ascontiguousarray(m)
-
-
-def _check_shape(shape, what) -> tuple:
-    shape = tuple(int(d) for d in shape)
-    if len(shape) != 3 or any(d < 1 for d in shape):
-        raise ValueError(f"{what} must be three positive extents, got {shape}")
-    if shape[0] * shape[1] * shape[2] > MAX_VOXELS:
-        raise ValueError(f"{what} {shape} has more than 2^31 - 1 voxels")
-    return shape
-
-
 def source_coordinates_np(m, out_shape, src_shape):
     """-> (p, inside): the three float64 coordinate arrays ``p_a = ((m[a,0] i + m[a,1] j) + m[a,2] k) + m[a,3]``, one rounded
     operation at a time (numpy never fuses), and the inside test ``-0.5 <= p_a <= n_a - 0.5`` on all three axes."""
-    m = _check_matrix(m)
+    m = check_matrix(m)
     i, j, k = (np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)]) for a, n in enumerate(out_shape))
     p = [np.broadcast_to(((m[a, 0] * i + m[a, 1] * j) + m[a, 2] * k) + m[a, 3], out_shape) for a in range(3)]
     inside = np.ones(out_shape, dtype=bool)
@@ -65,7 +49,7 @@ def keys_weight_np(x: np.ndarray) -> np.ndarray:
     return np.where(x <= f32(1), near, far).astype(f32)
 
 
-def _taps_np(p, n, method):
+def taps_np(p, n, method):
     """p: the float64 coordinates of the inside voxels along one axis -> ([index arrays], [float32 weight arrays])."""
     f32 = np.float32
     f = np.floor(p)
@@ -77,7 +61,7 @@ def _taps_np(p, n, method):
             [keys_weight_np(f32(1) + t), keys_weight_np(t), keys_weight_np(f32(1) - t), keys_weight_np(f32(2) - t)])
 
 
-def _weighted_sum_np(w, v):
+def weighted_sum_np(w, v):
     acc = w[0] * v[0]                                            # float32 arrays: every product and sum rounds to float32
     for wd, vd in zip(w[1:], v[1:]):
         acc = acc + wd * vd
@@ -93,12 +77,10 @@ def reslice_np(v: np.ndarray, m, out_shape, method: str = "linear", fill: float 
     ``f_a - 1 .. f_a + 2``, weights ``keys_weight_np`` at the distances ``1 + t, t, 1 - t, 2 - t`` (not renormalised; exactly
     (0, 1, 0, 0) at ``t = 0``).  Taps are clamped to the volume.  Reduction along z, then y, then x, each stage
     ``((w0 v0 + w1 v1) + w2 v2) + w3 v3`` in float32."""
-    v = np.asarray(v)
-    if v.dtype != np.float32 or v.ndim != 3 or v.size == 0:
-        raise ValueError(f"reslice_np: expected a non-empty float32 volume (X,Y,Z), got {v.dtype} {v.shape}")
+    v = volume_np(v, "reslice_np")
     if method not in METHODS:
         raise ValueError(f"Unknown interpolation method: {method}")
-    out_shape = _check_shape(out_shape, "out_shape")
+    out_shape = check_shape(out_shape, "out_shape")
     p, inside = source_coordinates_np(m, out_shape, v.shape)
     out = np.full(out_shape, np.float32(fill), dtype=np.float32)
     pin = [pa[inside] for pa in p]
@@ -106,12 +88,12 @@ def reslice_np(v: np.ndarray, m, out_shape, method: str = "linear", fill: float 
         q = [np.clip(np.floor(pa + 0.5).astype(np.int64), 0, n - 1) for pa, n in zip(pin, v.shape)]
         out[inside] = v[q[0], q[1], q[2]]
         return out
-    (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa, n, method) for pa, n in zip(pin, v.shape))
+    (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa, n, method) for pa, n in zip(pin, v.shape))
     rx = []
     for xa in ix:
-        ry = [_weighted_sum_np(wz, [v[xa, yb, zc] for zc in iz]) for yb in iy]
-        rx.append(_weighted_sum_np(wy, ry))
-    out[inside] = _weighted_sum_np(wx, rx)
+        ry = [weighted_sum_np(wz, [v[xa, yb, zc] for zc in iz]) for yb in iy]
+        rx.append(weighted_sum_np(wy, ry))
+    out[inside] = weighted_sum_np(wx, rx)
     return out
 
 
@@ -120,7 +102,7 @@ def reslice_mask_np(mask: np.ndarray, m, out_shape, fill: int = 0) -> np.ndarray
     mask = np.asarray(mask)
     if mask.dtype != np.uint8 or mask.ndim != 3 or mask.size == 0:
         raise ValueError(f"reslice_mask_np: expected a non-empty uint8 volume (X,Y,Z), got {mask.dtype} {mask.shape}")
-    out_shape = _check_shape(out_shape, "out_shape")
+    out_shape = check_shape(out_shape, "out_shape")
     p, inside = source_coordinates_np(m, out_shape, mask.shape)
     out = np.full(out_shape, _check_fill_u8(fill), dtype=np.uint8)
     q = [np.clip(np.floor(pa[inside] + 0.5).astype(np.int64), 0, n - 1) for pa, n in zip(p, mask.shape)]
@@ -136,31 +118,15 @@ def _check_fill_u8(fill) -> int:
 
 # ---------------------------------------------------------------- device
 
-def _check_tensor(t, dtypes, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{what} runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA tensor, got "
-                         f"{'a CPU tensor' if isinstance(t, torch.Tensor) else type(t).__name__}")
-    if t.dtype not in dtypes or t.dim() != 3 or t.numel() == 0 or not t.is_contiguous():
-        raise ValueError(f"{what}: expected a non-empty contiguous {' / '.join(str(d) for d in dtypes)} volume (X,Y,Z), got "
-                         f"{t.dtype} {tuple(t.shape)}{'' if t.is_contiguous() else ', not contiguous'}")
-    _check_shape(t.shape, f"{what}: the volume's shape")
-    return t
-
-
-def _matrix_arg(m):
-    m = _check_matrix(m)
-    return (L.C.c_double * 12)(*m.reshape(-1).tolist())
-
-
 def reslice(vol: torch.Tensor, m, out_shape, method: str = "linear", fill: float = 0.0) -> torch.Tensor:
     """vol: contiguous (X,Y,Z) float32 CUDA tensor; m: (3, 4) matrix, destination index -> source index (host, float64) -> the
     float32 CUDA volume of ``out_shape``, bit-equal to ``reslice_np``.  One launch, no host synchronisation."""
     if method not in METHODS:
         raise ValueError(f"Unknown interpolation method: {method}")
-    v = _check_tensor(vol, (torch.float32,), "reslice")
-    out_shape = _check_shape(out_shape, "out_shape")
+    v = cuda_tensor(vol, (torch.float32,), "reslice", ndim=3, limit=True)
+    out_shape = check_shape(out_shape, "out_shape")
     out = torch.empty(out_shape, dtype=torch.float32, device=v.device)
-    L.call("mrisr_f32_volume_reslice", v.data_ptr(), *v.shape, out.data_ptr(), *out_shape, _matrix_arg(m), METHODS[method], float(fill),
+    L.call("mrisr_f32_volume_reslice", v.data_ptr(), *v.shape, out.data_ptr(), *out_shape, matrix_arg(m), METHODS[method], float(fill),
            L.stream_ptr(), nbytes=4 * (v.numel() + out.numel()))
     return out
 
@@ -168,12 +134,12 @@ def reslice(vol: torch.Tensor, m, out_shape, method: str = "linear", fill: float
 def reslice_mask(mask: torch.Tensor, m, out_shape, fill: int = 0) -> torch.Tensor:
     """mask: contiguous (X,Y,Z) uint8 or bool CUDA tensor -> the uint8 CUDA volume of ``out_shape`` under the ``nearest`` rule,
     bit-equal to ``reslice_mask_np``.  One launch, no host synchronisation."""
-    k = _check_tensor(mask, (torch.uint8, torch.bool), "reslice_mask")
+    k = cuda_tensor(mask, (torch.uint8, torch.bool), "reslice_mask", ndim=3, limit=True)
     if k.dtype == torch.bool:
         k = k.view(torch.uint8)
-    out_shape = _check_shape(out_shape, "out_shape")
+    out_shape = check_shape(out_shape, "out_shape")
     out = torch.empty(out_shape, dtype=torch.uint8, device=k.device)
-    L.call("mrisr_u8_volume_reslice_nearest", k.data_ptr(), *k.shape, out.data_ptr(), *out_shape, _matrix_arg(m), _check_fill_u8(fill),
+    L.call("mrisr_u8_volume_reslice_nearest", k.data_ptr(), *k.shape, out.data_ptr(), *out_shape, matrix_arg(m), _check_fill_u8(fill),
            L.stream_ptr(), nbytes=k.numel() + out.numel())
     return out
 
@@ -192,6 +158,6 @@ def reslice_like(vol: torch.Tensor, src_affine, dst_affine, dst_shape, method: s
 def covered_share(src_shape, m, out_shape, device="cuda") -> torch.Tensor:
     """0-d float64 CUDA tensor: the share of the destination voxels whose centre lies inside the source volume - ``reslice_mask``
     of an all-ones mask, counted on the device."""
-    ones = torch.ones(_check_shape(src_shape, "src_shape"), dtype=torch.uint8, device=device)
+    ones = torch.ones(check_shape(src_shape, "src_shape"), dtype=torch.uint8, device=device)
     hit = reslice_mask(ones, m, out_shape)
     return hit.count_nonzero().to(torch.float64) / hit.numel()

@@ -29,8 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .volume_surface import _check_extents, _check_labels_np, _check_spacing, _edt_launch, edt_sq_np
-from .volume_tissue import _check_classes, _check_labels
+from ._volume_args import NO_CPU, check_classes, check_extents, check_spacing, cuda_device, cuda_tensor, u8_np, volume_np
+from .volume_surface import distance_transform_sq, edt_sq_np
 
 MAX_INTERFACES = 5                   # K <= 6 tissue classes
 MIN_BINS, MAX_BINS = 2, 64
@@ -58,7 +58,7 @@ def _check_interface(k) -> int:
     return int(k)
 
 
-def _check_bins(radius, bin_width):
+def check_bins(radius, bin_width):
     """-> (R, w, nb): the radius and the bin width as float32 and ``nb = ceil(2 radius / bin_width)`` of the numbers given."""
     try:
         r, w = float(radius), float(bin_width)
@@ -122,27 +122,25 @@ def edge_width(profile, min_count=8):
 def interface_sides_np(labels, k) -> np.ndarray:
     """uint8, the shape of ``labels``: 0 where ``labels == 0``, 1 where ``0 < labels <= k`` (the darker side: classes are ordered by
     brightness, as ``volume_tissue.segment_tissue`` returns them), 2 where ``labels > k``."""
-    labels = _check_labels_np(labels, None, "the labels")
+    labels = u8_np(labels, None, "the labels", ndim=3)
     k = _check_interface(k)
     return np.where(labels == 0, 0, np.where(labels <= k, 1, 2)).astype(np.uint8)
 
 
 def signed_distance_np(labels, k, spacing=(1, 1, 1)) -> np.ndarray:
     """float32, the shape of ``labels``: with ``sides = interface_sides_np(labels, k)`` and ``w`` the squared voxel sizes
-    (``volume_surface._check_spacing``), ``dA = sqrt32(edt_sq_np(sides, 1, w))`` and ``dB = sqrt32(edt_sq_np(sides, 2, w))``, each one
+    (``_volume_args.check_spacing``), ``dA = sqrt32(edt_sq_np(sides, 1, w))`` and ``dB = sqrt32(edt_sq_np(sides, 2, w))``, each one
     correctly rounded float32 square root, ``+inf`` where that side is absent.  ``s = +dA`` on side 2, ``s = -dB`` on side 1, NaN on
     side 0.  Distances run between voxel centres: no voxel has ``|s|`` below the smallest voxel size (module docstring)."""
-    w = _check_spacing(spacing)
+    w = check_spacing(spacing)
     sides = interface_sides_np(labels, k)
-    _check_extents(sides.shape, "signed_distance_np")
+    check_extents(sides.shape, "signed_distance_np")
     d_a, d_b = np.sqrt(edt_sq_np(sides, 1, w)), np.sqrt(edt_sq_np(sides, 2, w))
     return np.where(sides == 2, d_a, np.where(sides == 1, -d_b, np.float32(np.nan))).astype(np.float32)
 
 
 def _check_profile_np(vol, sdist):
-    vol, sdist = np.asarray(vol), np.asarray(sdist)
-    if vol.dtype != np.float32 or vol.ndim != 3 or vol.size == 0:
-        raise ValueError(f"edge_profile_np: expected a non-empty float32 volume (X, Y, Z), got {vol.dtype} {vol.shape}")
+    vol, sdist = volume_np(vol, "edge_profile_np"), np.asarray(sdist)
     if sdist.dtype != np.float32 or sdist.ndim != 4 or sdist.shape[1:] != vol.shape or not 1 <= sdist.shape[0] <= MAX_INTERFACES:
         raise ValueError(f"edge_profile_np: the signed distances are float32 (J, {', '.join(str(d) for d in vol.shape)}) with J in "
                          f"1..{MAX_INTERFACES}, got {sdist.dtype} {sdist.shape}")
@@ -155,7 +153,7 @@ def edge_profile_np(vol, sdist, radius=4.0, bin_width=0.5) -> EdgeProfile:
     voxel enters bin ``b = floor(fl32(fl32(s + R) / w))`` of interface ``j`` when ``s`` is finite, ``0 <= b < nb`` and ``vol`` is finite
     there.  ``count`` (J, nb) int64; ``sum_v``, ``sum_s``, ``sum_vv`` (J, nb) float64, taken over ``float64(v)``, ``float64(s)`` and
     ``float64(v) * float64(v)`` (``math.fsum``)."""
-    r32, w32, nb = _check_bins(radius, bin_width)
+    r32, w32, nb = check_bins(radius, bin_width)
     vol, sdist = _check_profile_np(vol, sdist)
     J = sdist.shape[0]
     count = np.zeros((J, nb), dtype=np.int64)
@@ -180,7 +178,7 @@ def edge_profile_np(vol, sdist, radius=4.0, bin_width=0.5) -> EdgeProfile:
 def edge_sharpness_np(vol, labels, classes=3, spacing=(1, 1, 1), radius=4.0, bin_width=0.5, min_count=8) -> EdgeSharpness:
     """The specification of ``edge_sharpness``: the signed distances of the ``classes - 1`` interfaces of ``labels``, the profile of
     ``vol`` across each and ``edge_width`` of it."""
-    K = _check_classes(classes)
+    K = check_classes(classes)
     sdist = np.stack([signed_distance_np(labels, k, spacing) for k in range(1, K)])
     profile = edge_profile_np(vol, sdist, radius, bin_width)
     return EdgeSharpness(*edge_width(profile, min_count), profile)
@@ -189,19 +187,11 @@ def edge_sharpness_np(vol, labels, classes=3, spacing=(1, 1, 1), radius=4.0, bin
 # ---------------------------------------------------------------- device
 
 def _check_f32(t, shape, what, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{what} runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA tensor")
-    if t.dtype != torch.float32 or t.numel() == 0 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError(f"{what}: {name} must be a non-empty contiguous float32 tensor"
-                         + (f" of shape {tuple(shape)}" if shape is not None else "") + f", got {t.dtype} {tuple(t.shape)}")
-    return t
+    return cuda_tensor(t, (torch.float32,), what, name=name, shape=shape)
 
 
 def _check_volume_labels(labels, what):
-    t = _check_labels(labels, None, what)
-    if t.dim() != 3:
-        raise ValueError(f"{what}: expected a volume (X, Y, Z), got {tuple(t.shape)}")
-    return t
+    return cuda_tensor(labels, (torch.uint8,), what, ndim=3)
 
 
 def interface_sides(labels: torch.Tensor, k, out=None) -> torch.Tensor:
@@ -209,7 +199,7 @@ def interface_sides(labels: torch.Tensor, k, out=None) -> torch.Tensor:
     ``out``: a uint8 CUDA tensor of that shape to write into."""
     t = _check_volume_labels(labels, "interface_sides")
     k = _check_interface(k)
-    out = torch.empty_like(t) if out is None else _check_labels(out, t.shape, "interface_sides (out)")
+    out = torch.empty_like(t) if out is None else cuda_tensor(out, (torch.uint8,), "interface_sides (out)", shape=t.shape)
     L.call("mrisr_u8_volume_interface_sides", t.data_ptr(), t.numel(), k, out.data_ptr(), L.stream_ptr(), nbytes=2 * t.numel())
     return out
 
@@ -220,15 +210,15 @@ def signed_distance(labels: torch.Tensor, k, spacing=(1, 1, 1), out=None, scratc
     transforms (``volume_surface.distance_transform_sq``'s kernels), the signed root.  ``out``: a contiguous float32 CUDA tensor of
     that shape to write into; ``scratch``: ``(sides uint8, dA float32, dB float32)`` of that shape, so that nothing is allocated."""
     t = _check_volume_labels(labels, "signed_distance")
-    k, w = _check_interface(k), _check_spacing(spacing)
-    _check_extents(tuple(t.shape), "signed_distance")
+    k, w = _check_interface(k), check_spacing(spacing)
+    check_extents(tuple(t.shape), "signed_distance")
     out = torch.empty(t.shape, dtype=torch.float32, device=t.device) if out is None else _check_f32(out, t.shape, "signed_distance", "out")
     if scratch is None:
         scratch = (torch.empty_like(t), torch.empty_like(out), torch.empty_like(out))
     sides, d_a, d_b = scratch
     interface_sides(t, k, out=sides)
-    _edt_launch(sides, t.shape, 1, w, d_a)
-    _edt_launch(sides, t.shape, 2, w, d_b)
+    distance_transform_sq(sides, 1, w, out=d_a)
+    distance_transform_sq(sides, 2, w, out=d_b)
     L.call("mrisr_f32_volume_signed_distance", sides.data_ptr(), d_a.data_ptr(), d_b.data_ptr(), t.numel(), out.data_ptr(), L.stream_ptr(),
            nbytes=13 * t.numel())
     return out
@@ -236,10 +226,10 @@ def signed_distance(labels: torch.Tensor, k, spacing=(1, 1, 1), out=None, scratc
 
 def signed_distances(labels: torch.Tensor, classes=3, spacing=(1, 1, 1)) -> torch.Tensor:
     """-> float32 CUDA tensor (classes - 1, X, Y, Z): ``signed_distance`` for ``k = 1 .. classes - 1``, one scratch set for all."""
-    K = _check_classes(classes)
+    K = check_classes(classes)
     t = _check_volume_labels(labels, "signed_distances")
-    _check_spacing(spacing)
-    _check_extents(tuple(t.shape), "signed_distances")
+    check_spacing(spacing)
+    check_extents(tuple(t.shape), "signed_distances")
     out = torch.empty((K - 1,) + tuple(t.shape), dtype=torch.float32, device=t.device)
     scratch = (torch.empty_like(t), torch.empty_like(out[0]), torch.empty_like(out[0]))
     for k in range(1, K):
@@ -257,11 +247,7 @@ class EdgeWorkspace:
             raise ValueError(f"interfaces must be an integer in 1..{MAX_INTERFACES}, got {interfaces!r}")
         if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not MIN_BINS <= bins <= MAX_BINS:
             raise ValueError(f"bins must be an integer in {MIN_BINS}..{MAX_BINS}, got {bins!r}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("EdgeWorkspace runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA device")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = cuda_device(device, "EdgeWorkspace")
         self.interfaces, self.bins, self.device = int(interfaces), int(bins), device
         nbytes = int(L.load().mrisr_f32_volume_edge_workspace_bytes(self.interfaces, self.bins))
         self.slots = torch.empty(nbytes // 8, dtype=torch.int64, device=device)
@@ -288,9 +274,9 @@ def edge_profile(vol: torch.Tensor, sdist: torch.Tensor, radius=4.0, bin_width=0
     another order of addition, the same bits on every run: a wave owns a fixed set of voxels, lanes that share a bin are added in a
     fixed tree, partial sums go to fixed slots and are added in slot order.  Two launches, no host synchronisation, no allocation
     with a ``workspace`` (an ``EdgeWorkspace(J, nb, device)``): capturable in a HIP graph."""
-    r32, w32, nb = _check_bins(radius, bin_width)
+    r32, w32, nb = check_bins(radius, bin_width)
     if not isinstance(vol, torch.Tensor) or not vol.is_cuda or not isinstance(sdist, torch.Tensor) or not sdist.is_cuda:
-        raise ValueError("edge_profile runs on an MI355X through libmrisr.so only (no CPU fallback): expected CUDA tensors")
+        raise ValueError(f"edge_profile {NO_CPU}: expected CUDA tensors")
     if vol.dim() != 3:
         raise ValueError(f"edge_profile: expected a volume (X, Y, Z), got {tuple(vol.shape)}")
     v = _check_f32(vol, None, "edge_profile", "vol")
@@ -319,7 +305,7 @@ def edge_sharpness(vol: torch.Tensor, labels: torch.Tensor = None, classes=3, sp
         sdist = signed_distances(labels, classes, spacing)
     ws = workspace
     if ws is None and isinstance(sdist, torch.Tensor) and sdist.is_cuda and sdist.dim() == 4:
-        ws = EdgeWorkspace(int(sdist.shape[0]), _check_bins(radius, bin_width)[2], sdist.device)
+        ws = EdgeWorkspace(int(sdist.shape[0]), check_bins(radius, bin_width)[2], sdist.device)
     edge_profile(vol, sdist, radius, bin_width, ws)                    # with ws None it raises: the arguments are wrong
     profile = ws.download()
     return EdgeSharpness(*edge_width(profile, min_count), profile)

@@ -50,8 +50,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .utils.nifti import _check_affine, grid_matrix, respaced_grid
-from .volume_reslice import _check_matrix, _check_shape, _check_tensor, _matrix_arg, _taps_np, _weighted_sum_np
+from ._volume_args import check_matrix, check_shape, cuda_tensor, matrix_arg, out_like, volume_np
+from .utils.nifti import check_affine, grid_matrix, respaced_grid
+from .volume_reslice import taps_np, weighted_sum_np
 
 MAX_STACKS = 8
 MAX_SAMPLES = 16
@@ -117,7 +118,7 @@ def default_profile_samples(profile: str, thickness_mm: float, out_voxel_mm: flo
 
 def voxel_sizes(affine) -> np.ndarray:
     """(3,) float64: the norms of the three columns of an index -> world affine, in mm."""
-    a = _check_affine(affine, "affine")
+    a = check_affine(affine, "affine")
     return np.linalg.norm(a[:3, :3], axis=0)
 
 
@@ -135,8 +136,8 @@ def default_output_grid(affines, shapes, spacing=None):
     """-> ``(affine_out, shape_out)``: a grid with the first stack's orientation, isotropic at the smallest voxel size of any stack
     (or at ``spacing`` mm), whose extent is the bounding box - along the first stack's axes - of the corners of all the stacks.
     The box is cut on the first stack's grid and handed to ``utils.nifti.respaced_grid``, which keeps the corner of its first cell."""
-    affines = [_check_affine(a, "affine") for a in affines]
-    shapes = [_check_shape(s, "shape") for s in shapes]
+    affines = [check_affine(a, "affine") for a in affines]
+    shapes = [check_shape(s, "shape") for s in shapes]
     if not affines or len(affines) != len(shapes):
         raise ValueError(f"default_output_grid takes one shape per affine, got {len(affines)} and {len(shapes)}")
     if spacing is None:
@@ -160,7 +161,7 @@ def default_output_grid(affines, shapes, spacing=None):
 def _check_geometry(g, what) -> StackGeometry:
     if not isinstance(g, StackGeometry):
         raise ValueError(f"{what}: a stack's geometry is a StackGeometry (stack_geometry), got {type(g).__name__}")
-    m, n = _check_matrix(g.to_output), _check_matrix(g.from_output)
+    m, n = check_matrix(g.to_output), check_matrix(g.from_output)
     if isinstance(g.slice_axis, bool) or not isinstance(g.slice_axis, (int, np.integer)) or not 0 <= g.slice_axis <= 2:
         raise ValueError(f"{what}: the slice axis is 0, 1 or 2, got {g.slice_axis!r}")
     o, w = np.asarray(g.offsets), np.asarray(g.weights)
@@ -177,7 +178,7 @@ def stack_geometry(affine, affine_out, slice_axis=None, profile: str = "box", th
     ``default_slice_axis``.  ``thickness_mm``: None takes the spacing along the slice axis (``rho = 1``).  ``samples``: None takes
     ``default_profile_samples`` at the smallest output voxel size.  ``world`` (4 x 4): a rigid transform, reference world -> this
     stack's world (``volume_register.RigidResult.world`` with the reference as the fixed scan), folded into both matrices."""
-    a, out = _check_affine(affine, "affine"), _check_affine(affine_out, "affine_out")
+    a, out = check_affine(affine, "affine"), check_affine(affine_out, "affine_out")
     axis = default_slice_axis(a) if slice_axis is None else slice_axis
     if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not 0 <= axis <= 2:
         raise ValueError(f"the slice axis is 0, 1 or 2, got {slice_axis!r}")
@@ -189,7 +190,7 @@ def stack_geometry(affine, affine_out, slice_axis=None, profile: str = "box", th
         samples = default_profile_samples(profile, thickness, float(voxel_sizes(out).min()))
     offsets, weights = slice_profile(profile, samples, thickness / spacing)
     if world is not None:
-        w = _check_affine(world, "world")
+        w = check_affine(world, "world")
         out = w @ out                                                # output index -> this stack's world
     return StackGeometry(grid_matrix(out, a), grid_matrix(a, out), int(axis), offsets, weights)
 
@@ -197,11 +198,7 @@ def stack_geometry(affine, affine_out, slice_axis=None, profile: str = "box", th
 # ---------------------------------------------------------------- numpy specification
 
 def _check_volume_np(v, what):
-    v = np.asarray(v)
-    if v.dtype != np.float32 or v.ndim != 3 or v.size == 0:
-        raise ValueError(f"{what}: expected a non-empty float32 volume (X,Y,Z), got {v.dtype} {v.shape}")
-    _check_shape(v.shape, f"{what}: the volume's shape")
-    return v
+    return volume_np(v, what, limit=True)
 
 
 def _check_step(step) -> np.float32:
@@ -291,12 +288,12 @@ def _gather_np(v, m, q, shape):
         inside &= (p[a] >= -0.5) & (p[a] <= v.shape[a] - 0.5)
     if not inside.any():
         return np.zeros(0, dtype=np.float32), inside
-    (ix, wx), (iy, wy), (iz, wz) = (_taps_np(pa[inside], n, "linear") for pa, n in zip(p, v.shape))
+    (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[inside], n, "linear") for pa, n in zip(p, v.shape))
     rx = []
     for xa in ix:
-        ry = [_weighted_sum_np(wz, [v[xa, yb, zc] for zc in iz]) for yb in iy]
-        rx.append(_weighted_sum_np(wy, ry))
-    return _weighted_sum_np(wx, rx), inside
+        ry = [weighted_sum_np(wz, [v[xa, yb, zc] for zc in iz]) for yb in iy]
+        rx.append(weighted_sum_np(wy, ry))
+    return weighted_sum_np(wx, rx), inside
 
 
 def _project_np(x, g, shape):
@@ -319,7 +316,7 @@ def simulate_stack_np(x, geometry: StackGeometry, stack_shape, fill: float = 0.0
     ``stack_residual_np`` where ``wsum >= 0.5`` and ``fill`` elsewhere."""
     x = _check_volume_np(x, "simulate_stack_np")
     g = _check_geometry(geometry, "simulate_stack_np")
-    shape = _check_shape(stack_shape, "stack_shape")
+    shape = check_shape(stack_shape, "stack_shape")
     acc, wsum = _project_np(x, g, shape)
     ok = wsum >= np.float32(0.5)
     out = np.full(shape, np.float32(fill), dtype=np.float32)
@@ -408,7 +405,7 @@ def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_I
     _check_stack_count(len(stacks), "combine_stacks_np")
     if len(geometries) != len(stacks):
         raise ValueError(f"combine_stacks_np: {len(stacks)} stacks and {len(geometries)} geometries")
-    shape_out, iterations = _check_shape(shape_out, "shape_out"), _check_iterations(iterations)
+    shape_out, iterations = check_shape(shape_out, "shape_out"), _check_iterations(iterations)
     _check_regulariser(_check_step(step), reg_lambda, reg_delta, reg_coeffs)
     x, cnt = stack_update_np(np.full(shape_out, np.float32(fill), dtype=np.float32), stacks, geometries, 1.0, clamp)
     initial = x.copy()
@@ -428,13 +425,8 @@ def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_I
 
 # ---------------------------------------------------------------- device
 
-def _check_out(out, like, others, what) -> torch.Tensor:
-    if out is None:
-        return torch.empty_like(like)
-    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != like.shape or not out.is_contiguous() \
-            or out.device != like.device or any(out.data_ptr() == o.data_ptr() for o in others):
-        raise ValueError(f"{what}: out must be another contiguous float32 tensor of shape {tuple(like.shape)} on {like.device}")
-    return out
+def _check_tensor(t, what) -> torch.Tensor:
+    return cuda_tensor(t, (torch.float32,), what, ndim=3, limit=True)
 
 
 def _region_bytes() -> int:
@@ -447,7 +439,7 @@ def _slots(device, count) -> torch.Tensor:
 
 def _residual(x, y, g, r, slots_ptr, stats_row):
     T = g.offsets.size
-    L.call("mrisr_f32_volume_stack_residual", x.data_ptr(), *x.shape, y.data_ptr(), *y.shape, _matrix_arg(g.to_output), g.slice_axis,
+    L.call("mrisr_f32_volume_stack_residual", x.data_ptr(), *x.shape, y.data_ptr(), *y.shape, matrix_arg(g.to_output), g.slice_axis,
            (L.C.c_double * T)(*g.offsets.tolist()), (L.C.c_float * T)(*g.weights.tolist()), T, r.data_ptr(), slots_ptr,
            L.ptr(stats_row), L.stream_ptr(), nbytes=4 * (x.numel() + 2 * y.numel()))
 
@@ -478,11 +470,11 @@ def stack_residual(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, ou
     """The device path of ``stack_residual_np`` -> ``(r, S, n)``: ``r`` bit for bit; ``S`` (0-d float64) within one spacing of the
     specification's sum and the same bits on every run, ``n`` (0-d int64) equal - both stay on the device.  Two launches (the
     residual; one wave that adds the fixed slots), no device-to-host read.  ``out``: another tensor like ``y``."""
-    x, y = _check_tensor(x, (torch.float32,), "stack_residual"), _check_tensor(y, (torch.float32,), "stack_residual")
+    x, y = _check_tensor(x, "stack_residual"), _check_tensor(y, "stack_residual")
     if x.device != y.device:
         raise ValueError(f"stack_residual: the estimate and the stack must share a device, got {x.device} and {y.device}")
     g = _check_geometry(geometry, "stack_residual")
-    r = _check_out(out, y, (x, y), "stack_residual")
+    r = out_like(out, y, (x, y), "stack_residual")
     row = torch.empty(2, dtype=torch.int64, device=x.device)
     _residual(x, y, g, r, _slots(x.device, 1).data_ptr(), row)
     return r, row[:1].view(torch.float64)[0], row[1]
@@ -493,7 +485,7 @@ def _check_stacks(volumes, geometries, device, what):
     _check_stack_count(len(volumes), what)
     if len(geometries) != len(volumes):
         raise ValueError(f"{what}: {len(volumes)} stacks and {len(geometries)} geometries")
-    volumes = [_check_tensor(v, (torch.float32,), f"{what}: stack {k}") for k, v in enumerate(volumes)]
+    volumes = [_check_tensor(v, f"{what}: stack {k}") for k, v in enumerate(volumes)]
     if any(v.device != device for v in volumes):
         raise ValueError(f"{what}: every stack must lie on {device}")
     return volumes, [_check_geometry(g, f"{what}: stack {k}") for k, g in enumerate(geometries)]
@@ -506,7 +498,7 @@ def stack_update(x: torch.Tensor, residuals, geometries, step: float = 1.0, clam
     ``reg_lambda > 0``: the regularised kernel, which reads the neighbours of a voxel - ``out`` must not be ``x`` - and the coverage
     counts of these stacks: ``coverage`` (uint8, like ``x``; ``cnt`` of an earlier call) is taken as given, None costs one launch of
     the plain kernel into scratch."""
-    x = _check_tensor(x, (torch.float32,), "stack_update")
+    x = _check_tensor(x, "stack_update")
     volumes, geometries = _check_stacks(residuals, geometries, x.device, "stack_update")
     step, lo = _check_step(step), _check_clamp(clamp)
     reg = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
@@ -515,7 +507,7 @@ def stack_update(x: torch.Tensor, residuals, geometries, step: float = 1.0, clam
         raise ValueError(f"stack_update: coverage must be a contiguous uint8 tensor of shape {tuple(x.shape)} on {x.device}")
     if reg[0] > 0 and isinstance(out, torch.Tensor) and out.data_ptr() == x.data_ptr():
         raise ValueError("stack_update: with reg_lambda > 0 the neighbours are read before the update: out must be another tensor than x")
-    out = x if out is x else _check_out(out, x, volumes, "stack_update")
+    out = x if out is x else out_like(out, x, volumes, "stack_update")
     cnt = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if cover else None
     if reg[0] > 0:
         if coverage is None:
@@ -535,8 +527,8 @@ class StackWorkspace:
     run in place, so the iterations alternate between the two."""
 
     def __init__(self, shape_out, stack_shapes, device, iterations: int = DEFAULT_ITERATIONS, regularised: bool = False):
-        self.shape_out = _check_shape(shape_out, "shape_out")
-        self.stack_shapes = tuple(_check_shape(s, "stack shape") for s in stack_shapes)
+        self.shape_out = check_shape(shape_out, "shape_out")
+        self.stack_shapes = tuple(check_shape(s, "stack shape") for s in stack_shapes)
         _check_stack_count(len(self.stack_shapes), "StackWorkspace")
         self.iterations = _check_iterations(iterations)
         self.key = (self.shape_out, self.stack_shapes, self.iterations)
@@ -579,9 +571,9 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
     regularised=True)`` - still ``K + 1`` launches and one read; with 0 the kernels and the bits are those without the keywords."""
     if not stacks:
         raise ValueError(f"combine_stacks: 1..{MAX_STACKS} stacks are combined, got 0")
-    first = _check_tensor(list(stacks)[0], (torch.float32,), "combine_stacks: stack 0")
+    first = _check_tensor(list(stacks)[0], "combine_stacks: stack 0")
     stacks, geometries = _check_stacks(stacks, geometries, first.device, "combine_stacks")
-    shape_out, iterations = _check_shape(shape_out, "shape_out"), _check_iterations(iterations)
+    shape_out, iterations = check_shape(shape_out, "shape_out"), _check_iterations(iterations)
     step, lo = _check_step(step), _check_clamp(clamp)
     reg = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
     reg = reg if reg[0] > 0 else None

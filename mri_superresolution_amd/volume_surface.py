@@ -28,11 +28,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._volume_args import MAX_EXTENT, check_classes, check_extents, check_spacing, cuda_device, cuda_tensor, u8_np      # noqa: F401  (MAX_EXTENT: this module's documented limit)
+from ._volume_args import check_weights as _check_weights      # private here as before; it lives there because check_spacing builds on it
 from .utils.imageops import np_percentile_f32
 from .volume_intensity import masked_percentiles, percentiles_workspace
-from .volume_tissue import _check_classes, _check_labels, _check_u8_np
 
-MAX_EXTENT = 1024                    # the longest axis of the transform: the device path stages whole lines in LDS
 P95 = 95.0
 
 
@@ -45,40 +45,10 @@ class SurfaceDistances(NamedTuple):
 
 # ---------------------------------------------------------------- checks shared by both paths
 
-def _check_weights(weights, what="weights") -> tuple:
-    """-> three float32 values, finite and positive."""
-    try:
-        with np.errstate(over="ignore"):
-            w = tuple(np.float32(x) for x in weights)
-    except (TypeError, ValueError):
-        w = ()
-    if len(w) != 3 or not all(np.isfinite(x) and x > 0 for x in w):
-        raise ValueError(f"{what} are three finite positive numbers (float32), got {weights!r}")
-    return w
-
-
-def _check_spacing(spacing) -> tuple:
-    """-> the weights of the transform: ``float32(s * s)`` per axis, the product taken in float64."""
-    try:
-        s = tuple(float(x) for x in spacing)
-    except (TypeError, ValueError):
-        s = ()
-    if len(s) != 3 or not all(math.isfinite(x) and x > 0 for x in s):
-        raise ValueError(f"spacing is three finite positive voxel sizes, got {spacing!r}")
-    return _check_weights(tuple(x * x for x in s), "the squared voxel sizes")
-
-
 def _check_value(value) -> int:
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= value <= 255:
         raise ValueError(f"value must be an integer in 0..255, got {value!r}")
     return int(value)
-
-
-def _check_extents(shape, what):
-    if len(shape) != 3:
-        raise ValueError(f"{what}: expected a volume (X, Y, Z), got {tuple(shape)}")
-    if max(shape) > MAX_EXTENT:
-        raise ValueError(f"{what}: an axis of {max(shape)} voxels is longer than the limit of {MAX_EXTENT}")
 
 
 def _finish(counts, sums, maxima, p95) -> SurfaceDistances:
@@ -97,18 +67,11 @@ def _finish(counts, sums, maxima, p95) -> SurfaceDistances:
 
 # ---------------------------------------------------------------- numpy specification
 
-def _check_labels_np(labels, shape, what):
-    labels = _check_u8_np(labels, shape, what)
-    if labels.ndim != 3:
-        raise ValueError(f"{what} must be a volume (X, Y, Z), got {labels.shape}")
-    return labels
-
-
 def boundary_np(labels, background=True) -> np.ndarray:
     """uint8, the shape of ``labels``: ``out[v] = labels[v]`` if ``labels[v] != 0`` and at least one of the 6 face neighbours differs,
     else 0.  ``background=True``: a neighbour differs if it lies outside the volume or carries another label, 0 included.
     ``background=False``: only if it lies inside the volume and carries another non-zero label - the interfaces between tissues."""
-    labels = _check_labels_np(labels, None, "the labels")
+    labels = u8_np(labels, None, "the labels", ndim=3)
     p = np.pad(labels.astype(np.int16), 1, constant_values=-1)           # -1: outside the volume
     X, Y, Z = labels.shape
     edge = np.zeros(labels.shape, dtype=bool)
@@ -130,9 +93,9 @@ def edt_sq_np(sites, value=0, weights=(1, 1, 1)) -> np.ndarray:
     ``sites[v] != 0`` when ``value == 0``.  ``g = 0`` at the sites and ``+inf`` elsewhere; then for axis 2, 1, 0:
     ``g'[i] = min_j fl32(g[j] + T[|i - j|])`` along that axis with ``T = distance_table_np(extent, weights[axis])``.  ``weights``: the
     squared voxel sizes, float32.  No site: ``+inf`` everywhere.  An axis is at most 1024 voxels."""
-    sites = _check_labels_np(sites, None, "the sites")
+    sites = u8_np(sites, None, "the sites", ndim=3)
     value, w = _check_value(value), _check_weights(weights)
-    _check_extents(sites.shape, "edt_sq_np")
+    check_extents(sites.shape, "edt_sq_np")
     g = np.where(sites == value if value else sites != 0, np.float32(0), np.float32(np.inf)).astype(np.float32)
     for axis in (2, 1, 0):
         n = g.shape[axis]
@@ -152,11 +115,11 @@ def surface_distances_np(a, b, classes=3, spacing=(1, 1, 1), background=True) ->
     rounded float32 square root), ``Dba`` the mirror image; ``hd = max(Dab.max(), Dba.max())``, ``hd95 = max(P95(Dab), P95(Dba))`` with
     numpy's float32 percentile (``utils.imageops.np_percentile_f32``), ``assd = (fsum(Dab) + fsum(Dba)) / (na + nb)`` in float64.  A
     class whose surface is empty on either side gives NaN in all three, decided from the counts: no infinity reaches a sum."""
-    K = _check_classes(classes)
-    w = _check_spacing(spacing)
-    a = _check_labels_np(a, None, "a")
-    b = _check_labels_np(b, a.shape, "b")
-    _check_extents(a.shape, "surface_distances_np")
+    K = check_classes(classes)
+    w = check_spacing(spacing)
+    a = u8_np(a, None, "a", ndim=3)
+    b = u8_np(b, a.shape, "b", ndim=3)
+    check_extents(a.shape, "surface_distances_np")
     bad = int((a > K).sum()) + int((b > K).sum())
     if bad:
         raise ValueError(f"{bad} voxel(s) carry a label above {K}")
@@ -181,10 +144,10 @@ def surface_distances_np(a, b, classes=3, spacing=(1, 1, 1), background=True) ->
 def label_boundary(labels: torch.Tensor, background=True, out=None) -> torch.Tensor:
     """The device form of ``boundary_np``: ``labels`` a contiguous uint8 CUDA volume (X, Y, Z) -> a uint8 CUDA volume, one launch for all
     classes.  ``out``: a uint8 CUDA tensor of that shape to write into (not ``labels`` itself)."""
-    t = _check_labels(labels, None, "label_boundary")
+    t = cuda_tensor(labels, (torch.uint8,), "label_boundary")
     if t.dim() != 3:
         raise ValueError(f"label_boundary: expected a volume (X, Y, Z), got {tuple(t.shape)}")
-    out = torch.empty_like(t) if out is None else _check_labels(out, t.shape, "label_boundary (out)")
+    out = torch.empty_like(t) if out is None else cuda_tensor(out, (torch.uint8,), "label_boundary (out)", shape=t.shape)
     L.call("mrisr_u8_volume_label_boundary", t.data_ptr(), *t.shape, int(bool(background)), 255, out.data_ptr(), None, L.stream_ptr(),
            nbytes=2 * t.numel())
     return out
@@ -200,9 +163,9 @@ def distance_transform_sq(sites: torch.Tensor, value=0, weights=(1, 1, 1), out=N
     """The device form of ``edt_sq_np``, the same contract: ``sites`` a contiguous uint8 CUDA volume (X, Y, Z), every axis at most 1024
     -> the float32 CUDA volume of squared distances, bit-equal to the specification, infinities included.  Three launches, in place
     in the result, no scratch volume.  ``out``: a contiguous float32 CUDA tensor of that shape to write into."""
-    t = _check_labels(sites, None, "distance_transform_sq")
+    t = cuda_tensor(sites, (torch.uint8,), "distance_transform_sq")
     value, w = _check_value(value), _check_weights(weights)
-    _check_extents(tuple(t.shape), "distance_transform_sq")
+    check_extents(tuple(t.shape), "distance_transform_sq")
     if out is None:
         out = torch.empty(t.shape, dtype=torch.float32, device=t.device)
     elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.shape != t.shape or not out.is_contiguous():
@@ -216,16 +179,12 @@ class SurfaceWorkspace:
     allocated inside the loop over the classes; it may serve call after call on one stream."""
 
     def __init__(self, shape, classes, device):
-        K = _check_classes(classes)
+        K = check_classes(classes)
         shape = tuple(int(d) for d in shape)
         if len(shape) != 3 or min(shape) < 1:
             raise ValueError(f"a volume shape (X, Y, Z) is expected, got {shape}")
-        _check_extents(shape, "SurfaceWorkspace")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("SurfaceWorkspace runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA device")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())      # a tensor's device carries its index
+        check_extents(shape, "SurfaceWorkspace")
+        device = cuda_device(device, "SurfaceWorkspace")
         self.shape, self.classes, self.device = shape, K, device
         self.boundary = [torch.empty(shape, dtype=torch.uint8, device=device) for _ in range(2)]
         self.d2 = torch.empty(shape, dtype=torch.float32, device=device)
@@ -257,11 +216,11 @@ def surface_distances(a: torch.Tensor, b: torch.Tensor, classes=3, spacing=(1, 1
     rounding of a float64 sum added in another order.  P95 is ``masked_percentiles`` of the gathered distances.  ``workspace``: a
     ``SurfaceWorkspace`` of this shape and class count; with one nothing is allocated here.  One download at the end covers all
     classes; a label above K is counted by the boundary kernel and raises ``ValueError`` then."""
-    K = _check_classes(classes)
-    w = _check_spacing(spacing)
-    a = _check_labels(a, None, "surface_distances")
-    b = _check_labels(b, a.shape, "surface_distances")
-    _check_extents(tuple(a.shape), "surface_distances")
+    K = check_classes(classes)
+    w = check_spacing(spacing)
+    a = cuda_tensor(a, (torch.uint8,), "surface_distances")
+    b = cuda_tensor(b, (torch.uint8,), "surface_distances", shape=a.shape)
+    check_extents(tuple(a.shape), "surface_distances")
     ws = SurfaceWorkspace(a.shape, K, a.device) if workspace is None else workspace
     if not isinstance(ws, SurfaceWorkspace) or ws.shape != tuple(a.shape) or ws.classes != K or ws.device != a.device:
         raise ValueError(f"the workspace must be a SurfaceWorkspace({tuple(a.shape)}, {K}, {a.device})")

@@ -27,12 +27,12 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .volume_intensity import RANGE, _check_mask, _check_vol, landmarks_np, masked_percentiles, percentiles_workspace
+from ._volume_args import MAX_CLASSES, MIN_CLASSES, check_classes, cuda_device, cuda_tensor, mask_tensor, u8_np, volume_np
+from .volume_intensity import RANGE, landmarks_np, masked_percentiles, percentiles_workspace
 
 logger = logging.getLogger(__name__)
 
 BINS = 256
-MIN_CLASSES, MAX_CLASSES = 2, 6
 MAX_BETA, MAX_ITERATIONS = 16.0, 100
 COST_SHIFT = 16                      # costs and beta are fixed point with 16 fractional bits
 COST_CAP = 1 << 30                   # cost + 6 beta_q stays below 2^31
@@ -54,14 +54,8 @@ class TissueSegmentation(NamedTuple):
 
 # ---------------------------------------------------------------- checks shared by both paths
 
-def _check_classes(classes) -> int:
-    if isinstance(classes, bool) or not isinstance(classes, (int, np.integer)) or not MIN_CLASSES <= classes <= MAX_CLASSES:
-        raise ValueError(f"classes must be an integer in {MIN_CLASSES}..{MAX_CLASSES}, got {classes!r}")
-    return int(classes)
-
-
 def _check_options(classes, beta, iterations):
-    K = _check_classes(classes)
+    K = check_classes(classes)
     try:
         b = float(beta)
     except (TypeError, ValueError):
@@ -85,21 +79,6 @@ def _range_scale(lo, hi):
 
 
 # ---------------------------------------------------------------- numpy specification
-
-def _check_vol_np(vol, what):
-    vol = np.asarray(vol)
-    if vol.dtype != np.float32 or vol.ndim != 3 or vol.size == 0:
-        raise ValueError(f"{what}: expected a non-empty float32 volume (X, Y, Z), got {vol.dtype} {vol.shape}")
-    return vol
-
-
-def _check_u8_np(a, shape, what):
-    a = np.asarray(a)
-    if a.dtype not in (np.uint8, np.bool_) or (shape is not None and a.shape != tuple(shape)) or a.size == 0:
-        raise ValueError(f"{what} must be a non-empty uint8 array" + (f" of shape {tuple(shape)}" if shape is not None else "")
-                         + f", got {a.dtype} {a.shape}")
-    return a.view(np.uint8)
-
 
 def quantise_np(vol, lo, hi) -> np.ndarray:
     """uint8, the shape of ``vol``: ``q = clip(int((v - lo) * scale), 0, 255)`` with ``scale = float32(256) / (hi - lo)``, every
@@ -129,7 +108,7 @@ def kmeans_hist_np(counts256, K) -> np.ndarray:
     (``_assign_bins``) and moves each centre to the mean bin of its cluster, float64 of two exact integer sums; an empty cluster
     keeps its centre.  It stops when no centre changes or after 50 rounds.  An empty histogram: the centres of K equal parts of
     the bin range.  Host-only: the device path calls this function on the downloaded counts."""
-    K = _check_classes(K)
+    K = check_classes(K)
     counts = np.asarray(counts256).astype(np.int64).reshape(-1)
     if counts.size != BINS or (counts < 0).any():
         raise ValueError(f"kmeans_hist_np: expected {BINS} non-negative counts, got {counts.shape}")
@@ -204,10 +183,10 @@ def cost_table_np(joint, prev=None):
 
 
 def _check_sweep_np(q, mask, labels, cost, beta_q):
-    q = _check_u8_np(q, None, "q")
+    q = u8_np(q, None, "q")
     if q.ndim != 3:
         raise ValueError(f"q must be a volume (X, Y, Z), got {q.shape}")
-    mask, labels = _check_u8_np(mask, q.shape, "the mask"), _check_u8_np(labels, q.shape, "the labels")
+    mask, labels = u8_np(mask, q.shape, "the mask"), u8_np(labels, q.shape, "the labels")
     cost = np.asarray(cost)
     if cost.dtype != np.int32 or cost.ndim != 2 or cost.shape[1] != BINS or not MIN_CLASSES <= cost.shape[0] <= MAX_CLASSES \
             or cost.min() < 0 or cost.max() > COST_CAP:
@@ -336,19 +315,19 @@ def segment_tissue_np(vol, mask, classes=3, beta=1.0, iterations=20) -> TissueSe
     of the bins is the masked 1st and 99th percentile (``volume_intensity.landmarks_np``).  ``iterations = 0`` returns the
     maximum-likelihood labels.  Nothing raises for a constant foreground or an empty mask: ``degenerate`` is set."""
     K, beta_q, T = _check_options(classes, beta, iterations)
-    vol = _check_vol_np(vol, "segment_tissue_np")
-    mask = _check_u8_np(mask, vol.shape, "the mask")
+    vol = volume_np(vol, "segment_tissue_np")
+    mask = u8_np(mask, vol.shape, "the mask")
     return _drive(_NumpyBackend(vol, mask, K), K, beta_q, T)
 
 
 def confusion_np(a, b, mask=None, classes=3) -> np.ndarray:
     """int64 (K + 1, K + 1): ``conf[i, j]`` = the voxels (inside ``mask``, when given) with ``a == i`` and ``b == j``.  A label above
     K among them is refused (``ValueError``)."""
-    K = _check_classes(classes)
-    a = _check_u8_np(a, None, "a")
-    b = _check_u8_np(b, a.shape, "b")
+    K = check_classes(classes)
+    a = u8_np(a, None, "a")
+    b = u8_np(b, a.shape, "b")
     if mask is not None:
-        sel = _check_u8_np(mask, a.shape, "the mask") != 0
+        sel = u8_np(mask, a.shape, "the mask") != 0
         a, b = a[sel], b[sel]
     a, b = a.reshape(-1).astype(np.int64), b.reshape(-1).astype(np.int64)
     bad = int(((a > K) | (b > K)).sum())
@@ -370,30 +349,17 @@ def dice_np(conf) -> np.ndarray:
 
 # ---------------------------------------------------------------- device
 
-def _check_labels(t, shape, what) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{what} runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA tensor")
-    if t.dtype != torch.uint8 or t.numel() == 0 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError(f"{what}: expected a non-empty contiguous uint8 tensor" + (f" of shape {tuple(shape)}" if shape is not None else "")
-                         + f", got {t.dtype} {tuple(t.shape)}")
-    return t
-
-
 class TissueWorkspace:
     """Every buffer of ``segment_tissue`` for volumes of ``shape`` and ``classes`` classes on ``device``, so that nothing is allocated
     inside the loop; it may serve call after call on one stream.  ``labels`` is the tensor a call returns: the next call with this
     workspace overwrites it."""
 
     def __init__(self, shape, classes, device):
-        K = _check_classes(classes)
+        K = check_classes(classes)
         shape = tuple(int(d) for d in shape)
         if len(shape) != 3 or min(shape) < 1:
             raise ValueError(f"a volume shape (X, Y, Z) is expected, got {shape}")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("TissueWorkspace runs on an MI355X through libmrisr.so only (no CPU fallback): expected a CUDA device")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())      # a tensor's device carries its index
+        device = cuda_device(device, "TissueWorkspace")
         self.shape, self.classes, self.device = shape, K, device
         self.q = torch.empty(shape, dtype=torch.uint8, device=device)
         self.labels = torch.empty(shape, dtype=torch.uint8, device=device)
@@ -459,12 +425,10 @@ def segment_tissue(vol: torch.Tensor, mask: torch.Tensor, classes=3, beta=1.0, i
     every field equal to the specification's.  ``workspace``: a ``TissueWorkspace`` of this shape and class count (its ``labels`` is
     returned).  Per iteration: three launches, one download of at most 12 KB and one upload of at most 6 KB (module docstring)."""
     K, beta_q, T = _check_options(classes, beta, iterations)
-    v = _check_vol(vol, "segment_tissue")
-    if v.dim() != 3:
-        raise ValueError(f"segment_tissue: expected a volume (X, Y, Z), got {tuple(v.shape)}")
+    v = cuda_tensor(vol, (torch.float32,), "segment_tissue", ndim=3)
     if mask is None:
         raise ValueError("segment_tissue: a mask is required (volume_eval.foreground_mask gives one)")
-    m = _check_mask(mask, v, "segment_tissue")
+    m = mask_tensor(mask, v.shape, "segment_tissue")
     ws = TissueWorkspace(v.shape, K, v.device) if workspace is None else workspace
     if not isinstance(ws, TissueWorkspace) or ws.shape != tuple(v.shape) or ws.classes != K or ws.device != v.device:
         raise ValueError(f"the workspace must be a TissueWorkspace({tuple(v.shape)}, {K}, {v.device})")
@@ -475,17 +439,10 @@ def label_confusion(a: torch.Tensor, b: torch.Tensor, mask=None, classes=3) -> n
     """The device form of ``confusion_np``: ``a``, ``b`` contiguous uint8 CUDA tensors of one shape, ``mask`` a uint8 or bool CUDA tensor
     of that shape or None -> the int64 (K + 1, K + 1) matrix on the host (one launch, one download of at most 400 bytes).  A label
     above K inside the mask is counted by the kernel, not tallied, and raises ``ValueError`` here."""
-    K = _check_classes(classes)
-    a = _check_labels(a, None, "label_confusion")
-    b = _check_labels(b, a.shape, "label_confusion")
-    m = None
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-            raise ValueError("label_confusion runs on an MI355X through libmrisr.so only (no CPU fallback): the mask must be a CUDA tensor")
-        if mask.dtype not in (torch.uint8, torch.bool) or mask.shape != a.shape or not mask.is_contiguous():
-            raise ValueError(f"label_confusion: the mask must be a contiguous uint8 or bool tensor of shape {tuple(a.shape)}, got "
-                             f"{mask.dtype} {tuple(mask.shape)}")
-        m = mask.view(torch.uint8)
+    K = check_classes(classes)
+    a = cuda_tensor(a, (torch.uint8,), "label_confusion")
+    b = cuda_tensor(b, (torch.uint8,), "label_confusion", shape=a.shape)
+    m = None if mask is None else mask_tensor(mask, a.shape, "label_confusion")
     cells = (K + 1) ** 2
     conf = torch.zeros(cells + 1, dtype=torch.int64, device=a.device)
     L.call("mrisr_u8_volume_confusion", a.data_ptr(), b.data_ptr(), L.ptr(m), a.numel(), K, conf.data_ptr(), L.stream_ptr(),

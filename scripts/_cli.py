@@ -1,0 +1,83 @@
+"""What the volume scripts share: the ``--cpu`` flag, the guarded ``main``, the upload of a frame, the joining
+and saving of frames, and the mask loading of ``evaluate_volume.py`` and ``segment_volume.py``.  A script imports it after the
+``REPO`` path insert.
+"""
+import logging
+import os
+
+import numpy as np
+import torch
+
+from mri_superresolution_amd.utils.nifti import grid_matrix, mask_frames, write_nifti
+from mri_superresolution_amd.volume_reslice import reslice_mask
+from mri_superresolution_amd.volume_stacks import voxel_sizes      # noqa: F401  (the scripts take it from here)
+
+logger = logging.getLogger("volume_cli")
+
+
+def add_cpu_flag(parser):
+    parser.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+
+
+def start_logging():
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+
+
+def require_gpu(args) -> torch.device:
+    if args.cpu or not torch.cuda.is_available():
+        raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
+    return torch.device("cuda")
+
+
+def log_device(device, log):
+    log.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+
+
+def run(body, args, log, doing) -> int:
+    """The ``main`` of a volume script: ``body(args, device)`` on the GPU -> 0; any exception is logged as ``Error during {doing}`` -> 1."""
+    start_logging()
+    try:
+        device = require_gpu(args)
+        log_device(device, log)
+        body(args, device)
+        return 0
+    except Exception as e:
+        log.error(f"Error during {doing}: {e}")
+        return 1
+
+
+def to_device(frame, device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(device)
+
+
+def join_frames(outs, ndim):
+    """The per-frame arrays of a scan of ``ndim`` axes: the one volume, or the frames along axis 3."""
+    return outs[0] if ndim == 3 else np.stack(outs, axis=3)
+
+
+def make_parent(path):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+
+
+def save_nifti(path, array, header):
+    make_parent(path)
+    write_nifti(path, array, header)
+
+
+def frame_tag(t, count) -> str:
+    return "frame " + str(t) + ": " if count > 1 else ""
+
+
+def load_mask(mask_path, ref, ref_affine=None):
+    """-> one uint8 frame per timepoint of the reference (``utils.nifti.mask_frames``).  ``ref_affine`` (``--align``): the mask may
+    lie on any grid and is resliced onto the reference's through the two affines with ``nearest``, on the device; the frames are
+    then CUDA tensors."""
+    count = 1 if ref.ndim == 3 else ref.shape[3]
+    masks, header = mask_frames(mask_path, None if ref_affine is not None else ref.shape[:3], count, "--mask")
+    if ref_affine is None:
+        return masks
+    m = grid_matrix(header.affine(), ref_affine)
+    distinct = masks if len(header.shape) == 4 else masks[:1]      # a 3-D mask is resliced once
+    out = [reslice_mask(torch.from_numpy(f).cuda(), m, ref.shape[:3]) for f in distinct]
+    logger.info(f"Mask {mask_path} {tuple(masks[0].shape)} resliced onto the reference grid {tuple(ref.shape[:3])} (nearest).")
+    return out if len(header.shape) == 4 else out * count

@@ -34,7 +34,8 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd import volume_stacks as S                                                     # noqa: E402
-from mri_superresolution_amd.utils.nifti import frames, header_for_grid, read_nifti, write_nifti           # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames, header_for_grid, read_nifti           # noqa: E402
+from scripts._cli import add_cpu_flag, join_frames, run, save_nifti                                          # noqa: E402
 
 logger = logging.getLogger("combine_stacks")
 
@@ -115,30 +116,21 @@ def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEF
     for path, vols in ((output_path, outs), (save_initial, initials)):
         if path is None:
             continue
-        data = vols[0] if scans[0][0].ndim == 3 else np.stack(vols, axis=3)
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        write_nifti(path, data, header)
+        data = join_frames(vols, scans[0][0].ndim)
+        save_nifti(path, data, header)
         result = data if result is None else result
     logger.info(f"Combined {len(inputs)} stacks into {tuple(result.shape)} ({iterations} iterations) saved to {output_path}")
     return result
 
 
+def _body(args, device):
+    combine_files(args.inputs, args.output, args.spacing, args.like, args.iterations, args.step, args.profile, args.thickness_mm,
+                  args.slice_axis, args.profile_samples, args.register, None if args.no_clamp else 0.0, args.fill, args.save_initial, device,
+                  args.regularise, args.regularise_delta)
+
+
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        check_options(args.inputs, args.iterations, args.step, args.slice_axis, args.thickness_mm, args.profile_samples, args.spacing,
-                      args.regularise, args.regularise_delta)
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        combine_files(args.inputs, args.output, args.spacing, args.like, args.iterations, args.step, args.profile, args.thickness_mm,
-                      args.slice_axis, args.profile_samples, args.register, None if args.no_clamp else 0.0, args.fill, args.save_initial, device,
-                      args.regularise, args.regularise_delta)
-        return 0
-    except Exception as e:
-        logger.error(f"Error during the reconstruction: {e}")
-        return 1
+    return run(_body, args, logger, "the reconstruction")
 
 
 def parse_args(argv=None):
@@ -161,7 +153,7 @@ def parse_args(argv=None):
     p.add_argument("--regularise", type=float, default=0.0, metavar="LAMBDA", help="weight of the Huber prior on the six face neighbours (default 0: none); "
                    "step * LAMBDA * (sum of the coefficients) <= 0.5")
     p.add_argument("--regularise_delta", type=float, default=float("inf"), metavar="D", help="clip the neighbour differences at D (default inf: quadratic prior)")
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     return p.parse_args(argv)
 
 

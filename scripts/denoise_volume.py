@@ -20,16 +20,16 @@ import logging
 import os
 import sys
 
-import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import frames as frames_of, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames as frames_of, read_nifti      # noqa: E402
 from mri_superresolution_amd.volume_denoise import denoise_volume                                  # noqa: E402
 from mri_superresolution_amd.volume_eval import foreground_mask                                    # noqa: E402
+from scripts._cli import add_cpu_flag, frame_tag, join_frames, run, save_nifti, to_device        # noqa: E402
 
 logger = logging.getLogger("denoise_volume")
 
@@ -45,42 +45,34 @@ def denoise_file(input_path, output_path, sigma=None, beta=1.0, radius=3, noise=
     frames = frames_of(data)
     outs, backgrounds, sigmas = [], [], []
     for t, frame in enumerate(frames):
-        vol = torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(device)
+        vol = to_device(frame, device)
         out, found = denoise_volume(vol, sigma=sigma, beta=beta, radius=radius, rician=noise == "rician", margin=noise_margin,
                                     return_noise=True)
         fg = vol[(foreground_mask(vol)[0] != 0) & torch.isfinite(vol)]
         median = float(fg.median()) if fg.numel() else float("nan")
         share = f"{100.0 * found['sigma'] / median:.2f} % of the foreground median {median:.6g}" if median > 0 else "no foreground median"
         origin = f"estimated from {found['count']} background voxels" if sigma is None else "given"
-        logger.info(f"{'frame ' + str(t) + ': ' if len(frames) > 1 else ''}sigma {found['sigma']:.9g} ({origin}), {share}")
+        logger.info(f"{frame_tag(t, len(frames))}sigma {found['sigma']:.9g} ({origin}), {share}")
         sigmas.append(found["sigma"])
         outs.append(out.cpu().numpy())
         if save_background:
             backgrounds.append(found["background"].to(torch.uint8).cpu().numpy())
-    result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
-    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
-    write_nifti(output_path, result, header)
+    result = join_frames(outs, data.ndim)
+    save_nifti(output_path, result, header)
     if save_background:
-        os.makedirs(os.path.dirname(os.path.abspath(save_background)), exist_ok=True)
-        write_nifti(save_background, backgrounds[0] if data.ndim == 3 else np.stack(backgrounds, axis=3), header)
+        save_nifti(save_background, join_frames(backgrounds, data.ndim), header)
         logger.info(f"Saved the background mask to {save_background}")
     logger.info(f"Denoised volume {tuple(data.shape)} ({noise}, radius {radius}, beta {beta:g}) saved to {output_path}")
     return result, sigmas
 
 
+def _body(args, device):
+    denoise_file(args.input, args.output, args.sigma, args.beta, args.radius, args.noise, args.noise_margin, args.save_background,
+                 device)
+
+
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        denoise_file(args.input, args.output, args.sigma, args.beta, args.radius, args.noise, args.noise_margin, args.save_background,
-                     device)
-        return 0
-    except Exception as e:
-        logger.error(f"Error during denoising: {e}")
-        return 1
+    return run(_body, args, logger, "denoising")
 
 
 def parse_args(argv=None):
@@ -94,7 +86,7 @@ def parse_args(argv=None):
                    help="rician (default): the weighted mean of the squared signal minus 2 sigma^2, then the root; gaussian: the plain weighted mean")
     p.add_argument("--noise_margin", type=int, default=3, help="the background is this many voxels (0..4) away from the Otsu foreground")
     p.add_argument("--save_background", type=str, default=None, help="write the background mask sigma was estimated from as a NIfTI with the input's header")
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     return p.parse_args(argv)
 
 

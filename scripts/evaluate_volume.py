@@ -116,15 +116,17 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd.utils.evalops import METRIC_COLUMNS          # noqa: E402
-from mri_superresolution_amd.utils.nifti import downscaled_affine, frames, grid_matrix, mask_frames, read_nifti, write_nifti   # noqa: E402
+from mri_superresolution_amd.utils.nifti import downscaled_affine, frames, grid_matrix, read_nifti, write_nifti   # noqa: E402
 from mri_superresolution_amd.volume_bias import match_bias as match_bias_field, sigmas_for                  # noqa: E402
 from mri_superresolution_amd.volume_deform import MAX_EXP_STEPS, MAX_LCC_RADIUS, register_deformable, register_diffeomorphic      # noqa: E402
 from mri_superresolution_amd.volume_denoise import denoise_volume                                             # noqa: E402
 from mri_superresolution_amd.volume_eval import downsample2, evaluate_volume, foreground_mask, otsu_threshold_value      # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity    # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
-from mri_superresolution_amd.volume_reslice import covered_share, reslice, reslice_mask    # noqa: E402
-from mri_superresolution_amd.volume_sharpness import _check_bins as check_edge_bins        # noqa: E402
+from mri_superresolution_amd.volume_reslice import covered_share, reslice    # noqa: E402
+from mri_superresolution_amd.volume_sharpness import check_bins as check_edge_bins        # noqa: E402
+from scripts._cli import (add_cpu_flag, join_frames, load_mask, log_device, make_parent, require_gpu, start_logging, to_device,   # noqa: E402
+                          voxel_sizes)
 
 logger = logging.getLogger("evaluate_volume")
 CSV_COLUMNS = ["scan", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # the column style of scripts/evaluate.py
@@ -145,26 +147,6 @@ def surface_columns(classes):
 def edge_columns(classes):
     """The columns ``--tissue_edges`` appends after those of ``--tissue_dice K`` and ``--tissue_surface``: one per interface."""
     return [f"{name}_{k}" for name in ("esw", "econ") for k in range(1, classes)]
-
-
-def voxel_sizes(affine):
-    """The voxel sizes along the three array axes in world units: the lengths of the affine's columns."""
-    return tuple(float(x) for x in np.linalg.norm(np.asarray(affine, dtype=np.float64)[:3, :3], axis=0))
-
-
-def load_mask(mask_path, ref, ref_affine=None):
-    """-> one uint8 frame per timepoint of the reference (``utils.nifti.mask_frames``).  ``ref_affine`` (``--align``): the mask may
-    lie on any grid and is resliced onto the reference's through the two affines with ``nearest``, on the device; the frames are
-    then CUDA tensors."""
-    count = 1 if ref.ndim == 3 else ref.shape[3]
-    masks, header = mask_frames(mask_path, None if ref_affine is not None else ref.shape[:3], count, "--mask")
-    if ref_affine is None:
-        return masks
-    m = grid_matrix(header.affine(), ref_affine)
-    distinct = masks if len(header.shape) == 4 else masks[:1]      # a 3-D mask is resliced once
-    out = [reslice_mask(torch.from_numpy(f).cuda(), m, ref.shape[:3]) for f in distinct]
-    logger.info(f"Mask {mask_path} {tuple(masks[0].shape)} resliced onto the reference grid {tuple(ref.shape[:3])} (nearest).")
-    return out if len(header.shape) == 4 else out * count
 
 
 def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0,
@@ -338,8 +320,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
         low_grid = downscaled_affine(ref_header.affine(), axes)
         if align == "rigid":
             # fixed = the reference, moving = the input, from the headers as they are (p0 = 0); W: reference world -> input world
-            fixed = torch.from_numpy(np.ascontiguousarray(frames(ref)[0], dtype=np.float32)).to(device)
-            moving = torch.from_numpy(np.ascontiguousarray(low_frames[0], dtype=np.float32)).to(device)
+            fixed, moving = to_device(frames(ref)[0], device), to_device(low_frames[0], device)
             found = register_rigid(fixed, ref_header.affine(), moving, low_header.affine(), bins=align_bins, init=align_init,
                                    mask_cost=align_mask == "otsu")
             p = found.p
@@ -408,7 +389,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                         values = [float(x) for x in found.width] + [float(x) for x in found.contrast / own.contrast]
                     rows[-1].update({c: v if region == "foreground" else "" for c, v in zip(edge_columns(tissue_dice), values)})
     if save_mask:
-        data = saved[0] if ref.ndim == 3 else np.stack(saved, axis=3)
+        data = join_frames(saved, ref.ndim)
         header = ref_header.copy()                              # the reference's, with the extents left after the crop
         dim = list(header.get("dim"))
         dim[1:4] = data.shape[:3]
@@ -448,10 +429,9 @@ def foreground_title(rows):
 
 
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+    start_logging()
     try:
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
+        device = require_gpu(args)
         if args.batch_size < 1:
             raise ValueError(f"--batch_size must be positive, got {args.batch_size}")
         if args.input and len(args.reference) != 1:
@@ -471,8 +451,7 @@ def main(args):
         if not 0 <= args.mask_close <= 4:
             raise ValueError(f"--mask_close must be in 0..4, got {args.mask_close}")
         from scripts.infer import find_best_checkpoint, load_model
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
+        log_device(device, logger)
         if args.checkpoint_path and os.path.exists(args.checkpoint_path):
             ckpt = args.checkpoint_path
         else:
@@ -513,7 +492,7 @@ def main(args):
             print(format_table(f"foreground, {title}" if region == "foreground" else title, mean, shown.get(region, ())))
             means += mean
         if args.output_csv:
-            os.makedirs(os.path.dirname(os.path.abspath(args.output_csv)), exist_ok=True)
+            make_parent(args.output_csv)
             columns = (CSV_COLUMNS_MASKED if args.mask else CSV_COLUMNS) + dice
             with open(args.output_csv, "w", newline="") as f:
                 wr = csv.DictWriter(f, fieldnames=columns)
@@ -536,7 +515,7 @@ def parse_args(argv=None):
     p.add_argument("--checkpoint_path", type=str, default=None)
     p.add_argument("--model_type", type=str, choices=["unet"], default="unet")
     p.add_argument("--base_filters", type=int, default=64)
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     p.add_argument("--use_amp", action="store_true", help="fp16 MFMA compute (the reference's autocast)")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--isotropic", action="store_true", help="double all three axes (the three-plane blend of infer_volume.py --isotropic)")

@@ -28,9 +28,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import frames as frames_of, mask_frames, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames as frames_of, mask_frames, read_nifti      # noqa: E402
 from mri_superresolution_amd.volume_bias import BiasWorkspace, correct_bias, match_bias, sigmas_for           # noqa: E402
 from mri_superresolution_amd.volume_eval import foreground_mask                                                # noqa: E402
+from scripts._cli import add_cpu_flag, frame_tag, join_frames, run, save_nifti, to_device      # noqa: E402
 
 logger = logging.getLogger("match_bias")
 
@@ -43,7 +44,7 @@ def _mask_frames(spec, data, count, what):
 
 
 def _on_device(frame, mask, device):
-    vol = torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(device)
+    vol = to_device(frame, device)
     return vol, (foreground_mask(vol)[0] if isinstance(mask, str) else torch.from_numpy(mask).to(device))
 
 
@@ -78,35 +79,26 @@ def match_file(input_path, output_path, like_path=None, sigma_mm=25.0, limit=4.0
                 target = _on_device(like_frames[t], like_masks[t], device)
             out, field = match_bias(src, target[0], smask, target[1], sigmas, limit, ws)
         lo, hi = torch.aminmax(field)
-        logger.info(f"{'frame ' + str(t) + ': ' if len(frames) > 1 else ''}field in [{float(lo):.4f}, {float(hi):.4f}]")
+        logger.info(f"{frame_tag(t, len(frames))}field in [{float(lo):.4f}, {float(hi):.4f}]")
         outs.append(out.cpu().numpy())
         fields.append(field.cpu().numpy())
-    result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
-    field = fields[0] if data.ndim == 3 else np.stack(fields, axis=3)
-    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
-    write_nifti(output_path, result, header)
+    result, field = join_frames(outs, data.ndim), join_frames(fields, data.ndim)
+    save_nifti(output_path, result, header)
     if save_field:
-        os.makedirs(os.path.dirname(os.path.abspath(save_field)), exist_ok=True)
-        write_nifti(save_field, field, header)
+        save_nifti(save_field, field, header)
         logger.info(f"Saved the field to {save_field}")
     logger.info(f"Corrected volume {tuple(data.shape)} saved to {output_path}")
     return result, field
 
 
+def _body(args, device):
+    if args.like is None and args.like_mask != "otsu":
+        raise ValueError("--like_mask goes with --like")
+    match_file(args.input, args.output, args.like, args.sigma_mm, args.limit, args.mask, args.like_mask, args.save_field, device)
+
+
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
-        if args.like is None and args.like_mask != "otsu":
-            raise ValueError("--like_mask goes with --like")
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        match_file(args.input, args.output, args.like, args.sigma_mm, args.limit, args.mask, args.like_mask, args.save_field, device)
-        return 0
-    except Exception as e:
-        logger.error(f"Error during bias-field matching: {e}")
-        return 1
+    return run(_body, args, logger, "bias-field matching")
 
 
 def parse_args(argv=None):
@@ -119,7 +111,7 @@ def parse_args(argv=None):
     p.add_argument("--mask", type=str, default="otsu", help="foreground of the input: otsu (default) or a NIfTI-1 mask")
     p.add_argument("--like_mask", type=str, default="otsu", help="foreground of --like: otsu (default) or a NIfTI-1 mask")
     p.add_argument("--save_field", type=str, default=None, help="write the field as a float32 NIfTI with the input's header")
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     return p.parse_args(argv)
 
 

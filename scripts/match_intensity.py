@@ -21,16 +21,16 @@ import logging
 import os
 import sys
 
-import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import frames as frames_of, mask_frames, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames as frames_of, mask_frames, read_nifti      # noqa: E402
 from mri_superresolution_amd.volume_eval import foreground_mask                                  # noqa: E402
 from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_intensity          # noqa: E402
+from scripts._cli import add_cpu_flag, frame_tag, join_frames, make_parent, run, save_nifti, to_device    # noqa: E402
 
 logger = logging.getLogger("match_intensity")
 MODES = {"landmarks": LANDMARKS, "range": RANGE}
@@ -46,7 +46,7 @@ def _mask_frames(spec, data, count, what):
 
 
 def _on_device(frame, mask, device):
-    vol = torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(device)
+    vol = to_device(frame, device)
     if isinstance(mask, str):
         return vol, foreground_mask(vol)[0]
     return vol, (None if mask is None else torch.from_numpy(mask).to(device))
@@ -73,15 +73,14 @@ def match_file(input_path, like_path, output_path, percentiles=LANDMARKS, mask="
         if t == 0 or len(like_frames) > 1:                       # a 3-D --like is uploaded (and masked) once
             target = _on_device(like_frames[t], like_masks[t], device)
         out, found = match_intensity(src, target[0], smask, target[1], percentiles)
-        logger.info(f"{'frame ' + str(t) + ': ' if len(frames) > 1 else ''}{found.source_count} source and {found.target_count} target "
+        logger.info(f"{frame_tag(t, len(frames))}{found.source_count} source and {found.target_count} target "
                     f"voxels; landmarks {format_landmarks(found)}")
         outs.append(out.cpu().numpy())
         founds.append(found)
-    result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
-    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
-    write_nifti(output_path, result, header)
+    result = join_frames(outs, data.ndim)
+    save_nifti(output_path, result, header)
     if save_landmarks:
-        os.makedirs(os.path.dirname(os.path.abspath(save_landmarks)), exist_ok=True)
+        make_parent(save_landmarks)
         with open(save_landmarks, "w") as f:
             for t, found in enumerate(founds):
                 f.write(f"# frame {t}: percentile, source landmark, target landmark ({found.source_count} / {found.target_count} voxels)\n")
@@ -92,21 +91,15 @@ def match_file(input_path, like_path, output_path, percentiles=LANDMARKS, mask="
     return result, founds
 
 
+def _body(args, device):
+    if args.percentiles is not None and args.mode is not None:
+        raise ValueError("--percentiles goes without --mode")
+    percentiles = tuple(args.percentiles) if args.percentiles is not None else MODES[args.mode or "landmarks"]
+    match_file(args.input, args.like, args.output, percentiles, args.mask, args.like_mask, args.save_landmarks, device)
+
+
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
-        if args.percentiles is not None and args.mode is not None:
-            raise ValueError("--percentiles goes without --mode")
-        percentiles = tuple(args.percentiles) if args.percentiles is not None else MODES[args.mode or "landmarks"]
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        match_file(args.input, args.like, args.output, percentiles, args.mask, args.like_mask, args.save_landmarks, device)
-        return 0
-    except Exception as e:
-        logger.error(f"Error during intensity matching: {e}")
-        return 1
+    return run(_body, args, logger, "intensity matching")
 
 
 def parse_args(argv=None):
@@ -120,7 +113,7 @@ def parse_args(argv=None):
     p.add_argument("--mask", type=str, default="otsu", help="foreground of the input: otsu (default), none, or a NIfTI-1 mask")
     p.add_argument("--like_mask", type=str, default="otsu", help="foreground of --like: otsu (default), none, or a NIfTI-1 mask")
     p.add_argument("--save_landmarks", type=str, default=None, help="write percentile, source landmark, target landmark as text")
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     return p.parse_args(argv)
 
 

@@ -39,17 +39,17 @@ import os
 import sys
 
 import numpy as np
-import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import frames as frames_of, header_for_grid, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames as frames_of, header_for_grid, read_nifti      # noqa: E402
 from mri_superresolution_amd.volume_deform import DEFAULT_ITERATIONS, MAX_EXP_STEPS, register_deformable, warp      # noqa: E402
 from mri_superresolution_amd.volume_deform import MAX_LCC_RADIUS, register_diffeomorphic, warp_matrix      # noqa: E402
 from mri_superresolution_amd.volume_register import register_rigid                             # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice                      # noqa: E402
+from scripts._cli import add_cpu_flag, join_frames, make_parent, run, save_nifti, to_device                 # noqa: E402
 
 logger = logging.getLogger("register_volume")
 
@@ -144,9 +144,9 @@ def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64
     check_options(nonrigid, nonrigid_exp_steps, nonrigid_resample, save_field, nonrigid_force, nonrigid_lcc_radius)
     fixed, fixed_header = read_nifti(fixed_path)
     moving, moving_header = read_nifti(moving_path)
-    frames = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)).to(device) for f in frames_of(moving)]
+    frames = [to_device(f, device) for f in frames_of(moving)]
     fixed0 = fixed if fixed.ndim == 3 else fixed[..., 0]
-    fixed0 = torch.from_numpy(np.ascontiguousarray(fixed0, dtype=np.float32)).to(device)
+    fixed0 = to_device(fixed0, device)
     fixed_affine, shape = fixed_header.affine(), tuple(fixed.shape[:3])
     result = register_rigid(fixed0, fixed_affine, frames[0], moving_header.affine(), bins=bins, mask_cost=mask == "otsu", init=init,
                             init_limit=init_limit, init_step=init_step)
@@ -160,41 +160,33 @@ def register_file(fixed_path, moving_path, output_path, interp="linear", bins=64
                                         nonrigid, nonrigid_exp_steps, (frames, result.matrix) if nonrigid_resample == "once" else None,
                                         nonrigid_force, nonrigid_lcc_radius)
         if save_field:
-            os.makedirs(os.path.dirname(os.path.abspath(save_field)), exist_ok=True)
             field = np.ascontiguousarray(np.moveaxis(deformed.field.cpu().numpy(), 0, 3))
             field_header = header_for_grid(fixed_header, shape, fixed_affine)
             dim = list(field_header.get("dim"))
             dim[0], dim[4] = 4, 3                                       # three frames: the components along the grid's axes
             field_header.set("dim", dim)
-            write_nifti(save_field, field, field_header)
+            save_nifti(save_field, field, field_header)
             logger.info(f"Field {tuple(field.shape)} (voxels of the fixed grid) saved to {save_field}")
-    data = outs[0].cpu().numpy() if moving.ndim == 3 else np.stack([o.cpu().numpy() for o in outs], axis=3)
+    data = join_frames([o.cpu().numpy() for o in outs], moving.ndim)
     logger.info(f"{100.0 * (1.0 - float(share)):.2f} % of the output voxels fell outside the moving scan (set to {fill:g}).")
-    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
-    write_nifti(output_path, data, header_for_grid(moving_header, shape, fixed_affine))
+    save_nifti(output_path, data, header_for_grid(moving_header, shape, fixed_affine))
     logger.info(f"Moving scan {tuple(moving.shape)} -> {tuple(data.shape)} ({interp}) saved to {output_path}")
     if save_transform:
-        os.makedirs(os.path.dirname(os.path.abspath(save_transform)), exist_ok=True)
+        make_parent(save_transform)
         np.savetxt(save_transform, result.world, fmt="%.17g", header="fixed world -> moving world (mm), 4 x 4")
         logger.info(f"Transform saved to {save_transform}")
     return data, result
 
 
+def _body(args, device):
+    register_file(args.fixed, args.moving, args.output, args.interp, args.bins, args.save_transform, args.fill, device, args.init,
+                  args.init_limit, args.init_step, args.mask, args.nonrigid, args.nonrigid_levels, args.nonrigid_iterations,
+                  args.nonrigid_sigma, args.nonrigid_max_step, args.save_field, args.nonrigid_exp_steps, args.nonrigid_resample,
+                  args.nonrigid_force, args.nonrigid_lcc_radius)
+
+
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        register_file(args.fixed, args.moving, args.output, args.interp, args.bins, args.save_transform, args.fill, device, args.init,
-                      args.init_limit, args.init_step, args.mask, args.nonrigid, args.nonrigid_levels, args.nonrigid_iterations,
-                      args.nonrigid_sigma, args.nonrigid_max_step, args.save_field, args.nonrigid_exp_steps, args.nonrigid_resample,
-                      args.nonrigid_force, args.nonrigid_lcc_radius)
-        return 0
-    except Exception as e:
-        logger.error(f"Error during registration: {e}")
-        return 1
+    return run(_body, args, logger, "registration")
 
 
 def parse_args(argv=None):
@@ -235,7 +227,7 @@ def parse_args(argv=None):
     p.add_argument("--nonrigid_max_step", type=float, default=2.0, help="--nonrigid demons: bound of one iteration's update in voxels")
     p.add_argument("--save_field", type=str, default=None,
                    help="--nonrigid demons: write the field as a 4-D float32 NIfTI of three frames (voxels of the fixed grid)")
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     return p.parse_args(argv)
 
 

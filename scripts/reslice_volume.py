@@ -25,8 +25,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import frames, grid_matrix, header_for_grid, read_nifti, respaced_grid, write_nifti   # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames, grid_matrix, header_for_grid, read_nifti, respaced_grid   # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice                                              # noqa: E402
+from scripts._cli import add_cpu_flag, join_frames, run, save_nifti                                                   # noqa: E402
 
 logger = logging.getLogger("reslice_volume")
 
@@ -43,26 +44,19 @@ def reslice_file(input_path, output_path, like=None, spacing=None, interp="linea
     m = grid_matrix(src_affine, dst_affine)
     outs = [reslice(torch.from_numpy(np.ascontiguousarray(f)).to(device), m, dst_shape, interp, fill) for f in frames(data)]
     share = covered_share(data.shape[:3], m, dst_shape, device)
-    result = outs[0].cpu().numpy() if data.ndim == 3 else np.stack([o.cpu().numpy() for o in outs], axis=3)
+    result = join_frames([o.cpu().numpy() for o in outs], data.ndim)
     logger.info(f"{100.0 * (1.0 - float(share)):.2f} % of the output voxels fell outside the input (set to {fill:g}).")
-    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
-    write_nifti(output_path, result, header_for_grid(header, dst_shape, dst_affine))
+    save_nifti(output_path, result, header_for_grid(header, dst_shape, dst_affine))
     logger.info(f"Resliced volume {tuple(data.shape)} -> {tuple(result.shape)} ({interp}) saved to {output_path}")
     return result
 
 
+def _body(args, device):
+    reslice_file(args.input, args.output, args.like, args.spacing, args.interp, args.fill, device)
+
+
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        reslice_file(args.input, args.output, args.like, args.spacing, args.interp, args.fill, device)
-        return 0
-    except Exception as e:
-        logger.error(f"Error during reslicing: {e}")
-        return 1
+    return run(_body, args, logger, "reslicing")
 
 
 def parse_args(argv=None):
@@ -75,7 +69,7 @@ def parse_args(argv=None):
                    help="voxel size in mm per axis on the input's own grid; 0 keeps an axis")
     p.add_argument("--interp", type=str, choices=["nearest", "linear", "cubic"], default="linear")
     p.add_argument("--fill", type=float, default=0.0, help="value of the output voxels whose centre lies outside the input")
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     return p.parse_args(argv)
 
 

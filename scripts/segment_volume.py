@@ -29,12 +29,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from mri_superresolution_amd.utils.nifti import frames, read_nifti, write_nifti      # noqa: E402
+from mri_superresolution_amd.utils.nifti import frames, read_nifti      # noqa: E402
 from mri_superresolution_amd.volume_eval import foreground_mask                      # noqa: E402
 from mri_superresolution_amd.volume_tissue import TissueWorkspace, dice, label_confusion, segment_tissue      # noqa: E402
 from mri_superresolution_amd.volume_surface import SurfaceWorkspace, surface_distances                      # noqa: E402
 from mri_superresolution_amd.volume_sharpness import edge_sharpness                                         # noqa: E402
-from scripts.evaluate_volume import load_mask, voxel_sizes                                        # noqa: E402
+from scripts._cli import add_cpu_flag, join_frames, load_mask, run, save_nifti, to_device, voxel_sizes      # noqa: E402
 
 logger = logging.getLogger("segment_volume")
 
@@ -64,7 +64,7 @@ def segment_file(input_path, output_path, classes=3, beta=1.0, iterations=20, ma
     surface_ws = SurfaceWorkspace(data.shape[:3], classes, device) if compare is not None else None
     outs, overlaps = [], []
     for t, frame in enumerate(frames(data)):
-        vol = torch.from_numpy(np.ascontiguousarray(frame, dtype=np.float32)).to(device)
+        vol = to_device(frame, device)
         m = foreground_mask(vol, mask_close, bool(mask_largest), mask_fill_holes)[0] if masks is None else torch.from_numpy(masks[t]).to(device)
         found = segment_tissue(vol, m, classes, beta, iterations, workspace=ws)
         what = f"{input_path}{f'[t={t}]' if data.ndim == 4 else ''}"
@@ -79,32 +79,25 @@ def segment_file(input_path, output_path, classes=3, beta=1.0, iterations=20, ma
             for name, values in (("ASSD", far.assd), ("HD95", far.hd95), ("HD", far.hd)):
                 print(f"{what} {name} against {compare}: " + "  ".join(f"class {k + 1} {d:.6f}" for k, d in enumerate(values)))
         if scan is not None:
-            theirs = torch.from_numpy(np.ascontiguousarray(frames(scan)[t], dtype=np.float32)).to(device)
+            theirs = to_device(frames(scan)[t], device)
             sharp = edge_sharpness(theirs, found.labels, classes, voxel_sizes(header.affine()))
             for name, values in (("edge width", sharp.width), ("edge contrast", sharp.contrast)):
                 print(f"{what} {name} of {edges}: " + "  ".join(f"interface {k + 1} {d:.6f}" for k, d in enumerate(values)))
         outs.append(found.labels.cpu().numpy())
-    result = outs[0] if data.ndim == 3 else np.stack(outs, axis=3)
-    os.makedirs(os.path.dirname(os.path.abspath(output_path)), exist_ok=True)
-    write_nifti(output_path, result, header.copy())
+    result = join_frames(outs, data.ndim)
+    save_nifti(output_path, result, header.copy())
     logger.info(f"Labels {tuple(result.shape)} saved to {output_path}")
     return result, (overlaps if other is not None else None)
 
 
+def _body(args, device):
+    fill = args.mask_fill_holes if args.mask_fill_holes in (None, "3d") else int(args.mask_fill_holes)
+    segment_file(args.input, args.output, args.classes, args.beta, args.iterations, args.mask, args.mask_close, args.mask_largest, fill,
+                 args.compare, device, args.edges)
+
+
 def main(args):
-    logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        if args.cpu or not torch.cuda.is_available():
-            raise RuntimeError("this build runs on MI355X only (hand-written HIP kernels, no CPU fallback)")
-        device = torch.device("cuda")
-        logger.info(f"Using device: {device} ({torch.cuda.get_device_name(0)})")
-        fill = args.mask_fill_holes if args.mask_fill_holes in (None, "3d") else int(args.mask_fill_holes)
-        segment_file(args.input, args.output, args.classes, args.beta, args.iterations, args.mask, args.mask_close, args.mask_largest, fill,
-                     args.compare, device, args.edges)
-        return 0
-    except Exception as e:
-        logger.error(f"Error during segmentation: {e}")
-        return 1
+    return run(_body, args, logger, "segmentation")
 
 
 def parse_args(argv=None):
@@ -124,7 +117,7 @@ def parse_args(argv=None):
     p.add_argument("--compare", type=str, default=None, help="print the Dice overlap per class with this label file (same shape)")
     p.add_argument("--edges", type=str, default=None,
                    help="print the 10 %% - 90 %% edge width and the contrast of this scan (same shape) across every interface of the labels")
-    p.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+    add_cpu_flag(p)
     return p.parse_args(argv)
 
 

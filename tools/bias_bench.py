@@ -19,13 +19,14 @@ voxel for the field (five volumes read, two written); ``tb_per_s`` = min_bytes o
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+
+from tools.benchutil import alternating_times      # noqa: E402
 
 
 def phantom(n, device, seed):
@@ -36,24 +37,6 @@ def phantom(n, device, seed):
     v = v * torch.exp(0.25 * x - 0.2 * y * y + 0.15 * z * x * seed)
     mask = ((x * x + y * y + z * z) <= 0.985 ** 2).to(torch.uint8).contiguous()      # a ball: about 50 % of the box
     return (1000.0 * (v + 0.01 * torch.randn(v.shape, device=device, generator=g)).clamp_min(0)).contiguous(), mask
-
-
-def alternating_times(fns, reps, warmup, inner):
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            times[k].append(e0.elapsed_time(e1) * 1e3 / inner)
-    return {k: {"us_median": round(statistics.median(v), 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1)} for k, v in times.items()}
 
 
 def main():

@@ -29,21 +29,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+from tools.benchutil import timed      # noqa: E402
+
 from mri_superresolution_amd import volume_deform as D                       # noqa: E402
 from mri_superresolution_amd.volume_bias import gaussian_taps                # noqa: E402
-
-
-def timed(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    stop.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(stop) / iters      # ms
 
 
 def torch_iteration(fixed, moving, u, taps, max_step):

@@ -14,13 +14,14 @@ of them, 10 planes per 8 voxels) and candidate; ``lds_reads``: 18 reads per plan
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+
+from tools.benchutil import alternating_times      # noqa: E402
 
 
 def phantom(n, sigma, device, seed):
@@ -60,24 +61,6 @@ def torch_nlm(v, inv_h2, two_sigma2, radius):
     wc = torch.where(wmax > 0, wmax, torch.ones_like(wmax))
     m = (num + wc * val) / (den + wc)
     return torch.sqrt((m - two_sigma2).clamp_min(0))
-
-
-def alternating_times(fns, reps, warmup, inner):
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            times[k].append(e0.elapsed_time(e1) * 1e3 / inner)
-    return {k: {"us_median": round(statistics.median(v), 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1)} for k, v in times.items()}
 
 
 def main():

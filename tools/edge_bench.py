@@ -29,21 +29,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+from tools.benchutil import timed      # noqa: E402
+
 from mri_superresolution_amd import volume_sharpness as V                    # noqa: E402
-
-
-def timed(fn, iters, warmup):
-    """ms per call: device events around the whole loop."""
-    for _ in range(warmup):
-        fn()
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    stop.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(stop) / iters
 
 
 def stats(t):
@@ -83,7 +71,7 @@ def main(args):
     vol_np = (300.0 * labels_np + np.random.default_rng(0).normal(0.0, 30.0, r.shape)).astype(np.float32)
     labels, vol = torch.from_numpy(labels_np).cuda(), torch.from_numpy(vol_np).cuda()
     voxels, J = vol.numel(), K - 1
-    nb = V._check_bins(args.radius, args.bin)[2]
+    nb = V.check_bins(args.radius, args.bin)[2]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     sdist = V.signed_distances(labels, K, args.spacing)

@@ -15,7 +15,6 @@ mask (1), the map 8 bytes a voxel.  Prints one JSON line."""
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -23,6 +22,8 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+
+from tools.benchutil import alternating_times_fine as alternating_times      # noqa: E402
 
 
 def phantom(n, device):
@@ -36,24 +37,6 @@ def phantom(n, device):
         v = v + a * torch.exp(-((x - cx) ** 2 + (y - cy) ** 2 + (z - cz) ** 2) / (2 * s * s))
     mask = ((x * x + y * y + z * z) <= 0.985 ** 2).to(torch.uint8).contiguous()      # a ball: 4 pi / 3 * 0.985^3 / 8 = 50 % of the box
     return (1000.0 * (v.clamp_min(0) + 0.01 * torch.randn(v.shape, device=device, generator=g))).contiguous(), mask
-
-
-def alternating_times(fns, reps, warmup, inner):
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            times[k].append(e0.elapsed_time(e1) * 1e3 / inner)
-    return {k: {"us_median": round(statistics.median(v), 2), "us_min": round(min(v), 2), "us_max": round(max(v), 2)} for k, v in times.items()}
 
 
 def main():

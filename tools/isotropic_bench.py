@@ -13,7 +13,6 @@ Prints one JSON line (profiles/NOTES.md, "Isotropic volumes")."""
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -23,20 +22,7 @@ import torch.nn.functional as F
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-
-def event_times(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1) * 1e3)
-    return {"us_median": round(statistics.median(times), 1), "us_min": round(min(times), 1)}
+from tools.benchutil import event_times      # noqa: E402
 
 
 def synthetic_volume(size, seed=0):

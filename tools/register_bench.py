@@ -23,7 +23,6 @@ import argparse
 import ctypes as C
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -33,6 +32,8 @@ import torch.nn.functional as F
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+
+from tools.benchutil import alternating_times_fine as alternating_times      # noqa: E402
 
 BINS = 64
 
@@ -56,24 +57,6 @@ def torch_theta(m, src, dst, device):
     off = (m[:, :3] @ (D - 1) + 2 * m[:, 3] + 1) / S - 1
     theta = np.hstack([lin[::-1, ::-1], off[::-1, None]])
     return torch.tensor(theta[None], dtype=torch.float32, device=device)
-
-
-def alternating_times(fns, reps, warmup, inner):
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(inner):
-                fn()
-            e1.record()
-            e1.synchronize()
-            times[k].append(e0.elapsed_time(e1) * 1e3 / inner)
-    return {k: {"us_median": round(statistics.median(v), 2), "us_min": round(min(v), 2), "us_max": round(max(v), 2)} for k, v in times.items()}
 
 
 def ellipsoid_mask(n, device, semi=0.78):

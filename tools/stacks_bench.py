@@ -39,21 +39,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+from tools.benchutil import timed      # noqa: E402
+
 from mri_superresolution_amd import volume_stacks as S                       # noqa: E402
-
-
-def timed(fn, iters, warmup):
-    """ms per call: device events around the whole loop."""
-    for _ in range(warmup):
-        fn()
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(iters):
-        fn()
-    stop.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(stop) / iters
 
 
 def stats(t):

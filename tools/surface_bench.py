@@ -30,6 +30,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from mri_superresolution_amd import volume_surface as S                      # noqa: E402
+from mri_superresolution_amd._volume_args import check_spacing               # noqa: E402
 
 
 def timed(fn, iters, warmup, prepare=None):
@@ -89,7 +90,7 @@ def main(args):
     a = torch.from_numpy(a_np).cuda()
     b = torch.from_numpy(np.roll(a_np, 2, axis=0)).cuda()
     voxels = a.numel()
-    w = S._check_spacing(args.spacing)
+    w = check_spacing(args.spacing)
     sites = S.label_boundary(b)
     value = 2
     out = torch.empty(a.shape, dtype=torch.float32, device="cuda")

@@ -13,7 +13,6 @@ Prints one JSON line (profiles/NOTES.md, "Whole-volume inference")."""
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -22,22 +21,9 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+from tools.benchutil import event_times      # noqa: E402
+
 WINDOW_LAUNCHES = 9 + 1 + 1      # mrisr_f32_percentile_bounds (init + 4 x (histogram, pick)), normalise, restore
-
-
-def event_times(fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1) * 1e3)
-    return {"us_median": round(statistics.median(times), 1), "us_min": round(min(times), 1)}
 
 
 def synthetic_slices(b, size, seed=0):
