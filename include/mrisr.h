@@ -990,6 +990,53 @@ int mrisr_f32_volume_stack_update_reg(const float* x, int X, int Y, int Z, const
                                       float lo, float lambda, float delta, const float* coeffs, const unsigned char* cover_in, float* out,
                                       unsigned char* cover, const void* workspace, void* stats_rows, void* stream);
 
+/* ---- Slice-to-volume motion correction of that reconstruction (extension; csrc/volume_slices.hip): the two projections with one
+ *      matrix PER SLICE and the cost of candidate poses of every slice.  A table is a DEVICE array of 12 doubles per slice (row-major
+ *      3 x 4, 8-byte aligned), complete before the launch; the entries are not checked (no host read) - one that is not finite fails
+ *      every inside test, so nothing is read out of bounds.  The specification is mri_superresolution_amd/volume_stacks.py
+ *      (stack_residual_slices_np, stack_update_slices_np, slice_cost_np).  No host synchronisation, no atomics of any kind. ---- */
+#define MRISR_SLICES_MAX 256
+#define MRISR_SLICE_CANDIDATES_MAX 13
+/* one stack as the per-slice update sees it: data DEVICE float32 (nx, ny, nz); from_output DEVICE, slices x 12 doubles: matrix s
+ * maps an OUTPUT voxel index to the continuous stack index under the pose of slice s; slices = the extent along slice_axis     */
+typedef struct mrisr_stack_slices_view {
+    const float* data;
+    int32_t nx, ny, nz, slice_axis;
+    const double* from_output;
+    int32_t slices, reserved_;
+} mrisr_stack_slices_view;
+/* mrisr_f32_volume_stack_residual with the matrix of a voxel's slice taken from to_output (DEVICE, slices x 12; slices = the
+ * extent along slice_axis, 1..256): bit for bit volume_stacks.stack_residual_slices_np.  workspace, stats_row, launches and the
+ * sums as there.  MRISR_E_ARG additionally: slices outside 1..256 or not the extent along the slice axis.                       */
+int mrisr_f32_volume_stack_residual_slices(const float* x, int X, int Y, int Z, const float* y, int SX, int SY, int SZ,
+                                           const double* to_output, int slices, int slice_axis, const double* offsets,
+                                           const float* weights, int T, float* r, void* workspace, void* stats_row, void* stream);
+/* The update with per-slice poses, bit for bit volume_stacks.stack_update_slices_np.  For an output voxel q and k = 0 .. K - 1:
+ * acc = wk = +0; for s = 0 .. slices_k - 1: p = from_output_k[s] q; z = p[slice_axis], d = |z - s| in double; the slice is skipped
+ * unless d < 1 and both in-plane coordinates lie in [-0.5, n - 0.5]; w = (float)(1 - d); g = the bilinear gather of plane s of
+ * data_k at the in-plane coordinates (clamped taps, the higher in-plane axis reduced first); acc = fl(acc + fl(w g)),
+ * wk = fl(wk + w).  wk >= 0.5f: sum = fl(sum + fl(acc / wk)), cnt += 1.  out, the clamp, cover, workspace and stats_rows as
+ * mrisr_f32_volume_stack_update.  ONE launch for all stacks; a workgroup stages the slice-axis rows of a table in LDS and rejects
+ * a slice on d before it reads the other two rows.  MRISR_E_ARG / MRISR_E_SHAPE as there, and: a null or misaligned table, a
+ * slice axis outside 0..2, slices outside 1..256 or not the extent along the slice axis.                                         */
+int mrisr_f32_volume_stack_update_slices(const float* x, int X, int Y, int Z, const mrisr_stack_slices_view* views, int K, float step,
+                                         int use_clamp, float lo, float* out, unsigned char* cover, const void* workspace,
+                                         void* stats_rows, void* stream);
+/* bytes of DEVICE workspace of mrisr_f32_volume_slice_cost (0: slices outside 1..256 or candidates outside 1..13); no
+ * initialisation needed, 8-byte aligned.                                                                                         */
+size_t mrisr_f32_volume_slice_cost_workspace_bytes(int slices, int candidates);
+/* out (DEVICE, slices x count x 6 doubles, overwritten) = n, sum y, sum m, sum y^2, sum m^2, sum y m over the voxels of slice s whose
+ * two in-plane indices are multiples of stride (1, 2 or 4) and whose simulated value m through candidates[s][c] (DEVICE, slices x
+ * count x 12 doubles: stack index -> output index) exists (the forward model of mrisr_f32_volume_stack_residual, weight sum >=
+ * 0.5f): volume_stacks.slice_cost_np.  n is exact, the sums are those of a fixed order of addition (lanes in a fixed tree, waves,
+ * tiles and workgroups in ascending order) - the same bits on every run.  y is read once for all candidates.  Two launches (the
+ * pairs; the slots).  MRISR_E_ARG: null or misaligned pointer, count outside 1..13, stride not 1, 2 or 4, slices outside 1..256
+ * or not the extent along the slice axis, slice_axis outside 0..2, T outside 1..16, a profile sample that is not finite;
+ * MRISR_E_SHAPE: an extent below 1 or more than 2^31 - 1 voxels on either grid.                                                  */
+int mrisr_f32_volume_slice_cost(const float* x, int X, int Y, int Z, const float* y, int SX, int SY, int SZ, const double* candidates,
+                                int slices, int count, int slice_axis, const double* offsets, const float* weights, int T, int stride,
+                                void* workspace, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,11 @@ class StackView(C.Structure):
                 ("m", C.c_double * 12)]
 
 
+class StackSlicesView(C.Structure):
+    _fields_ = [("data", _fp), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("slice_axis", C.c_int32),
+                ("from_output", _dp), ("slices", C.c_int32), ("reserved_", C.c_int32)]
+
+
 # every symbol include/mrisr.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "mrisr_last_error": (C.c_char_p, []),
@@ -217,10 +222,16 @@ SIGNATURES = {
     "mrisr_f32_volume_stack_update": (_i, [_fp, _i, _i, _i, C.POINTER(StackView), _i, _f, _i, _f, _fp, _vp, _vp, _vp, _vp]),
     "mrisr_f32_volume_stack_update_reg": (_i, [_fp, _i, _i, _i, C.POINTER(StackView), _i, _f, _i, _f, _f, _f, C.POINTER(C.c_float), _vp,
                                                _fp, _vp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_stack_residual_slices": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, _dp, _i, _i, C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_float), _i, _fp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_stack_update_slices": (_i, [_fp, _i, _i, _i, C.POINTER(StackSlicesView), _i, _f, _i, _f, _fp, _vp, _vp, _vp, _vp]),
+    "mrisr_f32_volume_slice_cost_workspace_bytes": (_sz, [_i, _i]),
+    "mrisr_f32_volume_slice_cost": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, _dp, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_float),
+                                         _i, _i, _vp, _dp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 329   # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 330   # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

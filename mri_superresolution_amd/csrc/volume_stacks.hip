@@ -23,19 +23,13 @@
 //                               elements per voxel, 16.6 KB with the flags) and, per staged voxel, whether it lies in the grid and
 //                               a stack covers it, are staged in LDS once.  The gathers are those of the plain kernel.
 //
+// The brick walk, the coordinate, the gather and the matrix check are those of volume_stacks.h, shared with csrc/volume_slices.hip.
 // The first two kernels walk the 2 x 2 x 64 bricks of the reslice and warp kernels, z fastest.  Nothing is uploaded and nothing
 // synchronises (HIP-graph capturable); no floating-point atomics: the same bits on every run.
-#include "volume_deform.h"
-#include "volume_taps.h"
-
-constexpr int kMaxStacks = MRISR_STACKS_MAX, kMaxSamples = MRISR_STACK_SAMPLES_MAX;
+#include "volume_stacks.h"
 
 struct StackMatrix {
     double m[3][4];
-};
-struct StackProfile {
-    double offset[kMaxSamples];
-    float weight[kMaxSamples];
 };
 struct StackViews {
     const float* data[kMaxStacks];
@@ -43,48 +37,6 @@ struct StackViews {
     int nslots[kMaxStacks];
     double m[kMaxStacks][3][4];
 };
-
-// voxel of thread tid in brick b (bricks numbered along z, then y, then x)
-__device__ __forceinline__ bool stack_brick_voxel(unsigned b, unsigned nby, unsigned nbz, int X, int Y, int Z, int& i, int& j, int& k) {
-    const unsigned bz = b % nbz, rest = b / nbz, by = rest % nby, bx = rest / nby;
-    const int tid = threadIdx.x;
-    k = (int)bz * kBZ + tid % kBZ, j = (int)by * kBY + tid / kBZ % kBY, i = (int)bx * kBX + tid / (kBZ * kBY);
-    return i < X && j < Y && k < Z;
-}
-
-// the linear gather of src (X, Y, Z) at p, inside [-0.5, n - 0.5] on every axis: the taps reduced along z, then y, then x
-__device__ __forceinline__ float linear_gather(const float* __restrict__ src, int X, int Y, int Z, const double* p) {
-    int ix[2], iy[2], iz[2];
-    float wx[2], wy[2], wz[2];
-    axis_taps<kLinear>(p[0], X, ix, wx);
-    axis_taps<kLinear>(p[1], Y, iy, wy);
-    axis_taps<kLinear>(p[2], Z, iz, wz);
-    float rx[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        float ry[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const float* row = src + ((size_t)ix[a] * Y + iy[b]) * Z;
-            const float v[2] = {row[iz[0]], row[iz[1]]};
-            ry[b] = weighted_sum<2>(wz, v);
-        }
-        rx[a] = weighted_sum<2>(wy, ry);
-    }
-    return weighted_sum<2>(wx, rx);
-}
-
-// p = m q and the inside test of a volume of extents n
-__device__ __forceinline__ bool stack_coordinate(const double (*m)[4], double q0, double q1, double q2, int n0, int n1, int n2, double* p) {
-    const int n[3] = {n0, n1, n2};
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        p[a] = grid_coordinate(m[a], q0, q1, q2);
-        inside = inside && p[a] >= -0.5 && p[a] <= (double)n[a] - 0.5;      // NaN compares false
-    }
-    return inside;
-}
 
 // at most kSlots workgroups walk the bricks of the STACK with a stride of the grid
 __global__ __launch_bounds__(256) void stack_residual_kernel(const float* __restrict__ x, int X, int Y, int Z, const float* __restrict__ y,
@@ -223,14 +175,6 @@ __global__ __launch_bounds__(256) void stack_update_reg_kernel(const float* __re
         out[idx] = xv;
         if (cover) cover[idx] = (unsigned char)cnt;
     }
-}
-
-static int check_matrix(const char* name, const double* m12, double (*m)[4]) {
-    for (int e = 0; e < 12; ++e) {
-        if (!isfinite(m12[e])) MRISR_FAIL(MRISR_E_ARG, "%s: matrix entry [%d][%d] is not finite", name, e / 4, e % 4);
-        m[e / 4][e % 4] = m12[e];
-    }
-    return MRISR_OK;
 }
 
 extern "C" size_t mrisr_f32_volume_stack_workspace_bytes(int K) {

@@ -38,8 +38,21 @@ Speed on an MI355X (``tools/stacks_bench.py --regularise``, 2026-10-20, 256^3 ou
 an iteration - 0.071 ms a residual launch, 0.19 ms the update - against 9.7 ms with torch's ``affine_grid`` + ``grid_sample``;
 regularised 0.50 ms an iteration, 0.23 ms the update launch (1.23 times the plain one), against 10.1 ms with torch.
 
-Not built: a 26-neighbour or true total-variation prior; an automatic choice of lambda; slice-to-volume motion correction within a
-stack; an exact adjoint (scatter) back-projection; intensity or bias matching between stacks inside the loop; more than 8 stacks.
+Slice-to-volume motion correction (``motion=MotionOptions(...)`` of ``combine_stacks_np`` / ``combine_stacks``; default off): a 2-D
+multi-slice stack is acquired slice by slice and the head moves in between, so every slice gets a rigid pose of its own.
+``slice_geometries``   the two matrices of ``stack_geometry`` per slice, from (S, 6) poses about the slices' centres (S <= 256).
+``stack_residual_slices_np``, ``simulate_stack_slices_np``, ``stack_update_slices_np``   the two projections with a matrix per slice; the
+                      update weights the slices near a voxel by ``1 - |z - s|``, leaves gaps uncovered and normalises overlaps.
+``slice_cost_np``, ``ncc_from_sums``, ``slice_compass_search``, ``register_slices_np``   the cost of up to 13 candidate poses of every
+                      slice (six float64 sums each), its NCC, and the compass search of ``volume_register`` for all slices at once.
+``stack_residual_slices``, ``stack_update_slices``, ``slice_cost``, ``register_slices``   the device path (``csrc/volume_slices.hip``): the
+                      projections bit for bit; the sums within 1e-12 and the same bits on every run; one device-to-host read per
+                      search iteration.  Measured quality and speed: README, DESIGN.md section 7.
+
+Not built: a 26-neighbour or true total-variation prior; an automatic choice of lambda; the regulariser together with per-slice
+poses (``NotImplementedError``); leave-one-stack-out targets for the slice registration (the estimate includes the stack itself);
+interleaved acquisition order; outlier slice rejection; motion smoothness over time; an exact adjoint (scatter) back-projection;
+intensity or bias matching between stacks inside the loop; more than 8 stacks.
 """
 from __future__ import annotations
 
@@ -56,6 +69,9 @@ from .volume_reslice import taps_np, weighted_sum_np
 
 MAX_STACKS = 8
 MAX_SAMPLES = 16
+MAX_SLICES = 256                 # per-slice poses: the slices of one stack
+MAX_CANDIDATES = 13              # poses of a slice scored in one launch: a point and its 12 compass neighbours
+COST_STRIDES = (1, 2, 4)
 PROFILES = ("box", "gaussian")
 DEFAULT_ITERATIONS = 8
 FWHM_PER_SIGMA = 2.0 * math.sqrt(2.0 * math.log(2.0))
@@ -75,6 +91,9 @@ class StackResult(NamedTuple):
     rms: np.ndarray              # (iterations, K) float64: the RMS of stack k's residual against the estimate BEFORE the iteration's update
     counts: np.ndarray           # (iterations, K) int64: the voxels of stack k that entered it (weight sum >= 0.5)
     coverage: np.ndarray         # (K + 1,) int64: the output voxels covered by 0, 1, ..., K stacks
+    motion: object = None        # with motion: per stack the (S, 6) float64 poses of its slices (tx, ty, tz mm, rx, ry, rz degrees)
+    motion_cost: object = None   # with motion: (rounds, K, 2) float64, the mean NCC of the active slices at a round's start and end
+    motion_detail: object = None # with motion: per stack the last round's SliceMotion (active flags, per-slice costs)
 
 
 # ---------------------------------------------------------------- host side: profiles and grids
@@ -279,10 +298,24 @@ def _index_axes(shape):
     return [np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)]) for a, n in enumerate(shape)]
 
 
-def _gather_np(v, m, q, shape):
+def _matrix_rows(m):
+    """The entries of a (3, 4) matrix as ``rows[a][c]``; ``_table_rows`` gives arrays in their place: one matrix per grid point."""
+    return [[m[a, c] for c in range(4)] for a in range(3)]
+
+
+def _table_rows(table, shape):
+    """``rows[a][c]`` of a table of matrices ``(..., 3, 4)`` whose leading axes are reshaped to ``shape`` (to broadcast on a grid)."""
+    return [[table[..., a, c].reshape(shape) for c in range(4)] for a in range(3)]
+
+
+def _coordinate_np(row, q):
+    return ((row[0] * q[0] + row[1] * q[1]) + row[2] * q[2]) + row[3]
+
+
+def _gather_rows_np(v, rows, q, shape):
     """-> ``(values at the inside points, inside)``: ``p_a = ((m[a,0] q0 + m[a,1] q1) + m[a,2] q2) + m[a,3]`` in float64, the
     inside test and the linear gather of ``reslice_np`` (taps clamped, reduction along z, then y, then x)."""
-    p = [np.broadcast_to(((m[a, 0] * q[0] + m[a, 1] * q[1]) + m[a, 2] * q[2]) + m[a, 3], shape) for a in range(3)]
+    p = [np.broadcast_to(_coordinate_np(rows[a], q), shape) for a in range(3)]
     inside = np.ones(shape, dtype=bool)
     for a in range(3):
         inside &= (p[a] >= -0.5) & (p[a] <= v.shape[a] - 0.5)
@@ -296,19 +329,27 @@ def _gather_np(v, m, q, shape):
     return weighted_sum_np(wx, rx), inside
 
 
-def _project_np(x, g, shape):
-    """-> ``(acc, wsum)`` of ``stack_residual_np`` on a stack of ``shape``."""
-    q0 = _index_axes(shape)
+def _gather_np(v, m, q, shape):
+    return _gather_rows_np(v, _matrix_rows(m), q, shape)
+
+
+def _project_rows_np(x, g, rows, q0, shape):
+    """-> ``(acc, wsum)`` of ``stack_residual_np`` on the grid points ``q0`` (three broadcastable index arrays) of ``shape``."""
     acc, wsum = np.zeros(shape, dtype=np.float32), np.zeros(shape, dtype=np.float32)
     with np.errstate(all="ignore"):
         for o, w in zip(g.offsets, g.weights):
             q = list(q0)
             q[g.slice_axis] = q0[g.slice_axis] + o
-            val, inside = _gather_np(x, g.to_output, q, shape)
+            val, inside = _gather_rows_np(x, rows, q, shape)
             if val.size:
                 acc[inside] = acc[inside] + w * val
                 wsum[inside] = wsum[inside] + w
     return acc, wsum
+
+
+def _project_np(x, g, shape):
+    """-> ``(acc, wsum)`` of ``stack_residual_np`` on a stack of ``shape``."""
+    return _project_rows_np(x, g, _matrix_rows(g.to_output), _index_axes(shape), shape)
 
 
 def simulate_stack_np(x, geometry: StackGeometry, stack_shape, fill: float = 0.0) -> np.ndarray:
@@ -393,21 +434,401 @@ def _rms_table(sums, counts):
         return np.where(counts > 0, np.sqrt(sums / np.maximum(counts, 1)), 0.0)
 
 
-def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_ITERATIONS, step: float = 1.0, clamp=0.0, fill: float = 0.0,
-                      on_iteration=None, reg_lambda: float = 0.0, reg_delta: float = math.inf, reg_coeffs=None) -> StackResult:
-    """The specification of ``combine_stacks``.  The initial estimate is ``stack_update_np`` of a volume of ``fill`` with ``step = 1``
-    and the stacks themselves in place of the residuals: the mean, over the stacks that cover a voxel, of their linear reslices; a
-    voxel no stack covers is ``fill`` to the end.  Then ``iterations`` times: ``r_k = stack_residual_np(x, y_k, g_k)`` for every
-    stack, ``x = stack_update_np(x, r, g, step, clamp)``.  ``on_iteration(it, x)`` is called with the initial estimate (``it = 0``)
-    and after every update.  ``reg_lambda``, ``reg_delta``, ``reg_coeffs``: the regulariser of ``stack_update_np``, in the updates of
-    the iterations alone - the initial estimate is never regularised."""
-    stacks, geometries = [_check_volume_np(y, "combine_stacks_np") for y in stacks], list(geometries)
-    _check_stack_count(len(stacks), "combine_stacks_np")
-    if len(geometries) != len(stacks):
-        raise ValueError(f"combine_stacks_np: {len(stacks)} stacks and {len(geometries)} geometries")
-    shape_out, iterations = check_shape(shape_out, "shape_out"), _check_iterations(iterations)
-    _check_regulariser(_check_step(step), reg_lambda, reg_delta, reg_coeffs)
-    x, cnt = stack_update_np(np.full(shape_out, np.float32(fill), dtype=np.float32), stacks, geometries, 1.0, clamp)
+# ---------------------------------------------------------------- slice-to-volume motion: geometry and specification
+
+def _in_plane(axis):
+    return tuple(a for a in range(3) if a != axis)
+
+
+def _check_table(table, slices, what) -> np.ndarray:
+    t = np.asarray(table, dtype=np.float64)
+    if t.shape != (slices, 3, 4) or not np.isfinite(t).all():
+        raise ValueError(f"{what}: the per-slice matrices must be ({slices}, 3, 4) and finite, got shape {t.shape}")
+    return np.ascontiguousarray(t)
+
+
+def _check_slice_count(slices, what) -> int:
+    if not 1 <= slices <= MAX_SLICES:
+        raise ValueError(f"{what}: per-slice poses take stacks of 1..{MAX_SLICES} slices, got {slices}")
+    return int(slices)
+
+
+def slice_centres(affine, stack_shape, slice_axis) -> np.ndarray:
+    """(S, 3) float64: the world position of the centre of every slice - index ``(n - 1) / 2`` in the plane, ``s`` along the axis."""
+    a, shape = check_affine(affine, "affine"), check_shape(stack_shape, "stack_shape")
+    idx = np.tile((np.asarray(shape, dtype=np.float64) - 1.0) / 2.0, (shape[slice_axis], 1))
+    idx[:, slice_axis] = np.arange(shape[slice_axis], dtype=np.float64)
+    return idx @ a[:3, :3].T + a[:3, 3]
+
+
+def slice_geometries(affine, affine_out, stack_shape, slice_axis, params, world=None):
+    """-> ``(to_output, from_output)``, both (S, 3, 4) float64: ``stack_geometry``'s two matrices with a rigid pose per slice.
+    ``params`` (S, 6): ``(tx, ty, tz, rx, ry, rz)`` of slice ``s`` in mm and degrees; ``W_s = volume_register.rigid_world(params[s],
+    centre_s)`` about the world position of the slice's centre is folded as ``stack_geometry`` folds ``world``:
+    ``out_s = W_s @ world @ affine_out``, ``M_s = grid_matrix(out_s, affine)``, ``N_s = grid_matrix(affine, out_s)``.  ``params = 0``
+    gives the stack's own matrices to the last bit, S times.  More than 256 slices: ``ValueError``."""
+    from .volume_register import rigid_world
+    a, out = check_affine(affine, "affine"), check_affine(affine_out, "affine_out")
+    shape = check_shape(stack_shape, "stack_shape")
+    if isinstance(slice_axis, bool) or not isinstance(slice_axis, (int, np.integer)) or not 0 <= slice_axis <= 2:
+        raise ValueError(f"the slice axis is 0, 1 or 2, got {slice_axis!r}")
+    S = _check_slice_count(shape[slice_axis], "slice_geometries")
+    params = np.asarray(params, dtype=np.float64)
+    if params.shape != (S, 6) or not np.isfinite(params).all():
+        raise ValueError(f"slice_geometries: the parameters are ({S}, 6) and finite, got shape {params.shape}")
+    if world is not None:
+        out = check_affine(world, "world") @ out
+    centres = slice_centres(a, shape, int(slice_axis))
+    to_output, from_output = np.empty((S, 3, 4)), np.empty((S, 3, 4))
+    for s in range(S):
+        out_s = rigid_world(params[s], centres[s]) @ out
+        to_output[s], from_output[s] = grid_matrix(out_s, a), grid_matrix(a, out_s)
+    return to_output, from_output
+
+
+def _project_slices_np(x, g, shape, to_output_s):
+    grid = [1, 1, 1]
+    grid[g.slice_axis] = shape[g.slice_axis]
+    return _project_rows_np(x, g, _table_rows(to_output_s, grid), _index_axes(shape), shape)
+
+
+def simulate_stack_slices_np(x, geometry: StackGeometry, stack_shape, to_output_s, fill: float = 0.0) -> np.ndarray:
+    """``simulate_stack_np`` with the voxels of slice ``s`` going through ``to_output_s[s]`` (S, 3, 4) in place of ``M``."""
+    x, g = _check_volume_np(x, "simulate_stack_slices_np"), _check_geometry(geometry, "simulate_stack_slices_np")
+    shape = check_shape(stack_shape, "stack_shape")
+    table = _check_table(to_output_s, _check_slice_count(shape[g.slice_axis], "simulate_stack_slices_np"), "simulate_stack_slices_np")
+    acc, wsum = _project_slices_np(x, g, shape, table)
+    ok = wsum >= np.float32(0.5)
+    out = np.full(shape, np.float32(fill), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        out[ok] = acc[ok] / wsum[ok]
+    return out
+
+
+def stack_residual_slices_np(x, y, geometry: StackGeometry, to_output_s):
+    """``stack_residual_np`` -> ``(r, (S, n))`` with the voxels of slice ``s`` using ``to_output_s[s]`` (S, 3, 4) in place of ``M``:
+    the same operations voxel by voxel, so equal tables reproduce ``stack_residual_np`` bit for bit."""
+    x, y = _check_volume_np(x, "stack_residual_slices_np"), _check_volume_np(y, "stack_residual_slices_np")
+    g = _check_geometry(geometry, "stack_residual_slices_np")
+    table = _check_table(to_output_s, _check_slice_count(y.shape[g.slice_axis], "stack_residual_slices_np"), "stack_residual_slices_np")
+    acc, wsum = _project_slices_np(x, g, y.shape, table)
+    ok = wsum >= np.float32(0.5)
+    r = np.zeros(y.shape, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        r[ok] = y[ok] - acc[ok] / wsum[ok]
+    r64 = r[ok].astype(np.float64)
+    return r, (math.fsum(r64 * r64), int(ok.sum()))
+
+
+def _not_built_with_motion(reg_lambda, what):
+    if float(reg_lambda) != 0.0:
+        raise NotImplementedError(f"{what}: the regulariser (reg_lambda > 0) together with per-slice poses is not built")
+
+
+def stack_update_slices_np(x, residuals, geometries, from_output_s, step: float = 1.0, clamp=0.0, reg_lambda: float = 0.0):
+    """-> ``(x', cnt)``: ``stack_update_np`` with a pose per slice.  ``from_output_s[k]`` (S_k, 3, 4): ``N_{k,s}``.  For every output
+    voxel ``q`` and stack ``k`` ascending, from ``acc = +0``, ``wk = +0`` (float32) and for ``s = 0 .. S_k - 1`` ascending:
+    ``p = N_{k,s} q`` (the coordinate rule of ``stack_residual_np``); ``z = p[slice_axis]``, ``d = |z - s|`` in float64; the slice is
+    skipped unless ``d < 1`` and both in-plane coordinates lie in ``[-0.5, n - 0.5]``; else ``w = float32(1 - d)`` (the difference in
+    float64), ``g`` = the bilinear gather of slice ``s`` of the residual at the two in-plane coordinates (``taps_np(..., "linear")``,
+    ``weighted_sum_np``, the higher in-plane axis reduced first), ``acc = acc + w g``, ``wk = wk + w``.  The stack covers the voxel
+    when ``wk >= 0.5``: ``sum = sum + acc / wk``, ``cnt += 1``.  The step, the clamp and the uncovered voxels: ``stack_update_np``.
+
+    With equal matrices this is ``stack_update_np`` up to rounding: ``wk`` sums to 1 between two slices, the border slice alone is
+    replicated, and ``wk < 0.5`` is the inside test along the slice axis.  With motion, gaps between slices stay uncovered and
+    overlapping slices are normalised.  ``reg_lambda > 0`` is not built here: ``NotImplementedError``."""
+    _not_built_with_motion(reg_lambda, "stack_update_slices_np")
+    x = _check_volume_np(x, "stack_update_slices_np")
+    residuals, geometries, tables = list(residuals), list(geometries), list(from_output_s)
+    _check_stack_count(len(residuals), "stack_update_slices_np")
+    if len(geometries) != len(residuals) or len(tables) != len(residuals):
+        raise ValueError(f"stack_update_slices_np: {len(residuals)} stacks, {len(geometries)} geometries and {len(tables)} tables")
+    step, lo = _check_step(step), _check_clamp(clamp)
+    q = _index_axes(x.shape)
+    total, cnt = np.zeros(x.shape, dtype=np.float32), np.zeros(x.shape, dtype=np.uint8)
+    with np.errstate(all="ignore"):
+        for k, (r, g, table) in enumerate(zip(residuals, geometries, tables)):
+            what = f"stack_update_slices_np: stack {k}"
+            r, g = _check_volume_np(r, what), _check_geometry(g, what)
+            axis, (a, b) = g.slice_axis, _in_plane(g.slice_axis)
+            table = _check_table(table, _check_slice_count(r.shape[axis], what), what)
+            acc, wk = np.zeros(x.shape, dtype=np.float32), np.zeros(x.shape, dtype=np.float32)
+            for s in range(r.shape[axis]):
+                rows = _matrix_rows(table[s])
+                d = np.abs(np.broadcast_to(_coordinate_np(rows[axis], q), x.shape) - float(s))
+                ok = d < 1.0
+                if not ok.any():
+                    continue
+                pa, pb = (np.broadcast_to(_coordinate_np(rows[c], q), x.shape) for c in (a, b))
+                ok = ok & (pa >= -0.5) & (pa <= r.shape[a] - 0.5) & (pb >= -0.5) & (pb <= r.shape[b] - 0.5)
+                if not ok.any():
+                    continue
+                w = (1.0 - d[ok]).astype(np.float32)
+                (ia, wa), (ib, wb) = taps_np(pa[ok], r.shape[a], "linear"), taps_np(pb[ok], r.shape[b], "linear")
+                plane = np.take(r, s, axis=axis)
+                val = weighted_sum_np(wa, [weighted_sum_np(wb, [plane[u, v] for v in ib]) for u in ia])
+                acc[ok] = acc[ok] + w * val
+                wk[ok] = wk[ok] + w
+            hit = wk >= np.float32(0.5)
+            total[hit] = total[hit] + acc[hit] / wk[hit]
+            cnt[hit] += 1
+        out = x.copy()
+        hit = cnt > 0
+        new = x[hit] + step * (total[hit] / cnt[hit].astype(np.float32))
+        if lo is not None:
+            new = np.where(new < lo, lo, new)
+        out[hit] = new
+    return out, cnt
+
+
+def _check_cost_args(shape, axis, cand_to_output, stride, what):
+    S = _check_slice_count(shape[axis], what)
+    cand = np.asarray(cand_to_output, dtype=np.float64)
+    if cand.ndim != 4 or cand.shape[0] != S or not 1 <= cand.shape[1] <= MAX_CANDIDATES or cand.shape[2:] != (3, 4) \
+            or not np.isfinite(cand).all():
+        raise ValueError(f"{what}: the candidates are ({S}, 1..{MAX_CANDIDATES}, 3, 4) and finite, got shape {cand.shape}")
+    if stride not in COST_STRIDES:
+        raise ValueError(f"{what}: stride must be one of {COST_STRIDES}, got {stride!r}")
+    return np.ascontiguousarray(cand), int(stride)
+
+
+def strided_slice_count(shape, slice_axis, stride) -> int:
+    """The voxels of one slice whose two in-plane indices are multiples of ``stride``."""
+    a, b = _in_plane(slice_axis)
+    return -(-int(shape[a]) // stride) * -(-int(shape[b]) // stride)
+
+
+def slice_cost_np(x, y, geometry: StackGeometry, cand_to_output, stride: int = 1) -> np.ndarray:
+    """-> (S, C, 6) float64.  For slice ``s`` and candidate ``c`` (``C <= 13``): over the voxels of the slice whose two in-plane indices
+    are multiples of ``stride`` (1, 2 or 4), simulated as ``m = acc / wsum`` through ``cand_to_output[s, c]`` with the profile
+    (``stack_residual_np``'s forward model) and kept where ``wsum >= 0.5``: ``n, sum y, sum m, sum y^2, sum m^2, sum y m`` - the
+    products formed in float64 (exact), the sums correctly rounded (``math.fsum``)."""
+    x, y = _check_volume_np(x, "slice_cost_np"), _check_volume_np(y, "slice_cost_np")
+    g = _check_geometry(geometry, "slice_cost_np")
+    cand, stride = _check_cost_args(y.shape, g.slice_axis, cand_to_output, stride, "slice_cost_np")
+    S, C = cand.shape[:2]
+    a, b = _in_plane(g.slice_axis)
+    ia, ib = np.arange(0, y.shape[a], stride), np.arange(0, y.shape[b], stride)
+    shape = (S, C, ia.size, ib.size)
+    q = [None, None, None]
+    q[g.slice_axis] = np.arange(S, dtype=np.float64).reshape(S, 1, 1, 1)
+    q[a], q[b] = ia.astype(np.float64).reshape(1, 1, -1, 1), ib.astype(np.float64).reshape(1, 1, 1, -1)
+    acc, wsum = _project_rows_np(x, g, _table_rows(cand, (S, C, 1, 1)), q, shape)
+    ok = wsum >= np.float32(0.5)
+    with np.errstate(all="ignore"):
+        m = np.where(ok, acc / np.where(ok, wsum, np.float32(1)), np.float32(0)).astype(np.float64)
+    ys = np.moveaxis(y, g.slice_axis, 0)[:, ::stride, ::stride].astype(np.float64)      # (S, rows, cols), the lower in-plane axis first
+    out = np.zeros((S, C, 6))
+    for s in range(S):
+        for c in range(C):
+            keep = ok[s, c]
+            yv, mv = ys[s][keep], m[s, c][keep]
+            out[s, c] = (yv.size, math.fsum(yv), math.fsum(mv), math.fsum(yv * yv), math.fsum(mv * mv), math.fsum(yv * mv))
+    return out
+
+
+def ncc_from_sums(sums, min_count=1) -> np.ndarray:
+    """The normalised cross-correlation of ``y`` and ``m`` from ``(..., 6)`` sums ``n, sum y, sum m, sum y^2, sum m^2, sum y m``, in
+    float64: ``cov / sqrt(var_y var_m)`` with ``var_y = sum y^2 - (sum y)^2 / n`` and so on; ``-inf`` where ``n < min_count`` (an
+    array broadcasts), ``n < 1`` or a variance is not positive.  The specification path and the device path share it."""
+    sums = np.asarray(sums, dtype=np.float64)
+    n, sy, sm, syy, smm, sym = (sums[..., e] for e in range(6))
+    with np.errstate(all="ignore"):
+        nn = np.maximum(n, 1.0)
+        vy, vm, cov = syy - sy * sy / nn, smm - sm * sm / nn, sym - sy * sm / nn
+        ok = (n >= min_count) & (n >= 1) & (vy > 0) & (vm > 0)
+        return np.where(ok, cov / np.sqrt(np.where(ok, vy * vm, 1.0)), -np.inf)
+
+
+def slice_compass_search(cost_batch, p0, levels, limits, active=None, max_iterations=1000):
+    """``volume_register.compass_search`` for all the slices of a stack at once -> ``(params (S, 6), best (S,), start (S,), trace)``.
+    Every slice has its own point, step vector and best value; ONE ``cost_batch(cands (S, C, 6), stride) -> (S, C)`` call per
+    iteration covers them all.  A level is ``(stride, step[6], min_translation_step)``.  At each level every slice's point is scored
+    (``C = 1``; ``start`` is that of the first level); then, while a live slice is left, the 12 candidates ``p +- step[a] e_a`` of
+    every slice - axis ascending, ``+`` before ``-`` - are scored in one call; a candidate beyond ``limits = (mm, deg)`` in any
+    component scores ``-inf``; a slice moves to its first argmax only if that is strictly greater than its best, otherwise its six
+    steps halve.  A slice is live while it is active and its translation step is at least the level's stop; the others resubmit
+    their point 12 times and ignore the values.  Inactive slices (``active`` (S,) bool, None: all active) keep ``p0``.  ``trace``:
+    one dict per call - ``level``, ``stride``, ``kind``, ``p``, ``step``, ``values``, ``accepted`` (per slice, -1: none), ``best``."""
+    p = np.array(p0, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6 or not np.isfinite(p).all():
+        raise ValueError(f"slice_compass_search: the start is (S, 6) and finite, got shape {p.shape}")
+    S = p.shape[0]
+    active = np.ones(S, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(S).copy()
+    lim = np.array([float(limits[0])] * 3 + [float(limits[1])] * 3)
+    if not (lim > 0).all():
+        raise ValueError(f"slice_compass_search: the limits are two positive numbers (mm, degrees), got {limits!r}")
+    best, start, trace, rows = np.full(S, -np.inf), None, [], np.arange(S)
+    for li, (stride, step0, min_t) in enumerate(levels):
+        step0 = np.asarray(step0, dtype=np.float64)
+        if step0.shape != (6,) or not (step0 > 0).all() or not np.isfinite(step0).all() or not min_t > 0:
+            raise ValueError(f"level {li}: six positive steps and a positive stop, got {step0.tolist()} and {min_t}")
+        step = np.tile(step0, (S, 1))
+        best = np.asarray(cost_batch(p[:, None, :].copy(), stride), dtype=np.float64).reshape(S).copy()
+        start = best.copy() if start is None else start
+        trace.append({"level": li, "stride": stride, "kind": "start", "p": p.copy(), "step": step.copy(), "values": best[:, None].copy(),
+                      "accepted": np.full(S, -1), "best": best.copy()})
+        for _ in range(max_iterations):
+            live = active & (step[:, 0] >= min_t)
+            if not live.any():
+                break
+            cands = np.repeat(p[:, None, :], 12, axis=1)
+            for a in range(6):
+                cands[live, 2 * a, a] += step[live, a]
+                cands[live, 2 * a + 1, a] -= step[live, a]
+            vals = np.asarray(cost_batch(cands.copy(), stride), dtype=np.float64).reshape(S, 12)
+            vals = np.where((np.abs(cands) > lim).any(axis=2), -np.inf, vals)
+            j = np.argmax(vals, axis=1)                                   # the first of equal maxima
+            move = live & (vals[rows, j] > best)
+            entry = {"level": li, "stride": stride, "kind": "probe", "p": p.copy(), "step": step.copy(), "values": vals,
+                     "accepted": np.where(move, j, -1)}
+            p[move], best[move] = cands[move, j[move]], vals[move, j[move]]
+            step[live & ~move] /= 2
+            entry["best"] = best.copy()
+            trace.append(entry)
+    return p, best, start, trace
+
+
+def in_plane_voxel_size(affine, slice_axis) -> float:
+    """The mean of the two in-plane voxel sizes of a stack, in mm."""
+    return float(np.mean(voxel_sizes(affine)[list(_in_plane(slice_axis))]))
+
+
+def default_slice_levels(affine, slice_axis):
+    """``[(2, 2v x 3 + 2 deg x 3, v / 2), (1, v / 2 x 3 + 0.5 deg x 3, v / 8)]`` with ``v = in_plane_voxel_size``."""
+    v = in_plane_voxel_size(affine, slice_axis)
+    return [(2, (2 * v,) * 3 + (2.0,) * 3, 0.5 * v), (1, (0.5 * v,) * 3 + (0.5,) * 3, v / 8)]
+
+
+def active_slices(sums, min_contrast) -> np.ndarray:
+    """(S,) bool from the (S, 6) sums of the slices' current poses: a slice is active when the standard deviation of its ``y`` is at
+    least ``min_contrast`` times that of the pooled stack (air and the crown of the head fall below) and positive."""
+    sums = np.asarray(sums, dtype=np.float64)
+    n, sy, syy = sums[:, 0], sums[:, 1], sums[:, 3]
+    with np.errstate(all="ignore"):
+        sd = np.sqrt(np.maximum(syy - sy * sy / np.maximum(n, 1.0), 0.0) / np.maximum(n, 1.0))
+        N, SY, SYY = n.sum(), sy.sum(), syy.sum()
+        pooled = math.sqrt(max(SYY - SY * SY / max(N, 1.0), 0.0) / max(N, 1.0))
+    return (n > 0) & (sd > 0) & (sd >= float(min_contrast) * pooled)
+
+
+def slice_corner_displacement(params_a, params_b, affine, stack_shape, slice_axis) -> np.ndarray:
+    """(S,) float64: per slice, the largest distance in mm, over the four corner voxels of the slice, between their positions under
+    the poses ``params_a[s]`` and ``params_b[s]`` (``rigid_world`` about the slice's centre)."""
+    from .volume_register import rigid_world
+    a, shape = check_affine(affine, "affine"), check_shape(stack_shape, "stack_shape")
+    centres = slice_centres(a, shape, slice_axis)
+    pa, pb = np.asarray(params_a, dtype=np.float64), np.asarray(params_b, dtype=np.float64)
+    u, v = _in_plane(slice_axis)
+    out = np.zeros(shape[slice_axis])
+    for s in range(shape[slice_axis]):
+        idx = np.zeros((4, 4))
+        idx[:, 3], idx[:, slice_axis] = 1.0, s
+        idx[:, u], idx[:, v] = [0, 0, shape[u] - 1, shape[u] - 1], [0, shape[v] - 1, 0, shape[v] - 1]
+        world = a @ idx.T
+        d = ((rigid_world(pa[s], centres[s]) - rigid_world(pb[s], centres[s])) @ world)[:3]
+        out[s] = np.sqrt((d * d).sum(axis=0)).max()
+    return out
+
+
+class MotionOptions(NamedTuple):
+    """What ``combine_stacks(_np)(..., motion=...)`` needs to move single slices: the grids - the geometries alone do not say where a
+    slice's centre lies in the world - and the search's settings."""
+    affines: tuple                   # per stack: index -> world (4, 4)
+    affine_out: np.ndarray           # the output grid's index -> world
+    worlds: tuple = None             # per stack: None or the (4, 4) ``world`` folded into its geometry
+    rounds: int = 2
+    limit_mm: float = 10.0
+    limit_deg: float = 10.0
+    min_contrast: float = 0.1
+    levels: tuple = None             # per stack: the search levels; None: ``default_slice_levels``
+
+
+class SliceMotion(NamedTuple):
+    params: np.ndarray               # (S, 6) float64: tx, ty, tz (mm), rx, ry, rz (degrees) per slice
+    active: np.ndarray               # (S,) bool: the slices that were searched
+    start: np.ndarray                # (S,) float64: the cost (NCC) at the start, at the first level's stride
+    end: np.ndarray                  # (S,) float64: the cost after the search, at the last level's stride
+    trace: list
+
+
+def _check_motion(motion, count, what) -> MotionOptions:
+    if not isinstance(motion, MotionOptions):
+        raise ValueError(f"{what}: motion is a MotionOptions, got {type(motion).__name__}")
+    affines = tuple(check_affine(a, "affine") for a in motion.affines)
+    worlds = (None,) * count if motion.worlds is None else tuple(motion.worlds)
+    levels = (None,) * count if motion.levels is None else tuple(motion.levels)
+    if len(affines) != count or len(worlds) != count or len(levels) != count:
+        raise ValueError(f"{what}: motion needs one affine (and world, and list of levels) per stack ({count})")
+    if isinstance(motion.rounds, bool) or not isinstance(motion.rounds, (int, np.integer)) or motion.rounds < 0:
+        raise ValueError(f"{what}: motion rounds is an integer that is not negative, got {motion.rounds!r}")
+    if not (motion.limit_mm > 0 and motion.limit_deg > 0 and 0 <= motion.min_contrast < np.inf):
+        raise ValueError(f"{what}: the motion limits must be positive and min_contrast not negative")
+    return motion._replace(affines=affines, affine_out=check_affine(motion.affine_out, "affine_out"), worlds=worlds, levels=levels)
+
+
+def _register_slices(sums_of, shape, axis, affine, affine_out, world, params0, levels, limits, min_contrast) -> SliceMotion:
+    """The search of ``register_slices_np`` / ``register_slices``: ``sums_of(cand_to_output (S, C, 3, 4), stride) -> (S, C, 6)``."""
+    S = _check_slice_count(shape[axis], "register_slices")
+    p0 = np.zeros((S, 6)) if params0 is None else np.array(params0, dtype=np.float64)
+    levels = default_slice_levels(affine, axis) if levels is None else list(levels)
+
+    def sums(cands, stride):
+        tables = [slice_geometries(affine, affine_out, shape, axis, cands[:, c], world)[0] for c in range(cands.shape[1])]
+        return sums_of(np.stack(tables, axis=1), stride)
+
+    active = active_slices(sums(p0[:, None, :], levels[0][0])[:, 0], min_contrast)
+
+    def cost_batch(cands, stride):
+        return ncc_from_sums(sums(cands, stride), 0.25 * strided_slice_count(shape, axis, stride))
+
+    params, best, start, trace = slice_compass_search(cost_batch, p0, levels, limits, active)
+    return SliceMotion(params, active, start, best, trace)
+
+
+def register_slices_np(x, y, geometry: StackGeometry, affine, affine_out, params0=None, world=None, levels=None, limits=(10.0, 10.0),
+                       min_contrast: float = 0.1) -> SliceMotion:
+    """The specification of ``register_slices``: the pose of every slice of the stack ``y`` against the estimate ``x``.  The current
+    poses (``params0``, None: zeros) are scored first (``slice_cost_np`` at the first level's stride); ``active_slices`` of those sums
+    picks the slices to search; ``slice_compass_search`` maximises ``ncc_from_sums(slice_cost_np(...), min_count)`` over the poses,
+    ``min_count`` a quarter of a slice's strided voxel count, the candidates turned into matrices by ``slice_geometries``."""
+    x, y = _check_volume_np(x, "register_slices_np"), _check_volume_np(y, "register_slices_np")
+    g = _check_geometry(geometry, "register_slices_np")
+    return _register_slices(lambda cand, stride: slice_cost_np(x, y, g, cand, stride), y.shape, g.slice_axis, affine, affine_out, world,
+                            params0, levels, limits, min_contrast)
+
+
+def _motion_rounds(motion, stacks_shapes, geometries, register, rebuild):
+    """The rounds of ``combine_stacks(_np)`` with motion.  ``register(k, params_k, levels_k) -> SliceMotion`` against the current
+    estimate; ``rebuild(to_output_s, from_output_s)`` makes the estimate from scratch.  -> ``(params per stack, motion_cost, last)``:
+    ``motion_cost[round][k] = (mean cost of the active slices at the start, at the end)``; ``last``: the final round's SliceMotion."""
+    K = len(geometries)
+    params = [np.zeros((shape[g.slice_axis], 6)) for shape, g in zip(stacks_shapes, geometries)]
+    costs, last = [], [None] * K
+    for _ in range(motion.rounds):
+        row = []
+        for k in range(K):
+            last[k] = register(k, params[k], motion.levels[k])
+            act = last[k].active
+            finite = act & np.isfinite(last[k].start) & np.isfinite(last[k].end)
+            row.append((float(last[k].start[finite].mean()) if finite.any() else float("nan"),
+                        float(last[k].end[finite].mean()) if finite.any() else float("nan")))
+        params = [m.params for m in last]
+        costs.append(row)
+        tables = [slice_geometries(motion.affines[k], motion.affine_out, stacks_shapes[k], geometries[k].slice_axis, params[k], motion.worlds[k])
+                  for k in range(K)]
+        rebuild([t[0] for t in tables], [t[1] for t in tables])
+    return params, np.asarray(costs, dtype=np.float64).reshape(motion.rounds, K, 2), last
+
+
+def _reconstruct_np(stacks, geometries, shape_out, iterations, step, clamp, fill, on_iteration=None, reg=(0.0, math.inf, None), tables=None):
+    """The initial estimate and ``iterations`` updates -> ``(x, initial, sums, counts, cnt)``.  ``tables``: None, or the per-slice
+    ``(to_output_s, from_output_s)`` lists, which select the ``*_slices_np`` forms of both steps."""
+    x0 = np.full(shape_out, np.float32(fill), dtype=np.float32)
+    if tables is None:
+        x, cnt = stack_update_np(x0, stacks, geometries, 1.0, clamp)
+    else:
+        x, cnt = stack_update_slices_np(x0, stacks, geometries, tables[1], 1.0, clamp)
     initial = x.copy()
     if on_iteration is not None:
         on_iteration(0, x)
@@ -415,12 +836,57 @@ def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_I
     for it in range(iterations):
         res = []
         for k, (y, g) in enumerate(zip(stacks, geometries)):
-            r, (sums[it, k], counts[it, k]) = stack_residual_np(x, y, g)
+            r, (sums[it, k], counts[it, k]) = stack_residual_np(x, y, g) if tables is None else stack_residual_slices_np(x, y, g, tables[0][k])
             res.append(r)
-        x = stack_update_np(x, res, geometries, step, clamp, reg_lambda, reg_delta, reg_coeffs)[0]
+        if tables is None:
+            x = stack_update_np(x, res, geometries, step, clamp, *reg)[0]
+        else:
+            x = stack_update_slices_np(x, res, geometries, tables[1], step, clamp)[0]
         if on_iteration is not None:
             on_iteration(it + 1, x)
-    return StackResult(x, initial, _rms_table(sums, counts), counts, np.bincount(cnt.reshape(-1), minlength=len(stacks) + 1).astype(np.int64))
+    return x, initial, sums, counts, cnt
+
+
+def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_ITERATIONS, step: float = 1.0, clamp=0.0, fill: float = 0.0,
+                      on_iteration=None, reg_lambda: float = 0.0, reg_delta: float = math.inf, reg_coeffs=None, motion=None) -> StackResult:
+    """The specification of ``combine_stacks``.  The initial estimate is ``stack_update_np`` of a volume of ``fill`` with ``step = 1``
+    and the stacks themselves in place of the residuals: the mean, over the stacks that cover a voxel, of their linear reslices; a
+    voxel no stack covers is ``fill`` to the end.  Then ``iterations`` times: ``r_k = stack_residual_np(x, y_k, g_k)`` for every
+    stack, ``x = stack_update_np(x, r, g, step, clamp)``.  ``on_iteration(it, x)`` is called with the initial estimate (``it = 0``)
+    and after every update.  ``reg_lambda``, ``reg_delta``, ``reg_coeffs``: the regulariser of ``stack_update_np``, in the updates of
+    the iterations alone - the initial estimate is never regularised.
+
+    ``motion`` (a ``MotionOptions``; None: everything above, the same operations as without the keyword): slice-to-volume motion
+    correction.  The reconstruction above is round 0.  Then ``motion.rounds`` times: (1) every stack's slices are registered to the
+    current estimate (``register_slices_np``, from the poses of the round before; the estimate includes the stack itself -
+    leave-one-out is not built); (2) the estimate is rebuilt from scratch - initial estimate, then ``iterations`` - with
+    ``stack_update_slices_np`` / ``stack_residual_slices_np`` on the new ``slice_geometries``.  ``volume``, ``initial``, ``rms``,
+    ``counts`` and ``coverage`` are the last rebuild's; ``on_iteration`` sees round 0 alone.  With ``reg_lambda > 0``:
+    ``NotImplementedError`` (not built)."""
+    stacks, geometries = [_check_volume_np(y, "combine_stacks_np") for y in stacks], list(geometries)
+    _check_stack_count(len(stacks), "combine_stacks_np")
+    if len(geometries) != len(stacks):
+        raise ValueError(f"combine_stacks_np: {len(stacks)} stacks and {len(geometries)} geometries")
+    shape_out, iterations = check_shape(shape_out, "shape_out"), _check_iterations(iterations)
+    _check_regulariser(_check_step(step), reg_lambda, reg_delta, reg_coeffs)
+    if motion is not None:
+        _not_built_with_motion(reg_lambda, "combine_stacks_np")
+        motion = _check_motion(motion, len(stacks), "combine_stacks_np")
+        geometries = [_check_geometry(g, f"combine_stacks_np: stack {k}") for k, g in enumerate(geometries)]
+    state = list(_reconstruct_np(stacks, geometries, shape_out, iterations, step, clamp, fill, on_iteration, (reg_lambda, reg_delta, reg_coeffs)))
+    extra = ()
+    if motion is not None:
+        def register(k, params, levels):
+            return register_slices_np(state[0], stacks[k], geometries[k], motion.affines[k], motion.affine_out, params, motion.worlds[k],
+                                      levels, (motion.limit_mm, motion.limit_deg), motion.min_contrast)
+
+        def rebuild(to_output_s, from_output_s):
+            state[:] = _reconstruct_np(stacks, geometries, shape_out, iterations, step, clamp, fill, tables=(to_output_s, from_output_s))
+
+        extra = _motion_rounds(motion, [y.shape for y in stacks], geometries, register, rebuild)
+    x, initial, sums, counts, cnt = state
+    return StackResult(x, initial, _rms_table(sums, counts), counts, np.bincount(cnt.reshape(-1), minlength=len(stacks) + 1).astype(np.int64),
+                       *extra)
 
 
 # ---------------------------------------------------------------- device
@@ -524,9 +990,10 @@ class StackWorkspace:
     the estimate, one residual volume per stack, the coverage counts, the fixed slots of the sums (one region per stack) and the
     stats buffer - one (double, int64) row per iteration and stack.  Made before a HIP-graph capture, it serves call after call on
     one stream.  ``regularised``: it also holds a second estimate - the regularised update reads the neighbours of a voxel and cannot
-    run in place, so the iterations alternate between the two."""
+    run in place, so the iterations alternate between the two.  ``motion``: it also holds, per stack, the two tables of per-slice
+    matrices (``MAX_SLICES`` x 12 doubles each) and the buffers of the slice cost (``SliceCostWorkspace``)."""
 
-    def __init__(self, shape_out, stack_shapes, device, iterations: int = DEFAULT_ITERATIONS, regularised: bool = False):
+    def __init__(self, shape_out, stack_shapes, device, iterations: int = DEFAULT_ITERATIONS, regularised: bool = False, motion: bool = False):
         self.shape_out = check_shape(shape_out, "shape_out")
         self.stack_shapes = tuple(check_shape(s, "stack shape") for s in stack_shapes)
         _check_stack_count(len(self.stack_shapes), "StackWorkspace")
@@ -538,6 +1005,11 @@ class StackWorkspace:
         self.cover = torch.empty(self.shape_out, dtype=torch.uint8, device=device)
         self.slots = _slots(device, len(self.stack_shapes))
         self.stats = torch.zeros((max(self.iterations, 1), len(self.stack_shapes), 2), dtype=torch.int64, device=device)
+        self.to_tables = self.from_tables = self.cost = None
+        if motion:
+            self.to_tables = [torch.zeros((MAX_SLICES, 12), dtype=torch.float64, device=device) for _ in self.stack_shapes]
+            self.from_tables = [torch.zeros((MAX_SLICES, 12), dtype=torch.float64, device=device) for _ in self.stack_shapes]
+            self.cost = SliceCostWorkspace(device)
 
     def region(self, k) -> int:
         return self.slots.data_ptr() + k * _region_bytes()
@@ -560,7 +1032,7 @@ def _iterate(ws, stacks, geometries, first, count, step, lo, reg=None):
 
 def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITERATIONS, step: float = 1.0, clamp=0.0, fill: float = 0.0,
                    workspace=None, graph: bool = False, check: bool = False, reg_lambda: float = 0.0, reg_delta: float = math.inf,
-                   reg_coeffs=None) -> StackResult:
+                   reg_coeffs=None, motion=None) -> StackResult:
     """The device path of ``combine_stacks_np``: ``volume`` and ``initial`` (CUDA tensors) bit for bit, ``counts`` and ``coverage``
     equal, ``rms`` from sums within one spacing.  An iteration is ``K + 1`` launches; the one device-to-host read - the stats rows
     and the coverage counts - is the last thing done.  ``graph``: the iteration loop is captured into a HIP graph and replayed
@@ -568,7 +1040,14 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
     ``StackWorkspace`` of these shapes and this iteration count.  ``check``: a volume that is not finite everywhere raises - the
     flag travels in the same read.  ``reg_lambda``, ``reg_delta``, ``reg_coeffs``: the regulariser of ``stack_update_np``; with
     ``reg_lambda > 0`` the iterations run the regularised kernel between the two estimates of a ``StackWorkspace(...,
-    regularised=True)`` - still ``K + 1`` launches and one read; with 0 the kernels and the bits are those without the keywords."""
+    regularised=True)`` - still ``K + 1`` launches and one read; with 0 the kernels and the bits are those without the keywords.
+
+    ``motion`` (a ``MotionOptions``; None: the launches and the bits of a call without the keyword): the rounds of
+    ``combine_stacks_np`` with ``register_slices`` - one launch pair and ONE device-to-host read of ``S C 6`` doubles per search
+    iteration - and the per-slice kernels of ``csrc/volume_slices.hip``; the workspace is a ``StackWorkspace(..., motion=True)``.  Every
+    round's rebuild is ``K + 1`` launches an iteration on tables that lie in the workspace, and with ``graph`` is captured and
+    replayed on its own - the same bits as eager.  The poses are not bit-compared with the specification's (near-ties of the cost at
+    1e-12 may resolve differently).  With ``reg_lambda > 0``: ``NotImplementedError`` (not built)."""
     if not stacks:
         raise ValueError(f"combine_stacks: 1..{MAX_STACKS} stacks are combined, got 0")
     first = _check_tensor(list(stacks)[0], "combine_stacks: stack 0")
@@ -577,8 +1056,12 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
     step, lo = _check_step(step), _check_clamp(clamp)
     reg = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
     reg = reg if reg[0] > 0 else None
+    if motion is not None:
+        _not_built_with_motion(reg_lambda, "combine_stacks")
+        motion = _check_motion(motion, len(stacks), "combine_stacks")
     if workspace is None:
-        workspace = StackWorkspace(shape_out, [y.shape for y in stacks], first.device, iterations, regularised=reg is not None)
+        workspace = StackWorkspace(shape_out, [y.shape for y in stacks], first.device, iterations, regularised=reg is not None,
+                                   motion=motion is not None)
     ws = workspace
     if not isinstance(ws, StackWorkspace) or ws.key != (shape_out, tuple(tuple(y.shape) for y in stacks), iterations) \
             or ws.x.device != first.device:
@@ -586,6 +1069,8 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
                          f"{iterations} iterations on {first.device}")
     if reg is not None and ws.x2 is None:
         raise ValueError("combine_stacks: reg_lambda > 0 needs a workspace with the second estimate: StackWorkspace(..., regularised=True)")
+    if motion is not None and ws.cost is None:
+        raise ValueError("combine_stacks: motion needs a workspace with the tables and the cost buffers: StackWorkspace(..., motion=True)")
     K = len(stacks)
     ws.x.fill_(float(fill))
     _update(ws.x, stacks, geometries, 1.0, lo, ws.x, ws.cover, None, None)
@@ -600,6 +1085,19 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
         g.replay()
     else:
         _iterate(ws, stacks, geometries, 0, iterations, step, lo, reg)
+    extra = ()
+    if motion is not None:
+        first_estimate = [initial]
+
+        def register(k, params, levels):
+            return register_slices(ws.x, stacks[k], geometries[k], motion.affines[k], motion.affine_out, params, motion.worlds[k], levels,
+                                   (motion.limit_mm, motion.limit_deg), motion.min_contrast, workspace=ws.cost)
+
+        def rebuild(to_output_s, from_output_s):
+            first_estimate[0] = _rebuild_slices(ws, stacks, geometries, to_output_s, from_output_s, iterations, step, lo, fill, graph)
+
+        extra = _motion_rounds(motion, [tuple(y.shape) for y in stacks], geometries, register, rebuild)
+        initial = first_estimate[0]
     volume = (ws.x2 if reg is not None and iterations % 2 else ws.x).clone()       # the estimate an odd count of regularised updates left
     tail = [torch.stack([(ws.cover == c).sum() for c in range(K + 1)])]
     if check:
@@ -610,4 +1108,151 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
     coverage = host[ws.stats.numel():ws.stats.numel() + K + 1].copy()
     if check and not host[-1]:
         raise ValueError("combine_stacks: the reconstructed volume is not finite everywhere")
-    return StackResult(volume, initial, _rms_table(sums, counts), counts, coverage)
+    return StackResult(volume, initial, _rms_table(sums, counts), counts, coverage, *extra)
+
+
+# ---------------------------------------------------------------- device: slice-to-volume motion
+
+def _table_tensor(table, slices, device, what) -> torch.Tensor:
+    """A (slices, 12) float64 table on ``device``: a numpy (slices, 3, 4) array is checked and uploaded, a tensor taken as given."""
+    if isinstance(table, torch.Tensor):
+        t = cuda_tensor(table, (torch.float64,), what, name="the table of per-slice matrices", shape=(slices, 12))
+        if t.device != device:
+            raise ValueError(f"{what}: the table of per-slice matrices must lie on {device}")
+        return t
+    return torch.from_numpy(_check_table(table, slices, what).reshape(slices, 12)).to(device)
+
+
+def _profile_args(g):
+    T = g.offsets.size
+    return (L.C.c_double * T)(*g.offsets.tolist()), (L.C.c_float * T)(*g.weights.tolist()), T
+
+
+def _residual_slices(x, y, g, table, r, slots_ptr, stats_row):
+    L.call("mrisr_f32_volume_stack_residual_slices", x.data_ptr(), *x.shape, y.data_ptr(), *y.shape, table.data_ptr(), y.shape[g.slice_axis],
+           g.slice_axis, *_profile_args(g), r.data_ptr(), slots_ptr, L.ptr(stats_row), L.stream_ptr(), nbytes=4 * (x.numel() + 2 * y.numel()))
+
+
+def _update_slices(x, volumes, geometries, tables, step, lo, out, cover, slots, stats_rows):
+    views = (L.StackSlicesView * len(volumes))()
+    for view, v, g, t in zip(views, volumes, geometries, tables):
+        view.data, (view.nx, view.ny, view.nz), view.slice_axis = v.data_ptr(), v.shape, g.slice_axis
+        view.from_output, view.slices = t.data_ptr(), v.shape[g.slice_axis]
+    L.call("mrisr_f32_volume_stack_update_slices", x.data_ptr(), *x.shape, views, len(volumes), float(step), int(lo is not None),
+           0.0 if lo is None else float(lo), out.data_ptr(), L.ptr(cover), L.ptr(slots), L.ptr(stats_rows), L.stream_ptr(),
+           nbytes=4 * (2 * x.numel() + sum(v.numel() for v in volumes)))
+
+
+def stack_residual_slices(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, to_output_s, out=None):
+    """The device path of ``stack_residual_slices_np`` -> ``(r, S, n)`` as ``stack_residual``: ``r`` bit for bit.  ``to_output_s``: a
+    numpy (S, 3, 4) array (uploaded) or a float64 CUDA tensor (S, 12).  CPU tensors raise."""
+    x, y = _check_tensor(x, "stack_residual_slices"), _check_tensor(y, "stack_residual_slices")
+    if x.device != y.device:
+        raise ValueError(f"stack_residual_slices: the estimate and the stack must share a device, got {x.device} and {y.device}")
+    g = _check_geometry(geometry, "stack_residual_slices")
+    table = _table_tensor(to_output_s, _check_slice_count(y.shape[g.slice_axis], "stack_residual_slices"), x.device, "stack_residual_slices")
+    r = out_like(out, y, (x, y), "stack_residual_slices")
+    row = torch.empty(2, dtype=torch.int64, device=x.device)
+    _residual_slices(x, y, g, table, r, _slots(x.device, 1).data_ptr(), row)
+    return r, row[:1].view(torch.float64)[0], row[1]
+
+
+def stack_update_slices(x: torch.Tensor, residuals, geometries, from_output_s, step: float = 1.0, clamp=0.0, out=None, cover: bool = False,
+                        reg_lambda: float = 0.0):
+    """The device path of ``stack_update_slices_np`` -> ``(x', cnt)``, bit for bit; ``cnt`` (uint8) only with ``cover=True``.  ONE
+    launch for all the stacks, no device-to-host read.  ``from_output_s``: per stack a numpy (S_k, 3, 4) array or a float64 CUDA
+    tensor (S_k, 12).  ``out``: a tensor like ``x`` - ``x`` itself updates in place.  ``reg_lambda > 0``: not built."""
+    _not_built_with_motion(reg_lambda, "stack_update_slices")
+    x = _check_tensor(x, "stack_update_slices")
+    volumes, geometries = _check_stacks(residuals, geometries, x.device, "stack_update_slices")
+    tables = list(from_output_s)
+    if len(tables) != len(volumes):
+        raise ValueError(f"stack_update_slices: {len(volumes)} stacks and {len(tables)} tables")
+    tables = [_table_tensor(t, _check_slice_count(v.shape[g.slice_axis], "stack_update_slices"), x.device, f"stack_update_slices: stack {k}")
+              for k, (t, v, g) in enumerate(zip(tables, volumes, geometries))]
+    step, lo = _check_step(step), _check_clamp(clamp)
+    out = x if out is x else out_like(out, x, volumes, "stack_update_slices")
+    cnt = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if cover else None
+    _update_slices(x, volumes, geometries, tables, step, lo, out, cnt, None, None)
+    return out, cnt
+
+
+class SliceCostWorkspace:
+    """The buffers of ``slice_cost`` for stacks of up to ``slices`` slices and ``candidates`` poses each: the candidates' matrices, the
+    fixed slots of the sums and the result.  Made once, it serves call after call on one stream; nothing in it needs initialising."""
+
+    def __init__(self, device, slices: int = MAX_SLICES, candidates: int = MAX_CANDIDATES):
+        self.slices, self.candidates = _check_slice_count(slices, "SliceCostWorkspace"), int(candidates)
+        if not 1 <= self.candidates <= MAX_CANDIDATES:
+            raise ValueError(f"SliceCostWorkspace: 1..{MAX_CANDIDATES} candidates, got {candidates}")
+        self.cand = torch.empty(self.slices * self.candidates * 12, dtype=torch.float64, device=device)
+        self.slots = torch.empty(int(L.load().mrisr_f32_volume_slice_cost_workspace_bytes(self.slices, self.candidates)) // 8,
+                                 dtype=torch.float64, device=device)
+        self.out = torch.empty(self.slices * self.candidates * 6, dtype=torch.float64, device=device)
+
+
+def slice_cost(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, cand_to_output, stride: int = 1, workspace=None) -> torch.Tensor:
+    """The device path of ``slice_cost_np`` -> a float64 CUDA tensor (S, C, 6) (a view of the workspace's result buffer): the counts
+    equal, the sums those of a fixed order of addition - within 1e-12 (relative) of the specification's, the same bits on every run.
+    ``cand_to_output``: numpy (S, C, 3, 4), uploaded into the workspace.  Two launches (the S C pairs; the slots), no atomics, no
+    device-to-host read.  CPU tensors raise."""
+    x, y = _check_tensor(x, "slice_cost"), _check_tensor(y, "slice_cost")
+    if x.device != y.device:
+        raise ValueError(f"slice_cost: the estimate and the stack must share a device, got {x.device} and {y.device}")
+    g = _check_geometry(geometry, "slice_cost")
+    cand, stride = _check_cost_args(y.shape, g.slice_axis, cand_to_output, stride, "slice_cost")
+    S, C = cand.shape[:2]
+    ws = SliceCostWorkspace(x.device, S, C) if workspace is None else workspace
+    if not isinstance(ws, SliceCostWorkspace) or ws.slices < S or ws.candidates < C or ws.cand.device != x.device:
+        raise ValueError(f"slice_cost: the workspace must be a SliceCostWorkspace for {S} slices and {C} candidates on {x.device}")
+    table, out = ws.cand[:S * C * 12], ws.out[:S * C * 6]
+    table.copy_(torch.from_numpy(cand.reshape(-1)))
+    L.call("mrisr_f32_volume_slice_cost", x.data_ptr(), *x.shape, y.data_ptr(), *y.shape, table.data_ptr(), S, C, g.slice_axis,
+           *_profile_args(g), stride, ws.slots.data_ptr(), out.data_ptr(), L.stream_ptr())
+    return out.view(S, C, 6)
+
+
+def register_slices(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, affine, affine_out, params0=None, world=None, levels=None,
+                    limits=(10.0, 10.0), min_contrast: float = 0.1, workspace=None) -> SliceMotion:
+    """The device path of ``register_slices_np``: the same search on the host (``slice_compass_search``, ``ncc_from_sums``) over the
+    sums of ``slice_cost`` - per search iteration one upload of the candidates' matrices, two launches and ONE device-to-host read of
+    ``S C 6`` doubles.  The poses are close to the specification's, not bit-equal (the sums differ at 1e-12)."""
+    x, y = _check_tensor(x, "register_slices"), _check_tensor(y, "register_slices")
+    g = _check_geometry(geometry, "register_slices")
+    ws = SliceCostWorkspace(x.device) if workspace is None else workspace
+    return _register_slices(lambda cand, stride: slice_cost(x, y, g, cand, stride, ws).cpu().numpy(), tuple(y.shape), g.slice_axis, affine,
+                            affine_out, world, params0, levels, limits, min_contrast)
+
+
+def _iterate_slices(ws, stacks, geometries, count, step, lo):
+    """``_iterate`` with the per-slice kernels on the tables of the workspace: ``K + 1`` launches an iteration, nothing allocated."""
+    to_tables = [t[:y.shape[g.slice_axis]] for t, y, g in zip(ws.to_tables, stacks, geometries)]
+    from_tables = [t[:y.shape[g.slice_axis]] for t, y, g in zip(ws.from_tables, stacks, geometries)]
+    for it in range(count):
+        for k, (y, g) in enumerate(zip(stacks, geometries)):
+            _residual_slices(ws.x, y, g, to_tables[k], ws.residuals[k], ws.region(k), None)
+        _update_slices(ws.x, ws.residuals, geometries, from_tables, step, lo, ws.x, None, ws.slots, ws.stats[it])
+
+
+def _rebuild_slices(ws, stacks, geometries, to_output_s, from_output_s, iterations, step, lo, fill, graph):
+    """The estimate from scratch with a pose per slice: the tables go into the workspace, then the initial estimate and
+    ``iterations`` updates (captured and replayed with ``graph``) -> the initial estimate."""
+    for k, (y, g) in enumerate(zip(stacks, geometries)):
+        S = _check_slice_count(y.shape[g.slice_axis], "combine_stacks")
+        ws.to_tables[k][:S].copy_(torch.from_numpy(_check_table(to_output_s[k], S, "combine_stacks").reshape(S, 12)))
+        ws.from_tables[k][:S].copy_(torch.from_numpy(_check_table(from_output_s[k], S, "combine_stacks").reshape(S, 12)))
+    from_tables = [t[:y.shape[g.slice_axis]] for t, y, g in zip(ws.from_tables, stacks, geometries)]
+    ws.x.fill_(float(fill))
+    _update_slices(ws.x, stacks, geometries, from_tables, 1.0, lo, ws.x, ws.cover, None, None)
+    initial = ws.x.clone()
+    if graph and iterations:
+        _iterate_slices(ws, stacks, geometries, 1, step, lo)
+        ws.x.copy_(initial)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            _iterate_slices(ws, stacks, geometries, iterations, step, lo)
+        g.replay()
+    else:
+        _iterate_slices(ws, stacks, geometries, iterations, step, lo)
+    return initial

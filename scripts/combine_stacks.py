@@ -17,7 +17,14 @@ writes the initial estimate (the mean of the stacks' linear reslices).  ``--regu
 prior of ``volume_stacks.stack_update_np`` on the six face neighbours to every update - on noisy stacks the plain iteration is past
 its best after two or three updates, with the prior it settles and can be run to convergence; ``--regularise_delta D`` (default inf:
 the quadratic prior) clips the neighbour differences at ``D`` intensity units, which keeps tissue steps and fine detail; the
-coefficients are ``volume_stacks.regulariser_coeffs`` of the output grid.  4-D inputs must agree in their frame count and are combined
+coefficients are ``volume_stacks.regulariser_coeffs`` of the output grid.  ``--motion slices`` (default ``none``) corrects motion
+between the slices of a stack: after the reconstruction with stack-wide matrices, ``--motion_rounds`` (2) times, every slice of every
+stack is registered rigidly to the current estimate (``volume_stacks.register_slices``: normalised cross-correlation, a compass search
+for all slices at once, poses within ``--motion_limit_mm`` / ``--motion_limit_deg`` (10 / 10); slices whose contrast is below
+``--motion_min_contrast`` (0.1) of the stack's keep their pose) and the estimate is rebuilt with a matrix per slice.  Per round and
+stack the active slices, the mean cost before and after and the largest displacement of a slice corner are logged; ``--save_motion
+F.csv`` writes a row per slice (of the last frame): stack, slice, the six parameters, the active flag, the cost at the start and the
+end of the last round.  ``--motion slices`` with ``--regularise`` is not built and is refused.  4-D inputs must agree in their frame count and are combined
 frame by frame.  The output is float32 under ``utils.nifti.header_for_grid`` of the first input's header.  Exit code 0 / 1 (error
 logged), as ``scripts/infer_volume.py``.
 """
@@ -40,6 +47,10 @@ from scripts._cli import add_cpu_flag, join_frames, run, save_nifti             
 logger = logging.getLogger("combine_stacks")
 
 
+MOTIONS = ("none", "slices")
+MOTION_WITH_REGULARISER = "--motion slices with --regularise is not built: the regularised update takes one matrix per stack"
+
+
 def per_stack(values, count, name, default):
     """One value for all the stacks, or one per stack."""
     if values is None:
@@ -50,8 +61,17 @@ def per_stack(values, count, name, default):
 
 
 def check_options(inputs, iterations=S.DEFAULT_ITERATIONS, step=1.0, slice_axis=None, thickness_mm=None, profile_samples=None, spacing=None,
-                  regularise=0.0, regularise_delta=float("inf")):
+                  regularise=0.0, regularise_delta=float("inf"), motion="none", motion_rounds=2, motion_limit_mm=10.0, motion_limit_deg=10.0,
+                  motion_min_contrast=0.1):
     """The checks that need no file: raises ``ValueError`` before anything is read."""
+    if motion not in MOTIONS:
+        raise ValueError(f"--motion is one of {MOTIONS}, got {motion!r}")
+    if motion != "none":
+        if regularise > 0:
+            raise ValueError(MOTION_WITH_REGULARISER)
+        if motion_rounds < 0 or not (motion_limit_mm > 0 and motion_limit_deg > 0 and motion_min_contrast >= 0):
+            raise ValueError("--motion_rounds must not be negative, --motion_limit_mm and --motion_limit_deg positive, "
+                             "--motion_min_contrast not negative")
     if not 1 <= len(inputs) <= S.MAX_STACKS:
         raise ValueError(f"1..{S.MAX_STACKS} stacks are combined, got {len(inputs)}")
     S._check_iterations(iterations), S._check_step(step)
@@ -71,9 +91,11 @@ def check_options(inputs, iterations=S.DEFAULT_ITERATIONS, step=1.0, slice_axis=
 
 def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEFAULT_ITERATIONS, step=1.0, profile="box", thickness_mm=None,
                   slice_axis=None, profile_samples=None, register="none", clamp=0.0, fill=0.0, save_initial=None, device="cuda",
-                  regularise=0.0, regularise_delta=float("inf")):
+                  regularise=0.0, regularise_delta=float("inf"), motion="none", motion_rounds=2, motion_limit_mm=10.0, motion_limit_deg=10.0,
+                  motion_min_contrast=0.1, save_motion=None):
     """NIfTI stacks -> one NIfTI volume; returns the output array (as written)."""
-    axes, thickness = check_options(inputs, iterations, step, slice_axis, thickness_mm, profile_samples, spacing, regularise, regularise_delta)
+    axes, thickness = check_options(inputs, iterations, step, slice_axis, thickness_mm, profile_samples, spacing, regularise, regularise_delta,
+                                    motion, motion_rounds, motion_limit_mm, motion_limit_deg, motion_min_contrast)
     scans = [read_nifti(p) for p in inputs]
     per_scan = [[np.ascontiguousarray(f, dtype=np.float32) for f in frames(d)] for d, _ in scans]
     if len({len(f) for f in per_scan}) != 1 or len({d.ndim for d, _ in scans}) != 1:
@@ -100,11 +122,19 @@ def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEF
     if regularise > 0:
         logger.info(f"regulariser: lambda {regularise:g}, delta {regularise_delta:g}, coefficients {[round(float(c), 6) for c in coeffs]} "
                     f"(output voxels of {np.round(S.voxel_sizes(affine_out), 3).tolist()} mm)")
-    ws = S.StackWorkspace(shape_out, shapes, device, iterations, regularised=regularise > 0)
+    options = {}
+    if motion == "slices":                                           # without the flag the call is the one it always was
+        options["motion"] = S.MotionOptions(tuple(affines), affine_out, tuple(worlds), motion_rounds, motion_limit_mm, motion_limit_deg,
+                                            motion_min_contrast)
+    ws = S.StackWorkspace(shape_out, shapes, device, iterations, regularised=regularise > 0, **({"motion": True} if options else {}))
     outs, initials = [], []
     for t in range(len(per_scan[0])):
         r = S.combine_stacks([torch.from_numpy(f[t]).to(device) for f in per_scan], geometries, shape_out, iterations, step, clamp, fill,
-                             workspace=ws, check=True, reg_lambda=regularise, reg_delta=regularise_delta, reg_coeffs=coeffs)
+                             workspace=ws, check=True, reg_lambda=regularise, reg_delta=regularise_delta, reg_coeffs=coeffs, **options)
+        if options:
+            log_motion(t, r, affines, shapes, geometries)
+            if save_motion is not None:
+                write_motion_csv(save_motion, r)
         for it in range(iterations):
             logger.info(f"frame {t} iteration {it + 1}: residual RMS per stack {[round(float(v), 4) for v in r.rms[it]]}")
         shares = r.coverage / float(r.coverage.sum())
@@ -123,10 +153,31 @@ def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEF
     return result
 
 
+def log_motion(t, r, affines, shapes, geometries):
+    """Per round and stack: the mean cost before and after; per stack: the active slices and the largest corner displacement."""
+    for rnd, row in enumerate(r.motion_cost):
+        for k, (before, after) in enumerate(row):
+            logger.info(f"frame {t} motion round {rnd + 1} stack {k}: mean NCC of the active slices {before:.5f} -> {after:.5f}")
+    for k, (p, m) in enumerate(zip(r.motion, r.motion_detail)):
+        d = S.slice_corner_displacement(p, np.zeros_like(p), affines[k], shapes[k], geometries[k].slice_axis)
+        logger.info(f"frame {t} stack {k}: {int(m.active.sum())} of {m.active.size} slices active, largest displacement of a slice corner "
+                    f"{float(d.max()):.3f} mm")
+
+
+def write_motion_csv(path, r):
+    """A row per slice: stack, slice, tx, ty, tz (mm), rx, ry, rz (degrees), active, the cost at the start and the end of the last round."""
+    with open(path, "w") as f:
+        f.write("stack,slice,tx,ty,tz,rx,ry,rz,active,cost_start,cost_end\n")
+        for k, (p, m) in enumerate(zip(r.motion, r.motion_detail)):
+            for s in range(p.shape[0]):
+                f.write(f"{k},{s}," + ",".join(repr(float(v)) for v in p[s]) + f",{int(m.active[s])},{float(m.start[s])!r},{float(m.end[s])!r}\n")
+
+
 def _body(args, device):
     combine_files(args.inputs, args.output, args.spacing, args.like, args.iterations, args.step, args.profile, args.thickness_mm,
                   args.slice_axis, args.profile_samples, args.register, None if args.no_clamp else 0.0, args.fill, args.save_initial, device,
-                  args.regularise, args.regularise_delta)
+                  args.regularise, args.regularise_delta, args.motion, args.motion_rounds, args.motion_limit_mm, args.motion_limit_deg,
+                  args.motion_min_contrast, args.save_motion)
 
 
 def main(args):
@@ -153,6 +204,12 @@ def parse_args(argv=None):
     p.add_argument("--regularise", type=float, default=0.0, metavar="LAMBDA", help="weight of the Huber prior on the six face neighbours (default 0: none); "
                    "step * LAMBDA * (sum of the coefficients) <= 0.5")
     p.add_argument("--regularise_delta", type=float, default=float("inf"), metavar="D", help="clip the neighbour differences at D (default inf: quadratic prior)")
+    p.add_argument("--motion", type=str, choices=list(MOTIONS), default="none", help="slices: register every slice to the estimate and rebuild it")
+    p.add_argument("--motion_rounds", type=int, default=2, help="rounds of slice registration and rebuild")
+    p.add_argument("--motion_limit_mm", type=float, default=10.0, help="largest translation of a slice, per component")
+    p.add_argument("--motion_limit_deg", type=float, default=10.0, help="largest rotation of a slice, per component")
+    p.add_argument("--motion_min_contrast", type=float, default=0.1, help="slices with less contrast than this share of the stack's keep their pose")
+    p.add_argument("--save_motion", type=str, default=None, metavar="F.csv", help="write the slices' poses, active flags and costs")
     add_cpu_flag(p)
     return p.parse_args(argv)
 
