@@ -2,14 +2,14 @@
 // and the back projection of csrc/volume_stacks.hip with one matrix PER SLICE, and the cost of a dozen candidate poses for every
 // slice of a stack in one launch.
 //
-// Restates stack_residual_slices_np / stack_update_slices_np / slice_cost_np of mri_superresolution_amd/volume_stacks.py operation by
+// Restates stack_residual_slices_np / stack_update_slices_np / slice_cost_np of mri_superresolution_amd/volume_slices.py operation by
 // operation (compiled with -ffp-contract=off); the first two are tested bit for bit, the float64 sums of the third are those of
 // another order of addition and the same bits on every run.  The tables of matrices are DEVICE arrays of 12 doubles per slice (row
 // major 3 x 4), written by the host before the launch; nothing is uploaded and nothing synchronises here (HIP-graph capturable).  A
 // table entry that is not finite fails every inside test (a NaN compares false), so no kernel reads outside its arrays.
 //
-//   f32_volume_stack_residual_slices   stack_residual_kernel with the matrix of the voxel's slice fetched from the table; the slots
-//                                      and the stats row are those of the plain kernel.
+//   f32_volume_stack_residual_slices   stack_residual_kernel with the matrix of the voxel's slice fetched from the table: the same
+//                                      stack_residual_voxel; the slots and the stats row are those of the plain kernel.
 //   f32_volume_stack_update_slices     ONE launch for all stacks, one thread per OUTPUT voxel.  Per stack the workgroup stages the
 //                                      slice-axis rows of its table (4 doubles per slice, at most 8 KB) in LDS; a thread walks the
 //                                      slices in ascending order and computes the through-plane coordinate z alone (three products)
@@ -56,16 +56,10 @@ __global__ __launch_bounds__(256) void stack_residual_slices_kernel(const float*
     for (unsigned b = blockIdx.x; b < nbricks; b += gridDim.x) {
         int i, j, k;
         if (!stack_brick_voxel(b, nby, nbz, SX, SY, SZ, i, j, k)) continue;
-        const size_t idx = ((size_t)i * SY + j) * SZ + k;
         const int slice = axis == 0 ? i : (axis == 1 ? j : k);
         double g[3][4];
         load_matrix(table + (size_t)slice * 12, g);
-        float sim, res = 0.f;
-        if (stack_simulate(x, X, Y, Z, g, axis, pr, T, (double)i, (double)j, (double)k, sim)) {
-            res = __fsub_rn(y[idx], sim);
-            sq.add((double)res * (double)res, 0.0, 1);      // the square of a float is exact in double
-        }
-        r[idx] = res;
+        stack_residual_voxel(x, X, Y, Z, y, g, axis, pr, T, i, j, k, ((size_t)i * SY + j) * SZ + k, r, sq);
     }
     block_sum_to_slot(sq, part, &slots[blockIdx.x]);
 }
@@ -76,8 +70,7 @@ __global__ __launch_bounds__(256) void stack_update_slices_kernel(const float* x
                                                                   unsigned nby, unsigned nbz, const DeformSlot* __restrict__ slots,
                                                                   StatsRow* __restrict__ rows) {
     __shared__ double zrow[kMaxSlices][4];
-    if (rows && blockIdx.x == 0 && threadIdx.x < 64)
-        for (int s = 0; s < K; ++s) finalize_force(slots + (size_t)s * kSlots, v.nslots[s], rows + s);
+    stack_update_stats(slots, v.nslots, K, rows);
     int i, j, k;
     const bool valid = stack_brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k);      // every thread stays for the barriers
     const double di = (double)i, dj = (double)j, dk = (double)k;
@@ -128,13 +121,7 @@ __global__ __launch_bounds__(256) void stack_update_slices_kernel(const float* x
     }
     if (!valid) return;
     const size_t idx = ((size_t)i * Y + j) * Z + k;
-    float xv = x[idx];
-    if (cnt > 0) {
-        xv = __fadd_rn(xv, __fmul_rn(step, __fdiv_rn(sum, (float)cnt)));
-        if (use_clamp && xv < lo) xv = lo;                  // a NaN stays
-    }
-    out[idx] = xv;
-    if (cover) cover[idx] = (unsigned char)cnt;
+    stack_update_store(x[idx], cnt, step, use_clamp, lo, out, cover, idx, [&] { return __fdiv_rn(sum, (float)cnt); });
 }
 
 // workgroup blockIdx.x owns slice blockIdx.x / groups and the tiles blockIdx.x % groups, + groups, ... of its strided plane of
@@ -226,15 +213,9 @@ extern "C" int mrisr_f32_volume_stack_update_slices(const float* x, int X, int Y
                                                     const void* workspace, void* stats_rows, void* stream) {
     const char* name = "f32_volume_stack_update_slices";
     if (!x || !views || !out) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
-    if (K < 1 || K > kMaxStacks) MRISR_FAIL(MRISR_E_ARG, "%s: %d stacks (1..%d)", name, K, kMaxStacks);
-    if (!isfinite(step)) MRISR_FAIL(MRISR_E_ARG, "%s: step %g is not finite", name, (double)step);
-    if (use_clamp != 0 && use_clamp != 1) MRISR_FAIL(MRISR_E_ARG, "%s: use_clamp %d (0 or 1)", name, use_clamp);
-    if (use_clamp && !isfinite(lo)) MRISR_FAIL(MRISR_E_ARG, "%s: the lower clamp %g is not finite", name, (double)lo);
-    if ((workspace == nullptr) != (stats_rows == nullptr)) MRISR_FAIL(MRISR_E_ARG, "%s: workspace and stats_rows go together", name);
+    if (const int rc = check_update_step(name, K, step, use_clamp, lo)) return rc;
     BrickGrid grid;
-    if (const int rc = check_field_volume(name, X, Y, Z, &grid)) return rc;
-    if (!aligned_to(x, 4) || !aligned_to(out, 4) || !aligned_to(workspace, 8) || !aligned_to(stats_rows, 8))
-        MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer", name);
+    if (const int rc = check_update_volume(name, x, X, Y, Z, out, workspace, stats_rows, &grid)) return rc;
     SliceViews v = {};
     for (int s = 0; s < K; ++s) {
         const mrisr_stack_slices_view& in = views[s];

@@ -23,19 +23,15 @@
 //                               elements per voxel, 16.6 KB with the flags) and, per staged voxel, whether it lies in the grid and
 //                               a stack covers it, are staged in LDS once.  The gathers are those of the plain kernel.
 //
-// The brick walk, the coordinate, the gather and the matrix check are those of volume_stacks.h, shared with csrc/volume_slices.hip.
+// The brick walk, the coordinate, the gather, the forward model, the residual of a voxel, the parts of an update kernel (stats
+// prologue, gather over the views, step-clamp-store epilogue) and the shared host checks are those of volume_stacks.h, shared with
+// csrc/volume_slices.hip.
 // The first two kernels walk the 2 x 2 x 64 bricks of the reslice and warp kernels, z fastest.  Nothing is uploaded and nothing
 // synchronises (HIP-graph capturable); no floating-point atomics: the same bits on every run.
 #include "volume_stacks.h"
 
 struct StackMatrix {
     double m[3][4];
-};
-struct StackViews {
-    const float* data[kMaxStacks];
-    int n[kMaxStacks][3];
-    int nslots[kMaxStacks];
-    double m[kMaxStacks][3][4];
 };
 
 // at most kSlots workgroups walk the bricks of the STACK with a stride of the grid
@@ -48,24 +44,7 @@ __global__ __launch_bounds__(256) void stack_residual_kernel(const float* __rest
     for (unsigned b = blockIdx.x; b < nbricks; b += gridDim.x) {
         int i, j, k;
         if (!stack_brick_voxel(b, nby, nbz, SX, SY, SZ, i, j, k)) continue;
-        const size_t idx = ((size_t)i * SY + j) * SZ + k;
-        const double di = (double)i, dj = (double)j, dk = (double)k;
-        const double along = axis == 0 ? di : (axis == 1 ? dj : dk);
-        float acc = 0.f, wsum = 0.f;
-        for (int t = 0; t < T; ++t) {
-            const double s = __dadd_rn(along, pr.offset[t]);
-            double p[3];
-            if (!stack_coordinate(g.m, axis == 0 ? s : di, axis == 1 ? s : dj, axis == 2 ? s : dk, X, Y, Z, p)) continue;
-            const float w = pr.weight[t];
-            acc = __fadd_rn(acc, __fmul_rn(w, linear_gather(x, X, Y, Z, p)));
-            wsum = __fadd_rn(wsum, w);
-        }
-        float res = 0.f;
-        if (wsum >= 0.5f) {
-            res = __fsub_rn(y[idx], __fdiv_rn(acc, wsum));
-            sq.add((double)res * (double)res, 0.0, 1);      // the square of a float is exact in double
-        }
-        r[idx] = res;
+        stack_residual_voxel(x, X, Y, Z, y, g.m, axis, pr, T, i, j, k, ((size_t)i * SY + j) * SZ + k, r, sq);
     }
     block_sum_to_slot(sq, part, &slots[blockIdx.x]);
 }
@@ -74,28 +53,13 @@ __global__ __launch_bounds__(256) void stack_residual_kernel(const float* __rest
 __global__ __launch_bounds__(256) void stack_update_kernel(const float* x, float* out, unsigned char* __restrict__ cover, int X, int Y,
                                                            int Z, StackViews v, int K, float step, int use_clamp, float lo, unsigned nby,
                                                            unsigned nbz, const DeformSlot* __restrict__ slots, StatsRow* __restrict__ rows) {
-    if (rows && blockIdx.x == 0 && threadIdx.x < 64)
-        for (int s = 0; s < K; ++s) finalize_force(slots + (size_t)s * kSlots, v.nslots[s], rows + s);
+    stack_update_stats(slots, v.nslots, K, rows);
     int i, j, k;
     if (!stack_brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k)) return;
     const size_t idx = ((size_t)i * Y + j) * Z + k;
-    const double di = (double)i, dj = (double)j, dk = (double)k;
-    float sum = 0.f;
-    int cnt = 0;
-#pragma unroll 1
-    for (int s = 0; s < K; ++s) {
-        double p[3];
-        if (!stack_coordinate(v.m[s], di, dj, dk, v.n[s][0], v.n[s][1], v.n[s][2], p)) continue;
-        sum = __fadd_rn(sum, linear_gather(v.data[s], v.n[s][0], v.n[s][1], v.n[s][2], p));
-        ++cnt;
-    }
-    float xv = x[idx];
-    if (cnt > 0) {
-        xv = __fadd_rn(xv, __fmul_rn(step, __fdiv_rn(sum, (float)cnt)));
-        if (use_clamp && xv < lo) xv = lo;                  // a NaN stays
-    }
-    out[idx] = xv;
-    if (cover) cover[idx] = (unsigned char)cnt;
+    float sum;
+    const int cnt = stack_gather_views(v, K, (double)i, (double)j, (double)k, sum);
+    stack_update_store(x[idx], cnt, step, use_clamp, lo, out, cover, idx, [&] { return __fdiv_rn(sum, (float)cnt); });
 }
 
 // the tile of the regularised update and its staged image (a halo of one on every side)
@@ -114,8 +78,7 @@ __global__ __launch_bounds__(256) void stack_update_reg_kernel(const float* __re
                                                                StatsRow* __restrict__ rows) {
     __shared__ float sx[kHalo];
     __shared__ unsigned char sok[kHalo];                    // 1: inside the grid and covered by a stack
-    if (rows && blockIdx.x == 0 && threadIdx.x < 64)
-        for (int s = 0; s < K; ++s) finalize_force(slots + (size_t)s * kSlots, v.nslots[s], rows + s);
+    stack_update_stats(slots, v.nslots, K, rows);
     const unsigned tz = blockIdx.x % ntz, rest = blockIdx.x / ntz, ty = rest % nty, tx = rest / nty;
     const int x0 = (int)tx * kRX, y0 = (int)ty * kRY, z0 = (int)tz * kRZ;
     for (int e = threadIdx.x; e < kHalo; e += 256) {
@@ -143,19 +106,11 @@ __global__ __launch_bounds__(256) void stack_update_reg_kernel(const float* __re
     for (int lx = 0; lx < kRX && x0 + lx < X; ++lx) {
         const int i = x0 + lx;
         const size_t idx = ((size_t)i * Y + j) * Z + k;
-        const double di = (double)i;
-        float sum = 0.f;
-        int cnt = 0;
-#pragma unroll 1
-        for (int s = 0; s < K; ++s) {
-            double p[3];
-            if (!stack_coordinate(v.m[s], di, dj, dk, v.n[s][0], v.n[s][1], v.n[s][2], p)) continue;
-            sum = __fadd_rn(sum, linear_gather(v.data[s], v.n[s][0], v.n[s][1], v.n[s][2], p));
-            ++cnt;
-        }
+        float sum;
+        const int cnt = stack_gather_views(v, K, (double)i, dj, dk, sum);
         const int h = ((lx + 1) * kHY + ly + 1) * kHZ + lz + 1;
-        float xv = sx[h];
-        if (cnt > 0) {
+        const float xv = sx[h];
+        stack_update_store(xv, cnt, step, use_clamp, lo, out, cover, idx, [&] {
             float reg = 0.f;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -168,12 +123,8 @@ __global__ __launch_bounds__(256) void stack_update_reg_kernel(const float* __re
                     reg = __fadd_rn(reg, __fmul_rn(pr.c[a], psi));
                 }
             }
-            const float m = __fdiv_rn(sum, (float)cnt);
-            xv = __fadd_rn(xv, __fmul_rn(step, __fadd_rn(m, __fmul_rn(pr.lambda, reg))));
-            if (use_clamp && xv < lo) xv = lo;              // a NaN stays
-        }
-        out[idx] = xv;
-        if (cover) cover[idx] = (unsigned char)cnt;
+            return __fadd_rn(__fdiv_rn(sum, (float)cnt), __fmul_rn(pr.lambda, reg));
+        });
     }
 }
 
@@ -186,16 +137,12 @@ extern "C" int mrisr_f32_volume_stack_residual(const float* x, int X, int Y, int
                                                void* stats_row, void* stream) {
     const char* name = "f32_volume_stack_residual";
     if (!x || !y || !m12 || !offsets || !weights || !r || !workspace) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
-    if (T < 1 || T > kMaxSamples) MRISR_FAIL(MRISR_E_ARG, "%s: %d profile samples (1..%d)", name, T, kMaxSamples);
+    if (T < 1 || T > kMaxSamples) MRISR_FAIL(MRISR_E_ARG, "%s: %d profile samples (1..%d)", name, T, kMaxSamples);      // before the axis and matrix checks, as before; check_profile repeats it
     if (slice_axis < 0 || slice_axis > 2) MRISR_FAIL(MRISR_E_ARG, "%s: slice axis %d (0..2)", name, slice_axis);
     StackMatrix g;
     if (const int rc = check_matrix(name, m12, g.m)) return rc;
-    StackProfile pr = {};
-    for (int t = 0; t < T; ++t) {
-        if (!isfinite(offsets[t]) || !isfinite(weights[t])) MRISR_FAIL(MRISR_E_ARG, "%s: profile sample %d is not finite", name, t);
-        pr.offset[t] = offsets[t];
-        pr.weight[t] = weights[t];
-    }
+    StackProfile pr;
+    if (const int rc = check_profile(name, offsets, weights, T, &pr)) return rc;
     BrickGrid out_grid, grid;
     if (const int rc = check_field_volume(name, X, Y, Z, &out_grid)) return rc;
     if (const int rc = check_field_volume(name, SX, SY, SZ, &grid)) return rc;
@@ -214,34 +161,37 @@ extern "C" int mrisr_f32_volume_stack_residual(const float* x, int X, int Y, int
     return MRISR_OK;
 }
 
-extern "C" int mrisr_f32_volume_stack_update(const float* x, int X, int Y, int Z, const mrisr_stack_view* views, int K, float step,
-                                             int use_clamp, float lo, float* out, unsigned char* cover, const void* workspace,
-                                             void* stats_rows, void* stream) {
-    const char* name = "f32_volume_stack_update";
-    if (!x || !views || !out) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
-    if (K < 1 || K > kMaxStacks) MRISR_FAIL(MRISR_E_ARG, "%s: %d stacks (1..%d)", name, K, kMaxStacks);
-    if (!isfinite(step)) MRISR_FAIL(MRISR_E_ARG, "%s: step %g is not finite", name, (double)step);
-    if (use_clamp != 0 && use_clamp != 1) MRISR_FAIL(MRISR_E_ARG, "%s: use_clamp %d (0 or 1)", name, use_clamp);
-    if (use_clamp && !isfinite(lo)) MRISR_FAIL(MRISR_E_ARG, "%s: the lower clamp %g is not finite", name, (double)lo);
-    if ((workspace == nullptr) != (stats_rows == nullptr)) MRISR_FAIL(MRISR_E_ARG, "%s: workspace and stats_rows go together", name);
-    BrickGrid grid;
-    if (const int rc = check_field_volume(name, X, Y, Z, &grid)) return rc;
-    if (!aligned_to(x, 4) || !aligned_to(out, 4) || !aligned_to(workspace, 8) || !aligned_to(stats_rows, 8))
-        MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer", name);
-    StackViews v = {};
+// the views of an update entry into the kernel argument: every stack's pointer (not null, aligned, neither out nor cover), matrix
+// and extents
+static int fill_stack_views(const char* name, const mrisr_stack_view* views, int K, const float* out, const unsigned char* cover,
+                            StackViews* v) {
+    *v = StackViews{};
     for (int s = 0; s < K; ++s) {
         const mrisr_stack_view& in = views[s];
         if (!in.data) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: null pointer", name, s);
         if (!aligned_to(in.data, 4)) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: misaligned pointer", name, s);
         if (in.data == out || (const void*)in.data == (const void*)cover)
             MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: out and cover must be buffers of their own", name, s);
-        if (const int rc = check_matrix(name, in.m, v.m[s])) return rc;
+        if (const int rc = check_matrix(name, in.m, v->m[s])) return rc;
         BrickGrid sg;
         if (const int rc = check_field_volume(name, in.nx, in.ny, in.nz, &sg)) return rc;
-        v.data[s] = in.data;
-        v.n[s][0] = in.nx, v.n[s][1] = in.ny, v.n[s][2] = in.nz;
-        v.nslots[s] = sg.nslots;
+        v->data[s] = in.data;
+        v->n[s][0] = in.nx, v->n[s][1] = in.ny, v->n[s][2] = in.nz;
+        v->nslots[s] = sg.nslots;
     }
+    return MRISR_OK;
+}
+
+extern "C" int mrisr_f32_volume_stack_update(const float* x, int X, int Y, int Z, const mrisr_stack_view* views, int K, float step,
+                                             int use_clamp, float lo, float* out, unsigned char* cover, const void* workspace,
+                                             void* stats_rows, void* stream) {
+    const char* name = "f32_volume_stack_update";
+    if (!x || !views || !out) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
+    if (const int rc = check_update_step(name, K, step, use_clamp, lo)) return rc;
+    BrickGrid grid;
+    if (const int rc = check_update_volume(name, x, X, Y, Z, out, workspace, stats_rows, &grid)) return rc;
+    StackViews v;
+    if (const int rc = fill_stack_views(name, views, K, out, cover, &v)) return rc;
     if ((const void*)cover == (const void*)x || (const void*)cover == (const void*)out)
         MRISR_FAIL(MRISR_E_ARG, "%s: cover must be a buffer of its own", name);
     stack_update_kernel<<<grid.nbricks, 256, 0, (hipStream_t)stream>>>(x, out, cover, X, Y, Z, v, K, step, use_clamp, lo, grid.nby, grid.nbz,
@@ -256,10 +206,7 @@ extern "C" int mrisr_f32_volume_stack_update_reg(const float* x, int X, int Y, i
                                                  void* stats_rows, void* stream) {
     const char* name = "f32_volume_stack_update_reg";
     if (!x || !views || !out || !coeffs || !cover_in) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
-    if (K < 1 || K > kMaxStacks) MRISR_FAIL(MRISR_E_ARG, "%s: %d stacks (1..%d)", name, K, kMaxStacks);
-    if (!isfinite(step)) MRISR_FAIL(MRISR_E_ARG, "%s: step %g is not finite", name, (double)step);
-    if (use_clamp != 0 && use_clamp != 1) MRISR_FAIL(MRISR_E_ARG, "%s: use_clamp %d (0 or 1)", name, use_clamp);
-    if (use_clamp && !isfinite(lo)) MRISR_FAIL(MRISR_E_ARG, "%s: the lower clamp %g is not finite", name, (double)lo);
+    if (const int rc = check_update_step(name, K, step, use_clamp, lo)) return rc;
     if (!isfinite(lambda) || lambda < 0.f) MRISR_FAIL(MRISR_E_ARG, "%s: lambda %g (finite, not negative)", name, (double)lambda);
     if (!(delta > 0.f)) MRISR_FAIL(MRISR_E_ARG, "%s: delta %g (positive, may be infinite)", name, (double)delta);
     StackPrior pr = {lambda, delta, {coeffs[0], coeffs[1], coeffs[2]}};
@@ -268,26 +215,11 @@ extern "C" int mrisr_f32_volume_stack_update_reg(const float* x, int X, int Y, i
     const double bound = (double)step * (double)lambda * (((double)pr.c[0] + (double)pr.c[1]) + (double)pr.c[2]);
     if (!(bound <= 0.5))
         MRISR_FAIL(MRISR_E_ARG, "%s: step * lambda * (c_0 + c_1 + c_2) = %g breaks the stability bound <= 0.5", name, bound);
-    if ((workspace == nullptr) != (stats_rows == nullptr)) MRISR_FAIL(MRISR_E_ARG, "%s: workspace and stats_rows go together", name);
     BrickGrid grid;
-    if (const int rc = check_field_volume(name, X, Y, Z, &grid)) return rc;
-    if (!aligned_to(x, 4) || !aligned_to(out, 4) || !aligned_to(workspace, 8) || !aligned_to(stats_rows, 8))
-        MRISR_FAIL(MRISR_E_ARG, "%s: misaligned pointer", name);
+    if (const int rc = check_update_volume(name, x, X, Y, Z, out, workspace, stats_rows, &grid)) return rc;
     if (out == x) MRISR_FAIL(MRISR_E_ARG, "%s: out must differ from x (the neighbours are read before the update)", name);
-    StackViews v = {};
-    for (int s = 0; s < K; ++s) {
-        const mrisr_stack_view& in = views[s];
-        if (!in.data) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: null pointer", name, s);
-        if (!aligned_to(in.data, 4)) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: misaligned pointer", name, s);
-        if (in.data == out || (const void*)in.data == (const void*)cover)
-            MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: out and cover must be buffers of their own", name, s);
-        if (const int rc = check_matrix(name, in.m, v.m[s])) return rc;
-        BrickGrid sg;
-        if (const int rc = check_field_volume(name, in.nx, in.ny, in.nz, &sg)) return rc;
-        v.data[s] = in.data;
-        v.n[s][0] = in.nx, v.n[s][1] = in.ny, v.n[s][2] = in.nz;
-        v.nslots[s] = sg.nslots;
-    }
+    StackViews v;
+    if (const int rc = fill_stack_views(name, views, K, out, cover, &v)) return rc;
     if ((const void*)cover_in == (const void*)x || (const void*)cover_in == (const void*)out)
         MRISR_FAIL(MRISR_E_ARG, "%s: cover_in must be a buffer of its own", name);
     if (cover && ((const void*)cover == (const void*)x || (const void*)cover == (const void*)out || cover == cover_in))

@@ -38,16 +38,9 @@ Speed on an MI355X (``tools/stacks_bench.py --regularise``, 2026-10-20, 256^3 ou
 an iteration - 0.071 ms a residual launch, 0.19 ms the update - against 9.7 ms with torch's ``affine_grid`` + ``grid_sample``;
 regularised 0.50 ms an iteration, 0.23 ms the update launch (1.23 times the plain one), against 10.1 ms with torch.
 
-Slice-to-volume motion correction (``motion=MotionOptions(...)`` of ``combine_stacks_np`` / ``combine_stacks``; default off): a 2-D
-multi-slice stack is acquired slice by slice and the head moves in between, so every slice gets a rigid pose of its own.
-``slice_geometries``   the two matrices of ``stack_geometry`` per slice, from (S, 6) poses about the slices' centres (S <= 256).
-``stack_residual_slices_np``, ``simulate_stack_slices_np``, ``stack_update_slices_np``   the two projections with a matrix per slice; the
-                      update weights the slices near a voxel by ``1 - |z - s|``, leaves gaps uncovered and normalises overlaps.
-``slice_cost_np``, ``ncc_from_sums``, ``slice_compass_search``, ``register_slices_np``   the cost of up to 13 candidate poses of every
-                      slice (six float64 sums each), its NCC, and the compass search of ``volume_register`` for all slices at once.
-``stack_residual_slices``, ``stack_update_slices``, ``slice_cost``, ``register_slices``   the device path (``csrc/volume_slices.hip``): the
-                      projections bit for bit; the sums within 1e-12 and the same bits on every run; one device-to-host read per
-                      search iteration.  Measured quality and speed: README, DESIGN.md section 7.
+Slice-to-volume motion correction (``motion=volume_slices.MotionOptions(...)`` of ``combine_stacks_np`` / ``combine_stacks``; default
+off) and everything with a pose per slice live in ``volume_slices.py``, which imports this module; the two ``combine_stacks`` reach it
+through an import inside the function, under ``if motion is not None``.
 
 Not built: a 26-neighbour or true total-variation prior; an automatic choice of lambda; the regulariser together with per-slice
 poses (``NotImplementedError``); leave-one-stack-out targets for the slice registration (the estimate includes the stack itself);
@@ -69,9 +62,6 @@ from .volume_reslice import taps_np, weighted_sum_np
 
 MAX_STACKS = 8
 MAX_SAMPLES = 16
-MAX_SLICES = 256                 # per-slice poses: the slices of one stack
-MAX_CANDIDATES = 13              # poses of a slice scored in one launch: a point and its 12 compass neighbours
-COST_STRIDES = (1, 2, 4)
 PROFILES = ("box", "gaussian")
 DEFAULT_ITERATIONS = 8
 FWHM_PER_SIGMA = 2.0 * math.sqrt(2.0 * math.log(2.0))
@@ -177,19 +167,24 @@ def default_output_grid(affines, shapes, spacing=None):
     return respaced_grid(box, extent, (spacing,) * 3)
 
 
+def _check_slice_axis(axis, prefix="") -> int:
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not 0 <= axis <= 2:
+        raise ValueError(f"{prefix}the slice axis is 0, 1 or 2, got {axis!r}")
+    return int(axis)
+
+
 def _check_geometry(g, what) -> StackGeometry:
     if not isinstance(g, StackGeometry):
         raise ValueError(f"{what}: a stack's geometry is a StackGeometry (stack_geometry), got {type(g).__name__}")
     m, n = check_matrix(g.to_output), check_matrix(g.from_output)
-    if isinstance(g.slice_axis, bool) or not isinstance(g.slice_axis, (int, np.integer)) or not 0 <= g.slice_axis <= 2:
-        raise ValueError(f"{what}: the slice axis is 0, 1 or 2, got {g.slice_axis!r}")
+    axis = _check_slice_axis(g.slice_axis, f"{what}: ")
     o, w = np.asarray(g.offsets), np.asarray(g.weights)
     if o.dtype != np.float64 or w.dtype != np.float32 or o.ndim != 1 or o.shape != w.shape or not 1 <= o.size <= MAX_SAMPLES:
         raise ValueError(f"{what}: a profile is 1..{MAX_SAMPLES} float64 offsets and as many float32 weights, got {o.dtype} {o.shape} "
                          f"and {w.dtype} {w.shape}")
     if not (np.isfinite(o).all() and np.isfinite(w).all()):
         raise ValueError(f"{what}: a profile sample is not finite")
-    return StackGeometry(m, n, int(g.slice_axis), np.ascontiguousarray(o), np.ascontiguousarray(w))
+    return StackGeometry(m, n, axis, np.ascontiguousarray(o), np.ascontiguousarray(w))
 
 
 def stack_geometry(affine, affine_out, slice_axis=None, profile: str = "box", thickness_mm=None, samples=None, world=None) -> StackGeometry:
@@ -198,9 +193,7 @@ def stack_geometry(affine, affine_out, slice_axis=None, profile: str = "box", th
     ``default_profile_samples`` at the smallest output voxel size.  ``world`` (4 x 4): a rigid transform, reference world -> this
     stack's world (``volume_register.RigidResult.world`` with the reference as the fixed scan), folded into both matrices."""
     a, out = check_affine(affine, "affine"), check_affine(affine_out, "affine_out")
-    axis = default_slice_axis(a) if slice_axis is None else slice_axis
-    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not 0 <= axis <= 2:
-        raise ValueError(f"the slice axis is 0, 1 or 2, got {slice_axis!r}")
+    axis = default_slice_axis(a) if slice_axis is None else _check_slice_axis(slice_axis)
     spacing = float(voxel_sizes(a)[axis])
     thickness = spacing if thickness_mm is None else float(thickness_mm)
     if not (np.isfinite(thickness) and thickness > 0):
@@ -211,7 +204,7 @@ def stack_geometry(affine, affine_out, slice_axis=None, profile: str = "box", th
     if world is not None:
         w = check_affine(world, "world")
         out = w @ out                                                # output index -> this stack's world
-    return StackGeometry(grid_matrix(out, a), grid_matrix(a, out), int(axis), offsets, weights)
+    return StackGeometry(grid_matrix(out, a), grid_matrix(a, out), axis, offsets, weights)
 
 
 # ---------------------------------------------------------------- numpy specification
@@ -245,6 +238,11 @@ def _check_iterations(iterations) -> int:
 def _check_stack_count(n, what):
     if not 1 <= n <= MAX_STACKS:
         raise ValueError(f"{what}: 1..{MAX_STACKS} stacks are combined, got {n}")
+
+
+def _check_same_count(stacks, others, what, things="geometries"):
+    if len(others) != len(stacks):
+        raise ValueError(f"{what}: {len(stacks)} stacks and {len(others)} {things}")
 
 
 def regulariser_coeffs(affine_out) -> np.ndarray:
@@ -347,9 +345,37 @@ def _project_rows_np(x, g, rows, q0, shape):
     return acc, wsum
 
 
-def _project_np(x, g, shape):
-    """-> ``(acc, wsum)`` of ``stack_residual_np`` on a stack of ``shape``."""
-    return _project_rows_np(x, g, _matrix_rows(g.to_output), _index_axes(shape), shape)
+def _simulated_np(acc, wsum, fill=0.0):
+    """-> ``(m, ok)``: the simulated values of a projection, ``acc / wsum`` where ``wsum >= 0.5`` (``ok``) and ``fill`` elsewhere."""
+    ok = wsum >= np.float32(0.5)
+    m = np.full(acc.shape, np.float32(fill), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        m[ok] = acc[ok] / wsum[ok]
+    return m, ok
+
+
+def _residual_np(x, y, g, rows):
+    """``stack_residual_np`` through ``rows`` -> ``(r, (S, n))``."""
+    m, ok = _simulated_np(*_project_rows_np(x, g, rows, _index_axes(y.shape), y.shape))
+    r = np.zeros(y.shape, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        r[ok] = y[ok] - m[ok]
+    r64 = r[ok].astype(np.float64)
+    return r, (math.fsum(r64 * r64), int(ok.sum()))
+
+
+def _step_np(x, total, cnt, step, lo, prior=None):
+    """The tail of every update: ``x + step * (total / float32(cnt) [+ prior])`` where ``cnt > 0``, clamped from below at ``lo`` (None:
+    no clamp); ``x`` where no stack covers the voxel."""
+    out = x.copy()
+    hit = cnt > 0
+    with np.errstate(all="ignore"):
+        m = total[hit] / cnt[hit].astype(np.float32)
+        new = x[hit] + step * (m if prior is None else m + prior[hit])
+        if lo is not None:
+            new = np.where(new < lo, lo, new)
+    out[hit] = new
+    return out
 
 
 def simulate_stack_np(x, geometry: StackGeometry, stack_shape, fill: float = 0.0) -> np.ndarray:
@@ -358,12 +384,7 @@ def simulate_stack_np(x, geometry: StackGeometry, stack_shape, fill: float = 0.0
     x = _check_volume_np(x, "simulate_stack_np")
     g = _check_geometry(geometry, "simulate_stack_np")
     shape = check_shape(stack_shape, "stack_shape")
-    acc, wsum = _project_np(x, g, shape)
-    ok = wsum >= np.float32(0.5)
-    out = np.full(shape, np.float32(fill), dtype=np.float32)
-    with np.errstate(all="ignore"):
-        out[ok] = acc[ok] / wsum[ok]
-    return out
+    return _simulated_np(*_project_rows_np(x, g, _matrix_rows(g.to_output), _index_axes(shape), shape), fill)[0]
 
 
 def stack_residual_np(x, y, geometry: StackGeometry):
@@ -375,13 +396,7 @@ def stack_residual_np(x, y, geometry: StackGeometry):
     sum of ``float64(r)^2`` over them (each square is exact), correctly rounded (``math.fsum``)."""
     x, y = _check_volume_np(x, "stack_residual_np"), _check_volume_np(y, "stack_residual_np")
     g = _check_geometry(geometry, "stack_residual_np")
-    acc, wsum = _project_np(x, g, y.shape)
-    ok = wsum >= np.float32(0.5)
-    r = np.zeros(y.shape, dtype=np.float32)
-    with np.errstate(all="ignore"):
-        r[ok] = y[ok] - acc[ok] / wsum[ok]
-    r64 = r[ok].astype(np.float64)
-    return r, (math.fsum(r64 * r64), int(ok.sum()))
+    return _residual_np(x, y, g, _matrix_rows(g.to_output))
 
 
 def stack_update_np(x, residuals, geometries, step: float = 1.0, clamp=0.0, reg_lambda: float = 0.0, reg_delta: float = math.inf,
@@ -403,8 +418,7 @@ def stack_update_np(x, residuals, geometries, step: float = 1.0, clamp=0.0, reg_
     x = _check_volume_np(x, "stack_update_np")
     residuals, geometries = list(residuals), list(geometries)
     _check_stack_count(len(residuals), "stack_update_np")
-    if len(geometries) != len(residuals):
-        raise ValueError(f"stack_update_np: {len(residuals)} stacks and {len(geometries)} geometries")
+    _check_same_count(residuals, geometries, "stack_update_np")
     step, lo = _check_step(step), _check_clamp(clamp)
     lam, delta, coeffs = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
     q = _index_axes(x.shape)
@@ -416,16 +430,8 @@ def stack_update_np(x, residuals, geometries, step: float = 1.0, clamp=0.0, reg_
             if val.size:
                 total[inside] = total[inside] + val
                 cnt[inside] += 1
-        out = x.copy()
-        hit = cnt > 0
-        if lam > 0:
-            new = x[hit] + step * (total[hit] / cnt[hit].astype(np.float32) + lam * _regulariser_np(x, cnt, delta, coeffs)[hit])
-        else:
-            new = x[hit] + step * (total[hit] / cnt[hit].astype(np.float32))
-        if lo is not None:
-            new = np.where(new < lo, lo, new)
-        out[hit] = new
-    return out, cnt
+        prior = lam * _regulariser_np(x, cnt, delta, coeffs) if lam > 0 else None
+    return _step_np(x, total, cnt, step, lo, prior), cnt
 
 
 def _rms_table(sums, counts):
@@ -434,414 +440,32 @@ def _rms_table(sums, counts):
         return np.where(counts > 0, np.sqrt(sums / np.maximum(counts, 1)), 0.0)
 
 
-# ---------------------------------------------------------------- slice-to-volume motion: geometry and specification
+def _steps_np(stacks, geometries, step, clamp, reg=(0.0, math.inf, None)):
+    """The two steps of ``_reconstruct_np`` with one matrix per stack."""
+    def residual(x, k):
+        return stack_residual_np(x, stacks[k], geometries[k])
 
-def _in_plane(axis):
-    return tuple(a for a in range(3) if a != axis)
+    def update(x, volumes, first):
+        return stack_update_np(x, volumes, geometries, 1.0, clamp) if first else stack_update_np(x, volumes, geometries, step, clamp, *reg)
 
-
-def _check_table(table, slices, what) -> np.ndarray:
-    t = np.asarray(table, dtype=np.float64)
-    if t.shape != (slices, 3, 4) or not np.isfinite(t).all():
-        raise ValueError(f"{what}: the per-slice matrices must be ({slices}, 3, 4) and finite, got shape {t.shape}")
-    return np.ascontiguousarray(t)
+    return residual, update
 
 
-def _check_slice_count(slices, what) -> int:
-    if not 1 <= slices <= MAX_SLICES:
-        raise ValueError(f"{what}: per-slice poses take stacks of 1..{MAX_SLICES} slices, got {slices}")
-    return int(slices)
-
-
-def slice_centres(affine, stack_shape, slice_axis) -> np.ndarray:
-    """(S, 3) float64: the world position of the centre of every slice - index ``(n - 1) / 2`` in the plane, ``s`` along the axis."""
-    a, shape = check_affine(affine, "affine"), check_shape(stack_shape, "stack_shape")
-    idx = np.tile((np.asarray(shape, dtype=np.float64) - 1.0) / 2.0, (shape[slice_axis], 1))
-    idx[:, slice_axis] = np.arange(shape[slice_axis], dtype=np.float64)
-    return idx @ a[:3, :3].T + a[:3, 3]
-
-
-def slice_geometries(affine, affine_out, stack_shape, slice_axis, params, world=None):
-    """-> ``(to_output, from_output)``, both (S, 3, 4) float64: ``stack_geometry``'s two matrices with a rigid pose per slice.
-    ``params`` (S, 6): ``(tx, ty, tz, rx, ry, rz)`` of slice ``s`` in mm and degrees; ``W_s = volume_register.rigid_world(params[s],
-    centre_s)`` about the world position of the slice's centre is folded as ``stack_geometry`` folds ``world``:
-    ``out_s = W_s @ world @ affine_out``, ``M_s = grid_matrix(out_s, affine)``, ``N_s = grid_matrix(affine, out_s)``.  ``params = 0``
-    gives the stack's own matrices to the last bit, S times.  More than 256 slices: ``ValueError``."""
-    from .volume_register import rigid_world
-    a, out = check_affine(affine, "affine"), check_affine(affine_out, "affine_out")
-    shape = check_shape(stack_shape, "stack_shape")
-    if isinstance(slice_axis, bool) or not isinstance(slice_axis, (int, np.integer)) or not 0 <= slice_axis <= 2:
-        raise ValueError(f"the slice axis is 0, 1 or 2, got {slice_axis!r}")
-    S = _check_slice_count(shape[slice_axis], "slice_geometries")
-    params = np.asarray(params, dtype=np.float64)
-    if params.shape != (S, 6) or not np.isfinite(params).all():
-        raise ValueError(f"slice_geometries: the parameters are ({S}, 6) and finite, got shape {params.shape}")
-    if world is not None:
-        out = check_affine(world, "world") @ out
-    centres = slice_centres(a, shape, int(slice_axis))
-    to_output, from_output = np.empty((S, 3, 4)), np.empty((S, 3, 4))
-    for s in range(S):
-        out_s = rigid_world(params[s], centres[s]) @ out
-        to_output[s], from_output[s] = grid_matrix(out_s, a), grid_matrix(a, out_s)
-    return to_output, from_output
-
-
-def _project_slices_np(x, g, shape, to_output_s):
-    grid = [1, 1, 1]
-    grid[g.slice_axis] = shape[g.slice_axis]
-    return _project_rows_np(x, g, _table_rows(to_output_s, grid), _index_axes(shape), shape)
-
-
-def simulate_stack_slices_np(x, geometry: StackGeometry, stack_shape, to_output_s, fill: float = 0.0) -> np.ndarray:
-    """``simulate_stack_np`` with the voxels of slice ``s`` going through ``to_output_s[s]`` (S, 3, 4) in place of ``M``."""
-    x, g = _check_volume_np(x, "simulate_stack_slices_np"), _check_geometry(geometry, "simulate_stack_slices_np")
-    shape = check_shape(stack_shape, "stack_shape")
-    table = _check_table(to_output_s, _check_slice_count(shape[g.slice_axis], "simulate_stack_slices_np"), "simulate_stack_slices_np")
-    acc, wsum = _project_slices_np(x, g, shape, table)
-    ok = wsum >= np.float32(0.5)
-    out = np.full(shape, np.float32(fill), dtype=np.float32)
-    with np.errstate(all="ignore"):
-        out[ok] = acc[ok] / wsum[ok]
-    return out
-
-
-def stack_residual_slices_np(x, y, geometry: StackGeometry, to_output_s):
-    """``stack_residual_np`` -> ``(r, (S, n))`` with the voxels of slice ``s`` using ``to_output_s[s]`` (S, 3, 4) in place of ``M``:
-    the same operations voxel by voxel, so equal tables reproduce ``stack_residual_np`` bit for bit."""
-    x, y = _check_volume_np(x, "stack_residual_slices_np"), _check_volume_np(y, "stack_residual_slices_np")
-    g = _check_geometry(geometry, "stack_residual_slices_np")
-    table = _check_table(to_output_s, _check_slice_count(y.shape[g.slice_axis], "stack_residual_slices_np"), "stack_residual_slices_np")
-    acc, wsum = _project_slices_np(x, g, y.shape, table)
-    ok = wsum >= np.float32(0.5)
-    r = np.zeros(y.shape, dtype=np.float32)
-    with np.errstate(all="ignore"):
-        r[ok] = y[ok] - acc[ok] / wsum[ok]
-    r64 = r[ok].astype(np.float64)
-    return r, (math.fsum(r64 * r64), int(ok.sum()))
-
-
-def _not_built_with_motion(reg_lambda, what):
-    if float(reg_lambda) != 0.0:
-        raise NotImplementedError(f"{what}: the regulariser (reg_lambda > 0) together with per-slice poses is not built")
-
-
-def stack_update_slices_np(x, residuals, geometries, from_output_s, step: float = 1.0, clamp=0.0, reg_lambda: float = 0.0):
-    """-> ``(x', cnt)``: ``stack_update_np`` with a pose per slice.  ``from_output_s[k]`` (S_k, 3, 4): ``N_{k,s}``.  For every output
-    voxel ``q`` and stack ``k`` ascending, from ``acc = +0``, ``wk = +0`` (float32) and for ``s = 0 .. S_k - 1`` ascending:
-    ``p = N_{k,s} q`` (the coordinate rule of ``stack_residual_np``); ``z = p[slice_axis]``, ``d = |z - s|`` in float64; the slice is
-    skipped unless ``d < 1`` and both in-plane coordinates lie in ``[-0.5, n - 0.5]``; else ``w = float32(1 - d)`` (the difference in
-    float64), ``g`` = the bilinear gather of slice ``s`` of the residual at the two in-plane coordinates (``taps_np(..., "linear")``,
-    ``weighted_sum_np``, the higher in-plane axis reduced first), ``acc = acc + w g``, ``wk = wk + w``.  The stack covers the voxel
-    when ``wk >= 0.5``: ``sum = sum + acc / wk``, ``cnt += 1``.  The step, the clamp and the uncovered voxels: ``stack_update_np``.
-
-    With equal matrices this is ``stack_update_np`` up to rounding: ``wk`` sums to 1 between two slices, the border slice alone is
-    replicated, and ``wk < 0.5`` is the inside test along the slice axis.  With motion, gaps between slices stay uncovered and
-    overlapping slices are normalised.  ``reg_lambda > 0`` is not built here: ``NotImplementedError``."""
-    _not_built_with_motion(reg_lambda, "stack_update_slices_np")
-    x = _check_volume_np(x, "stack_update_slices_np")
-    residuals, geometries, tables = list(residuals), list(geometries), list(from_output_s)
-    _check_stack_count(len(residuals), "stack_update_slices_np")
-    if len(geometries) != len(residuals) or len(tables) != len(residuals):
-        raise ValueError(f"stack_update_slices_np: {len(residuals)} stacks, {len(geometries)} geometries and {len(tables)} tables")
-    step, lo = _check_step(step), _check_clamp(clamp)
-    q = _index_axes(x.shape)
-    total, cnt = np.zeros(x.shape, dtype=np.float32), np.zeros(x.shape, dtype=np.uint8)
-    with np.errstate(all="ignore"):
-        for k, (r, g, table) in enumerate(zip(residuals, geometries, tables)):
-            what = f"stack_update_slices_np: stack {k}"
-            r, g = _check_volume_np(r, what), _check_geometry(g, what)
-            axis, (a, b) = g.slice_axis, _in_plane(g.slice_axis)
-            table = _check_table(table, _check_slice_count(r.shape[axis], what), what)
-            acc, wk = np.zeros(x.shape, dtype=np.float32), np.zeros(x.shape, dtype=np.float32)
-            for s in range(r.shape[axis]):
-                rows = _matrix_rows(table[s])
-                d = np.abs(np.broadcast_to(_coordinate_np(rows[axis], q), x.shape) - float(s))
-                ok = d < 1.0
-                if not ok.any():
-                    continue
-                pa, pb = (np.broadcast_to(_coordinate_np(rows[c], q), x.shape) for c in (a, b))
-                ok = ok & (pa >= -0.5) & (pa <= r.shape[a] - 0.5) & (pb >= -0.5) & (pb <= r.shape[b] - 0.5)
-                if not ok.any():
-                    continue
-                w = (1.0 - d[ok]).astype(np.float32)
-                (ia, wa), (ib, wb) = taps_np(pa[ok], r.shape[a], "linear"), taps_np(pb[ok], r.shape[b], "linear")
-                plane = np.take(r, s, axis=axis)
-                val = weighted_sum_np(wa, [weighted_sum_np(wb, [plane[u, v] for v in ib]) for u in ia])
-                acc[ok] = acc[ok] + w * val
-                wk[ok] = wk[ok] + w
-            hit = wk >= np.float32(0.5)
-            total[hit] = total[hit] + acc[hit] / wk[hit]
-            cnt[hit] += 1
-        out = x.copy()
-        hit = cnt > 0
-        new = x[hit] + step * (total[hit] / cnt[hit].astype(np.float32))
-        if lo is not None:
-            new = np.where(new < lo, lo, new)
-        out[hit] = new
-    return out, cnt
-
-
-def _check_cost_args(shape, axis, cand_to_output, stride, what):
-    S = _check_slice_count(shape[axis], what)
-    cand = np.asarray(cand_to_output, dtype=np.float64)
-    if cand.ndim != 4 or cand.shape[0] != S or not 1 <= cand.shape[1] <= MAX_CANDIDATES or cand.shape[2:] != (3, 4) \
-            or not np.isfinite(cand).all():
-        raise ValueError(f"{what}: the candidates are ({S}, 1..{MAX_CANDIDATES}, 3, 4) and finite, got shape {cand.shape}")
-    if stride not in COST_STRIDES:
-        raise ValueError(f"{what}: stride must be one of {COST_STRIDES}, got {stride!r}")
-    return np.ascontiguousarray(cand), int(stride)
-
-
-def strided_slice_count(shape, slice_axis, stride) -> int:
-    """The voxels of one slice whose two in-plane indices are multiples of ``stride``."""
-    a, b = _in_plane(slice_axis)
-    return -(-int(shape[a]) // stride) * -(-int(shape[b]) // stride)
-
-
-def slice_cost_np(x, y, geometry: StackGeometry, cand_to_output, stride: int = 1) -> np.ndarray:
-    """-> (S, C, 6) float64.  For slice ``s`` and candidate ``c`` (``C <= 13``): over the voxels of the slice whose two in-plane indices
-    are multiples of ``stride`` (1, 2 or 4), simulated as ``m = acc / wsum`` through ``cand_to_output[s, c]`` with the profile
-    (``stack_residual_np``'s forward model) and kept where ``wsum >= 0.5``: ``n, sum y, sum m, sum y^2, sum m^2, sum y m`` - the
-    products formed in float64 (exact), the sums correctly rounded (``math.fsum``)."""
-    x, y = _check_volume_np(x, "slice_cost_np"), _check_volume_np(y, "slice_cost_np")
-    g = _check_geometry(geometry, "slice_cost_np")
-    cand, stride = _check_cost_args(y.shape, g.slice_axis, cand_to_output, stride, "slice_cost_np")
-    S, C = cand.shape[:2]
-    a, b = _in_plane(g.slice_axis)
-    ia, ib = np.arange(0, y.shape[a], stride), np.arange(0, y.shape[b], stride)
-    shape = (S, C, ia.size, ib.size)
-    q = [None, None, None]
-    q[g.slice_axis] = np.arange(S, dtype=np.float64).reshape(S, 1, 1, 1)
-    q[a], q[b] = ia.astype(np.float64).reshape(1, 1, -1, 1), ib.astype(np.float64).reshape(1, 1, 1, -1)
-    acc, wsum = _project_rows_np(x, g, _table_rows(cand, (S, C, 1, 1)), q, shape)
-    ok = wsum >= np.float32(0.5)
-    with np.errstate(all="ignore"):
-        m = np.where(ok, acc / np.where(ok, wsum, np.float32(1)), np.float32(0)).astype(np.float64)
-    ys = np.moveaxis(y, g.slice_axis, 0)[:, ::stride, ::stride].astype(np.float64)      # (S, rows, cols), the lower in-plane axis first
-    out = np.zeros((S, C, 6))
-    for s in range(S):
-        for c in range(C):
-            keep = ok[s, c]
-            yv, mv = ys[s][keep], m[s, c][keep]
-            out[s, c] = (yv.size, math.fsum(yv), math.fsum(mv), math.fsum(yv * yv), math.fsum(mv * mv), math.fsum(yv * mv))
-    return out
-
-
-def ncc_from_sums(sums, min_count=1) -> np.ndarray:
-    """The normalised cross-correlation of ``y`` and ``m`` from ``(..., 6)`` sums ``n, sum y, sum m, sum y^2, sum m^2, sum y m``, in
-    float64: ``cov / sqrt(var_y var_m)`` with ``var_y = sum y^2 - (sum y)^2 / n`` and so on; ``-inf`` where ``n < min_count`` (an
-    array broadcasts), ``n < 1`` or a variance is not positive.  The specification path and the device path share it."""
-    sums = np.asarray(sums, dtype=np.float64)
-    n, sy, sm, syy, smm, sym = (sums[..., e] for e in range(6))
-    with np.errstate(all="ignore"):
-        nn = np.maximum(n, 1.0)
-        vy, vm, cov = syy - sy * sy / nn, smm - sm * sm / nn, sym - sy * sm / nn
-        ok = (n >= min_count) & (n >= 1) & (vy > 0) & (vm > 0)
-        return np.where(ok, cov / np.sqrt(np.where(ok, vy * vm, 1.0)), -np.inf)
-
-
-def slice_compass_search(cost_batch, p0, levels, limits, active=None, max_iterations=1000):
-    """``volume_register.compass_search`` for all the slices of a stack at once -> ``(params (S, 6), best (S,), start (S,), trace)``.
-    Every slice has its own point, step vector and best value; ONE ``cost_batch(cands (S, C, 6), stride) -> (S, C)`` call per
-    iteration covers them all.  A level is ``(stride, step[6], min_translation_step)``.  At each level every slice's point is scored
-    (``C = 1``; ``start`` is that of the first level); then, while a live slice is left, the 12 candidates ``p +- step[a] e_a`` of
-    every slice - axis ascending, ``+`` before ``-`` - are scored in one call; a candidate beyond ``limits = (mm, deg)`` in any
-    component scores ``-inf``; a slice moves to its first argmax only if that is strictly greater than its best, otherwise its six
-    steps halve.  A slice is live while it is active and its translation step is at least the level's stop; the others resubmit
-    their point 12 times and ignore the values.  Inactive slices (``active`` (S,) bool, None: all active) keep ``p0``.  ``trace``:
-    one dict per call - ``level``, ``stride``, ``kind``, ``p``, ``step``, ``values``, ``accepted`` (per slice, -1: none), ``best``."""
-    p = np.array(p0, dtype=np.float64)
-    if p.ndim != 2 or p.shape[1] != 6 or not np.isfinite(p).all():
-        raise ValueError(f"slice_compass_search: the start is (S, 6) and finite, got shape {p.shape}")
-    S = p.shape[0]
-    active = np.ones(S, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(S).copy()
-    lim = np.array([float(limits[0])] * 3 + [float(limits[1])] * 3)
-    if not (lim > 0).all():
-        raise ValueError(f"slice_compass_search: the limits are two positive numbers (mm, degrees), got {limits!r}")
-    best, start, trace, rows = np.full(S, -np.inf), None, [], np.arange(S)
-    for li, (stride, step0, min_t) in enumerate(levels):
-        step0 = np.asarray(step0, dtype=np.float64)
-        if step0.shape != (6,) or not (step0 > 0).all() or not np.isfinite(step0).all() or not min_t > 0:
-            raise ValueError(f"level {li}: six positive steps and a positive stop, got {step0.tolist()} and {min_t}")
-        step = np.tile(step0, (S, 1))
-        best = np.asarray(cost_batch(p[:, None, :].copy(), stride), dtype=np.float64).reshape(S).copy()
-        start = best.copy() if start is None else start
-        trace.append({"level": li, "stride": stride, "kind": "start", "p": p.copy(), "step": step.copy(), "values": best[:, None].copy(),
-                      "accepted": np.full(S, -1), "best": best.copy()})
-        for _ in range(max_iterations):
-            live = active & (step[:, 0] >= min_t)
-            if not live.any():
-                break
-            cands = np.repeat(p[:, None, :], 12, axis=1)
-            for a in range(6):
-                cands[live, 2 * a, a] += step[live, a]
-                cands[live, 2 * a + 1, a] -= step[live, a]
-            vals = np.asarray(cost_batch(cands.copy(), stride), dtype=np.float64).reshape(S, 12)
-            vals = np.where((np.abs(cands) > lim).any(axis=2), -np.inf, vals)
-            j = np.argmax(vals, axis=1)                                   # the first of equal maxima
-            move = live & (vals[rows, j] > best)
-            entry = {"level": li, "stride": stride, "kind": "probe", "p": p.copy(), "step": step.copy(), "values": vals,
-                     "accepted": np.where(move, j, -1)}
-            p[move], best[move] = cands[move, j[move]], vals[move, j[move]]
-            step[live & ~move] /= 2
-            entry["best"] = best.copy()
-            trace.append(entry)
-    return p, best, start, trace
-
-
-def in_plane_voxel_size(affine, slice_axis) -> float:
-    """The mean of the two in-plane voxel sizes of a stack, in mm."""
-    return float(np.mean(voxel_sizes(affine)[list(_in_plane(slice_axis))]))
-
-
-def default_slice_levels(affine, slice_axis):
-    """``[(2, 2v x 3 + 2 deg x 3, v / 2), (1, v / 2 x 3 + 0.5 deg x 3, v / 8)]`` with ``v = in_plane_voxel_size``."""
-    v = in_plane_voxel_size(affine, slice_axis)
-    return [(2, (2 * v,) * 3 + (2.0,) * 3, 0.5 * v), (1, (0.5 * v,) * 3 + (0.5,) * 3, v / 8)]
-
-
-def active_slices(sums, min_contrast) -> np.ndarray:
-    """(S,) bool from the (S, 6) sums of the slices' current poses: a slice is active when the standard deviation of its ``y`` is at
-    least ``min_contrast`` times that of the pooled stack (air and the crown of the head fall below) and positive."""
-    sums = np.asarray(sums, dtype=np.float64)
-    n, sy, syy = sums[:, 0], sums[:, 1], sums[:, 3]
-    with np.errstate(all="ignore"):
-        sd = np.sqrt(np.maximum(syy - sy * sy / np.maximum(n, 1.0), 0.0) / np.maximum(n, 1.0))
-        N, SY, SYY = n.sum(), sy.sum(), syy.sum()
-        pooled = math.sqrt(max(SYY - SY * SY / max(N, 1.0), 0.0) / max(N, 1.0))
-    return (n > 0) & (sd > 0) & (sd >= float(min_contrast) * pooled)
-
-
-def slice_corner_displacement(params_a, params_b, affine, stack_shape, slice_axis) -> np.ndarray:
-    """(S,) float64: per slice, the largest distance in mm, over the four corner voxels of the slice, between their positions under
-    the poses ``params_a[s]`` and ``params_b[s]`` (``rigid_world`` about the slice's centre)."""
-    from .volume_register import rigid_world
-    a, shape = check_affine(affine, "affine"), check_shape(stack_shape, "stack_shape")
-    centres = slice_centres(a, shape, slice_axis)
-    pa, pb = np.asarray(params_a, dtype=np.float64), np.asarray(params_b, dtype=np.float64)
-    u, v = _in_plane(slice_axis)
-    out = np.zeros(shape[slice_axis])
-    for s in range(shape[slice_axis]):
-        idx = np.zeros((4, 4))
-        idx[:, 3], idx[:, slice_axis] = 1.0, s
-        idx[:, u], idx[:, v] = [0, 0, shape[u] - 1, shape[u] - 1], [0, shape[v] - 1, 0, shape[v] - 1]
-        world = a @ idx.T
-        d = ((rigid_world(pa[s], centres[s]) - rigid_world(pb[s], centres[s])) @ world)[:3]
-        out[s] = np.sqrt((d * d).sum(axis=0)).max()
-    return out
-
-
-class MotionOptions(NamedTuple):
-    """What ``combine_stacks(_np)(..., motion=...)`` needs to move single slices: the grids - the geometries alone do not say where a
-    slice's centre lies in the world - and the search's settings."""
-    affines: tuple                   # per stack: index -> world (4, 4)
-    affine_out: np.ndarray           # the output grid's index -> world
-    worlds: tuple = None             # per stack: None or the (4, 4) ``world`` folded into its geometry
-    rounds: int = 2
-    limit_mm: float = 10.0
-    limit_deg: float = 10.0
-    min_contrast: float = 0.1
-    levels: tuple = None             # per stack: the search levels; None: ``default_slice_levels``
-
-
-class SliceMotion(NamedTuple):
-    params: np.ndarray               # (S, 6) float64: tx, ty, tz (mm), rx, ry, rz (degrees) per slice
-    active: np.ndarray               # (S,) bool: the slices that were searched
-    start: np.ndarray                # (S,) float64: the cost (NCC) at the start, at the first level's stride
-    end: np.ndarray                  # (S,) float64: the cost after the search, at the last level's stride
-    trace: list
-
-
-def _check_motion(motion, count, what) -> MotionOptions:
-    if not isinstance(motion, MotionOptions):
-        raise ValueError(f"{what}: motion is a MotionOptions, got {type(motion).__name__}")
-    affines = tuple(check_affine(a, "affine") for a in motion.affines)
-    worlds = (None,) * count if motion.worlds is None else tuple(motion.worlds)
-    levels = (None,) * count if motion.levels is None else tuple(motion.levels)
-    if len(affines) != count or len(worlds) != count or len(levels) != count:
-        raise ValueError(f"{what}: motion needs one affine (and world, and list of levels) per stack ({count})")
-    if isinstance(motion.rounds, bool) or not isinstance(motion.rounds, (int, np.integer)) or motion.rounds < 0:
-        raise ValueError(f"{what}: motion rounds is an integer that is not negative, got {motion.rounds!r}")
-    if not (motion.limit_mm > 0 and motion.limit_deg > 0 and 0 <= motion.min_contrast < np.inf):
-        raise ValueError(f"{what}: the motion limits must be positive and min_contrast not negative")
-    return motion._replace(affines=affines, affine_out=check_affine(motion.affine_out, "affine_out"), worlds=worlds, levels=levels)
-
-
-def _register_slices(sums_of, shape, axis, affine, affine_out, world, params0, levels, limits, min_contrast) -> SliceMotion:
-    """The search of ``register_slices_np`` / ``register_slices``: ``sums_of(cand_to_output (S, C, 3, 4), stride) -> (S, C, 6)``."""
-    S = _check_slice_count(shape[axis], "register_slices")
-    p0 = np.zeros((S, 6)) if params0 is None else np.array(params0, dtype=np.float64)
-    levels = default_slice_levels(affine, axis) if levels is None else list(levels)
-
-    def sums(cands, stride):
-        tables = [slice_geometries(affine, affine_out, shape, axis, cands[:, c], world)[0] for c in range(cands.shape[1])]
-        return sums_of(np.stack(tables, axis=1), stride)
-
-    active = active_slices(sums(p0[:, None, :], levels[0][0])[:, 0], min_contrast)
-
-    def cost_batch(cands, stride):
-        return ncc_from_sums(sums(cands, stride), 0.25 * strided_slice_count(shape, axis, stride))
-
-    params, best, start, trace = slice_compass_search(cost_batch, p0, levels, limits, active)
-    return SliceMotion(params, active, start, best, trace)
-
-
-def register_slices_np(x, y, geometry: StackGeometry, affine, affine_out, params0=None, world=None, levels=None, limits=(10.0, 10.0),
-                       min_contrast: float = 0.1) -> SliceMotion:
-    """The specification of ``register_slices``: the pose of every slice of the stack ``y`` against the estimate ``x``.  The current
-    poses (``params0``, None: zeros) are scored first (``slice_cost_np`` at the first level's stride); ``active_slices`` of those sums
-    picks the slices to search; ``slice_compass_search`` maximises ``ncc_from_sums(slice_cost_np(...), min_count)`` over the poses,
-    ``min_count`` a quarter of a slice's strided voxel count, the candidates turned into matrices by ``slice_geometries``."""
-    x, y = _check_volume_np(x, "register_slices_np"), _check_volume_np(y, "register_slices_np")
-    g = _check_geometry(geometry, "register_slices_np")
-    return _register_slices(lambda cand, stride: slice_cost_np(x, y, g, cand, stride), y.shape, g.slice_axis, affine, affine_out, world,
-                            params0, levels, limits, min_contrast)
-
-
-def _motion_rounds(motion, stacks_shapes, geometries, register, rebuild):
-    """The rounds of ``combine_stacks(_np)`` with motion.  ``register(k, params_k, levels_k) -> SliceMotion`` against the current
-    estimate; ``rebuild(to_output_s, from_output_s)`` makes the estimate from scratch.  -> ``(params per stack, motion_cost, last)``:
-    ``motion_cost[round][k] = (mean cost of the active slices at the start, at the end)``; ``last``: the final round's SliceMotion."""
-    K = len(geometries)
-    params = [np.zeros((shape[g.slice_axis], 6)) for shape, g in zip(stacks_shapes, geometries)]
-    costs, last = [], [None] * K
-    for _ in range(motion.rounds):
-        row = []
-        for k in range(K):
-            last[k] = register(k, params[k], motion.levels[k])
-            act = last[k].active
-            finite = act & np.isfinite(last[k].start) & np.isfinite(last[k].end)
-            row.append((float(last[k].start[finite].mean()) if finite.any() else float("nan"),
-                        float(last[k].end[finite].mean()) if finite.any() else float("nan")))
-        params = [m.params for m in last]
-        costs.append(row)
-        tables = [slice_geometries(motion.affines[k], motion.affine_out, stacks_shapes[k], geometries[k].slice_axis, params[k], motion.worlds[k])
-                  for k in range(K)]
-        rebuild([t[0] for t in tables], [t[1] for t in tables])
-    return params, np.asarray(costs, dtype=np.float64).reshape(motion.rounds, K, 2), last
-
-
-def _reconstruct_np(stacks, geometries, shape_out, iterations, step, clamp, fill, on_iteration=None, reg=(0.0, math.inf, None), tables=None):
-    """The initial estimate and ``iterations`` updates -> ``(x, initial, sums, counts, cnt)``.  ``tables``: None, or the per-slice
-    ``(to_output_s, from_output_s)`` lists, which select the ``*_slices_np`` forms of both steps."""
-    x0 = np.full(shape_out, np.float32(fill), dtype=np.float32)
-    if tables is None:
-        x, cnt = stack_update_np(x0, stacks, geometries, 1.0, clamp)
-    else:
-        x, cnt = stack_update_slices_np(x0, stacks, geometries, tables[1], 1.0, clamp)
+def _reconstruct_np(stacks, shape_out, iterations, fill, residual, update, on_iteration=None):
+    """The initial estimate and ``iterations`` updates -> ``(x, initial, sums, counts, cnt)``, over a pair of steps (``_steps_np``, or
+    ``volume_slices._slice_steps_np`` with a pose per slice): ``residual(x, k) -> (r, (S, n))`` of stack ``k``; ``update(x, volumes,
+    first) -> (x', cnt)`` - ``first``: the initial estimate, from the stacks themselves with step 1 and never regularised."""
+    x, cnt = update(np.full(shape_out, np.float32(fill), dtype=np.float32), stacks, True)
     initial = x.copy()
     if on_iteration is not None:
         on_iteration(0, x)
     sums, counts = np.zeros((iterations, len(stacks))), np.zeros((iterations, len(stacks)), dtype=np.int64)
     for it in range(iterations):
         res = []
-        for k, (y, g) in enumerate(zip(stacks, geometries)):
-            r, (sums[it, k], counts[it, k]) = stack_residual_np(x, y, g) if tables is None else stack_residual_slices_np(x, y, g, tables[0][k])
+        for k in range(len(stacks)):
+            r, (sums[it, k], counts[it, k]) = residual(x, k)
             res.append(r)
-        if tables is None:
-            x = stack_update_np(x, res, geometries, step, clamp, *reg)[0]
-        else:
-            x = stack_update_slices_np(x, res, geometries, tables[1], step, clamp)[0]
+        x = update(x, res, False)[0]
         if on_iteration is not None:
             on_iteration(it + 1, x)
     return x, initial, sums, counts, cnt
@@ -856,34 +480,27 @@ def combine_stacks_np(stacks, geometries, shape_out, iterations: int = DEFAULT_I
     and after every update.  ``reg_lambda``, ``reg_delta``, ``reg_coeffs``: the regulariser of ``stack_update_np``, in the updates of
     the iterations alone - the initial estimate is never regularised.
 
-    ``motion`` (a ``MotionOptions``; None: everything above, the same operations as without the keyword): slice-to-volume motion
+    ``motion`` (a ``volume_slices.MotionOptions``; None: everything above, the same operations as without the keyword): slice-to-volume motion
     correction.  The reconstruction above is round 0.  Then ``motion.rounds`` times: (1) every stack's slices are registered to the
-    current estimate (``register_slices_np``, from the poses of the round before; the estimate includes the stack itself -
+    current estimate (``volume_slices.register_slices_np``, from the poses of the round before; the estimate includes the stack itself -
     leave-one-out is not built); (2) the estimate is rebuilt from scratch - initial estimate, then ``iterations`` - with
     ``stack_update_slices_np`` / ``stack_residual_slices_np`` on the new ``slice_geometries``.  ``volume``, ``initial``, ``rms``,
     ``counts`` and ``coverage`` are the last rebuild's; ``on_iteration`` sees round 0 alone.  With ``reg_lambda > 0``:
     ``NotImplementedError`` (not built)."""
     stacks, geometries = [_check_volume_np(y, "combine_stacks_np") for y in stacks], list(geometries)
     _check_stack_count(len(stacks), "combine_stacks_np")
-    if len(geometries) != len(stacks):
-        raise ValueError(f"combine_stacks_np: {len(stacks)} stacks and {len(geometries)} geometries")
+    _check_same_count(stacks, geometries, "combine_stacks_np")
     shape_out, iterations = check_shape(shape_out, "shape_out"), _check_iterations(iterations)
     _check_regulariser(_check_step(step), reg_lambda, reg_delta, reg_coeffs)
     if motion is not None:
-        _not_built_with_motion(reg_lambda, "combine_stacks_np")
-        motion = _check_motion(motion, len(stacks), "combine_stacks_np")
+        from . import volume_slices
+        motion = volume_slices._check_motion(motion, len(stacks), reg_lambda, "combine_stacks_np")
         geometries = [_check_geometry(g, f"combine_stacks_np: stack {k}") for k, g in enumerate(geometries)]
-    state = list(_reconstruct_np(stacks, geometries, shape_out, iterations, step, clamp, fill, on_iteration, (reg_lambda, reg_delta, reg_coeffs)))
+    state = list(_reconstruct_np(stacks, shape_out, iterations, fill, *_steps_np(stacks, geometries, step, clamp, (reg_lambda, reg_delta, reg_coeffs)),
+                                 on_iteration))
     extra = ()
     if motion is not None:
-        def register(k, params, levels):
-            return register_slices_np(state[0], stacks[k], geometries[k], motion.affines[k], motion.affine_out, params, motion.worlds[k],
-                                      levels, (motion.limit_mm, motion.limit_deg), motion.min_contrast)
-
-        def rebuild(to_output_s, from_output_s):
-            state[:] = _reconstruct_np(stacks, geometries, shape_out, iterations, step, clamp, fill, tables=(to_output_s, from_output_s))
-
-        extra = _motion_rounds(motion, [y.shape for y in stacks], geometries, register, rebuild)
+        extra = volume_slices._motion_np(motion, state, stacks, geometries, shape_out, iterations, step, clamp, fill)
     x, initial, sums, counts, cnt = state
     return StackResult(x, initial, _rms_table(sums, counts), counts, np.bincount(cnt.reshape(-1), minlength=len(stacks) + 1).astype(np.int64),
                        *extra)
@@ -903,11 +520,14 @@ def _slots(device, count) -> torch.Tensor:
     return torch.empty(count * _region_bytes() // 8, dtype=torch.int64, device=device)
 
 
-def _residual(x, y, g, r, slots_ptr, stats_row):
+def _profile_args(g):
     T = g.offsets.size
+    return (L.C.c_double * T)(*g.offsets.tolist()), (L.C.c_float * T)(*g.weights.tolist()), T
+
+
+def _residual(x, y, g, r, slots_ptr, stats_row):
     L.call("mrisr_f32_volume_stack_residual", x.data_ptr(), *x.shape, y.data_ptr(), *y.shape, matrix_arg(g.to_output), g.slice_axis,
-           (L.C.c_double * T)(*g.offsets.tolist()), (L.C.c_float * T)(*g.weights.tolist()), T, r.data_ptr(), slots_ptr,
-           L.ptr(stats_row), L.stream_ptr(), nbytes=4 * (x.numel() + 2 * y.numel()))
+           *_profile_args(g), r.data_ptr(), slots_ptr, L.ptr(stats_row), L.stream_ptr(), nbytes=4 * (x.numel() + 2 * y.numel()))
 
 
 def _views_arg(volumes, geometries):
@@ -918,27 +538,40 @@ def _views_arg(volumes, geometries):
     return views
 
 
+def _step_args(step, lo):
+    """``step, use_clamp, lo`` of the update entry points."""
+    return float(step), int(lo is not None), 0.0 if lo is None else float(lo)
+
+
+def _update_bytes(x, volumes) -> int:
+    return 4 * (2 * x.numel() + sum(v.numel() for v in volumes))
+
+
 def _update(x, volumes, geometries, step, lo, out, cover, slots, stats_rows):
-    L.call("mrisr_f32_volume_stack_update", x.data_ptr(), *x.shape, _views_arg(volumes, geometries), len(volumes), float(step),
-           int(lo is not None), 0.0 if lo is None else float(lo), out.data_ptr(), L.ptr(cover), L.ptr(slots), L.ptr(stats_rows),
-           L.stream_ptr(), nbytes=4 * (2 * x.numel() + sum(v.numel() for v in volumes)))
+    L.call("mrisr_f32_volume_stack_update", x.data_ptr(), *x.shape, _views_arg(volumes, geometries), len(volumes), *_step_args(step, lo),
+           out.data_ptr(), L.ptr(cover), L.ptr(slots), L.ptr(stats_rows), L.stream_ptr(), nbytes=_update_bytes(x, volumes))
 
 
 def _update_reg(x, volumes, geometries, step, lo, reg, coverage, out, cover, slots, stats_rows):
     lam, delta, coeffs = reg
-    L.call("mrisr_f32_volume_stack_update_reg", x.data_ptr(), *x.shape, _views_arg(volumes, geometries), len(volumes), float(step),
-           int(lo is not None), 0.0 if lo is None else float(lo), float(lam), float(delta), (L.C.c_float * 3)(*coeffs.tolist()),
-           coverage.data_ptr(), out.data_ptr(), L.ptr(cover), L.ptr(slots), L.ptr(stats_rows), L.stream_ptr(),
-           nbytes=4 * (2 * x.numel() + sum(v.numel() for v in volumes)) + x.numel())
+    L.call("mrisr_f32_volume_stack_update_reg", x.data_ptr(), *x.shape, _views_arg(volumes, geometries), len(volumes), *_step_args(step, lo),
+           float(lam), float(delta), (L.C.c_float * 3)(*coeffs.tolist()), coverage.data_ptr(), out.data_ptr(), L.ptr(cover), L.ptr(slots),
+           L.ptr(stats_rows), L.stream_ptr(), nbytes=_update_bytes(x, volumes) + x.numel())
+
+
+def _check_pair(x, y, what):
+    """The estimate and a stack of one entry: two float32 CUDA volumes on one device."""
+    x, y = _check_tensor(x, what), _check_tensor(y, what)
+    if x.device != y.device:
+        raise ValueError(f"{what}: the estimate and the stack must share a device, got {x.device} and {y.device}")
+    return x, y
 
 
 def stack_residual(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, out=None):
     """The device path of ``stack_residual_np`` -> ``(r, S, n)``: ``r`` bit for bit; ``S`` (0-d float64) within one spacing of the
     specification's sum and the same bits on every run, ``n`` (0-d int64) equal - both stay on the device.  Two launches (the
     residual; one wave that adds the fixed slots), no device-to-host read.  ``out``: another tensor like ``y``."""
-    x, y = _check_tensor(x, "stack_residual"), _check_tensor(y, "stack_residual")
-    if x.device != y.device:
-        raise ValueError(f"stack_residual: the estimate and the stack must share a device, got {x.device} and {y.device}")
+    x, y = _check_pair(x, y, "stack_residual")
     g = _check_geometry(geometry, "stack_residual")
     r = out_like(out, y, (x, y), "stack_residual")
     row = torch.empty(2, dtype=torch.int64, device=x.device)
@@ -949,8 +582,7 @@ def stack_residual(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, ou
 def _check_stacks(volumes, geometries, device, what):
     volumes, geometries = list(volumes), list(geometries)
     _check_stack_count(len(volumes), what)
-    if len(geometries) != len(volumes):
-        raise ValueError(f"{what}: {len(volumes)} stacks and {len(geometries)} geometries")
+    _check_same_count(volumes, geometries, what)
     volumes = [_check_tensor(v, f"{what}: stack {k}") for k, v in enumerate(volumes)]
     if any(v.device != device for v in volumes):
         raise ValueError(f"{what}: every stack must lie on {device}")
@@ -1007,6 +639,7 @@ class StackWorkspace:
         self.stats = torch.zeros((max(self.iterations, 1), len(self.stack_shapes), 2), dtype=torch.int64, device=device)
         self.to_tables = self.from_tables = self.cost = None
         if motion:
+            from .volume_slices import MAX_SLICES, SliceCostWorkspace
             self.to_tables = [torch.zeros((MAX_SLICES, 12), dtype=torch.float64, device=device) for _ in self.stack_shapes]
             self.from_tables = [torch.zeros((MAX_SLICES, 12), dtype=torch.float64, device=device) for _ in self.stack_shapes]
             self.cost = SliceCostWorkspace(device)
@@ -1015,19 +648,55 @@ class StackWorkspace:
         return self.slots.data_ptr() + k * _region_bytes()
 
 
-def _iterate(ws, stacks, geometries, first, count, step, lo, reg=None):
-    """``count`` iterations from row ``first``, ``K + 1`` launches each: the residual of every stack against the estimate, then the
-    update in place, whose first wave adds the residuals' slots into the iteration's stats rows.  Nothing is allocated.  ``reg``
-    (``_check_regulariser``): the regularised update, from ``ws.x`` into ``ws.x2`` in the even iterations and back in the odd ones,
-    with the coverage counts in ``ws.cover``."""
-    for it in range(first, first + count):
-        x, out = (ws.x, ws.x) if reg is None else ((ws.x, ws.x2) if it % 2 == 0 else (ws.x2, ws.x))
-        for k, (y, g) in enumerate(zip(stacks, geometries)):
-            _residual(x, y, g, ws.residuals[k], ws.region(k), None)
-        if reg is None:
-            _update(x, ws.residuals, geometries, step, lo, out, None, ws.slots, ws.stats[it])
+def _launchers(ws, stacks, geometries, step, lo, reg=None):
+    """-> ``(residual, update, alternate)`` for ``_iterate`` and ``_reconstruct``, with one matrix per stack.  ``residual(x, k)``: the
+    residual of stack ``k`` against ``x`` into ``ws.residuals[k]`` and region ``k`` of the slots.  ``update(x, out, rows)``: the update
+    from the residuals, whose first wave adds those slots into the stats ``rows``; ``rows`` None: the initial estimate - the stacks
+    themselves, step 1, the coverage counts into ``ws.cover``.  ``reg`` (``_check_regulariser``): the regularised update, which reads
+    ``ws.cover`` and cannot run in place, so the iterations alternate between the two estimates."""
+    def residual(x, k):
+        _residual(x, stacks[k], geometries[k], ws.residuals[k], ws.region(k), None)
+
+    def update(x, out, rows):
+        if rows is None:
+            _update(x, stacks, geometries, 1.0, lo, out, ws.cover, None, None)
+        elif reg is None:
+            _update(x, ws.residuals, geometries, step, lo, out, None, ws.slots, rows)
         else:
-            _update_reg(x, ws.residuals, geometries, step, lo, reg, ws.cover, out, None, ws.slots, ws.stats[it])
+            _update_reg(x, ws.residuals, geometries, step, lo, reg, ws.cover, out, None, ws.slots, rows)
+
+    return residual, update, reg is not None
+
+
+def _iterate(ws, first, count, residual, update, alternate):
+    """``count`` iterations from row ``first``, ``K + 1`` launches each: the residual of every stack against the estimate, then the
+    update.  Nothing is allocated.  ``alternate``: from ``ws.x`` into ``ws.x2`` in the even iterations and back in the odd ones; else
+    in place."""
+    for it in range(first, first + count):
+        x, out = (ws.x, ws.x) if not alternate else ((ws.x, ws.x2) if it % 2 == 0 else (ws.x2, ws.x))
+        for k in range(len(ws.residuals)):
+            residual(x, k)
+        update(x, out, ws.stats[it])
+
+
+def _reconstruct(ws, iterations, fill, graph, residual, update, alternate):
+    """The estimate from scratch in the workspace -> the initial estimate (a clone): fill, the initial update with the coverage
+    counts, then ``iterations`` of ``_iterate`` - with ``graph`` captured into a HIP graph and replayed, after one eager iteration as
+    a warm-up (it loads the code objects) whose result is undone."""
+    ws.x.fill_(float(fill))
+    update(ws.x, ws.x, None)
+    initial = ws.x.clone()
+    if graph and iterations:
+        _iterate(ws, 0, 1, residual, update, alternate)
+        ws.x.copy_(initial)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            _iterate(ws, 0, iterations, residual, update, alternate)
+        g.replay()
+    else:
+        _iterate(ws, 0, iterations, residual, update, alternate)
+    return initial
 
 
 def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITERATIONS, step: float = 1.0, clamp=0.0, fill: float = 0.0,
@@ -1042,8 +711,8 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
     ``reg_lambda > 0`` the iterations run the regularised kernel between the two estimates of a ``StackWorkspace(...,
     regularised=True)`` - still ``K + 1`` launches and one read; with 0 the kernels and the bits are those without the keywords.
 
-    ``motion`` (a ``MotionOptions``; None: the launches and the bits of a call without the keyword): the rounds of
-    ``combine_stacks_np`` with ``register_slices`` - one launch pair and ONE device-to-host read of ``S C 6`` doubles per search
+    ``motion`` (a ``volume_slices.MotionOptions``; None: the launches and the bits of a call without the keyword): the rounds of
+    ``combine_stacks_np`` with ``volume_slices.register_slices`` - one launch pair and ONE device-to-host read of ``S C 6`` doubles per search
     iteration - and the per-slice kernels of ``csrc/volume_slices.hip``; the workspace is a ``StackWorkspace(..., motion=True)``.  Every
     round's rebuild is ``K + 1`` launches an iteration on tables that lie in the workspace, and with ``graph`` is captured and
     replayed on its own - the same bits as eager.  The poses are not bit-compared with the specification's (near-ties of the cost at
@@ -1057,8 +726,8 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
     reg = _check_regulariser(step, reg_lambda, reg_delta, reg_coeffs)
     reg = reg if reg[0] > 0 else None
     if motion is not None:
-        _not_built_with_motion(reg_lambda, "combine_stacks")
-        motion = _check_motion(motion, len(stacks), "combine_stacks")
+        from . import volume_slices
+        motion = volume_slices._check_motion(motion, len(stacks), reg_lambda, "combine_stacks")
     if workspace is None:
         workspace = StackWorkspace(shape_out, [y.shape for y in stacks], first.device, iterations, regularised=reg is not None,
                                    motion=motion is not None)
@@ -1072,32 +741,10 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
     if motion is not None and ws.cost is None:
         raise ValueError("combine_stacks: motion needs a workspace with the tables and the cost buffers: StackWorkspace(..., motion=True)")
     K = len(stacks)
-    ws.x.fill_(float(fill))
-    _update(ws.x, stacks, geometries, 1.0, lo, ws.x, ws.cover, None, None)
-    initial = ws.x.clone()
-    if graph and iterations:
-        _iterate(ws, stacks, geometries, 0, 1, step, lo, reg)
-        ws.x.copy_(initial)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            _iterate(ws, stacks, geometries, 0, iterations, step, lo, reg)
-        g.replay()
-    else:
-        _iterate(ws, stacks, geometries, 0, iterations, step, lo, reg)
+    initial = _reconstruct(ws, iterations, fill, graph, *_launchers(ws, stacks, geometries, step, lo, reg))
     extra = ()
     if motion is not None:
-        first_estimate = [initial]
-
-        def register(k, params, levels):
-            return register_slices(ws.x, stacks[k], geometries[k], motion.affines[k], motion.affine_out, params, motion.worlds[k], levels,
-                                   (motion.limit_mm, motion.limit_deg), motion.min_contrast, workspace=ws.cost)
-
-        def rebuild(to_output_s, from_output_s):
-            first_estimate[0] = _rebuild_slices(ws, stacks, geometries, to_output_s, from_output_s, iterations, step, lo, fill, graph)
-
-        extra = _motion_rounds(motion, [tuple(y.shape) for y in stacks], geometries, register, rebuild)
-        initial = first_estimate[0]
+        initial, extra = volume_slices._motion(motion, ws, initial, stacks, geometries, iterations, step, lo, fill, graph)
     volume = (ws.x2 if reg is not None and iterations % 2 else ws.x).clone()       # the estimate an odd count of regularised updates left
     tail = [torch.stack([(ws.cover == c).sum() for c in range(K + 1)])]
     if check:
@@ -1110,149 +757,3 @@ def combine_stacks(stacks, geometries, shape_out, iterations: int = DEFAULT_ITER
         raise ValueError("combine_stacks: the reconstructed volume is not finite everywhere")
     return StackResult(volume, initial, _rms_table(sums, counts), counts, coverage, *extra)
 
-
-# ---------------------------------------------------------------- device: slice-to-volume motion
-
-def _table_tensor(table, slices, device, what) -> torch.Tensor:
-    """A (slices, 12) float64 table on ``device``: a numpy (slices, 3, 4) array is checked and uploaded, a tensor taken as given."""
-    if isinstance(table, torch.Tensor):
-        t = cuda_tensor(table, (torch.float64,), what, name="the table of per-slice matrices", shape=(slices, 12))
-        if t.device != device:
-            raise ValueError(f"{what}: the table of per-slice matrices must lie on {device}")
-        return t
-    return torch.from_numpy(_check_table(table, slices, what).reshape(slices, 12)).to(device)
-
-
-def _profile_args(g):
-    T = g.offsets.size
-    return (L.C.c_double * T)(*g.offsets.tolist()), (L.C.c_float * T)(*g.weights.tolist()), T
-
-
-def _residual_slices(x, y, g, table, r, slots_ptr, stats_row):
-    L.call("mrisr_f32_volume_stack_residual_slices", x.data_ptr(), *x.shape, y.data_ptr(), *y.shape, table.data_ptr(), y.shape[g.slice_axis],
-           g.slice_axis, *_profile_args(g), r.data_ptr(), slots_ptr, L.ptr(stats_row), L.stream_ptr(), nbytes=4 * (x.numel() + 2 * y.numel()))
-
-
-def _update_slices(x, volumes, geometries, tables, step, lo, out, cover, slots, stats_rows):
-    views = (L.StackSlicesView * len(volumes))()
-    for view, v, g, t in zip(views, volumes, geometries, tables):
-        view.data, (view.nx, view.ny, view.nz), view.slice_axis = v.data_ptr(), v.shape, g.slice_axis
-        view.from_output, view.slices = t.data_ptr(), v.shape[g.slice_axis]
-    L.call("mrisr_f32_volume_stack_update_slices", x.data_ptr(), *x.shape, views, len(volumes), float(step), int(lo is not None),
-           0.0 if lo is None else float(lo), out.data_ptr(), L.ptr(cover), L.ptr(slots), L.ptr(stats_rows), L.stream_ptr(),
-           nbytes=4 * (2 * x.numel() + sum(v.numel() for v in volumes)))
-
-
-def stack_residual_slices(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, to_output_s, out=None):
-    """The device path of ``stack_residual_slices_np`` -> ``(r, S, n)`` as ``stack_residual``: ``r`` bit for bit.  ``to_output_s``: a
-    numpy (S, 3, 4) array (uploaded) or a float64 CUDA tensor (S, 12).  CPU tensors raise."""
-    x, y = _check_tensor(x, "stack_residual_slices"), _check_tensor(y, "stack_residual_slices")
-    if x.device != y.device:
-        raise ValueError(f"stack_residual_slices: the estimate and the stack must share a device, got {x.device} and {y.device}")
-    g = _check_geometry(geometry, "stack_residual_slices")
-    table = _table_tensor(to_output_s, _check_slice_count(y.shape[g.slice_axis], "stack_residual_slices"), x.device, "stack_residual_slices")
-    r = out_like(out, y, (x, y), "stack_residual_slices")
-    row = torch.empty(2, dtype=torch.int64, device=x.device)
-    _residual_slices(x, y, g, table, r, _slots(x.device, 1).data_ptr(), row)
-    return r, row[:1].view(torch.float64)[0], row[1]
-
-
-def stack_update_slices(x: torch.Tensor, residuals, geometries, from_output_s, step: float = 1.0, clamp=0.0, out=None, cover: bool = False,
-                        reg_lambda: float = 0.0):
-    """The device path of ``stack_update_slices_np`` -> ``(x', cnt)``, bit for bit; ``cnt`` (uint8) only with ``cover=True``.  ONE
-    launch for all the stacks, no device-to-host read.  ``from_output_s``: per stack a numpy (S_k, 3, 4) array or a float64 CUDA
-    tensor (S_k, 12).  ``out``: a tensor like ``x`` - ``x`` itself updates in place.  ``reg_lambda > 0``: not built."""
-    _not_built_with_motion(reg_lambda, "stack_update_slices")
-    x = _check_tensor(x, "stack_update_slices")
-    volumes, geometries = _check_stacks(residuals, geometries, x.device, "stack_update_slices")
-    tables = list(from_output_s)
-    if len(tables) != len(volumes):
-        raise ValueError(f"stack_update_slices: {len(volumes)} stacks and {len(tables)} tables")
-    tables = [_table_tensor(t, _check_slice_count(v.shape[g.slice_axis], "stack_update_slices"), x.device, f"stack_update_slices: stack {k}")
-              for k, (t, v, g) in enumerate(zip(tables, volumes, geometries))]
-    step, lo = _check_step(step), _check_clamp(clamp)
-    out = x if out is x else out_like(out, x, volumes, "stack_update_slices")
-    cnt = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if cover else None
-    _update_slices(x, volumes, geometries, tables, step, lo, out, cnt, None, None)
-    return out, cnt
-
-
-class SliceCostWorkspace:
-    """The buffers of ``slice_cost`` for stacks of up to ``slices`` slices and ``candidates`` poses each: the candidates' matrices, the
-    fixed slots of the sums and the result.  Made once, it serves call after call on one stream; nothing in it needs initialising."""
-
-    def __init__(self, device, slices: int = MAX_SLICES, candidates: int = MAX_CANDIDATES):
-        self.slices, self.candidates = _check_slice_count(slices, "SliceCostWorkspace"), int(candidates)
-        if not 1 <= self.candidates <= MAX_CANDIDATES:
-            raise ValueError(f"SliceCostWorkspace: 1..{MAX_CANDIDATES} candidates, got {candidates}")
-        self.cand = torch.empty(self.slices * self.candidates * 12, dtype=torch.float64, device=device)
-        self.slots = torch.empty(int(L.load().mrisr_f32_volume_slice_cost_workspace_bytes(self.slices, self.candidates)) // 8,
-                                 dtype=torch.float64, device=device)
-        self.out = torch.empty(self.slices * self.candidates * 6, dtype=torch.float64, device=device)
-
-
-def slice_cost(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, cand_to_output, stride: int = 1, workspace=None) -> torch.Tensor:
-    """The device path of ``slice_cost_np`` -> a float64 CUDA tensor (S, C, 6) (a view of the workspace's result buffer): the counts
-    equal, the sums those of a fixed order of addition - within 1e-12 (relative) of the specification's, the same bits on every run.
-    ``cand_to_output``: numpy (S, C, 3, 4), uploaded into the workspace.  Two launches (the S C pairs; the slots), no atomics, no
-    device-to-host read.  CPU tensors raise."""
-    x, y = _check_tensor(x, "slice_cost"), _check_tensor(y, "slice_cost")
-    if x.device != y.device:
-        raise ValueError(f"slice_cost: the estimate and the stack must share a device, got {x.device} and {y.device}")
-    g = _check_geometry(geometry, "slice_cost")
-    cand, stride = _check_cost_args(y.shape, g.slice_axis, cand_to_output, stride, "slice_cost")
-    S, C = cand.shape[:2]
-    ws = SliceCostWorkspace(x.device, S, C) if workspace is None else workspace
-    if not isinstance(ws, SliceCostWorkspace) or ws.slices < S or ws.candidates < C or ws.cand.device != x.device:
-        raise ValueError(f"slice_cost: the workspace must be a SliceCostWorkspace for {S} slices and {C} candidates on {x.device}")
-    table, out = ws.cand[:S * C * 12], ws.out[:S * C * 6]
-    table.copy_(torch.from_numpy(cand.reshape(-1)))
-    L.call("mrisr_f32_volume_slice_cost", x.data_ptr(), *x.shape, y.data_ptr(), *y.shape, table.data_ptr(), S, C, g.slice_axis,
-           *_profile_args(g), stride, ws.slots.data_ptr(), out.data_ptr(), L.stream_ptr())
-    return out.view(S, C, 6)
-
-
-def register_slices(x: torch.Tensor, y: torch.Tensor, geometry: StackGeometry, affine, affine_out, params0=None, world=None, levels=None,
-                    limits=(10.0, 10.0), min_contrast: float = 0.1, workspace=None) -> SliceMotion:
-    """The device path of ``register_slices_np``: the same search on the host (``slice_compass_search``, ``ncc_from_sums``) over the
-    sums of ``slice_cost`` - per search iteration one upload of the candidates' matrices, two launches and ONE device-to-host read of
-    ``S C 6`` doubles.  The poses are close to the specification's, not bit-equal (the sums differ at 1e-12)."""
-    x, y = _check_tensor(x, "register_slices"), _check_tensor(y, "register_slices")
-    g = _check_geometry(geometry, "register_slices")
-    ws = SliceCostWorkspace(x.device) if workspace is None else workspace
-    return _register_slices(lambda cand, stride: slice_cost(x, y, g, cand, stride, ws).cpu().numpy(), tuple(y.shape), g.slice_axis, affine,
-                            affine_out, world, params0, levels, limits, min_contrast)
-
-
-def _iterate_slices(ws, stacks, geometries, count, step, lo):
-    """``_iterate`` with the per-slice kernels on the tables of the workspace: ``K + 1`` launches an iteration, nothing allocated."""
-    to_tables = [t[:y.shape[g.slice_axis]] for t, y, g in zip(ws.to_tables, stacks, geometries)]
-    from_tables = [t[:y.shape[g.slice_axis]] for t, y, g in zip(ws.from_tables, stacks, geometries)]
-    for it in range(count):
-        for k, (y, g) in enumerate(zip(stacks, geometries)):
-            _residual_slices(ws.x, y, g, to_tables[k], ws.residuals[k], ws.region(k), None)
-        _update_slices(ws.x, ws.residuals, geometries, from_tables, step, lo, ws.x, None, ws.slots, ws.stats[it])
-
-
-def _rebuild_slices(ws, stacks, geometries, to_output_s, from_output_s, iterations, step, lo, fill, graph):
-    """The estimate from scratch with a pose per slice: the tables go into the workspace, then the initial estimate and
-    ``iterations`` updates (captured and replayed with ``graph``) -> the initial estimate."""
-    for k, (y, g) in enumerate(zip(stacks, geometries)):
-        S = _check_slice_count(y.shape[g.slice_axis], "combine_stacks")
-        ws.to_tables[k][:S].copy_(torch.from_numpy(_check_table(to_output_s[k], S, "combine_stacks").reshape(S, 12)))
-        ws.from_tables[k][:S].copy_(torch.from_numpy(_check_table(from_output_s[k], S, "combine_stacks").reshape(S, 12)))
-    from_tables = [t[:y.shape[g.slice_axis]] for t, y, g in zip(ws.from_tables, stacks, geometries)]
-    ws.x.fill_(float(fill))
-    _update_slices(ws.x, stacks, geometries, from_tables, 1.0, lo, ws.x, ws.cover, None, None)
-    initial = ws.x.clone()
-    if graph and iterations:
-        _iterate_slices(ws, stacks, geometries, 1, step, lo)
-        ws.x.copy_(initial)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            _iterate_slices(ws, stacks, geometries, iterations, step, lo)
-        g.replay()
-    else:
-        _iterate_slices(ws, stacks, geometries, iterations, step, lo)
-    return initial

@@ -19,7 +19,7 @@ its best after two or three updates, with the prior it settles and can be run to
 the quadratic prior) clips the neighbour differences at ``D`` intensity units, which keeps tissue steps and fine detail; the
 coefficients are ``volume_stacks.regulariser_coeffs`` of the output grid.  ``--motion slices`` (default ``none``) corrects motion
 between the slices of a stack: after the reconstruction with stack-wide matrices, ``--motion_rounds`` (2) times, every slice of every
-stack is registered rigidly to the current estimate (``volume_stacks.register_slices``: normalised cross-correlation, a compass search
+stack is registered rigidly to the current estimate (``volume_slices.register_slices``: normalised cross-correlation, a compass search
 for all slices at once, poses within ``--motion_limit_mm`` / ``--motion_limit_deg`` (10 / 10); slices whose contrast is below
 ``--motion_min_contrast`` (0.1) of the stack's keep their pose) and the estimate is rebuilt with a matrix per slice.  Per round and
 stack the active slices, the mean cost before and after and the largest displacement of a slice corner are logged; ``--save_motion
@@ -40,6 +40,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+from mri_superresolution_amd import volume_slices as V                                                     # noqa: E402
 from mri_superresolution_amd import volume_stacks as S                                                     # noqa: E402
 from mri_superresolution_amd.utils.nifti import frames, header_for_grid, read_nifti           # noqa: E402
 from scripts._cli import add_cpu_flag, join_frames, run, save_nifti                                          # noqa: E402
@@ -124,7 +125,7 @@ def combine_files(inputs, output_path, spacing=None, like=None, iterations=S.DEF
                     f"(output voxels of {np.round(S.voxel_sizes(affine_out), 3).tolist()} mm)")
     options = {}
     if motion == "slices":                                           # without the flag the call is the one it always was
-        options["motion"] = S.MotionOptions(tuple(affines), affine_out, tuple(worlds), motion_rounds, motion_limit_mm, motion_limit_deg,
+        options["motion"] = V.MotionOptions(tuple(affines), affine_out, tuple(worlds), motion_rounds, motion_limit_mm, motion_limit_deg,
                                             motion_min_contrast)
     ws = S.StackWorkspace(shape_out, shapes, device, iterations, regularised=regularise > 0, **({"motion": True} if options else {}))
     outs, initials = [], []
@@ -159,7 +160,7 @@ def log_motion(t, r, affines, shapes, geometries):
         for k, (before, after) in enumerate(row):
             logger.info(f"frame {t} motion round {rnd + 1} stack {k}: mean NCC of the active slices {before:.5f} -> {after:.5f}")
     for k, (p, m) in enumerate(zip(r.motion, r.motion_detail)):
-        d = S.slice_corner_displacement(p, np.zeros_like(p), affines[k], shapes[k], geometries[k].slice_axis)
+        d = V.slice_corner_displacement(p, np.zeros_like(p), affines[k], shapes[k], geometries[k].slice_axis)
         logger.info(f"frame {t} stack {k}: {int(m.active.sum())} of {m.active.size} slices active, largest displacement of a slice corner "
                     f"{float(d.max()):.3f} mm")
 

@@ -5,6 +5,7 @@ import functools
 
 import numpy as np
 
+from mri_superresolution_amd import volume_slices as V
 from mri_superresolution_amd import volume_stacks as S
 from stackutil import oblique_affine, phantom, rmse, thick_grid
 
@@ -48,8 +49,8 @@ def moved_stacks(truth, factor, seed=0, noise=0.0, moved=True, affine_out=None):
     for axis in range(3):
         a, shape = thick_grid(truth.shape, axis, factor, affine_out)
         g = S.stack_geometry(a, affine_out, axis, "box", samples=factor)
-        p = injected_params(shape[axis], S.in_plane_voxel_size(a, axis), seed + axis) if moved else np.zeros((shape[axis], 6))
-        y = S.simulate_stack_slices_np(truth, g, shape, S.slice_geometries(a, affine_out, shape, axis, p)[0])
+        p = injected_params(shape[axis], V.in_plane_voxel_size(a, axis), seed + axis) if moved else np.zeros((shape[axis], 6))
+        y = V.simulate_stack_slices_np(truth, g, shape, V.slice_geometries(a, affine_out, shape, axis, p)[0])
         if noise:
             y = (y + rng.normal(0.0, noise, shape)).astype(np.float32)
         stacks.append(y)
@@ -63,14 +64,14 @@ def rms_corner_displacement(params_a, params_b, affines, shapes, geometries, act
     """The RMS, over the (active) slices of all stacks, of ``slice_corner_displacement`` between two sets of poses, in mm."""
     d = []
     for k, (pa, pb) in enumerate(zip(params_a, params_b)):
-        dk = S.slice_corner_displacement(pa, pb, affines[k], shapes[k], geometries[k].slice_axis)
+        dk = V.slice_corner_displacement(pa, pb, affines[k], shapes[k], geometries[k].slice_axis)
         d.append(dk if actives is None else dk[np.asarray(actives[k], dtype=bool)])
     d = np.concatenate(d)
     return float(np.sqrt(np.mean(d * d))) if d.size else 0.0
 
 
 def motion_options(affines, affine_out=None, **kw):
-    return S.MotionOptions(tuple(affines), np.eye(4) if affine_out is None else affine_out, **kw)
+    return V.MotionOptions(tuple(affines), np.eye(4) if affine_out is None else affine_out, **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -90,7 +91,7 @@ def quality_case(factor, noise=0.0, moved=True, rounds=1, iterations=4, structur
             "recovered": rms_corner_displacement(fixed.motion, zeros, affines, shapes, geometries, actives),
             "largest": max(float(np.abs(p[a]).max()) if a.any() else 0.0 for p, a in zip(fixed.motion, actives)),
             "active": [int(a.sum()) for a in actives], "slices": [s[g.slice_axis] for s, g in zip(shapes, geometries)],
-            "motion_cost": fixed.motion_cost, "stop": min(lv[-1][2] for lv in (S.default_slice_levels(a, g.slice_axis)
+            "motion_cost": fixed.motion_cost, "stop": min(lv[-1][2] for lv in (V.default_slice_levels(a, g.slice_axis)
                                                                              for a, g in zip(affines, geometries)))}
 
 

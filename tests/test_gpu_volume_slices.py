@@ -1,7 +1,8 @@
 """Slice-to-volume motion correction on the device against its numpy specification: the per-slice residual and update bit for bit
 (slice axes 0, 1, 2, an oblique stack, T = 1 and 4, poses that open a gap, overlap two slices and push one out of the volume, K = 1
 and 3, extents that are no multiple of a brick), the slice cost (counts equal, sums within 1e-12, the same bits on every run), the
-search on the moved phantom stacks, and the graph replay of the motion rounds."""
+search on the moved phantom stacks, the graph replay of the motion rounds, and the per-slice residual with the stack's own matrix
+repeated against the plain residual kernel (one shared body: the same bits)."""
 import functools
 
 import numpy as np
@@ -9,8 +10,9 @@ import pytest
 import torch
 
 import sliceutil as U
+from mri_superresolution_amd import volume_slices as V
 from mri_superresolution_amd import volume_stacks as S
-from stackutil import same_bits
+from stackutil import oblique_affine, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -34,7 +36,7 @@ def _case(axis, slices, oblique=False, samples=None):
     y, g, a = U.small_stack(axis, slices, oblique)
     if samples is not None:
         g = S.stack_geometry(a, np.eye(4), axis, "box", samples=samples)
-    M, N = S.slice_geometries(a, np.eye(4), y.shape, axis, U.hand_poses(slices, axis, float(S.voxel_sizes(a)[axis])))
+    M, N = V.slice_geometries(a, np.eye(4), y.shape, axis, U.hand_poses(slices, axis, float(S.voxel_sizes(a)[axis])))
     return y, g, M, N
 
 
@@ -45,8 +47,8 @@ CASES = [(0, 5, False, None), (1, 7, False, None), (2, 5, False, 1), (2, 7, True
 def test_residual_slices_bit_equal(axis, slices, oblique, samples):
     y, g, M, _ = _case(axis, slices, oblique, samples)
     x = _estimate()
-    r_np, (s_np, n_np) = S.stack_residual_slices_np(x, y, g, M)
-    r, s, n = S.stack_residual_slices(_dev(x), _dev(y), g, M)
+    r_np, (s_np, n_np) = V.stack_residual_slices_np(x, y, g, M)
+    r, s, n = V.stack_residual_slices(_dev(x), _dev(y), g, M)
     assert same_bits(r.cpu().numpy(), r_np) and int(n) == n_np
     assert abs(float(s) - s_np) <= np.spacing(s_np)
     if slices >= 5:                                                   # the slice pushed out of the volume holds no residual
@@ -57,16 +59,16 @@ def test_residual_slices_bit_equal(axis, slices, oblique, samples):
 def test_update_slices_bit_equal(cases):
     x = _estimate()
     stacks = [_case(*c) for c in cases]
-    res = [S.stack_residual_slices_np(x, y, g, M)[0] for y, g, M, _ in stacks]
+    res = [V.stack_residual_slices_np(x, y, g, M)[0] for y, g, M, _ in stacks]
     geometries, tables = [c[1] for c in stacks], [c[3] for c in stacks]
     for step, clamp in ((1.0, 0.0), (0.7, None)):
-        want, cnt_np = S.stack_update_slices_np(x, res, geometries, tables, step, clamp)
-        got, cnt = S.stack_update_slices(_dev(x), [_dev(r) for r in res], geometries, tables, step, clamp, cover=True)
+        want, cnt_np = V.stack_update_slices_np(x, res, geometries, tables, step, clamp)
+        got, cnt = V.stack_update_slices(_dev(x), [_dev(r) for r in res], geometries, tables, step, clamp, cover=True)
         assert np.array_equal(cnt.cpu().numpy(), cnt_np) and same_bits(got.cpu().numpy(), want)
     assert 0 < int((cnt_np > 0).sum()) < cnt_np.size                  # gaps and the grid's rim stay uncovered
     # in place, with tables that lie on the device already
     xd = _dev(x)
-    out, none = S.stack_update_slices(xd, [_dev(r) for r in res], geometries, [_dev(t.reshape(-1, 12)) for t in tables], 0.7, None, out=xd)
+    out, none = V.stack_update_slices(xd, [_dev(r) for r in res], geometries, [_dev(t.reshape(-1, 12)) for t in tables], 0.7, None, out=xd)
     assert out is xd and none is None and same_bits(xd.cpu().numpy(), want)
 
 
@@ -74,15 +76,15 @@ def test_slices_reject_cpu_tensors_and_regulariser():
     y, g, M, N = _case(0, 5)
     x = _estimate()
     with pytest.raises(ValueError, match="no CPU fallback"):
-        S.stack_residual_slices(torch.from_numpy(x.copy()), torch.from_numpy(y), g, M)
+        V.stack_residual_slices(torch.from_numpy(x.copy()), torch.from_numpy(y), g, M)
     with pytest.raises(ValueError, match="no CPU fallback"):
-        S.stack_update_slices(torch.from_numpy(x.copy()), [torch.from_numpy(y)], [g], [N])
+        V.stack_update_slices(torch.from_numpy(x.copy()), [torch.from_numpy(y)], [g], [N])
     with pytest.raises(ValueError, match="no CPU fallback"):
-        S.slice_cost(torch.from_numpy(x.copy()), torch.from_numpy(y), g, M[:, None])
+        V.slice_cost(torch.from_numpy(x.copy()), torch.from_numpy(y), g, M[:, None])
     with pytest.raises(NotImplementedError, match="not built"):
-        S.stack_update_slices(_dev(x), [_dev(y)], [g], [N], reg_lambda=0.05)
+        V.stack_update_slices(_dev(x), [_dev(y)], [g], [N], reg_lambda=0.05)
     with pytest.raises(ValueError):
-        S.stack_residual_slices(_dev(x), _dev(y), g, M[:4])
+        V.stack_residual_slices(_dev(x), _dev(y), g, M[:4])
 
 
 def _candidates(axis, slices, oblique, C, seed):
@@ -90,25 +92,25 @@ def _candidates(axis, slices, oblique, C, seed):
     rng = np.random.default_rng(seed)
     base = U.hand_poses(slices, axis, float(S.voxel_sizes(a)[axis]))
     cands = base[:, None, :] + rng.uniform(-1.0, 1.0, (slices, C, 6)) * ([1.0] * 3 + [3.0] * 3)
-    return y, g, np.stack([S.slice_geometries(a, np.eye(4), y.shape, axis, cands[:, c])[0] for c in range(C)], axis=1)
+    return y, g, np.stack([V.slice_geometries(a, np.eye(4), y.shape, axis, cands[:, c])[0] for c in range(C)], axis=1)
 
 
 @pytest.mark.parametrize("axis,slices,oblique,C,stride", [(2, 7, True, 13, 1), (0, 5, False, 13, 2), (1, 7, False, 1, 2), (1, 1, False, 1, 1)])
 def test_slice_cost(axis, slices, oblique, C, stride):
     y, g, cand = _candidates(axis, slices, oblique, C, 11)
     x = _estimate()
-    want = S.slice_cost_np(x, y, g, cand, stride)
+    want = V.slice_cost_np(x, y, g, cand, stride)
     xd, yd = _dev(x), _dev(y)
-    ws = S.SliceCostWorkspace(DEV, slices, C)
-    first = S.slice_cost(xd, yd, g, cand, stride, ws).cpu().numpy().copy()
+    ws = V.SliceCostWorkspace(DEV, slices, C)
+    first = V.slice_cost(xd, yd, g, cand, stride, ws).cpu().numpy().copy()
     for buf in (ws.slots, ws.out, ws.cand):                           # garbage in the workspace in between
         buf.view(torch.int64).fill_(0x7FF8DEADBEEF0000)
-    second = S.slice_cost(xd, yd, g, cand, stride, ws).cpu().numpy()
+    second = V.slice_cost(xd, yd, g, cand, stride, ws).cpu().numpy()
     assert np.array_equal(first.view(np.uint64), second.view(np.uint64))
     assert first.shape == want.shape == (slices, C, 6) and np.array_equal(first[..., 0], want[..., 0])
     assert np.abs(first - want).max() <= 1e-12 * np.abs(want).max() and (np.abs(first - want) <= 1e-12 * np.abs(want)).all()
     if slices >= 5:
-        assert not want[slices - 1].any() and want[..., 0].max() > 0.5 * S.strided_slice_count(y.shape, axis, stride)
+        assert not want[slices - 1].any() and want[..., 0].max() > 0.5 * V.strided_slice_count(y.shape, axis, stride)
 
 
 @functools.lru_cache(maxsize=None)
@@ -123,7 +125,7 @@ def test_register_slices_recovers_poses():
     thick slice's pose is weakly determined): the bound is that plus a quarter of the gap to 1."""
     truth, stacks, geometries, affines, params = _moved()
     k = 2
-    m = S.register_slices(_dev(truth), _dev(stacks[k]), geometries[k], affines[k], np.eye(4), limits=(3.0, 6.0))
+    m = V.register_slices(_dev(truth), _dev(stacks[k]), geometries[k], affines[k], np.eye(4), limits=(3.0, 6.0))
     left = U.rms_corner_displacement([m.params], [params[k]], [affines[k]], [stacks[k].shape], [geometries[k]], [m.active])
     injected = U.rms_corner_displacement([params[k]], [np.zeros_like(params[k])], [affines[k]], [stacks[k].shape], [geometries[k]], [m.active])
     print(f"left {left:.4f} mm of {injected:.4f} mm injected, {int(m.active.sum())} of {m.active.size} slices active")
@@ -147,11 +149,31 @@ def test_combine_stacks_motion_graph_equals_eager():
     assert np.array_equal(eager.rms.view(np.uint64), graph.rms.view(np.uint64)) and np.array_equal(eager.coverage, graph.coverage)
     assert eager.motion_cost.shape == (1, 3, 2) and any(np.abs(p).max() > 0 for p in eager.motion)
     # the rebuild is the specification's on the poses the device found
-    tables = [S.slice_geometries(a, np.eye(4), y.shape, g.slice_axis, p) for a, y, g, p in zip(affines, stacks, geometries, eager.motion)]
-    want = S._reconstruct_np(stacks, geometries, truth.shape, 2, 1.0, 0.0, 0.0, tables=([t[0] for t in tables], [t[1] for t in tables]))
+    tables = [V.slice_geometries(a, np.eye(4), y.shape, g.slice_axis, p) for a, y, g, p in zip(affines, stacks, geometries, eager.motion)]
+    want = S._reconstruct_np(stacks, truth.shape, 2, 0.0,
+                             *V._slice_steps_np(stacks, geometries, [t[0] for t in tables], [t[1] for t in tables], 1.0, 0.0))
     assert same_bits(eager.volume.cpu().numpy(), want[0]) and same_bits(eager.initial.cpu().numpy(), want[1])
     # without the keyword nothing changes
     plain = S.combine_stacks(ys, geometries, truth.shape, 2)
     assert plain.motion is None and same_bits(plain.volume.cpu().numpy(), S.combine_stacks_np(stacks, geometries, truth.shape, 2).volume)
     with pytest.raises(NotImplementedError, match="not built"):
         S.combine_stacks(ys, geometries, truth.shape, 2, reg_lambda=0.03, motion=motion)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_residual_repeated_tables_bit_equal_on_device(axis):
+    """The device twin of ``test_residual_repeated_tables_bit_equal``: the stack's own matrix S times gives the bits of the plain
+    kernel - ``r``, the sum and the count.  Both kernels run one shared body; the test guards against the two drifting apart."""
+    rng = np.random.default_rng(40 + axis)
+    shape_out, shape = (12, 10, 9), [7, 9, 11]
+    shape[axis] = 5
+    voxel = [1.0, 1.0, 1.0]
+    voxel[axis] = (shape_out[axis] - 2.0) / 5
+    a = oblique_affine(shape_out, shape, voxel, (6.0, -8.0, 11.0), (0.3, -0.2, 0.4))
+    g = S.stack_geometry(a, np.eye(4), axis, "gaussian", samples=3)
+    x, y = _dev(rng.uniform(0.0, 900.0, shape_out).astype(np.float32)), _dev(rng.uniform(0.0, 900.0, shape).astype(np.float32))
+    table = np.repeat(g.to_output[None], 5, axis=0)
+    r0, s0, n0 = S.stack_residual(x, y, g)
+    r1, s1, n1 = V.stack_residual_slices(x, y, g, table)
+    assert same_bits(r0.cpu().numpy(), r1.cpu().numpy()) and r0.cpu().numpy().any()
+    assert int(s0.view(torch.int64)) == int(s1.view(torch.int64)) and int(n0) == int(n1) and 0 < int(n0) <= y.numel()

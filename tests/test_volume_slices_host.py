@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import sliceutil as U
+from mri_superresolution_amd import volume_slices as V
 from mri_superresolution_amd import volume_stacks as S
 from stackutil import oblique_affine, orthogonal_stacks, phantom, rotation, same_bits
 
@@ -21,13 +22,13 @@ RMSE_RATIO, POSE_RATIO = 0.6009, 0.9812
 
 
 def _zero_tables(stacks, affines, which):
-    return [S.slice_geometries(a, np.eye(4), y.shape, k, np.zeros((y.shape[k], 6)))[which] for k, (y, a) in enumerate(zip(stacks, affines))]
+    return [V.slice_geometries(a, np.eye(4), y.shape, k, np.zeros((y.shape[k], 6)))[which] for k, (y, a) in enumerate(zip(stacks, affines))]
 
 
 def test_slice_geometries_zero_is_stack_geometry():
     stacks, geometries, affines = orthogonal_stacks(phantom(), 3)
     for k, (y, g, a) in enumerate(zip(stacks, geometries, affines)):
-        M, N = S.slice_geometries(a, np.eye(4), y.shape, k, np.zeros((y.shape[k], 6)))
+        M, N = V.slice_geometries(a, np.eye(4), y.shape, k, np.zeros((y.shape[k], 6)))
         assert M.shape == N.shape == (y.shape[k], 3, 4) and M.dtype == N.dtype == np.float64
         assert all(np.array_equal(M[s].view(np.uint64), g.to_output.view(np.uint64)) for s in range(y.shape[k]))
         assert all(np.array_equal(N[s].view(np.uint64), g.from_output.view(np.uint64)) for s in range(y.shape[k]))
@@ -37,7 +38,7 @@ def test_slice_geometries_zero_is_stack_geometry():
     from mri_superresolution_amd.volume_register import rigid_world
     world = rigid_world((1.0, -2.0, 0.5, 3.0, 4.0, -5.0), (9.0, 9.0, 9.0))
     g = S.stack_geometry(a, np.eye(4), 2, world=world)
-    M, N = S.slice_geometries(a, np.eye(4), shape, 2, np.zeros((5, 6)), world=world)
+    M, N = V.slice_geometries(a, np.eye(4), shape, 2, np.zeros((5, 6)), world=world)
     assert all(np.array_equal(M[s], g.to_output) and np.array_equal(N[s], g.from_output) for s in range(5))
 
 
@@ -46,7 +47,7 @@ def test_slice_geometries_moves_one_slice_and_checks():
     a = oblique_affine((18, 20, 23), shape, (1.0, 1.0, 4.2))
     p = np.zeros((5, 6))
     p[2] = (1.0, 0.0, 0.0, 0.0, 0.0, 10.0)
-    M, N = S.slice_geometries(a, np.eye(4), shape, 2, p)
+    M, N = V.slice_geometries(a, np.eye(4), shape, 2, p)
     g = S.stack_geometry(a, np.eye(4), 2)
     assert np.array_equal(M[1], g.to_output) and not np.array_equal(M[2], g.to_output)
     # M_s and N_s are inverse to each other
@@ -57,9 +58,9 @@ def test_slice_geometries_moves_one_slice_and_checks():
     centre = np.array([8.0, 9.0, 2.0, 1.0])
     assert np.allclose(M[2] @ centre, g.to_output @ centre - rotation(0.0, 0.0, 10.0).T @ (1.0, 0.0, 0.0), atol=1e-9)
     with pytest.raises(ValueError):
-        S.slice_geometries(a, np.eye(4), shape, 2, np.zeros((4, 6)))
+        V.slice_geometries(a, np.eye(4), shape, 2, np.zeros((4, 6)))
     with pytest.raises(ValueError, match="256"):
-        S.slice_geometries(np.eye(4), np.eye(4), (2, 2, 257), 2, np.zeros((257, 6)))
+        V.slice_geometries(np.eye(4), np.eye(4), (2, 2, 257), 2, np.zeros((257, 6)))
 
 
 def test_residual_repeated_tables_bit_equal():
@@ -68,9 +69,9 @@ def test_residual_repeated_tables_bit_equal():
     x = (truth * np.float32(0.9) + np.float32(20)).astype(np.float32)
     for y, g, table in zip(stacks, geometries, _zero_tables(stacks, affines, 0)):
         r0, (s0, n0) = S.stack_residual_np(x, y, g)
-        r1, (s1, n1) = S.stack_residual_slices_np(x, y, g, table)
+        r1, (s1, n1) = V.stack_residual_slices_np(x, y, g, table)
         assert same_bits(r0, r1) and s0 == s1 and n0 == n1
-        assert same_bits(S.simulate_stack_np(x, g, y.shape), S.simulate_stack_slices_np(x, g, y.shape, table))
+        assert same_bits(S.simulate_stack_np(x, g, y.shape), V.simulate_stack_slices_np(x, g, y.shape, table))
 
 
 def test_update_repeated_tables():
@@ -79,7 +80,7 @@ def test_update_repeated_tables():
     x = np.full(truth.shape, np.float32(100))
     res = [S.stack_residual_np(x, y, g)[0] for y, g in zip(stacks, geometries)]
     a, ca = S.stack_update_np(truth, res, geometries)
-    b, cb = S.stack_update_slices_np(truth, res, geometries, _zero_tables(stacks, affines, 1))
+    b, cb = V.stack_update_slices_np(truth, res, geometries, _zero_tables(stacks, affines, 1))
     diff = float(np.abs(a - b).max())
     print(f"aligned: largest difference {diff:.8g}, largest residual {max(float(np.abs(r).max()) for r in res):.8g}")
     assert np.array_equal(ca, cb) and diff <= 2 * UPDATE_DIFF_ALIGNED
@@ -88,7 +89,7 @@ def test_update_repeated_tables():
     g = S.stack_geometry(aff, np.eye(4), 2, samples=4)
     r = S.stack_residual_np(x, S.simulate_stack_np(truth, g, shape), g)[0]
     a, ca = S.stack_update_np(truth, [r], [g])
-    b, cb = S.stack_update_slices_np(truth, [r], [g], [S.slice_geometries(aff, np.eye(4), shape, 2, np.zeros((9, 6)))[1]])
+    b, cb = V.stack_update_slices_np(truth, [r], [g], [V.slice_geometries(aff, np.eye(4), shape, 2, np.zeros((9, 6)))[1]])
     diff = float(np.abs(a - b).max())
     print(f"oblique: largest difference {diff:.8g}, largest residual {float(np.abs(r).max()):.8g}")
     assert np.array_equal(ca, cb) and 0 < int(ca.sum()) < ca.size and diff <= 2 * UPDATE_DIFF_OBLIQUE
@@ -99,12 +100,12 @@ def test_update_gap_overlap_and_outside():
     spacing = float(S.voxel_sizes(a)[2])
     x = np.zeros(U.SMALL_OUT, dtype=np.float32)
     ones = np.ones_like(y)
-    cover = lambda p: S.stack_update_slices_np(x, [ones], [g], [S.slice_geometries(a, np.eye(4), y.shape, 2, p)[1]])
+    cover = lambda p: V.stack_update_slices_np(x, [ones], [g], [V.slice_geometries(a, np.eye(4), y.shape, 2, p)[1]])
     (v0, c0), (v1, c1) = cover(np.zeros((5, 6))), cover(U.hand_poses(5, 2, spacing))
     assert c1.sum() < c0.sum()                                        # the gap and the slice pushed out leave voxels uncovered
     assert np.array_equal(v1[c1 > 0], np.ones(int((c1 > 0).sum()), dtype=np.float32))      # overlaps are normalised: a stack of ones gives ones
     with pytest.raises(NotImplementedError, match="not built"):
-        S.stack_update_slices_np(x, [ones], [g], [np.zeros((5, 3, 4))], reg_lambda=0.1)
+        V.stack_update_slices_np(x, [ones], [g], [np.zeros((5, 3, 4))], reg_lambda=0.1)
 
 
 def _quadratic_cost(optima, calls):
@@ -124,7 +125,7 @@ def test_slice_compass_search():
     p0 = np.zeros((7, 6))
     p0[2] = 0.25
     calls = []
-    p, best, start, trace = S.slice_compass_search(_quadratic_cost(optima, calls), p0, levels, (10.0, 10.0), active)
+    p, best, start, trace = V.slice_compass_search(_quadratic_cost(optima, calls), p0, levels, (10.0, 10.0), active)
     assert all(c[0] == 7 and c[1] in (1, 12) for c in calls) and len(calls) == len(trace)      # one call per iteration, all slices
     ok = np.array([0, 1, 3, 5, 6])
     assert np.abs(p[ok] - optima[ok]).max() <= 0.125                  # to the last step size (the last probed step is 0.125)
@@ -132,7 +133,7 @@ def test_slice_compass_search():
     assert np.abs(p).max() <= 10.0 and p[4, 0] == 10.0               # a limit is never crossed
     assert all(np.abs(t["p"]).max() <= 10.0 for t in trace)
     assert np.array_equal(start, -((p0 - optima) ** 2).sum(axis=1)) and (best[active] >= start[active]).all()
-    p2, best2, start2, trace2 = S.slice_compass_search(_quadratic_cost(optima, []), p0, levels, (10.0, 10.0), active)
+    p2, best2, start2, trace2 = V.slice_compass_search(_quadratic_cost(optima, []), p0, levels, (10.0, 10.0), active)
     assert np.array_equal(p, p2) and np.array_equal(best, best2) and len(trace) == len(trace2)
     for t, u in zip(trace, trace2):
         assert t["kind"] == u["kind"] and all(np.array_equal(t[key], u[key]) for key in ("p", "step", "values", "accepted", "best"))
@@ -147,18 +148,18 @@ def test_slice_outside_the_volume_scores_minus_inf():
     y, g, a = stacks[2], geometries[2], affines[2]
     p = np.zeros((y.shape[2], 6))
     p[3, :3] = 500.0
-    cand = S.slice_geometries(a, np.eye(4), y.shape, 2, p)[0][:, None]
+    cand = V.slice_geometries(a, np.eye(4), y.shape, 2, p)[0][:, None]
     for stride in (1, 2):
-        sums = S.slice_cost_np(truth, y, g, cand, stride)
+        sums = V.slice_cost_np(truth, y, g, cand, stride)
         assert sums.shape == (y.shape[2], 1, 6) and not sums[3].any()
-        ncc = S.ncc_from_sums(sums, 0.25 * S.strided_slice_count(y.shape, 2, stride))
+        ncc = V.ncc_from_sums(sums, 0.25 * V.strided_slice_count(y.shape, 2, stride))
         assert ncc[3, 0] == -np.inf and np.isfinite(np.delete(ncc[:, 0], 3)[1:-1]).all()
-        assert sums[1, 0, 0] == S.strided_slice_count(y.shape, 2, stride)
-    assert (S.ncc_from_sums(S.slice_cost_np(truth, y, g, cand, 1), 1)[1:-1, 0][[0, 1, 3, 4]] > 0.999).all()      # the stacks' own poses fit
+        assert sums[1, 0, 0] == V.strided_slice_count(y.shape, 2, stride)
+    assert (V.ncc_from_sums(V.slice_cost_np(truth, y, g, cand, 1), 1)[1:-1, 0][[0, 1, 3, 4]] > 0.999).all()      # the stacks' own poses fit
     with pytest.raises(ValueError):
-        S.slice_cost_np(truth, y, g, np.repeat(cand, 14, axis=1), 1)
+        V.slice_cost_np(truth, y, g, np.repeat(cand, 14, axis=1), 1)
     with pytest.raises(ValueError):
-        S.slice_cost_np(truth, y, g, cand, 3)
+        V.slice_cost_np(truth, y, g, cand, 3)
 
 
 def test_ncc_from_sums():
@@ -166,9 +167,9 @@ def test_ncc_from_sums():
     y, m = rng.normal(100, 10, 500), rng.normal(50, 5, 500)
     m = m + 0.3 * (y - 100)
     sums = np.array([500, y.sum(), m.sum(), (y * y).sum(), (m * m).sum(), (y * m).sum()])
-    assert abs(S.ncc_from_sums(sums) - np.corrcoef(y, m)[0, 1]) < 1e-10
-    assert S.ncc_from_sums(sums, 501) == -np.inf
-    assert S.ncc_from_sums(np.array([10, 50.0, 30, 250, 100, 150])) == -np.inf      # y constant: no variance
+    assert abs(V.ncc_from_sums(sums) - np.corrcoef(y, m)[0, 1]) < 1e-10
+    assert V.ncc_from_sums(sums, 501) == -np.inf
+    assert V.ncc_from_sums(np.array([10, 50.0, 30, 250, 100, 150])) == -np.inf      # y constant: no variance
 
 
 def test_motion_with_regulariser_is_not_built():

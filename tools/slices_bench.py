@@ -33,13 +33,14 @@ if REPO not in sys.path:
 from tools.benchutil import timed      # noqa: E402
 from tools.stacks_bench import stats, torch_iteration      # noqa: E402
 
+from mri_superresolution_amd import volume_slices as V                       # noqa: E402
 from mri_superresolution_amd import volume_stacks as S                       # noqa: E402
 
 
 def main(args):
     if not torch.cuda.is_available():
         raise SystemExit("this tool measures on an MI355X: no GPU found")
-    n, ns, T, C = args.size, args.slices, args.samples, S.MAX_CANDIDATES
+    n, ns, T, C = args.size, args.slices, args.samples, V.MAX_CANDIDATES
     rng = np.random.default_rng(0)
     stacks, geometries, affines, poses = [], [], [], []
     for axis in range(3):
@@ -54,15 +55,15 @@ def main(args):
     ws = S.StackWorkspace((n, n, n), [y.shape for y in stacks], "cuda", 2, motion=True)
     ws.x.copy_(torch.from_numpy(rng.uniform(0, 900, (n, n, n)).astype(np.float32)))
     for k in range(3):
-        M, N = S.slice_geometries(affines[k], np.eye(4), stacks[k].shape, k, poses[k])
+        M, N = V.slice_geometries(affines[k], np.eye(4), stacks[k].shape, k, poses[k])
         ws.to_tables[k][:ns].copy_(torch.from_numpy(M.reshape(ns, 12)))
         ws.from_tables[k][:ns].copy_(torch.from_numpy(N.reshape(ns, 12)))
         S._residual(ws.x, stacks[k], geometries[k], ws.residuals[k], ws.region(k), None)
     from_tables = [t[:ns] for t in ws.from_tables]
     y, g = stacks[2], geometries[2]
     cands = np.repeat(poses[2][:, None, :], C, axis=1) + rng.uniform(-0.5, 0.5, (ns, C, 6))
-    cand = np.stack([S.slice_geometries(affines[2], np.eye(4), y.shape, 2, cands[:, c])[0] for c in range(C)], axis=1)
-    S.slice_cost(ws.x, y, g, cand, 1, ws.cost)                             # the candidates lie in the workspace from here on
+    cand = np.stack([V.slice_geometries(affines[2], np.eye(4), y.shape, 2, cands[:, c])[0] for c in range(C)], axis=1)
+    V.slice_cost(ws.x, y, g, cand, 1, ws.cost)                             # the candidates lie in the workspace from here on
     table, out = ws.cost.cand[:ns * C * 12], ws.cost.out[:ns * C * 6]
 
     def cost():
@@ -78,8 +79,8 @@ def main(args):
             torch_iteration(ws.x, [y], [g], 1.0)
 
     def search_iter():
-        tabs = np.stack([S.slice_geometries(affines[2], np.eye(4), y.shape, 2, cands[:, c])[0] for c in range(12)], axis=1)
-        return S.slice_cost(ws.x, y, g, tabs, 1, ws.cost).cpu().numpy()
+        tabs = np.stack([V.slice_geometries(affines[2], np.eye(4), y.shape, 2, cands[:, c])[0] for c in range(12)], axis=1)
+        return V.slice_cost(ws.x, y, g, tabs, 1, ws.cost).cpu().numpy()
 
     lo = np.float32(0)
     scratch = torch.empty_like(ws.x)
@@ -87,7 +88,7 @@ def main(args):
     for _ in range(args.rounds):
         t["cost"].append(timed(cost, args.iters, args.warmup))
         t["residual_x13"].append(timed(residual_x13, args.iters, args.warmup))
-        t["update_slices"].append(timed(lambda: S._update_slices(ws.x, ws.residuals, geometries, from_tables, 1.0, lo, scratch, None, None, None),
+        t["update_slices"].append(timed(lambda: V._update_slices(ws.x, ws.residuals, geometries, from_tables, 1.0, lo, scratch, None, None, None),
                                         args.iters, args.warmup))
         t["update"].append(timed(lambda: S._update(ws.x, ws.residuals, geometries, 1.0, lo, scratch, None, None, None), args.iters, args.warmup))
         t["torch_x13"].append(timed(torch_x13, args.torch_iters, 1))

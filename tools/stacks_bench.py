@@ -8,7 +8,7 @@ The output is --size^3; the three stacks are size x size x slices voxels, thick 
 --samples samples.  Timed with device events around a loop, in alternating order, --rounds times each; the median is reported with
 the smallest and the largest:
 
-  iteration   K residual launches and the update (``volume_stacks._iterate`` on a ``StackWorkspace``);
+  iteration   K residual launches and the update (``volume_stacks._iterate`` with ``_launchers`` on a ``StackWorkspace``);
   residual    the residual launch of one stack (the median over the three stacks is reported per stack);
   update      the update launch alone;
   torch       the same iteration with ``affine_grid`` + ``grid_sample`` (trilinear, border padding): per stack T sampled volumes,
@@ -114,17 +114,19 @@ def main(args):
     dst = torch.empty_like(buf)
     t = {k: [] for k in ("iteration", "residual", "update", "torch", "copy_residual", "copy_update")}
     lo = np.float32(0)
+    plain = S._launchers(ws, stacks, geometries, 1.0, lo)
     if args.regularise:
         t.update({k: [] for k in ("iteration_reg", "update_reg", "torch_reg")})
         lam, delta = 0.03, 60.0
         reg = S._check_regulariser(1.0, lam, delta, None)
+        regularised = S._launchers(ws, stacks, geometries, 1.0, lo, reg)
         S._update(ws.x, stacks, geometries, 1.0, lo, ws.x2, ws.cover, None, None)      # the coverage counts: geometry only
         ws.x.copy_(x0)
     for _ in range(args.rounds):
         if args.regularise:
-            t["iteration_reg"].append(0.5 * timed(lambda: S._iterate(ws, stacks, geometries, 0, 2, 1.0, lo, reg), args.iters, args.warmup))
+            t["iteration_reg"].append(0.5 * timed(lambda: S._iterate(ws, 0, 2, *regularised), args.iters, args.warmup))
             ws.x.copy_(x0)
-        t["iteration"].append(timed(lambda: S._iterate(ws, stacks, geometries, 0, 1, 1.0, np.float32(0)), args.iters, args.warmup))
+        t["iteration"].append(timed(lambda: S._iterate(ws, 0, 1, *plain), args.iters, args.warmup))
         per = [timed(lambda k=k: S._residual(ws.x, stacks[k], geometries[k], ws.residuals[k], ws.region(k), None), args.iters, args.warmup)
                for k in range(3)]
         t["residual"].append(float(np.median(per)))
@@ -138,7 +140,7 @@ def main(args):
         t["copy_residual"].append(timed(lambda: dst[:res_bytes // 2].copy_(buf[:res_bytes // 2]), args.iters, args.warmup))
         t["copy_update"].append(timed(lambda: dst[:upd_bytes // 2].copy_(buf[:upd_bytes // 2]), args.iters, args.warmup))
     ws.x.copy_(x0)
-    S._iterate(ws, stacks, geometries, 0, 1, 1.0, np.float32(0))
+    S._iterate(ws, 0, 1, *plain)
     theirs = torch_iteration(x0, stacks, geometries, 1.0)
     diff = float((ws.x - theirs).abs().max())
     med = {k: float(np.median(v)) for k, v in t.items()}
@@ -152,7 +154,7 @@ def main(args):
               "largest_difference_from_torch": diff}
     if args.regularise:
         ws.x.copy_(x0)
-        S._iterate(ws, stacks, geometries, 0, 1, 1.0, lo, reg)
+        S._iterate(ws, 0, 1, *regularised)
         result.update({"reg_lambda": lam, "reg_delta": delta, "iteration_reg_ms": stats(t["iteration_reg"]),
                        "update_reg_ms": stats(t["update_reg"]), "torch_reg_iteration_ms": stats(t["torch_reg"]),
                        "update_reg_over_update": round(med["update_reg"] / med["update"], 3),
