@@ -231,7 +231,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 330   # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 331  # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -156,7 +156,9 @@ __device__ __forceinline__ void up2_coord(int dst, int in_size, int& i0, int& i1
 }
 
 // candidate high-res rows of a bilinear x2 (align_corners) adjoint and their weights for low-res index y:
-// src(Y) = Y (n-1)/(2n-1) touches row y only for Y in [2y-1, 2y+2] (checked exhaustively for n <= 512)
+// src(Y) = Y (n-1)/(2n-1) touches row y only for Y in [2y-1, 2y+2] (checked with a float32 emulation of up2_coord for
+// every n <= 4200 and for 8191, 8192, 16384, 16385, 30000, 65536 by
+// tests/test_norm_fwd_ref_host.py::test_adjoint_window_claim, which also holds the engine's largest extents inside that range)
 constexpr int kUpAdj = 4;
 __device__ __forceinline__ void up2_adjoint_weights(int y, int in_size, int* idx, float* w) {
 #pragma unroll

@@ -153,6 +153,10 @@ extern "C" int mrisr_conv_forward(const mrisr_conv_desc* d, void* stream) {
     if (d->relu_mask && (d->out_mode != MRISR_OUT_PLAIN || d->Cout % (mrisr_vec(d->dtype))))
         MRISR_FAIL(MRISR_E_UNSUPPORTED, "conv_forward: relu_mask needs a plain output with Cout a multiple of the 16-byte vector");
     if (d->stats && (d->groups <= 0 || d->Cout % d->groups)) MRISR_FAIL(MRISR_E_SHAPE, "conv_forward: Cout %d not divisible by groups %d", d->Cout, d->groups);
+    // the statistics are those of the SHUFFLED tensor (Cout / 4 channels): fewer channels than groups would reach the
+    // stand-alone gn_stats pass with a group size of zero (Cout 16, 8 groups)
+    if (d->stats && d->out_mode == MRISR_OUT_PIXEL_SHUFFLE2 && (d->Cout / 4) % d->groups)
+        MRISR_FAIL(MRISR_E_SHAPE, "conv_forward: pixel shuffle leaves %d channels, not divisible by groups %d", d->Cout / 4, d->groups);
     if (conv_ring_eligible(d, p)) return launch_conv_ring(d, p, (hipStream_t)stream);
     if (conv_pc_eligible(d, p)) return launch_conv_pc(d, p, (hipStream_t)stream);
     if (conv1x1_gemm_eligible(d, p)) return launch_conv1x1_gemm(d, p, (hipStream_t)stream);

@@ -28,11 +28,14 @@ __global__ void gn_finalize_kernel(const double* __restrict__ stats, const float
     const double mean = s / count;
     double var = ss / count - mean * mean;
     if (var < 0) var = 0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    // scale and shift are each the float32 rounding of the float64 value: in float32, beta - mean * scale carries the roundings
+    // of rstd, scale, mean and the product, 4 ulp of mean * scale where the mean is many deviations from zero
+    const double rstd_d = 1.0 / sqrt(var + (double)eps);
+    const float rstd = (float)rstd_d;
     const float m = (float)mean;
-    const float sc = gamma[c] * rstd;
-    scale[idx] = sc;
-    shift[idx] = beta[c] - m * sc;
+    const double sc = (double)gamma[c] * rstd_d;
+    scale[idx] = (float)sc;
+    shift[idx] = (float)((double)beta[c] - mean * sc);
     if (c == g * gs) {
         meanrstd[((size_t)n * groups + g) * 2] = m;
         meanrstd[((size_t)n * groups + g) * 2 + 1] = rstd;

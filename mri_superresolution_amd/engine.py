@@ -21,6 +21,11 @@ from . import _lib as L
 from .launch import GN_GROUPS, Consumer, dgrad_desc, gn_finalize, marshal_consumers
 from .tuning import TUNING
 
+# Largest input extent of a training pass: the bilinear x2 adjoint (mrisr_upsample2_adjoint, mrisr_conv_upadj) gathers the four
+# high-resolution rows common.h's up2_adjoint_weights names, which is checked for every extent up to this one
+# (tests/test_norm_fwd_ref_host.py::test_adjoint_window_claim); every low-resolution extent of a pass is at most the input's.
+MAX_TRAIN_EXTENT = 4200
+
 
 def _dt(dtype: torch.dtype) -> int:
     if dtype == torch.bfloat16:
@@ -331,6 +336,8 @@ class UNetEngine:
         mins = 2 ** (self.depth - 1)
         if H < mins or W < mins:
             raise ValueError(f"input must be at least {mins}x{mins} ({self.depth - 1} 2x2 max-pools)")
+        if training and max(H, W) > MAX_TRAIN_EXTENT:
+            raise ValueError(f"training input {H}x{W}: extents above {MAX_TRAIN_EXTENT} are outside the checked range of the bilinear adjoint")
         st = L.stream_ptr()
         f = self.f
         p = _Pass()
