@@ -1037,6 +1037,19 @@ int mrisr_f32_volume_slice_cost(const float* x, int X, int Y, int Z, const float
                                 int slices, int count, int slice_axis, const double* offsets, const float* weights, int T, int stride,
                                 void* workspace, double* out, void* stream);
 
+/* ---- Zero-filled x2 interpolation and k-space truncation (extension; csrc/volume_kspace.hip): one dense circulant transform along
+ *      one axis of a float32 volume (X, Y, Z), C order.  The specification is mri_superresolution_amd/volume_kspace.py. ---- */
+#define MRISR_CIRCULANT_UP2 0       /* a line of n samples (1..512) becomes 2n:  dst[2i + s] = sum_j table[s n + (i - j) mod n] src[j] */
+#define MRISR_CIRCULANT_DOWN2 1     /* a line of N samples (even, 2..1024) becomes N / 2:  dst[i] = sum_j table[(2i - j) mod N] src[j] */
+/* The lines are those along axis (0..2); dst has that extent doubled (up2) or halved (down2) and the two others as they are.  table
+ * (DEVICE): 2n floats for up2 (volume_kspace.zerofill_table), N for down2 (truncate_table).  Every output is 0 + t src[0] + t src[1]
+ * + ... over j ascending, each product and each sum rounded to float32, no fma: bit for bit volume_kspace.zerofill2_np /
+ * truncate2_np of that one axis, on every run and for every launch shape.  One launch, no workspace, no atomics, no host
+ * synchronisation.  MRISR_E_ARG: null or misaligned pointer, src == dst, axis outside 0..2, unknown mode; MRISR_E_SHAPE: an extent
+ * outside 1..32767, a line longer than the mode's limit, an odd line for down2, more than 2^31 - 1 voxels in src or dst.           */
+int mrisr_f32_volume_line_circulant(const float* src, int X, int Y, int Z, int axis, int mode, const float* table, float* dst,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -593,10 +593,21 @@ class VolumeScores(OrderedDict):
         self.tissue_edges = None
 
 
+_DEGRADE_WARNED = False
+
+
+def _warn_degrade_ignored(degrade):
+    global _DEGRADE_WARNED
+    if not _DEGRADE_WARNED:
+        logger.warning(f"degrade={degrade!r} is ignored: the low-resolution volume is given.")
+        _DEGRADE_WARNED = True
+
+
 def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic: bool = False, axis: int = 2, val_range: float = None,
                     batch_size: int = 16, use_amp: bool = False, use_graph: bool = True, graph_cache: dict = None, mask=None,
                     mask_close: int = 0, mask_largest: bool = False, mask_fill_holes=None, tissue_dice: int = 0, tissue_surface: bool = False,
-                    spacing=None, tissue_edges: bool = False, edge_radius: float = 4.0, edge_bin: float = 0.5) -> "VolumeScores":
+                    spacing=None, tissue_edges: bool = False, edge_radius: float = 4.0, edge_bin: float = 0.5, zerofill: str = None,
+                    degrade: str = "mean") -> "VolumeScores":
     """Scores the U-Net and the interpolation baselines against the ground truth ``ref`` (float32 CUDA volume).
 
     The doubled axes are all three with ``isotropic``, else the two in-plane axes of the slices across ``axis``.  ``lr=None``
@@ -605,7 +616,7 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     ``ref.max() - ref.min()`` (of the cropped volume).  Returns ``{method: (5,) float64 CUDA tensor}`` in the order ``unet``
     (``enhance_volume`` or ``enhance_volume_isotropic``, float32), ``unet_axis2_linear`` (``isotropic`` only:
     ``enhance_volume_isotropic(planes=(2,))``, the single-pass alternative to the blend), ``linear``, ``cubic`` (``upscale2`` of
-    the same ``lr`` over the same axes).
+    the same ``lr`` over the same axes), then ``zerofill`` on request (below).
 
     ``mask``: ``None``, ``"otsu"`` (``foreground_mask`` of the cropped REFERENCE volume with ``close_radius=mask_close``, taken once
     and shared by every method) or a uint8 / bool CUDA tensor of ``ref``'s shape (it gets the reference's crop; ``mask_close`` is
@@ -627,7 +638,13 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
     ``tissue_edges`` (needs ``tissue_dice``): ``.tissue_edges`` is ``{method: EdgeSharpness}``, the 10 % - 90 % width and the contrast of
     every method's output across the ``tissue_dice - 1`` interfaces between the tissue classes of the REFERENCE's label volume
     (``volume_sharpness``): the signed distances to them are taken once, with ``spacing``, and each output and the ``reference`` row get
-    one ``edge_profile`` pass with ``edge_radius`` and ``edge_bin`` in the unit of ``spacing``."""
+    one ``edge_profile`` pass with ``edge_radius`` and ``edge_bin`` in the unit of ``spacing``.
+
+    ``zerofill`` (``"none"`` or ``"hamming"``, the k-space window; None: off): a method ``zerofill`` (``zerofill_hamming``) is scored
+    after ``cubic`` - ``volume_kspace.zerofill2`` of the same ``lr`` over the same axes, what a scanner's interpolated matrix shows -
+    with everything the other rows get.  ``degrade`` (``"mean"``, ``"kspace"`` or ``"kspace_hamming"``): with a k-space setting the
+    low-resolution volume derived from ``ref`` is ``volume_kspace.truncate2`` of it, the degradation of the 2-D training path, in place
+    of ``downsample2``; a given ``lr`` is taken as it is, with one warning.  Both defaults leave a run as it was."""
     # the checks that need no data come first, the device check after them
     if not isinstance(ref, torch.Tensor) or ref.dtype != torch.float32 or ref.dim() != 3 or ref.numel() == 0:
         raise ValueError(f"expected a non-empty float32 volume (X,Y,Z), got {getattr(ref, 'dtype', type(ref))} "
@@ -638,6 +655,12 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
         raise ValueError(f"batch_size must be positive, got {batch_size}")
     if val_range is not None and not val_range > 0:
         raise ValueError(f"val_range must be positive, got {val_range}")
+    if zerofill is not None or degrade != "mean":
+        from .volume_kspace import truncate2, zerofill2
+        if zerofill not in (None, "none", "hamming"):
+            raise ValueError(f"zerofill must be None, 'none' or 'hamming', got {zerofill!r}")
+        if degrade not in ("mean", "kspace", "kspace_hamming"):
+            raise ValueError(f"degrade must be 'mean', 'kspace' or 'kspace_hamming', got {degrade!r}")
     if tissue_dice != 0:
         from .volume_tissue import TissueWorkspace, dice, label_confusion, segment_tissue
         check_classes(tissue_dice)
@@ -692,8 +715,10 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
             if isinstance(mask, torch.Tensor):
                 mask = mask[:crop[0], :crop[1], :crop[2]]
         ref = ref.contiguous()
-        lr = downsample2(ref, axes)
+        lr = downsample2(ref, axes) if degrade == "mean" else truncate2(ref, axes, "hamming" if degrade == "kspace_hamming" else "none")
     else:
+        if degrade != "mean":
+            _warn_degrade_ignored(degrade)
         ref, lr = ref.contiguous(), lr.contiguous()
     if val_range is None:
         val_range = float((ref.max() - ref.min()).item())
@@ -743,6 +768,8 @@ def evaluate_volume(model, ref: torch.Tensor, lr: torch.Tensor = None, isotropic
         scored("unet", enhance_volume(model, lr, axis=axis, **common))
     for method in ("linear", "cubic"):
         scored(method, upscale2(lr, method, axes))
+    if zerofill is not None:
+        scored("zerofill" if zerofill == "none" else f"zerofill_{zerofill}", zerofill2(lr, axes, zerofill))
     if tissue_dice:
         scored("reference", ref)
     if mask is not None:

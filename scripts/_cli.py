@@ -1,4 +1,4 @@
-"""What the volume scripts share: the ``--cpu`` flag, the guarded ``main``, the upload of a frame, the joining
+"""What the volume scripts share: the ``--cpu`` flag, the k-space flags, the guarded ``main``, the upload of a frame, the joining
 and saving of frames, and the mask loading of ``evaluate_volume.py`` and ``segment_volume.py``.  A script imports it after the
 ``REPO`` path insert.
 """
@@ -17,6 +17,27 @@ logger = logging.getLogger("volume_cli")
 
 def add_cpu_flag(parser):
     parser.add_argument("--cpu", action="store_true", help="REFUSED: this build runs on an MI355X through libmrisr.so only (there is no CPU fallback)")
+
+
+def add_kspace_flags(parser):
+    """``--zerofill`` and ``--degrade`` of ``evaluate_volume.py`` (``volume_kspace``); ``kspace_options`` reads them back."""
+    parser.add_argument("--zerofill", type=str, choices=["none", "hamming"], default=None,
+                        help="add the baseline an MR scanner gives: k-space zero-filling (periodic sinc interpolation) of the same "
+                             "low-resolution volume, as the row zerofill - with the k-space window hamming as zerofill_hamming "
+                             "(no row unless the flag is present)")
+    parser.add_argument("--degrade", type=str, choices=["mean", "kspace", "kspace_hamming"], default="mean",
+                        help="how the low-resolution volume is made from the reference: the mean over pairs, or k-space truncation "
+                             "(kspace_hamming: with a Hamming window), the degradation of the 2-D training path; ignored with --input")
+
+
+def kspace_options(args) -> dict:
+    """-> the keywords of ``score_scan`` / ``volume_eval.evaluate_volume`` for the two flags; empty when neither is used."""
+    chosen = {}
+    if args.zerofill is not None:
+        chosen["zerofill"] = args.zerofill
+    if args.degrade != "mean":
+        chosen["degrade"] = args.degrade
+    return chosen
 
 
 def start_logging():

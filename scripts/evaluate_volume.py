@@ -101,6 +101,14 @@ one pass per method then gives the mean intensity of its output as a function of
 after the Dice and surface columns: ``esw_1 ... esw_{K-1}``, the 10 % - 90 % width of that edge-spread function in millimetres (smaller
 is sharper), and ``econ_1 ... econ_{K-1}``, the contrast of its two plateaus as a ratio to the reference row's (1 in the row
 ``reference``); empty in the rows of the whole volume, NaN where a crossing is not reached.  Without the switch a run is as it was.
+
+``--zerofill none|hamming`` adds the baseline an MR reader expects first: what the scanner itself shows as its "interpolated matrix",
+k-space padded with zeros and transformed back - periodic sinc interpolation of the same low-resolution volume over the same axes
+(``volume_kspace.zerofill2``; ``csrc/volume_kspace.hip``), ``hamming`` with that window on k-space.  The row ``zerofill``
+(``zerofill_hamming``) follows ``cubic`` and is scored like every other.  ``--degrade kspace|kspace_hamming`` makes the low-resolution
+volume of a run without ``--input`` by truncating the reference's k-space to its centre (``volume_kspace.truncate2``), the resolution
+loss of the 2-D training path (``csrc/lowfield.hip``), instead of the mean over pairs; the tables' titles then say so.  With ``--input``
+it is ignored, with a warning.  Without the two flags a run writes the bytes it wrote before.
 """
 import argparse
 import csv
@@ -125,8 +133,8 @@ from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_int
 from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice    # noqa: E402
 from mri_superresolution_amd.volume_sharpness import check_bins as check_edge_bins        # noqa: E402
-from scripts._cli import (add_cpu_flag, join_frames, load_mask, log_device, make_parent, require_gpu, start_logging, to_device,   # noqa: E402
-                          voxel_sizes)
+from scripts._cli import (add_cpu_flag, add_kspace_flags, join_frames, kspace_options, load_mask, log_device, make_parent,   # noqa: E402
+                          require_gpu, start_logging, to_device, voxel_sizes)
 
 logger = logging.getLogger("evaluate_volume")
 CSV_COLUMNS = ["scan", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # the column style of scripts/evaluate.py
@@ -273,7 +281,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
                match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
                denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0, tissue_surface=False, deform_force="ssd",
-               deform_lcc_radius=2, tissue_edges=False, edge_radius_mm=4.0, edge_bin_mm=0.5):
+               deform_lcc_radius=2, tissue_edges=False, edge_radius_mm=4.0, edge_bin_mm=0.5, zerofill=None, degrade="mean"):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -291,7 +299,9 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     classes with the reference's (``""`` in the rows of the whole volume), and a last method ``reference`` is scored.
     ``tissue_surface`` (needs ``tissue_dice``): those rows also carry ``surface_columns(K)``, in the world units of the reference's header.
     ``tissue_edges`` (needs ``tissue_dice``): those rows also carry ``edge_columns(K)``, the widths in those units and the contrasts as
-    ratios to the row ``reference``'s; ``edge_radius_mm`` and ``edge_bin_mm`` set the profile's range and bins."""
+    ratios to the row ``reference``'s; ``edge_radius_mm`` and ``edge_bin_mm`` set the profile's range and bins.
+    ``zerofill`` (``"none"`` / ``"hamming"``): a method ``zerofill`` (``zerofill_hamming``) follows ``cubic``; ``degrade`` (``"kspace"`` /
+    ``"kspace_hamming"``): the low-resolution volume is the reference's truncated k-space (``volume_eval.evaluate_volume``)."""
     check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
                   denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask, tissue_surface,
                   deform_force, deform_lcc_radius, tissue_edges, edge_radius_mm, edge_bin_mm)
@@ -353,7 +363,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                               use_amp=use_amp, use_graph=use_graph, graph_cache=graphs, mask=m, mask_close=mask_close, mask_largest=mask_largest,
                               mask_fill_holes=mask_fill_holes, tissue_dice=tissue_dice, tissue_surface=tissue_surface,
                               spacing=voxel_sizes(ref_header.affine()) if tissue_surface or tissue_edges else None,
-                              **(dict(tissue_edges=True, edge_radius=edge_radius_mm, edge_bin=edge_bin_mm) if tissue_edges else {}))
+                              **(dict(tissue_edges=True, edge_radius=edge_radius_mm, edge_bin=edge_bin_mm) if tissue_edges else {}),
+                              **(dict(zerofill=zerofill) if zerofill is not None else {}), **(dict(degrade=degrade) if degrade != "mean" else {}))
         scan = name if len(ref_frames) == 1 else f"{name}[t={t}]"
         if mask is None:
             values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
@@ -464,6 +475,7 @@ def main(args):
         dice = dice_columns(args.tissue_dice) + (surface_columns(args.tissue_dice) if args.tissue_surface else [])
         dice += edge_columns(args.tissue_dice) if args.tissue_edges else []
         shown = {"foreground": dice}                     # the tables of the whole volume stay as they are
+        degraded = f" (degrade {args.degrade})" if args.degrade != "mean" else ""
         for path in args.reference:
             scan_rows = score_scan(model, path, input_path=args.input, isotropic=args.isotropic, axis=args.axis, data_range=args.data_range,
                                    batch_size=args.batch_size, use_amp=args.use_amp, use_graph=not args.no_graph, device=device,
@@ -476,11 +488,11 @@ def main(args):
                                    deform_exp_steps=args.deform_exp_steps, deform_force=args.deform_force,
                                    deform_lcc_radius=args.deform_lcc_radius, tissue_dice=args.tissue_dice,
                                    tissue_surface=args.tissue_surface, tissue_edges=args.tissue_edges,
-                                   edge_radius_mm=args.edge_radius_mm, edge_bin_mm=args.edge_bin_mm)
+                                   edge_radius_mm=args.edge_radius_mm, edge_bin_mm=args.edge_bin_mm, **kspace_options(args))
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
-                    print(format_table(foreground_title(part) if region == "foreground" else scan, part, shown.get(region, ())))
+                    print(format_table(foreground_title(part) if region == "foreground" else scan + degraded, part, shown.get(region, ())))
             rows += scan_rows
         means = []
         for region in regions:
@@ -489,7 +501,7 @@ def main(args):
             mean = mean_rows(part, dice)
             if region is not None:
                 mean = [{**r, "region": region} for r in mean]
-            print(format_table(f"foreground, {title}" if region == "foreground" else title, mean, shown.get(region, ())))
+            print(format_table(f"foreground, {title}" if region == "foreground" else title + degraded, mean, shown.get(region, ())))
             means += mean
         if args.output_csv:
             make_parent(args.output_csv)
@@ -580,6 +592,7 @@ def parse_args(argv=None):
                         "(needs --tissue_dice)")
     p.add_argument("--edge_radius_mm", type=float, default=4.0, help="--tissue_edges: the profile runs this far either side of an interface")
     p.add_argument("--edge_bin_mm", type=float, default=0.5, help="--tissue_edges: the width of a bin of the profile (at most 64 bins)")
+    add_kspace_flags(p)
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 
