@@ -35,16 +35,9 @@
 //                              at most 16 KB of LDS per workgroup, far from the CU's 160 KB.
 //   f32_volume_jacobian_stats  det(I + grad u) by the gradient rule of the force, its minimum and the count of det <= 0 through the
 //                              same slots, finalised by a launch of one wave.
+// The brick walk, the slots and the volume check are volume_bricks.h's (through volume_deform.h), gather and gather_at volume_taps.h's.
 #include "volume_deform.h"
 #include "volume_taps.h"
-
-// voxel of thread tid in brick b (bricks numbered along z, then y, then x)
-__device__ __forceinline__ bool brick_voxel(unsigned b, unsigned nby, unsigned nbz, int X, int Y, int Z, int& i, int& j, int& k) {
-    const unsigned bz = b % nbz, rest = b / nbz, by = rest % nby, bx = rest / nby;
-    const int tid = threadIdx.x;
-    k = (int)bz * kBZ + tid % kBZ, j = (int)by * kBY + tid / kBZ % kBY, i = (int)bx * kBX + tid / (kBZ * kBY);
-    return i < X && j < Y && k < Z;
-}
 
 // the coordinate of voxel (i, j, k) under the field and the inside test
 __device__ __forceinline__ bool field_coordinate(const float* __restrict__ u, size_t n, size_t idx, int i, int j, int k, int X, int Y,
@@ -60,38 +53,6 @@ __device__ __forceinline__ bool field_coordinate(const float* __restrict__ u, si
     return inside;
 }
 
-// the taps of the three axes reduced along z, then y, then x
-template <int N>
-__device__ __forceinline__ float gather_at(const float* __restrict__ src, int Y, int Z, const int* ix, const int* iy, const int* iz,
-                                           const float* wx, const float* wy, const float* wz) {
-    float rx[N];
-#pragma unroll
-    for (int a = 0; a < N; ++a) {
-        float ry[N];
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-            const float* row = src + ((size_t)ix[a] * Y + iy[b]) * Z;
-            float v[N];
-#pragma unroll
-            for (int c = 0; c < N; ++c) v[c] = row[iz[c]];
-            ry[b] = weighted_sum<N>(wz, v);
-        }
-        rx[a] = weighted_sum<N>(wy, ry);
-    }
-    return weighted_sum<N>(wx, rx);
-}
-
-template <int METHOD>
-__device__ __forceinline__ float gather(const float* __restrict__ src, int X, int Y, int Z, const double* p) {
-    constexpr int N = METHOD == kLinear ? 2 : 4;
-    int ix[N], iy[N], iz[N];
-    float wx[N], wy[N], wz[N];
-    axis_taps<METHOD>(p[0], X, ix, wx);
-    axis_taps<METHOD>(p[1], Y, iy, wy);
-    axis_taps<METHOD>(p[2], Z, iz, wz);
-    return gather_at<N>(src, Y, Z, ix, iy, iz, wx, wy, wz);
-}
-
 template <int METHOD>
 __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ moving, const float* __restrict__ u, int X, int Y, int Z,
                                                    float fill, float* __restrict__ out, unsigned nby, unsigned nbz) {
@@ -103,10 +64,6 @@ __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ mov
     const bool inside = field_coordinate(u, n, idx, i, j, k, X, Y, Z, ua, p);
     out[idx] = inside ? gather<METHOD>(moving, X, Y, Z, p) : fill;
 }
-
-struct Matrix34 {
-    double m[3][4];
-};
 
 // moving (SX, SY, SZ) at M (x + u(x)): the coordinate under the field, then grid_coordinate's order, then the inside test of the source
 template <int METHOD>
@@ -401,10 +358,7 @@ extern "C" int mrisr_f32_volume_warp_matrix(const float* moving, int SX, int SY,
     if (method != kLinear && method != kCubic)
         MRISR_FAIL(MRISR_E_ARG, "f32_volume_warp_matrix: method %d (MRISR_RESAMPLE_LINEAR or _CUBIC)", method);
     Matrix34 m;
-    for (int e = 0; e < 12; ++e) {
-        if (!isfinite(m12[e])) MRISR_FAIL(MRISR_E_ARG, "f32_volume_warp_matrix: matrix entry [%d][%d] is not finite", e / 4, e % 4);
-        m.m[e / 4][e % 4] = m12[e];
-    }
+    if (const int rc = check_matrix34("f32_volume_warp_matrix", m12, m.m)) return rc;
     BrickGrid source, g;
     if (const int rc = check_field_volume("f32_volume_warp_matrix (moving)", SX, SY, SZ, &source)) return rc;
     if (const int rc = check_field_volume("f32_volume_warp_matrix", X, Y, Z, &g)) return rc;

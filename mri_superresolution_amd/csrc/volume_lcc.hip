@@ -22,7 +22,7 @@
 //                            d. adds the ring in order (axis 0), runs the regression and the epilogue for plane i - R: the
 //                               6-neighbour gradient of fixed, a coalesced read of u and a coalesced write of three components.
 //                          The count n is an integer sum (exact either way).  Float64 adds only, no atomics: a thread adds
-//                          float64(w) of its ok voxels as a pair (volume_deform.h), the workgroup leaves its slot, the smoothing
+//                          float64(w) of its ok voxels as a pair (volume_bricks.h), the workgroup leaves its slot, the smoothing
 //                          pass that follows (or a launch of one wave) adds the slots - the same bits on every run.
 //
 // LDS per workgroup: 40 (8 + 2R)(32 + 2R) + 40 (8 + 2R) 32 bytes of channels and sums plus 4 bytes per element of counts:

@@ -64,16 +64,8 @@ __device__ __forceinline__ int value_bin(float v, const BinRule& r) {
 // the moving value at sample (i, j, k) under matrix m; false: outside
 __device__ __forceinline__ bool moving_value(const float* __restrict__ mov, int MX, int MY, int MZ, const double* m, int i, int j, int k,
                                              float* out) {
-    const double di = (double)i, dj = (double)j, dk = (double)k;
-    const int n[3] = {MX, MY, MZ};
     double p[3];
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        p[a] = grid_coordinate(m + 4 * a, di, dj, dk);
-        inside = inside && p[a] >= -0.5 && p[a] <= (double)n[a] - 0.5;
-    }
-    if (!inside) return false;
+    if (!matrix_coordinate((const double (*)[4])m, (double)i, (double)j, (double)k, MX, MY, MZ, p)) return false;
     int ix[2], iy[2], iz[2];
     float wx[2], wy[2], wz[2];
     axis_taps<kLinear>(p[0], MX, ix, wx);

@@ -92,10 +92,7 @@ __global__ __launch_bounds__(256) void volume_reslice_kernel(const T* __restrict
 static int check_reslice(const char* name, const void* src, int SX, int SY, int SZ, const void* dst, int DX, int DY, int DZ,
                          const double* m12, GridMatrix* g) {
     if (!src || !dst || !m12) MRISR_FAIL(MRISR_E_ARG, "%s: null pointer", name);
-    for (int e = 0; e < 12; ++e) {
-        if (!isfinite(m12[e])) MRISR_FAIL(MRISR_E_ARG, "%s: matrix entry [%d][%d] is not finite", name, e / 4, e % 4);
-        g->m[e / 4][e % 4] = m12[e];
-    }
+    if (const int rc = check_matrix34(name, m12, g->m)) return rc;
     if (SX < 1 || SY < 1 || SZ < 1 || DX < 1 || DY < 1 || DZ < 1)
         MRISR_FAIL(MRISR_E_SHAPE, "%s: %d x %d x %d -> %d x %d x %d (every extent at least 1)", name, SX, SY, SZ, DX, DY, DZ);
     const long long sxy = (long long)SX * SY, dxy = (long long)DX * DY;

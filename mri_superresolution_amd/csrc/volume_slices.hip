@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void stack_residual_slices_kernel(const float*
     PairSum sq = {0.0, 0.0, 0};
     for (unsigned b = blockIdx.x; b < nbricks; b += gridDim.x) {
         int i, j, k;
-        if (!stack_brick_voxel(b, nby, nbz, SX, SY, SZ, i, j, k)) continue;
+        if (!brick_voxel(b, nby, nbz, SX, SY, SZ, i, j, k)) continue;
         const int slice = axis == 0 ? i : (axis == 1 ? j : k);
         double g[3][4];
         load_matrix(table + (size_t)slice * 12, g);
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void stack_update_slices_kernel(const float* x
     __shared__ double zrow[kMaxSlices][4];
     stack_update_stats(slots, v.nslots, K, rows);
     int i, j, k;
-    const bool valid = stack_brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k);      // every thread stays for the barriers
+    const bool valid = brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k);      // every thread stays for the barriers
     const double di = (double)i, dj = (double)j, dk = (double)k;
     float sum = 0.f;
     int cnt = 0;

@@ -10,7 +10,7 @@
 //                               estimate to acc and w_t to wsum (float32, t ascending); r = y - acc / wsum where wsum >= 0.5, else +0.
 //                               The float64 sum of r^2 and the count of such voxels leave the launch as in
 //                               mrisr_f32_volume_demons_force: a thread's (sum, rounding error) pair, the waves and the workgroup in
-//                               a fixed order, one slot per workgroup (volume_deform.h), added by one wave of a LATER launch.
+//                               a fixed order, one slot per workgroup (volume_bricks.h), added by one wave of a LATER launch.
 //   f32_volume_stack_update     ONE launch for all stacks, one thread per OUTPUT voxel: for k ascending, the linear gather of r_k
 //                               where the voxel lies inside stack k; x' = x + step * (sum / cnt) where cnt > 0, clamped from below
 //                               there.  The views (pointer, extents, matrix) travel by value in the kernel arguments.  Its first
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void stack_residual_kernel(const float* __rest
     PairSum sq = {0.0, 0.0, 0};
     for (unsigned b = blockIdx.x; b < nbricks; b += gridDim.x) {
         int i, j, k;
-        if (!stack_brick_voxel(b, nby, nbz, SX, SY, SZ, i, j, k)) continue;
+        if (!brick_voxel(b, nby, nbz, SX, SY, SZ, i, j, k)) continue;
         stack_residual_voxel(x, X, Y, Z, y, g.m, axis, pr, T, i, j, k, ((size_t)i * SY + j) * SZ + k, r, sq);
     }
     block_sum_to_slot(sq, part, &slots[blockIdx.x]);
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void stack_update_kernel(const float* x, float
                                                            unsigned nbz, const DeformSlot* __restrict__ slots, StatsRow* __restrict__ rows) {
     stack_update_stats(slots, v.nslots, K, rows);
     int i, j, k;
-    if (!stack_brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k)) return;
+    if (!brick_voxel(blockIdx.x, nby, nbz, X, Y, Z, i, j, k)) return;
     const size_t idx = ((size_t)i * Y + j) * Z + k;
     float sum;
     const int cnt = stack_gather_views(v, K, (double)i, (double)j, (double)k, sum);
@@ -140,7 +140,7 @@ extern "C" int mrisr_f32_volume_stack_residual(const float* x, int X, int Y, int
     if (T < 1 || T > kMaxSamples) MRISR_FAIL(MRISR_E_ARG, "%s: %d profile samples (1..%d)", name, T, kMaxSamples);      // before the axis and matrix checks, as before; check_profile repeats it
     if (slice_axis < 0 || slice_axis > 2) MRISR_FAIL(MRISR_E_ARG, "%s: slice axis %d (0..2)", name, slice_axis);
     StackMatrix g;
-    if (const int rc = check_matrix(name, m12, g.m)) return rc;
+    if (const int rc = check_matrix34(name, m12, g.m)) return rc;
     StackProfile pr;
     if (const int rc = check_profile(name, offsets, weights, T, &pr)) return rc;
     BrickGrid out_grid, grid;
@@ -172,7 +172,7 @@ static int fill_stack_views(const char* name, const mrisr_stack_view* views, int
         if (!aligned_to(in.data, 4)) MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: misaligned pointer", name, s);
         if (in.data == out || (const void*)in.data == (const void*)cover)
             MRISR_FAIL(MRISR_E_ARG, "%s: stack %d: out and cover must be buffers of their own", name, s);
-        if (const int rc = check_matrix(name, in.m, v->m[s])) return rc;
+        if (const int rc = check_matrix34(name, in.m, v->m[s])) return rc;
         BrickGrid sg;
         if (const int rc = check_field_volume(name, in.nx, in.ny, in.nz, &sg)) return rc;
         v->data[s] = in.data;

@@ -52,7 +52,7 @@ from . import _lib as L
 from ._volume_args import check_matrix, check_shape, cuda_tensor, matrix_arg, out_like, three_sigmas, volume_np
 from .volume_bias import gaussian_taps
 from .volume_eval import downsample2, downsample2_np, upscale2, upscale2_np
-from .volume_reslice import taps_np, weighted_sum_np
+from .volume_reslice import sample_np
 
 MAX_RADIUS = 16
 DEN_MIN = np.float32(1e-9)                 # MRISR_DEFORM_DEN_MIN: below it a voxel has neither a gradient nor a difference
@@ -84,6 +84,21 @@ def _check_field_np(u, shape, what):
     return u
 
 
+def _check_field4_np(u, what):
+    u = np.asarray(u)
+    if u.dtype != np.float32 or u.ndim != 4 or u.shape[0] != 3 or u.size == 0:
+        raise ValueError(f"{what}: expected a non-empty float32 field (3,X,Y,Z), got {u.dtype} {u.shape}")
+    check_shape(u.shape[1:], f"{what}: the volume's shape")
+    return u
+
+
+def _check_pair_np(fixed, moving, what):
+    fixed, moving = _check_volume_np(fixed, what), _check_volume_np(moving, what)
+    if fixed.shape != moving.shape:
+        raise ValueError(f"{what}: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
+    return np.ascontiguousarray(fixed), np.ascontiguousarray(moving)
+
+
 def _check_method(method):
     if method not in METHODS:
         raise ValueError(f"Unknown interpolation method: {method} (linear or cubic)")
@@ -97,33 +112,29 @@ def _check_max_step(max_step) -> np.float32:
     return m
 
 
-def _coordinates_np(u):
-    """-> (p, inside): ``p_a = float64(i_a) + float64(u_a)`` and the test ``-0.5 <= p_a <= n_a - 0.5`` on all three axes (a NaN or
-    infinite displacement fails it)."""
-    shape = u.shape[1:]
-    p = []
+def _field_coordinates_np(u):
+    """The three float64 arrays ``float64(i_a) + float64(u_a)`` of a field ``u`` (3, X, Y, Z): one double addition each."""
+    with np.errstate(invalid="ignore"):
+        return [np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)]) + u[a].astype(np.float64)
+                for a, n in enumerate(u.shape[1:])]
+
+
+def _sample_inside_np(moving, p, shape, method, fill):
+    """-> ``(out, inside)``: ``moving`` sampled at the coordinates ``p`` (on a grid of ``shape``) that pass the inside test
+    ``-0.5 <= p_a <= n_a - 0.5`` on all three axes of ``moving`` (a NaN fails it), ``fill`` elsewhere."""
     inside = np.ones(shape, dtype=bool)
     with np.errstate(invalid="ignore"):
-        for a, n in enumerate(shape):
-            i = np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)])
-            pa = i + u[a].astype(np.float64)
+        for pa, n in zip(p, moving.shape):
             inside &= (pa >= -0.5) & (pa <= n - 0.5)
-            p.append(pa)
-    return p, inside
+    out = np.full(shape, np.float32(fill), dtype=np.float32)
+    if inside.any():
+        with np.errstate(all="ignore"):
+            out[inside] = sample_np([moving], [pa[inside] for pa in p], method)[0]
+    return out, inside
 
 
 def _warp_np(moving, u, method, fill):
-    p, inside = _coordinates_np(u)
-    out = np.full(moving.shape, np.float32(fill), dtype=np.float32)
-    if inside.any():
-        with np.errstate(all="ignore"):
-            (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
-            rx = []
-            for xa in ix:
-                ry = [weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
-                rx.append(weighted_sum_np(wy, ry))
-            out[inside] = weighted_sum_np(wx, rx)
-    return out, inside
+    return _sample_inside_np(moving, _field_coordinates_np(u), moving.shape, method, fill)
 
 
 def warp_np(moving, u, method: str = "linear", fill: float = 0.0) -> np.ndarray:
@@ -156,28 +167,34 @@ def gradient_np(f) -> np.ndarray:
     return np.stack([_gradient_axis_np(f, a) for a in range(3)])
 
 
+def _thirion_np(d, g, max_step, keep, weight=None):
+    """Thirion's rule -> the three update components: ``den = ((g0 g0 + g1 g1) + g2 g2) + d d``; ``s = d / den`` where
+    ``den > DEN_MIN``, else 0; with a ``weight``, ``s = s weight``; ``upd_a = -(s g_a)`` clamped to ``[-max_step, max_step]`` by
+    comparisons, 0 outside ``keep`` and where it is not a number.  Every operation float32; call under ``np.errstate``."""
+    g2 = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]
+    den = g2 + d * d
+    has = den > DEN_MIN
+    s = np.where(has, d / np.where(has, den, np.float32(1)), np.float32(0)).astype(np.float32)
+    if weight is not None:
+        s = s * weight
+    upd = []
+    for a in range(3):
+        x = -(s * g[a])
+        x = np.where(x > max_step, max_step, np.where(x < -max_step, -max_step, x))
+        upd.append(np.where(keep & ~np.isnan(x), x, np.float32(0)).astype(np.float32))
+    return upd
+
+
 def _demons_update_np(fixed, moving, u, max_step, fill, what):
     """-> ``(u, upd, stats)``: the checked field, the three cleaned update components and the (sum of d^2, count) row, as
     ``demons_force_np`` states them."""
-    fixed = _check_volume_np(fixed, what)
-    moving = _check_volume_np(moving, what)
-    if fixed.shape != moving.shape:
-        raise ValueError(f"{what}: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
+    fixed, moving = _check_pair_np(fixed, moving, what)
     u = _check_field_np(u, fixed.shape, what)
     ms = _check_max_step(max_step)
     warped, inside = _warp_np(moving, u, "linear", fill)
     with np.errstate(all="ignore"):
         d = warped - fixed
-        g = gradient_np(fixed)
-        g2 = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]
-        den = g2 + d * d
-        ok = den > DEN_MIN
-        s = np.where(ok, d / np.where(ok, den, np.float32(1)), np.float32(0)).astype(np.float32)
-        upd = []
-        for a in range(3):
-            x = -(s * g[a])
-            x = np.where(x > ms, ms, np.where(x < -ms, -ms, x))
-            upd.append(np.where(inside & ~np.isnan(x), x, np.float32(0)).astype(np.float32))
+        upd = _thirion_np(d, gradient_np(fixed), ms, inside)
     keep = inside & np.isfinite(d)
     dd = d[keep].astype(np.float64)
     return u, upd, (math.fsum(dd * dd), int(keep.sum()))
@@ -246,10 +263,7 @@ def _window_sums_np(c, r):
 def _lcc_update_np(fixed, moving, u, radius, max_step, what):
     """-> ``(u, upd, stats)``: the checked field, the three cleaned update components and the (sum of w, count) row, as
     ``lcc_force_np`` states them."""
-    fixed = _check_volume_np(fixed, what)
-    moving = _check_volume_np(moving, what)
-    if fixed.shape != moving.shape:
-        raise ValueError(f"{what}: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
+    fixed, moving = _check_pair_np(fixed, moving, what)
     u = _check_field_np(u, fixed.shape, what)
     r = _check_lcc_radius(radius)
     ms = _check_max_step(max_step)
@@ -269,17 +283,7 @@ def _lcc_update_np(fixed, moving, u, radius, max_step, what):
         ok = valid & (n >= 2) & (B > 0) & (C > 0) & (A != 0) & np.isfinite(d64) & np.isfinite(w64)
         d = np.where(ok, d64, 0.0).astype(np.float32)
         w = np.where(ok, w64, 0.0).astype(np.float32)
-        g = gradient_np(fixed)
-        g2 = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]
-        den = g2 + d * d
-        has = den > DEN_MIN
-        s = np.where(has, d / np.where(has, den, np.float32(1)), np.float32(0)).astype(np.float32)
-        s = s * w
-        upd = []
-        for a in range(3):
-            x = -(s * g[a])
-            x = np.where(x > ms, ms, np.where(x < -ms, -ms, x))
-            upd.append(np.where(ok & ~np.isnan(x), x, np.float32(0)).astype(np.float32))
+        upd = _thirion_np(d, gradient_np(fixed), ms, ok, w)
     return u, upd, (math.fsum(w[ok].astype(np.float64)), int(ok.sum()))
 
 
@@ -316,14 +320,6 @@ def lcc_update_np(fixed, moving, u, radius: int = 2, max_step: float = 2.0, scal
         return np.stack([x * sc for x in upd]), stats
 
 
-def _check_field4_np(u, what):
-    u = np.asarray(u)
-    if u.dtype != np.float32 or u.ndim != 4 or u.shape[0] != 3 or u.size == 0:
-        raise ValueError(f"{what}: expected a non-empty float32 field (3,X,Y,Z), got {u.dtype} {u.shape}")
-    check_shape(u.shape[1:], f"{what}: the volume's shape")
-    return u
-
-
 def compose_np(u, v) -> np.ndarray:
     """``v_a + U_a``, float32 ``(3, X, Y, Z)``: ``U_a`` is ``u_a`` interpolated linearly at ``p = float64(i) + float64(v)`` (the coordinate
     of ``warp_np``), so that ``warp(warp(m, u), v)`` samples ``m`` at ``x + compose_np(u, v)(x)``, up to interpolation.  Each ``p_a``
@@ -337,25 +333,14 @@ def compose_np(u, v) -> np.ndarray:
     u, v = _check_field4_np(u, "compose_np"), _check_field4_np(v, "compose_np")
     if u.shape != v.shape:
         raise ValueError(f"compose_np: the fields must share a grid, got shapes {u.shape} and {v.shape}")
-    shape = u.shape[1:]
-    p, number = [], np.ones(shape, dtype=bool)
     with np.errstate(invalid="ignore"):
-        for a, n in enumerate(shape):
-            i = np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)])
-            pa = i + v[a].astype(np.float64)
-            pa = np.where(pa < 0.0, 0.0, np.where(pa > n - 1.0, n - 1.0, pa))
-            number &= ~np.isnan(pa)
-            p.append(pa)
+        p = [np.where(pa < 0.0, 0.0, np.where(pa > n - 1.0, n - 1.0, pa)) for pa, n in zip(_field_coordinates_np(v), u.shape[1:])]
+    number = ~(np.isnan(p[0]) | np.isnan(p[1]) | np.isnan(p[2]))
     out = np.full(u.shape, np.float32(np.nan), dtype=np.float32)
     if number.any():
         with np.errstate(all="ignore"):
-            (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[number], n, "linear") for pa, n in zip(p, shape))
-            for a in range(3):
-                rx = []
-                for xa in ix:
-                    ry = [weighted_sum_np(wz, [u[a][xa, yb, zc] for zc in iz]) for yb in iy]
-                    rx.append(weighted_sum_np(wy, ry))
-                out[a][number] = v[a][number] + weighted_sum_np(wx, rx)
+            for a, ua in enumerate(sample_np(list(u), [pa[number] for pa in p], "linear")):
+                out[a][number] = v[a][number] + ua
     return out
 
 
@@ -390,24 +375,10 @@ def warp_matrix_np(moving, m, u, method: str = "linear", fill: float = 0.0) -> n
     m = check_matrix(m)
     u = _check_field4_np(u, "warp_matrix_np")
     _check_method(method)
-    shape = u.shape[1:]
+    q = _field_coordinates_np(u)
     with np.errstate(invalid="ignore"):
-        q = [np.arange(n, dtype=np.float64).reshape([-1 if a == b else 1 for b in range(3)]) + u[a].astype(np.float64)
-             for a, n in enumerate(shape)]
         p = [((m[a, 0] * q[0] + m[a, 1] * q[1]) + m[a, 2] * q[2]) + m[a, 3] for a in range(3)]
-        inside = np.ones(shape, dtype=bool)
-        for a in range(3):
-            inside &= (p[a] >= -0.5) & (p[a] <= moving.shape[a] - 0.5)
-    out = np.full(shape, np.float32(fill), dtype=np.float32)
-    if inside.any():
-        with np.errstate(all="ignore"):
-            (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[inside], n, method) for pa, n in zip(p, moving.shape))
-            rx = []
-            for xa in ix:
-                ry = [weighted_sum_np(wz, [moving[xa, yb, zc] for zc in iz]) for yb in iy]
-                rx.append(weighted_sum_np(wy, ry))
-            out[inside] = weighted_sum_np(wx, rx)
-    return out
+    return _sample_inside_np(moving, p, u.shape[1:], method, fill)[0]
 
 
 def _check_sigmas(sigmas_vox) -> list:
@@ -440,9 +411,7 @@ def smooth_field_np(v, sigmas_vox) -> np.ndarray:
     """A separable Gaussian of each component of the field ``v`` over axis 2, then 1, then 0 of the volume: taps
     ``volume_bias.gaussian_taps``, added in ascending order to a sum that starts at 0, every product and sum float32; the border is
     replicated (``np.pad(mode="edge")``).  ``ValueError`` for a radius past 16 taps."""
-    v = np.asarray(v)
-    if v.dtype != np.float32 or v.ndim != 4 or v.shape[0] != 3 or v.size == 0:
-        raise ValueError(f"smooth_field_np: expected a non-empty float32 field (3,X,Y,Z), got {v.dtype} {v.shape}")
+    v = _check_field4_np(v, "smooth_field_np")
     taps = _check_sigmas(sigmas_vox)
     for axis in (2, 1, 0):
         v = _pass_np(v, taps[axis], axis)
@@ -453,9 +422,7 @@ def jacobian_stats_np(u):
     """-> ``(min det, count of det <= 0)`` of ``J = I + grad u``: ``J[a][b] = gradient_np(u_a)[b]``, ``J[a][a] = 1 + J[a][a]``,
     ``det = (J00 (J11 J22 - J12 J21) - J01 (J10 J22 - J12 J20)) + J02 (J10 J21 - J11 J20)`` - the expansion along the first row, every
     operation float32.  A determinant that is not a number enters neither; the minimum of none is +inf; ``-0.0`` is returned as 0."""
-    u = np.asarray(u)
-    if u.dtype != np.float32 or u.ndim != 4 or u.shape[0] != 3 or u.size == 0:
-        raise ValueError(f"jacobian_stats_np: expected a non-empty float32 field (3,X,Y,Z), got {u.dtype} {u.shape}")
+    u = _check_field4_np(u, "jacobian_stats_np")
     with np.errstate(all="ignore"):
         J = [list(gradient_np(u[a])) for a in range(3)]
         for a in range(3):
@@ -496,11 +463,26 @@ def _schedule(shape, levels, iterations) -> tuple:
     return tuple(zip(shapes, its))
 
 
-def _check_pair_np(fixed, moving, what):
-    fixed, moving = _check_volume_np(fixed, what), _check_volume_np(moving, what)
-    if fixed.shape != moving.shape:
-        raise ValueError(f"{what}: the scans must share a grid, got shapes {fixed.shape} and {moving.shape}")
-    return np.ascontiguousarray(fixed), np.ascontiguousarray(moving)
+def _register_np(fixed, moving, levels, iterations, sigma_vox, max_step, fill, method, force, lcc_radius, what, step) -> DeformResult:
+    """The frame of the two specifications, the counterpart of ``_register``: the checks, the pyramid, the hand-over between levels
+    and the final warp around ``step(f, m, u, sigmas) -> (u', stats row)``, one iteration on one level."""
+    fixed, moving = _check_pair_np(fixed, moving, what)
+    _check_force(force, lcc_radius)
+    schedule = _schedule(fixed.shape, levels, iterations)
+    sigmas = (float(sigma_vox),) * 3
+    _check_sigmas(sigmas), _check_max_step(max_step), _check_method(method)
+    pyramid = [(fixed, moving)]
+    for _ in schedule[1:]:
+        pyramid.insert(0, tuple(downsample2_np(v) for v in pyramid[0]))
+    u = np.zeros((3,) + schedule[0][0], dtype=np.float32)
+    stats = []
+    for level, ((shape, its), (f, m)) in enumerate(zip(schedule, pyramid)):
+        if level:
+            u = np.stack([upscale2_np(np.ascontiguousarray(u[a]), "linear") * np.float32(2) for a in range(3)])
+        for _ in range(its):
+            u, row = step(f, m, u, sigmas)
+            stats.append(row)
+    return DeformResult(u, warp_np(moving, u, method, fill), stats, jacobian_stats_np(u), schedule)
 
 
 def register_deformable_np(fixed, moving, levels: int = 3, iterations=DEFAULT_ITERATIONS, sigma_vox: float = 1.5, max_step: float = 2.0,
@@ -511,24 +493,12 @@ def register_deformable_np(fixed, moving, levels: int = 3, iterations=DEFAULT_IT
     the field goes to the next level as ``upscale2_np(u_a, "linear") * 2`` per component; ``warped = warp_np(moving, field, method,
     fill)`` once at the end.  Identical scans leave the field exactly zero.  ``force="lcc"``: the iteration takes
     ``lcc_force_np(fixed_l, moving_l, u, lcc_radius, max_step)`` instead and the rows of ``stats`` are its ``(S, n_ok)``."""
-    fixed, moving = _check_pair_np(fixed, moving, "register_deformable_np")
-    _check_force(force, lcc_radius)
-    schedule = _schedule(fixed.shape, levels, iterations)
-    sigmas = (float(sigma_vox),) * 3
-    _check_sigmas(sigmas), _check_max_step(max_step), _check_method(method)
-    pyramid = [(fixed, moving)]
-    for _ in schedule[1:]:
-        pyramid.insert(0, tuple(downsample2_np(v) for v in pyramid[0]))
-    u = np.zeros((3,) + schedule[0][0], dtype=np.float32)
-    stats = []
-    for level, ((shape, its), (f, m)) in enumerate(zip(schedule, pyramid)):
-        if level:
-            u = np.stack([upscale2_np(np.ascontiguousarray(u[a]), "linear") * np.float32(2) for a in range(3)])
-        for _ in range(its):
-            v, row = lcc_force_np(f, m, u, lcc_radius, max_step) if force == "lcc" else demons_force_np(f, m, u, max_step, fill)
-            u = smooth_field_np(v, sigmas)
-            stats.append(row)
-    return DeformResult(u, warp_np(moving, u, method, fill), stats, jacobian_stats_np(u), schedule)
+    def step(f, m, u, sigmas):
+        v, row = lcc_force_np(f, m, u, lcc_radius, max_step) if force == "lcc" else demons_force_np(f, m, u, max_step, fill)
+        return smooth_field_np(v, sigmas), row
+
+    return _register_np(fixed, moving, levels, iterations, sigma_vox, max_step, fill, method, force, lcc_radius,
+                        "register_deformable_np", step)
 
 
 def register_diffeomorphic_np(fixed, moving, levels: int = 3, iterations=DEFAULT_ITERATIONS, sigma_vox: float = 1.5, max_step: float = 2.0,
@@ -539,27 +509,16 @@ def register_diffeomorphic_np(fixed, moving, levels: int = 3, iterations=DEFAULT
     ``u = smooth_field_np(compose_np(u, w), (sigma_vox,) * 3)``.  Thirion's update is at most half a voxel, so with the default
     ``exp_steps = 2`` the sub-steps are at most an eighth.  Identical scans leave the field exactly zero.  ``force="lcc"``:
     ``lcc_update_np(fixed_l, moving_l, u, lcc_radius, max_step, 2^-exp_steps)`` instead, rows ``(S, n_ok)``."""
-    fixed, moving = _check_pair_np(fixed, moving, "register_diffeomorphic_np")
-    _check_force(force, lcc_radius)
-    schedule = _schedule(fixed.shape, levels, iterations)
-    sigmas = (float(sigma_vox),) * 3
-    _check_sigmas(sigmas), _check_max_step(max_step), _check_method(method)
     scale = np.float32(2.0 ** -_check_exp_steps(exp_steps))
-    pyramid = [(fixed, moving)]
-    for _ in schedule[1:]:
-        pyramid.insert(0, tuple(downsample2_np(v) for v in pyramid[0]))
-    u = np.zeros((3,) + schedule[0][0], dtype=np.float32)
-    stats = []
-    for level, ((shape, its), (f, m)) in enumerate(zip(schedule, pyramid)):
-        if level:
-            u = np.stack([upscale2_np(np.ascontiguousarray(u[a]), "linear") * np.float32(2) for a in range(3)])
-        for _ in range(its):
-            w, row = lcc_update_np(f, m, u, lcc_radius, max_step, scale) if force == "lcc" else demons_update_np(f, m, u, max_step, fill, scale)
-            for _ in range(exp_steps):
-                w = compose_np(w, w)
-            u = smooth_field_np(compose_np(u, w), sigmas)
-            stats.append(row)
-    return DeformResult(u, warp_np(moving, u, method, fill), stats, jacobian_stats_np(u), schedule)
+
+    def step(f, m, u, sigmas):
+        w, row = lcc_update_np(f, m, u, lcc_radius, max_step, scale) if force == "lcc" else demons_update_np(f, m, u, max_step, fill, scale)
+        for _ in range(exp_steps):
+            w = compose_np(w, w)
+        return smooth_field_np(compose_np(u, w), sigmas), row
+
+    return _register_np(fixed, moving, levels, iterations, sigma_vox, max_step, fill, method, force, lcc_radius,
+                        "register_diffeomorphic_np", step)
 
 
 # ---------------------------------------------------------------- device
@@ -573,6 +532,21 @@ def _check_field(u, shape, device, what) -> torch.Tensor:
     if tuple(u.shape) != (3,) + tuple(shape) or u.device != device:
         raise ValueError(f"{what}: the field must have shape {(3,) + tuple(shape)} on {device}, got {tuple(u.shape)} on {u.device}")
     return u
+
+
+def _check_field4(u, what) -> torch.Tensor:
+    u = cuda_tensor(u, (torch.float32,), what)
+    if u.dim() != 4 or u.shape[0] != 3:
+        raise ValueError(f"{what}: a field is (3, X, Y, Z), got shape {tuple(u.shape)}")
+    check_shape(u.shape[1:], f"{what}: the volume's shape")
+    return u
+
+
+def _check_pair(fixed, moving, what):
+    f, m = _check_volume(fixed, what), _check_volume(moving, what)
+    if f.shape != m.shape or f.device != m.device:
+        raise ValueError(f"{what}: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    return f, m
 
 
 def _slots(device) -> torch.Tensor:
@@ -614,9 +588,7 @@ def demons_force(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, max
     """The device path of ``demons_force_np`` -> ``(v, S, n)``: ``v`` bit for bit; ``S`` (0-d float64) within one spacing of the
     specification's sum and the same bits on every run, ``n`` (0-d int64) equal - both stay on the device.  Two launches (the
     force; one wave that adds the fixed slots), no device-to-host read.  ``out``: another tensor like ``u``."""
-    f, m = _check_volume(fixed, "demons_force"), _check_volume(moving, "demons_force")
-    if f.shape != m.shape or f.device != m.device:
-        raise ValueError(f"demons_force: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    f, m = _check_pair(fixed, moving, "demons_force")
     u = _check_field(u, f.shape, f.device, "demons_force")
     _check_max_step(max_step)
     v = out_like(out, u, (u, f, m), "demons_force")
@@ -628,10 +600,8 @@ def demons_force(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, max
 def smooth_field(v: torch.Tensor, sigmas_vox, out=None) -> torch.Tensor:
     """v: contiguous float32 CUDA field (3, X, Y, Z) -> ``smooth_field_np``, bit for bit.  Three launches (axis 2, 1, 0), all three
     components in each.  ``out``: another tensor like ``v``."""
-    v = cuda_tensor(v, (torch.float32,), "smooth_field")
-    if v.dim() != 4 or v.shape[0] != 3:
-        raise ValueError(f"smooth_field: a field is (3, X, Y, Z), got shape {tuple(v.shape)}")
-    shape = check_shape(v.shape[1:], "smooth_field: the volume's shape")
+    v = _check_field4(v, "smooth_field")
+    shape = tuple(v.shape[1:])
     taps = [torch.from_numpy(w).to(v.device) for w in _check_sigmas(sigmas_vox)]
     out = out_like(out, v, (v,), "smooth_field")
     tmp = torch.empty_like(v)
@@ -647,10 +617,8 @@ def _jacobian(u, shape, min_det, count, slots):
 def jacobian_stats(u: torch.Tensor):
     """u: contiguous float32 CUDA field (3, X, Y, Z) -> ``(min det, count of det <= 0)`` of ``jacobian_stats_np`` as a 0-d float32 and a
     0-d int64 tensor on the device.  Two launches, no device-to-host read."""
-    u = cuda_tensor(u, (torch.float32,), "jacobian_stats")
-    if u.dim() != 4 or u.shape[0] != 3:
-        raise ValueError(f"jacobian_stats: a field is (3, X, Y, Z), got shape {tuple(u.shape)}")
-    shape = check_shape(u.shape[1:], "jacobian_stats: the volume's shape")
+    u = _check_field4(u, "jacobian_stats")
+    shape = tuple(u.shape[1:])
     min_det = torch.empty(1, dtype=torch.float32, device=u.device)
     count = torch.empty(1, dtype=torch.int64, device=u.device)
     _jacobian(u, shape, min_det, count, _slots(u.device))
@@ -725,9 +693,7 @@ def _register(fixed, moving, levels, iterations, sigma_vox, max_step, fill, meth
     *ws_extra, force=force, lcc_radius=lcc_radius)`` is the workspace it needs."""
     force, lcc_radius = _check_force(force, lcc_radius)
     force_key = ("lcc", lcc_radius) if force == "lcc" else ()
-    f, m = _check_volume(fixed, what), _check_volume(moving, what)
-    if f.shape != m.shape or f.device != m.device:
-        raise ValueError(f"{what}: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    f, m = _check_pair(fixed, moving, what)
     _check_max_step(max_step), _check_method(method)
     if workspace is None:
         workspace = ws_type(f.shape, f.device, levels, iterations, sigma_vox, *ws_extra, force=force, lcc_radius=lcc_radius)
@@ -773,14 +739,6 @@ def _register(fixed, moving, levels, iterations, sigma_vox, max_step, fill, meth
 
 # ---------------------------------------------------------------- device: the diffeomorphic variant
 
-def _check_field4(u, what) -> torch.Tensor:
-    u = cuda_tensor(u, (torch.float32,), what)
-    if u.dim() != 4 or u.shape[0] != 3:
-        raise ValueError(f"{what}: a field is (3, X, Y, Z), got shape {tuple(u.shape)}")
-    check_shape(u.shape[1:], f"{what}: the volume's shape")
-    return u
-
-
 def _compose(u, v, out, shape):
     L.call("mrisr_f32_volume_field_compose", u.data_ptr(), v.data_ptr(), *shape, out.data_ptr(), L.stream_ptr(),
            nbytes=36 * int(np.prod(shape)))                                                                   # 6 floats read, 3 written
@@ -805,9 +763,7 @@ def demons_update(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, ma
                   out=None):
     """The device path of ``demons_update_np`` -> ``(w, S, n)`` as ``demons_force`` returns them: the same kernel, writing
     ``upd * scale``.  ``out``: another tensor like ``u``."""
-    f, m = _check_volume(fixed, "demons_update"), _check_volume(moving, "demons_update")
-    if f.shape != m.shape or f.device != m.device:
-        raise ValueError(f"demons_update: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    f, m = _check_pair(fixed, moving, "demons_update")
     u = _check_field(u, f.shape, f.device, "demons_update")
     _check_max_step(max_step)
     scale = _check_scale(scale)
@@ -818,9 +774,7 @@ def demons_update(fixed: torch.Tensor, moving: torch.Tensor, u: torch.Tensor, ma
 
 
 def _lcc_entry(what, fixed, moving, u, radius, max_step, scale, update, out):
-    f, m = _check_volume(fixed, what), _check_volume(moving, what)
-    if f.shape != m.shape or f.device != m.device:
-        raise ValueError(f"{what}: the scans must share a grid and a device, got shapes {tuple(f.shape)} and {tuple(m.shape)}")
+    f, m = _check_pair(fixed, moving, what)
     u = _check_field(u, f.shape, f.device, what)
     radius = _check_lcc_radius(radius)
     _check_max_step(max_step)

@@ -68,6 +68,15 @@ def weighted_sum_np(w, v):
     return acc
 
 
+def sample_np(volumes, p, method):
+    """The sampler of every volume tool.  ``volumes``: float32 volumes of one shape ``(X, Y, Z)``; ``p``: the three float64 coordinate
+    arrays of the selected voxels (all inside, or clamped into the volume) -> one float32 array per volume: ``taps_np`` along
+    every axis, computed once for all volumes, the taps reduced along z, then y, then x with ``weighted_sum_np``."""
+    (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa, n, method) for pa, n in zip(p, volumes[0].shape))
+    return [weighted_sum_np(wx, [weighted_sum_np(wy, [weighted_sum_np(wz, [v[xa, yb, zc] for zc in iz]) for yb in iy]) for xa in ix])
+            for v in volumes]
+
+
 def reslice_np(v: np.ndarray, m, out_shape, method: str = "linear", fill: float = 0.0) -> np.ndarray:
     """The specification of ``reslice``.  ``v``: float32 (X, Y, Z); ``m``: (3, 4) float64, destination index -> source index.
 
@@ -88,12 +97,7 @@ def reslice_np(v: np.ndarray, m, out_shape, method: str = "linear", fill: float 
         q = [np.clip(np.floor(pa + 0.5).astype(np.int64), 0, n - 1) for pa, n in zip(pin, v.shape)]
         out[inside] = v[q[0], q[1], q[2]]
         return out
-    (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa, n, method) for pa, n in zip(pin, v.shape))
-    rx = []
-    for xa in ix:
-        ry = [weighted_sum_np(wz, [v[xa, yb, zc] for zc in iz]) for yb in iy]
-        rx.append(weighted_sum_np(wy, ry))
-    out[inside] = weighted_sum_np(wx, rx)
+    out[inside] = sample_np([v], pin, method)[0]
     return out
 
 

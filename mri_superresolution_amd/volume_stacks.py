@@ -58,7 +58,7 @@ import torch
 from . import _lib as L
 from ._volume_args import check_matrix, check_shape, cuda_tensor, matrix_arg, out_like, volume_np
 from .utils.nifti import check_affine, grid_matrix, respaced_grid
-from .volume_reslice import taps_np, weighted_sum_np
+from .volume_reslice import sample_np
 
 MAX_STACKS = 8
 MAX_SAMPLES = 16
@@ -319,12 +319,7 @@ def _gather_rows_np(v, rows, q, shape):
         inside &= (p[a] >= -0.5) & (p[a] <= v.shape[a] - 0.5)
     if not inside.any():
         return np.zeros(0, dtype=np.float32), inside
-    (ix, wx), (iy, wy), (iz, wz) = (taps_np(pa[inside], n, "linear") for pa, n in zip(p, v.shape))
-    rx = []
-    for xa in ix:
-        ry = [weighted_sum_np(wz, [v[xa, yb, zc] for zc in iz]) for yb in iy]
-        rx.append(weighted_sum_np(wy, ry))
-    return weighted_sum_np(wx, rx), inside
+    return sample_np([v], [pa[inside] for pa in p], "linear")[0], inside
 
 
 def _gather_np(v, m, q, shape):
