@@ -258,7 +258,8 @@ int mrisr_act_bwd_apply_fused(int dtype, const void* x, const float* scale, cons
 /* ONE-PASS form of mrisr_act_bwd_reduce + mrisr_act_bwd_apply_fused (csrc/norm.hip: act_bwd_onepass_kernel) for nodes whose
  * consumers are all plain (MRISR_SP_NONE), have the node's geometry and no blend weight; 16-bit storage.  x and every
  * consumer gradient are read from HBM once instead of twice: the blocks of an image keep their operands in registers across
- * an in-kernel image barrier (`arrive`: [N][mrisr_act_bwd_onepass_barrier_words()] uint32).  red ([mrisr_act_bwd_onepass_slots()][N][C][2] fp32, = fin->red:
+ * an in-kernel image barrier (`arrive`: [N][mrisr_act_bwd_onepass_barrier_words()] uint32 - the barrier's counters and flags, then the
+ * image's table of gamma-weighted group sums, the only sums a block reads after the barrier).  red ([mrisr_act_bwd_onepass_slots()][N][C][2] fp32, = fin->red:
  * the per-(n,c) sums spread over 16 copies) and arrive must be ZERO on entry.  mrisr_act_bwd_onepass_ok() != 0 tells whether a node qualifies (channel count, blocks per image <= 256: one
  * image's blocks must be resident together); the entry point refuses the others with MRISR_E_UNSUPPORTED.
  * Replaces the GroupNorm + LeakyReLU part of autograd's backward of DoubleConv (/root/reference/models/unet_model.py:28-37). */

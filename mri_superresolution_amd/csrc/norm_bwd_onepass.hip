@@ -5,9 +5,13 @@
 // act_bwd_reduce_kernel<T,0> + act_bwd_apply_fused_kernel<T,true> do in two launches that each read x and every consumer
 // gradient from HBM (5 tensor passes for one consumer, 7 for two), in one launch that reads them ONCE (3 / 4 passes):
 // a block keeps its pixels' x and consumer-gradient vectors in registers across the reduction.
-//   phase 1: per-(n,c) sums of g and g*xhat of the block's pixels -> atomics into red[n][c][2] (as the reduce kernel)
+//   phase 1: per-(n,c) sums of g and g*xhat of the block's pixels -> atomics into red[n][c][2] (as the reduce kernel), and the
+//            block's gamma-weighted GROUP sums -> atomics into the image's table of 2 * groups floats behind the barrier words
 //   image barrier: the blocks of image n count themselves in arrive[n] and wait until all of them have
-//   phase 2: coefficients from red[n] (as gn_bwd_coefs), dx from the registers
+//   phase 2: coefficients from the image's group sums (gn_bwd_coefs' formulas), dx from the registers
+//   afterwards: the block that completed the image's count turns red[n] into the image's share of dgamma / dbeta
+// Only the group sums cross the barrier: dx = g cA + x cB + cC needs S1 and S2 of the group and nothing per channel (cA is
+// local), so a block reads 16 x 2 * groups words after the barrier, not 16 x 2 C.
 // The barrier is safe because the workgroups of a 2-D grid start in linear order (x fastest): the blocks of image n are
 // all dispatched before any block of image n+1, so the ones a waiting block needs are resident or next in line - as long
 // as ONE image's blocks fit on the chip together, which the host guarantees with a wide margin (<= 256 blocks of 256
@@ -19,95 +23,176 @@ constexpr int kOnePassMaxBlocks = 256;
 // the per-(n,c) sums are spread over this many copies of red[] (block index mod kOnePassSlots): the blocks of an image all
 // add into the same C x 2 words right before they wait for each other, and 256 same-address atomics in a row (performed at
 // the memory side) took ~25 us per image
+// (an image of fewer blocks uses as many copies as it has blocks: block index mod min(kOnePassSlots, blocks per image))
 constexpr int kOnePassSlots = 16;
 constexpr int kOnePassGroups = 16;      // block groups of the image barrier
-constexpr int kOnePassWords = 544;      // barrier words per image: 16 group counters, the image counter, 16 group flags - 64 bytes apart
+constexpr int kOnePassSyncWords = 544;  // barrier words per image: 16 group counters, the image counter, 16 group flags - 64 bytes apart
+// behind them the image's table of gamma-weighted group sums, float [kOnePassSlots][kOnePassTabStride]: a copy holds
+// sum gamma g of the groups, then sum gamma g xhat of the groups (2 * groups <= 2 * kMaxGroups words, 256 bytes apart).  Zero
+// on entry like the rest (0u reads as 0.0f), and on cache lines of the image's own (2176 + 4096 bytes per image).
+constexpr int kOnePassTabStride = 2 * kMaxGroups;
+constexpr int kOnePassWords = kOnePassSyncWords + kOnePassSlots * kOnePassTabStride;
+
+// Phase profile (timing builds only: tools/build_src_variant.sh NAME norm_bwd_onepass.hip -DMRISR_ONEPASS_PT, read by tools/gn_bwd_bench.py;
+// never compiled into libmrisr.so): s_memtime stamps around the parts of a launch - 0 loads + sums, 1 block reduction + atomics until the
+// block may be counted, 2 the wait at the image barrier, 3 barrier -> coefficients, 4 the dx stores, 5 the dgamma / dbeta share - taken by
+// thread 0 of the middle block of the middle image; every stamp first waits for the thread's outstanding memory operations.
+struct OnePassPT {
+#ifdef MRISR_ONEPASS_PT
+    unsigned long long t, acc[6];
+    __device__ __forceinline__ void start() {
+        for (int k = 0; k < 6; ++k) acc[k] = 0;
+        t = __builtin_amdgcn_s_memtime();
+    }
+    __device__ __forceinline__ void mark(int k) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        const unsigned long long now = __builtin_amdgcn_s_memtime();
+        acc[k] += now - t;
+        t = now;
+    }
+    __device__ __forceinline__ void flush();
+#else
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void mark(int) {}
+    __device__ __forceinline__ void flush() {}
+#endif
+};
+#ifdef MRISR_ONEPASS_PT
+static __device__ unsigned long long g_onepass_cycles[8];      // the six parts, -, launches
+__device__ __forceinline__ void OnePassPT::flush() {
+    if (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.y / 2) {
+        for (int k = 0; k < 6; ++k) atomicAdd(&g_onepass_cycles[k], acc[k]);
+        atomicAdd(&g_onepass_cycles[7], 1ull);
+    }
+}
+// out8 == NULL: reset
+extern "C" int mrisr_debug_onepass_cycles(unsigned long long* out8) {
+    unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (!out8) return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_onepass_cycles), v, sizeof(v));
+    const int rc = (int)hipMemcpyFromSymbol(v, HIP_SYMBOL(g_onepass_cycles), sizeof(v));
+    for (int k = 0; k < 8; ++k) out8[k] = v[k];
+    return rc;
+}
+#endif
 
 __device__ __forceinline__ float ld_coherent(const float* p) {      // red[] is written by other blocks of THIS launch
     return __hip_atomic_load((const GLOBAL_AS float*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // The part every one-pass kernel shares.  In: this thread's sums of g (sA) and g*x (sB) over its pixels, channels c .. c+VEC-1 of
-// image n.  Block reduction -> atomics into this block's copy of red[] -> image barrier -> coefficients of dx = g cA + x cB + cC
-// for the thread's channels (act_bwd_finalize_kernel's formulas), dgamma / dbeta added once per image.  Every thread of the block
-// calls it.  lds: 256 * VEC * 2 + 2 * kMaxGroups floats.
+// image n.  Block reduction -> atomics into this block's copy of red[] (per channel: for dgamma / dbeta, read by nobody here) and
+// into its copy of the image's group table (the block's sum gamma g and sum gamma g xhat per group) -> image barrier ->
+// coefficients of dx = g cA + x cB + cC for the thread's channels (act_bwd_finalize_kernel's formulas) from the group table.
+// Every thread of the block calls it.  lds: 256 * VEC * 2 + 2 * kMaxGroups floats.  state (LDS): bit 0 the block gave up
+// waiting, bit 1 the block completed the image's count (it owes the image's onepass_affine_grads).
 template <int VEC>
 __device__ __forceinline__ void onepass_meet(const ActBwdParams& p, const FinDev& fin, unsigned* __restrict__ arrive, float* lds,
-                                             int* timed_out, int n, int c, int nvec, int ppb, int pl, float* sA, float* sB,
-                                             float* ca, float* cb, float* cc) {
-    const int t = threadIdx.x, gs = p.C / p.groups;
+                                             int* state, int n, int c, int nvec, int ppb, float* sA, float* sB,
+                                             float* ca, float* cb, float* cc, OnePassPT& pt) {
+    // (groups is a power of two - the entry point checks it - and so is C / 8, hence the group size: shifts, not divisions,
+    // next to 130 live registers)
+    const int t = threadIdx.x, gs = p.C / p.groups, gs_sh = __ffs(gs) - 1, g2 = 2 * p.groups, g2_sh = __ffs(g2) - 1;
+    const int nslots = min((int)gridDim.x, kOnePassSlots), slot = blockIdx.x % nslots;
+    unsigned* img = arrive + (size_t)n * kOnePassWords;
+    float* tab = (float*)(img + kOnePassSyncWords);      // [kOnePassSlots][kOnePassTabStride]
+    float* part = lds + 256 * VEC * 2;                   // [2][groups]: this block's gamma-weighted group sums
     sums_to_xhat<VEC>(p.meanrstd, n, p.groups, gs, c, sA, sB);      // per thread (8 pixels)
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
         lds[(t * VEC + e) * 2] = sA[e];
         lds[(t * VEC + e) * 2 + 1] = sB[e];
     }
-    if (t == 0) *timed_out = 0;
+    if (t < 2 * kMaxGroups) part[t] = 0.f;
+    if (t == 0) *state = 0;
     __syncthreads();
     for (int i = t; i < nvec * VEC * 2; i += 256) {
         const int j = i >> 1, which = i & 1;
         const int cvj = j / VEC, e = j - cvj * VEC;
         float s = 0.f;
         for (int q = 0; q < ppb; ++q) s += lds[((q * nvec + cvj) * VEC + e) * 2 + which];
-        atomic_add_f32(&p.red[(((size_t)(blockIdx.x % kOnePassSlots) * p.N + n) * p.C + cvj * VEC + e) * 2 + which], s);
+        atomicAdd(&part[which * p.groups + (j >> gs_sh)], fin.gamma[j] * s);
+        lds[i] = s;      // row 0 of the column only this thread reads: kept for the red[] atomics below
     }
+    __syncthreads();
+    // The group table first, then red[]: no load stands behind an atomic (vmcnt counts in order, so the wait for a gamma load
+    // issued after an atomic is a wait for that atomic's acknowledgement), and all of them are in flight together.
+    if (t < g2) atomic_add_f32(&tab[slot * kOnePassTabStride + t], part[t]);
+    for (int i = t; i < nvec * VEC * 2; i += 256) atomic_add_f32(&p.red[((size_t)slot * p.N + n) * p.C * 2 + i], lds[i]);
     // ---- image barrier.  Everything that crosses it goes through agent-scope RELAXED atomics (the sums above, the counter,
-    // the reads of red[] below), which are performed at the memory side: no release / acquire fences - on this multi-XCD part
-    // each of them writes back or invalidates a whole L2, and with 4096 blocks doing so the launch ran 8x slower than the
-    // two launches it replaces.  `s_waitcnt vmcnt(0)`: this thread's atomics have been acknowledged before it is counted.
+    // the reads of the group table below), which are performed at the memory side: no release / acquire fences - on this
+    // multi-XCD part each of them writes back or invalidates a whole L2, and with 4096 blocks doing so the launch ran 8x
+    // slower than the two launches it replaces.  `s_waitcnt vmcnt(0)`: this thread's atomics - group table AND red[], which
+    // the image's last block reads once it has seen everybody counted - have been acknowledged before it is counted.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    pt.mark(1);
     if (t == 0) {
         // Two-level count, then a release flag per group of blocks: 256 blocks bumping and then polling ONE word is a chain of
         // 256 same-address atomics at the memory side (~40 us per image, measured).  Block b belongs to group b % 16: it bumps
         // its group's counter; the block that completes a group bumps the image's counter; the block that completes the image
         // sets the 16 group flags; everybody polls its own group's flag (16 pollers per word, one cache line per word).
-        unsigned* img = arrive + (size_t)n * kOnePassWords;
         const unsigned nblk = gridDim.x, g = blockIdx.x % kOnePassGroups;
         const unsigned ngroups = min(nblk, (unsigned)kOnePassGroups), members = (nblk - g + kOnePassGroups - 1) / kOnePassGroups;
         if (__hip_atomic_fetch_add(img + g * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == members) {
             if (__hip_atomic_fetch_add(img + 256, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == ngroups) {
                 for (unsigned k = 0; k < ngroups; ++k)
                     __hip_atomic_store(img + 272 + k * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                *state |= 2;
             }
         }
         int spin = 0;
         while (__hip_atomic_load(img + 272 + g * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
             __builtin_amdgcn_s_sleep(16);      // ~0.5 us between polls
-            if (++spin > 600000) { *timed_out = 1; break; }
+            if (++spin > 600000) { *state |= 1; break; }
         }
     }
     asm volatile("" ::: "memory");
     __syncthreads();
-    const bool bad = *timed_out != 0;
+    const bool bad = (*state & 1) != 0;
+    pt.mark(2);
 
-    // ---- coefficients of image n (act_bwd_finalize_kernel's formulas; red read around the L1)
-    float* s12 = lds;
-    if (t < 2 * kMaxGroups) s12[t] = 0.f;
+    // ---- coefficients of image n (act_bwd_finalize_kernel's formulas; the table read around the L1): the copies in use,
+    // one word per thread at the network's 8 groups, added up in copy order
+    float* s12 = part;
+    for (int i = t; i < nslots * g2; i += 256) {
+        lds[i] = ld_coherent(tab + (i >> g2_sh) * kOnePassTabStride + (i & (g2 - 1)));
+    }
     __syncthreads();
-    const float* rn = fin.red + (size_t)n * p.C * 2;
-    const size_t slot_stride = (size_t)p.N * p.C * 2;
-    float* sums = lds + 2 * kMaxGroups;            // [C][2]: the image's per-channel sums, all slots added up
-    for (int j = t; j < 2 * p.C; j += 256) {
+    if (t < g2) {
         float v = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < kOnePassSlots; ++sl) v += ld_coherent(rn + sl * slot_stride + j);
-        sums[j] = v;
-        atomicAdd(&s12[(j & 1) * kMaxGroups + (j >> 1) / gs], fin.gamma[j >> 1] * v);
+        for (int sl = 0; sl < nslots; ++sl) v += lds[sl * g2 + t];
+        s12[t] = v;
     }
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < VEC; ++e) {
-        const int g = (c + e) / gs;
+        const int g = (c + e) >> gs_sh;
         const float mean = fin.meanrstd[((size_t)n * fin.groups + g) * 2], rstd = fin.meanrstd[((size_t)n * fin.groups + g) * 2 + 1];
-        const float S1 = s12[g] * fin.inv_count, S2 = s12[kMaxGroups + g] * fin.inv_count;
+        const float S1 = s12[g] * fin.inv_count, S2 = s12[fin.groups + g] * fin.inv_count;
         ca[e] = rstd * fin.gamma[c + e];
         cb[e] = -rstd * rstd * S2;
         cc[e] = bad ? __builtin_nanf("") : mean * rstd * rstd * S2 - rstd * S1;
-        if (blockIdx.x == 0 && pl == 0) {          // one block per image adds the image's share of dgamma / dbeta
-            atomic_add_f32(&fin.dbeta[c + e], sums[2 * (c + e)]);
-            atomic_add_f32(&fin.dgamma[c + e], sums[2 * (c + e) + 1]);
+    }
+    pt.mark(3);
+}
+
+// After the block's dx stores: the block that completed image n's count (every block's red[] atomics had been acknowledged
+// before it was counted) adds the image's share of dgamma / dbeta - the per-channel sums of all copies in use.  Nobody waits
+// for it.  Every thread of the block calls it.
+__device__ __forceinline__ void onepass_affine_grads(const ActBwdParams& p, const FinDev& fin, const int* state, int n) {
+    if (!(*state & 2)) return;
+    const int nslots = min((int)gridDim.x, kOnePassSlots);
+    const float* rn = fin.red + (size_t)n * p.C * 2;
+    const size_t slot_stride = (size_t)p.N * p.C * 2;
+    for (int j = threadIdx.x; j < 2 * p.C; j += 256) {
+        float v = 0.f;
+        if (nslots == kOnePassSlots) {      // all 16 loads in flight together: this block is the tail of the image
+#pragma unroll
+            for (int sl = 0; sl < kOnePassSlots; ++sl) v += ld_coherent(rn + sl * slot_stride + j);
+        } else {
+            for (int sl = 0; sl < nslots; ++sl) v += ld_coherent(rn + sl * slot_stride + j);
         }
+        atomic_add_f32(((j & 1) ? fin.dgamma : fin.dbeta) + (j >> 1), v);
     }
 }
 
@@ -116,8 +201,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
                                                               unsigned* __restrict__ arrive) {
     constexpr int VEC = Vec16<T>::N, PPT = kOnePassPPT;
     __shared__ float lds[256 * VEC * 2 + 2 * kMaxGroups];
-    __shared__ int timed_out;
+    __shared__ int meet_state;
     const int t = threadIdx.x, n = blockIdx.y;
+    OnePassPT pt;
+    pt.start();
     const int nvec = p.C / VEC, ppb = 256 / nvec;             // host-checked: nvec is a power of two <= 256
     const int cv = t & (nvec - 1), pl = t / nvec, c = cv * VEC;
     const int HW = p.H * p.W, gs = p.C / p.groups;
@@ -159,7 +246,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         }
     }
     float ca[VEC], cb[VEC], cc[VEC];
-    onepass_meet<VEC>(p, fin, arrive, lds, &timed_out, n, c, nvec, ppb, pl, sA, sB, ca, cb, cc);
+    pt.mark(0);
+    onepass_meet<VEC>(p, fin, arrive, lds, &meet_state, n, c, nvec, ppb, sA, sB, ca, cb, cc, pt);
     T* ob = dx + (size_t)n * HW * p.C + c;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
@@ -177,6 +265,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
             store_vec16(ob + (size_t)pix * p.C, o);
         }
     }
+    pt.mark(4);
+    onepass_affine_grads(p, fin, &meet_state, n);
+    pt.mark(5);
+    pt.flush();
 }
 
 // The same for a node whose activation is ALSO max-pooled (the encoder skips: one 2x2-pool consumer + at most one plain
@@ -189,8 +281,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
                                                                                                                   const FinDev fin, unsigned* __restrict__ arrive) {
     constexpr int VEC = Vec16<T>::N, WPT = kOnePassWPT;
     __shared__ float lds[256 * VEC * 2 + 2 * kMaxGroups];
-    __shared__ int timed_out;
+    __shared__ int meet_state;
     const int t = threadIdx.x, n = blockIdx.y;
+    OnePassPT pt;
+    pt.start();
     const int nvec = p.C / VEC, ppb = 256 / nvec;
     const int cv = t & (nvec - 1), pl = t / nvec, c = cv * VEC;
     const int W = p.W, Hp = p.H / 2, Wp = W / 2, HWp = Hp * Wp;
@@ -258,7 +352,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         }
     }
     float ca[VEC], cb[VEC], cc[VEC];
-    onepass_meet<VEC>(p, fin, arrive, lds, &timed_out, n, c, nvec, ppb, pl, sA, sB, ca, cb, cc);
+    pt.mark(0);
+    onepass_meet<VEC>(p, fin, arrive, lds, &meet_state, n, c, nvec, ppb, sA, sB, ca, cb, cc, pt);
     T* ob = dx + (size_t)n * p.H * W * p.C + c;
 #pragma unroll
     for (int i = 0; i < WPT; ++i) {
@@ -276,6 +371,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
             for (int q = 0; q < 4; ++q) store_vec16(ob + (size_t)o4[q] * p.C, ov[q]);
         }
     }
+    pt.mark(4);
+    onepass_affine_grads(p, fin, &meet_state, n);
+    pt.mark(5);
+    pt.flush();
 }
 
 // Does a node qualify for the one-pass kernel?  (16-bit storage, plain consumers of the node's own geometry without blend
@@ -307,7 +406,7 @@ extern "C" int mrisr_act_bwd_onepass_ok(int dtype, int nconsumers, const mrisr_c
     return (HW / 4 + wpblk - 1) / wpblk <= kOnePassMaxBlocks ? 2 : 0;
 }
 
-// red: [kOnePassSlots = 16][N][C][2] floats and arrive: [N][kOnePassWords = 544] barrier words, both ZERO on entry (the engine's per-backward arena).
+// red: [kOnePassSlots = 16][N][C][2] floats and arrive: [N][kOnePassWords = 1568] words (barrier words + group table), both ZERO on entry (the engine's per-backward arena).
 extern "C" int mrisr_act_bwd_onepass_slots(void) { return kOnePassSlots; }
 extern "C" int mrisr_act_bwd_onepass_barrier_words(void) { return kOnePassWords; }
 extern "C" int mrisr_act_bwd_onepass(int dtype, const void* x, const float* scale, const float* shift, const float* meanrstd,
@@ -321,6 +420,9 @@ extern "C" int mrisr_act_bwd_onepass(int dtype, const void* x, const float* scal
     int frc = make_fin_dev(fd, fin, C, "act_bwd_onepass: fin", false);
     if (frc) return frc;
     if (fin->alpha_slots) MRISR_FAIL(MRISR_E_UNSUPPORTED, "act_bwd_onepass: blend branches take the two-pass kernels");
+    // onepass_meet indexes the group table with shifts and masks.  (groups divides C and C / 8 is a power of two, so this
+    // holds for every node that qualifies today; checked on its own so that relaxing either rule cannot corrupt the table.)
+    if (fin->groups & (fin->groups - 1)) MRISR_FAIL(MRISR_E_UNSUPPORTED, "act_bwd_onepass: groups %d is not a power of two", fin->groups);
     ActBwdParams p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.scale = scale; p.shift = shift; p.meanrstd = meanrstd; p.red = red;
