@@ -1051,6 +1051,21 @@ int mrisr_f32_volume_slice_cost(const float* x, int X, int Y, int Z, const float
 int mrisr_f32_volume_line_circulant(const float* src, int X, int Y, int Z, int axis, int mode, const float* table, float* dst,
                                     void* stream);
 
+/* ---- Gibbs-ringing removal by local subvoxel shifts (extension; csrc/volume_unring.hip; Kellner et al., MRM 2016) along one axis of
+ *      a float32 volume (X, Y, Z), C order.  The specification is mri_superresolution_amd/volume_unring.py (unring_axis_np). ----
+ * The lines are those along axis (0..2), n samples each (8..512), the border periodic; dst has the shape of src.  table (DEVICE): 2K
+ * rows of n floats (volume_unring.shift_table: the periodic sinc kernel at the offsets +1, -1, +2, -2, ... +K, -K over 2K);
+ * fractions (DEVICE): those 2K offsets as floats (shift_fractions).  Per line: candidate 0 is the line itself, candidate m the line
+ * re-sampled with row m (0 + t src[0] + t src[1] + ... over j ascending); of every candidate the total variation of the win_lo ..
+ * win_hi differences to the left and to the right of a sample is formed, and the sample takes the value, interpolated back to its
+ * own position, of the first candidate and side whose variation is strictly the smallest.  Every product, difference and sum is
+ * rounded to float32, no fma: bit for bit unring_axis_np, NaN and Inf included, on every run and for every launch shape.  One
+ * launch, no workspace, no atomics, no host synchronisation.  MRISR_E_ARG: null or misaligned pointer, src and dst overlapping,
+ * axis outside 0..2, K outside 1..32, not 1 <= win_lo <= win_hi <= 4; MRISR_E_SHAPE: an extent outside 1..32767, a line outside
+ * 8..512, more than 2^31 - 1 voxels.                                                                                            */
+int mrisr_f32_volume_unring_axis(const float* src, int X, int Y, int Z, int axis, int K, int win_lo, int win_hi, const float* table,
+                                 const float* fractions, float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

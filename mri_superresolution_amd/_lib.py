@@ -229,10 +229,11 @@ SIGNATURES = {
     "mrisr_f32_volume_slice_cost": (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, _dp, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_float),
                                          _i, _i, _vp, _dp, _vp]),
     "mrisr_f32_volume_line_circulant": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _fp, _vp]),
+    "mrisr_f32_volume_unring_axis": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 332  # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 333  # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -63,17 +63,18 @@ def kspace_weights(n: int, window: str = "none") -> np.ndarray:
     return c
 
 
-def _rows(n_grid, period, quarters, window, dtype):
+def _rows(n_grid, period, quarters, window, dtype, parts=4):
     """row[d] = (1 / period) sum_k c_k w_k cos(2 pi k (d + q / 4) / period) for every ``q`` of ``quarters``, the sum over ``k`` ascending
     in float64.  The phase ``k (4 d + q)`` is reduced modulo ``4 period`` in integers and folded onto the half circle before the
-    cosine is taken, so mirrored entries - ``D_0[d]`` and ``D_1[-d]`` - are the same float64."""
+    cosine is taken, so mirrored entries - ``D_0[d]`` and ``D_1[-d]`` - are the same float64.  ``parts``: the offsets are ``q / parts``
+    of a sample instead of quarters (``volume_unring.shift_table``)."""
     ck = kspace_weights(n_grid, window)
     d = np.arange(period, dtype=np.int64)
-    full = 4 * period
+    full = parts * period
     rows = np.zeros((len(quarters), period), dtype=np.float64)
     for r, q in enumerate(quarters):
         for k, c in enumerate(ck):
-            m = (k * (4 * d + q)) % full
+            m = (k * (parts * d + q)) % full
             m = np.minimum(m, full - m)
             rows[r] += c * np.cos((2.0 * np.pi / full) * m.astype(np.float64))
     rows /= period

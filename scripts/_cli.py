@@ -1,4 +1,4 @@
-"""What the volume scripts share: the ``--cpu`` flag, the k-space flags, the guarded ``main``, the upload of a frame, the joining
+"""What the volume scripts share: the ``--cpu`` flag, the k-space flags, the unring flags, the guarded ``main``, the upload of a frame, the joining
 and saving of frames, and the mask loading of ``evaluate_volume.py`` and ``segment_volume.py``.  A script imports it after the
 ``REPO`` path insert.
 """
@@ -38,6 +38,46 @@ def kspace_options(args) -> dict:
     if args.degrade != "mean":
         chosen["degrade"] = args.degrade
     return chosen
+
+
+def add_unring_flags(parser, flag, when):
+    """``--unring`` of ``infer_volume.py`` / ``--unring_input`` of ``evaluate_volume.py`` with the sub-options (``volume_unring``); absent
+    from the namespace unless given, so the parsed defaults are those of a build without them.  ``unring_options`` reads them back."""
+    import argparse
+    parser.add_argument(f"--{flag}", action="store_true", default=argparse.SUPPRESS,
+                        help=f"(extension) take the Gibbs ringing of a truncated k-space out {when}: local subvoxel shifts along "
+                             "--unring_axes, fused in one kernel per axis (default: off)")
+    parser.add_argument("--unring_axes", type=int, nargs="+", choices=[0, 1, 2], default=argparse.SUPPRESS,
+                        help=f"(extension) the axes of --{flag} (default: 0 1 2)")
+    parser.add_argument("--unring_shifts", type=int, default=argparse.SUPPRESS,
+                        help=f"(extension) K of --{flag}: 2K sub-voxel shifts are tried, 1..32 (default: 20)")
+    parser.add_argument("--unring_window", type=int, nargs=2, default=argparse.SUPPRESS, metavar=("A", "B"),
+                        help=f"(extension) the differences a..b either side of a voxel judge a shift of --{flag}, 1 <= a <= b <= 4 (default: 1 3)")
+
+
+def unring_options(args, flag):
+    """-> None without the flag (a sub-option alone is an error), else the keywords of ``unring_frame``."""
+    given = [o for o in ("unring_axes", "unring_shifts", "unring_window") if hasattr(args, o)]
+    if not getattr(args, flag, False):
+        if given:
+            raise ValueError(f"--{given[0]} goes with --{flag}")
+        return None
+    return dict(axes=tuple(getattr(args, "unring_axes", (0, 1, 2))), K=getattr(args, "unring_shifts", 20),
+                window=tuple(getattr(args, "unring_window", (1, 3))))
+
+
+def unring_frame(vol, options, log, what="") -> torch.Tensor:
+    """One CUDA volume -> unringed float32 (``volume_unring.unring``); minimum, maximum and the total variation along each axis are
+    logged before and after."""
+    from mri_superresolution_amd.volume_unring import total_variation, unring
+    vol = vol.float().contiguous()
+    out = unring(vol, **options)
+    for name, v in (("before", vol), ("after", out)):
+        tv = ", ".join(f"{t:.6g}" for t in total_variation(v))
+        log.info(f"{what}unring {name}: min {float(v.min()):.6g}, max {float(v.max()):.6g}, total variation per axis {tv}")
+    log.info(f"{what}unringed along the axes {' '.join(str(a) for a in sorted(options['axes']))} (K = {options['K']}, window "
+             f"{options['window'][0]}..{options['window'][1]})")
+    return out
 
 
 def start_logging():

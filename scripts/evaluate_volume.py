@@ -68,6 +68,13 @@ from the background or given with ``--denoise_sigma``, ``--denoise_beta`` (defau
 ``--denoise_radius`` (default 3) its search window.  Sigma and the background count are logged.  The default, ``none``, leaves a
 run as it was.
 
+``--unring_input`` takes the Gibbs ringing of a truncated k-space out of every input frame on its own grid, after
+``--denoise_input`` and BEFORE the ``--align`` reslice (interpolation destroys the ringing's period): Kellner's local subvoxel shifts
+(``volume_unring.unring``, ``csrc/volume_unring.hip``) along ``--unring_axes`` (default all three, 8..512 voxels each) with
+``--unring_shifts`` K (default 20) and ``--unring_window`` a b (default 1 3).  Without ``--input`` it goes with ``--degrade kspace`` /
+``kspace_hamming`` and unrings the low-resolution volume that degradation makes (even extents on the doubled axes).  Minimum,
+maximum and total variation are logged before and after, and the tables' titles name the step.  Without the flag a run is as it was.
+
 ``--deform_input demons`` (with ``--input``) handles what a rigid transform cannot: the non-rigid geometry between two scanners
 (gradient non-linearity, susceptibility distortion).  After the ``--align`` reslice, ``--match_intensity`` and ``--match_bias``,
 every input frame is warped onto ``downsample2`` of its reference frame (the input's grid, or the grid ``--align`` implies) through a
@@ -133,8 +140,9 @@ from mri_superresolution_amd.volume_intensity import LANDMARKS, RANGE, match_int
 from mri_superresolution_amd.volume_register import register_rigid                         # noqa: E402
 from mri_superresolution_amd.volume_reslice import covered_share, reslice    # noqa: E402
 from mri_superresolution_amd.volume_sharpness import check_bins as check_edge_bins        # noqa: E402
-from scripts._cli import (add_cpu_flag, add_kspace_flags, join_frames, kspace_options, load_mask, log_device, make_parent,   # noqa: E402
-                          require_gpu, start_logging, to_device, voxel_sizes)
+from mri_superresolution_amd.volume_kspace import truncate2                  # noqa: E402
+from scripts._cli import (add_cpu_flag, add_kspace_flags, add_unring_flags, join_frames, kspace_options, load_mask, log_device,   # noqa: E402
+                          make_parent, require_gpu, start_logging, to_device, unring_frame, unring_options, voxel_sizes)
 
 logger = logging.getLogger("evaluate_volume")
 CSV_COLUMNS = ["scan", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # the column style of scripts/evaluate.py
@@ -215,15 +223,18 @@ def check_options(input_path, align, align_interp, align_init, align_mask, match
 
 
 def upload_input(frame, device="cuda", denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, onto=None,
-                 what="input"):
+                 what="input", unring=None):
     """One input frame (a numpy array) -> the CUDA tensor the rest of the run works on: uploaded, with ``denoise_input="nlm"``
     denoised on its own grid (``volume_denoise.denoise_volume``, sigma estimated from the frame's background unless given), and only
-    then, with ``onto = (matrix, shape, interpolation)``, resliced (``--align``).  ``"none"`` and no ``onto``: the upload alone."""
+    then, with ``onto = (matrix, shape, interpolation)``, resliced (``--align``).  ``unring`` (the keywords of ``volume_unring.unring``):
+    unringed on its own grid after the denoising and before the reslice.  ``"none"``, no ``unring`` and no ``onto``: the upload alone."""
     lr = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
     if denoise_input != "none":
         lr, noise = denoise_volume(lr, sigma=denoise_sigma, beta=denoise_beta, radius=denoise_radius, return_noise=True)
         logger.info(f"{what} denoised (nlm, radius {denoise_radius}, beta {denoise_beta:g}): sigma {noise['sigma']:.6g}"
                     + (f" from {noise['count']} background voxels" if denoise_sigma is None else " (given)"))
+    if unring is not None:
+        lr = unring_frame(lr, unring, logger, f"{what}: ")
     if onto is not None:
         lr = reslice(lr, *onto)
     return lr
@@ -281,7 +292,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
                match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
                denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0, tissue_surface=False, deform_force="ssd",
-               deform_lcc_radius=2, tissue_edges=False, edge_radius_mm=4.0, edge_bin_mm=0.5, zerofill=None, degrade="mean"):
+               deform_lcc_radius=2, tissue_edges=False, edge_radius_mm=4.0, edge_bin_mm=0.5, zerofill=None, degrade="mean", unring_input=None):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -301,11 +312,16 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     ``tissue_edges`` (needs ``tissue_dice``): those rows also carry ``edge_columns(K)``, the widths in those units and the contrasts as
     ratios to the row ``reference``'s; ``edge_radius_mm`` and ``edge_bin_mm`` set the profile's range and bins.
     ``zerofill`` (``"none"`` / ``"hamming"``): a method ``zerofill`` (``zerofill_hamming``) follows ``cubic``; ``degrade`` (``"kspace"`` /
-    ``"kspace_hamming"``): the low-resolution volume is the reference's truncated k-space (``volume_eval.evaluate_volume``)."""
+    ``"kspace_hamming"``): the low-resolution volume is the reference's truncated k-space (``volume_eval.evaluate_volume``).
+    ``unring_input`` (the keywords of ``volume_unring.unring``: axes, K, window): every input frame is unringed on its own grid after
+    ``denoise_input`` and before ``align`` (``upload_input``); without ``input_path`` the low-resolution volume a k-space ``degrade`` makes
+    is unringed instead (even extents on the doubled axes)."""
     check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
                   denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask, tissue_surface,
                   deform_force, deform_lcc_radius, tissue_edges, edge_radius_mm, edge_bin_mm)
     noise_options = (denoise_input, denoise_sigma, denoise_beta, denoise_radius)
+    if unring_input is not None and not input_path and degrade == "mean":
+        raise ValueError("--unring_input goes with --input or with --degrade kspace / kspace_hamming")
     ref, ref_header = read_nifti(reference_path)
     low, low_header = read_nifti(input_path) if input_path else (None, None)
     if low is not None and low.ndim != ref.ndim:
@@ -341,7 +357,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             del fixed, moving
         m = grid_matrix(low_header.affine(), low_grid)
         low_frames = [upload_input(f, device, *noise_options, onto=(m, low_shape, align_interp),
-                                   what=f"{input_path}{f'[t={t}]' if len(low_frames) > 1 else ''}") for t, f in enumerate(low_frames)]
+                                   what=f"{input_path}{f'[t={t}]' if len(low_frames) > 1 else ''}", unring=unring_input)
+                      for t, f in enumerate(low_frames)]
         share = float(covered_share(low.shape[:3], m, low_shape, device))
         logger.info(f"{input_path} {tuple(low.shape[:3])} resliced onto the low-resolution grid {low_shape} of {reference_path} "
                     f"({align_interp}); it covers {100.0 * share:.2f} % of that grid.")
@@ -353,10 +370,18 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
         lr, m = None, mask
         if low_frames is not None:      # with --align the frames are on the device already
             lr = low_frames[t] if align else upload_input(low_frames[t], device, *noise_options,
-                                                          what=f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}")
+                                                          what=f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}",
+                                                          unring=unring_input)
+        made = unring_input is not None and lr is None       # the truncated k-space of the reference, made here and unringed
+        if made:
+            if any(vol.shape[a] % 2 for a in axes):
+                raise ValueError(f"--unring_input with --degrade {degrade}: the reference {tuple(vol.shape)} has an odd extent on a doubled axis")
+            vol = vol.float().contiguous()
+            lr = unring_frame(truncate2(vol, axes, "hamming" if degrade == "kspace_hamming" else "none"), unring_input, logger,
+                              f"{name}{f'[t={t}]' if len(ref_frames) > 1 else ''} (degrade {degrade}): ")
         if masks is not None:
             m = masks[t] if align else torch.from_numpy(masks[t]).to(device)
-        if lr is not None:
+        if lr is not None and not made:
             lr = prepare_input(lr, vol, match, match_bias, axes, bias_sigmas, f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}",
                                reference_path, deform_input, align_interp, deform_exp_steps, deform_force, deform_lcc_radius)
         res = evaluate_volume(model, vol, lr=lr, isotropic=isotropic, axis=axis, val_range=data_range, batch_size=batch_size,
@@ -364,7 +389,7 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                               mask_fill_holes=mask_fill_holes, tissue_dice=tissue_dice, tissue_surface=tissue_surface,
                               spacing=voxel_sizes(ref_header.affine()) if tissue_surface or tissue_edges else None,
                               **(dict(tissue_edges=True, edge_radius=edge_radius_mm, edge_bin=edge_bin_mm) if tissue_edges else {}),
-                              **(dict(zerofill=zerofill) if zerofill is not None else {}), **(dict(degrade=degrade) if degrade != "mean" else {}))
+                              **(dict(zerofill=zerofill) if zerofill is not None else {}), **(dict(degrade=degrade) if degrade != "mean" and not made else {}))
         scan = name if len(ref_frames) == 1 else f"{name}[t={t}]"
         if mask is None:
             values = torch.stack(list(res.values())).cpu().numpy()            # one download per volume
@@ -476,6 +501,9 @@ def main(args):
         dice += edge_columns(args.tissue_dice) if args.tissue_edges else []
         shown = {"foreground": dice}                     # the tables of the whole volume stay as they are
         degraded = f" (degrade {args.degrade})" if args.degrade != "mean" else ""
+        unring_input = unring_options(args, "unring_input")
+        if unring_input is not None:                     # what it goes with: score_scan's rule
+            degraded += f" (input unringed along {' '.join(str(a) for a in sorted(unring_input['axes']))}, K = {unring_input['K']})"
         for path in args.reference:
             scan_rows = score_scan(model, path, input_path=args.input, isotropic=args.isotropic, axis=args.axis, data_range=args.data_range,
                                    batch_size=args.batch_size, use_amp=args.use_amp, use_graph=not args.no_graph, device=device,
@@ -488,7 +516,8 @@ def main(args):
                                    deform_exp_steps=args.deform_exp_steps, deform_force=args.deform_force,
                                    deform_lcc_radius=args.deform_lcc_radius, tissue_dice=args.tissue_dice,
                                    tissue_surface=args.tissue_surface, tissue_edges=args.tissue_edges,
-                                   edge_radius_mm=args.edge_radius_mm, edge_bin_mm=args.edge_bin_mm, **kspace_options(args))
+                                   edge_radius_mm=args.edge_radius_mm, edge_bin_mm=args.edge_bin_mm, **kspace_options(args),
+                                   **(dict(unring_input=unring_input) if unring_input is not None else {}))
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -528,6 +557,8 @@ def parse_args(argv=None):
     p.add_argument("--model_type", type=str, choices=["unet"], default="unet")
     p.add_argument("--base_filters", type=int, default=64)
     add_cpu_flag(p)
+    add_unring_flags(p, "unring_input", "of every --input frame on its own grid, after --denoise_input and before --align (without --input: "
+                                        "of the low-resolution volume --degrade kspace makes)")
     p.add_argument("--use_amp", action="store_true", help="fp16 MFMA compute (the reference's autocast)")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--isotropic", action="store_true", help="double all three axes (the three-plane blend of infer_volume.py --isotropic)")

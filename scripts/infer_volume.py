@@ -24,6 +24,11 @@ enhancement (``volume_reslice.reslice``, ``--spacing_interp linear|cubic``): a 1
 Rician non-local-means filter of ``volume_denoise.denoise_volume`` (``csrc/volume_denoise.hip``), sigma estimated per volume from
 the air around the head or given with ``--denoise_sigma``; ``--denoise_beta`` (default 1) scales the filter's strength,
 ``--denoise_radius`` (default 3) is its search radius.  The default, ``none``, leaves a run as it was.
+
+``--unring`` takes the Gibbs ringing of a truncated k-space out after ``--denoise`` and before the ``--spacing`` reslice and the
+windowing (interpolation destroys the ringing's period): Kellner's local subvoxel shifts along ``--unring_axes`` (default all
+three, 8..512 voxels each) with ``--unring_shifts`` K (default 20) and ``--unring_window`` a b (default 1 3), ``volume_unring.unring``
+(``csrc/volume_unring.hip``).  Minimum, maximum and total variation are logged before and after.  Without the flag a run is as it was.
 """
 import argparse
 import logging
@@ -41,6 +46,7 @@ from mri_superresolution_amd.utils.nifti import frames, grid_matrix, header_for_
 from mri_superresolution_amd.volume import enhance_volume, enhance_volume_isotropic   # noqa: E402
 from mri_superresolution_amd.volume_denoise import denoise_volume        # noqa: E402
 from mri_superresolution_amd.volume_reslice import reslice               # noqa: E402
+from scripts._cli import add_unring_flags, unring_frame, unring_options   # noqa: E402
 from scripts.infer import find_best_checkpoint, load_model               # noqa: E402
 
 logger = logging.getLogger("infer_volume")
@@ -48,10 +54,12 @@ logger = logging.getLogger("infer_volume")
 
 def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_amp=False, use_graph=True, output_dtype="float32",
                    device="cuda", isotropic=False, spacing=None, spacing_interp="linear", denoise="none", denoise_sigma=None,
-                   denoise_beta=1.0, denoise_radius=3):
+                   denoise_beta=1.0, denoise_radius=3, unring=None):
     """NIfTI file -> NIfTI file; returns the output array (as written).  ``spacing`` (three voxel sizes in mm, 0 or ``None`` keeps
     an axis): every volume is resliced to that spacing on the device before it is windowed and enhanced.  ``denoise="nlm"``: every
-    volume is denoised before that (``volume_denoise.denoise_volume``; ``denoise_sigma`` None: estimated from its background)."""
+    volume is denoised before that (``volume_denoise.denoise_volume``; ``denoise_sigma`` None: estimated from its background).  ``unring`` (the keywords of
+    ``volume_unring.unring``: axes, K, window): every volume is unringed after the denoising and before the reslice, which would
+    destroy the ringing's period."""
     if denoise not in ("none", "nlm"):
         raise ValueError(f"--denoise is none or nlm, got {denoise!r}")
     data, header = read_nifti(input_path)
@@ -78,6 +86,8 @@ def process_volume(model, input_path, output_path, axis=2, batch_size=16, use_am
             vol, noise = denoise_volume(vol, sigma=denoise_sigma, beta=denoise_beta, radius=denoise_radius, return_noise=True)
             logger.info(f"Denoised (nlm, radius {denoise_radius}, beta {denoise_beta:g}): sigma {noise['sigma']:.6g}"
                         + (f" from {noise['count']} background voxels" if denoise_sigma is None else " (given)"))
+        if unring is not None:
+            vol = unring_frame(vol, unring, logger)
         if regrid is not None:
             vol = reslice(vol, regrid, shape, spacing_interp)
         if isotropic:
@@ -115,7 +125,7 @@ def main(args):
                        args.output_dtype, device, isotropic=args.isotropic, spacing=getattr(args, "spacing", None),
                        spacing_interp=getattr(args, "spacing_interp", "linear"), denoise=getattr(args, "denoise", "none"),
                        denoise_sigma=getattr(args, "denoise_sigma", None), denoise_beta=getattr(args, "denoise_beta", 1.0),
-                       denoise_radius=getattr(args, "denoise_radius", 3))
+                       denoise_radius=getattr(args, "denoise_radius", 3), unring=unring_options(args, "unring"))
         logger.info("Inference completed successfully!")
         return 0
     except Exception as e:
@@ -155,6 +165,7 @@ def parse_args(argv=None):
                    help="(extension) the noise level of --denoise in intensity units (default: estimated from the air around the head)")
     p.add_argument("--denoise_beta", type=float, default=argparse.SUPPRESS, help="(extension) strength of --denoise (default: 1)")
     p.add_argument("--denoise_radius", type=int, default=argparse.SUPPRESS, help="(extension) search radius of --denoise, 1..5 (default: 3)")
+    add_unring_flags(p, "unring", "of the uploaded volume after --denoise and before --spacing and the windowing")
     return p.parse_args(argv)
 
 
