@@ -230,10 +230,11 @@ SIGNATURES = {
                                          _i, _i, _vp, _dp, _vp]),
     "mrisr_f32_volume_line_circulant": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _fp, _vp]),
     "mrisr_f32_volume_unring_axis": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
+    "mrisr_f32_volume_add_noise": (_i, [_fp, _i, _i, _i, _i, _f, C.c_uint64, _fp, _fp, _fp, _fp, _vp]),
 }
 
 _lib = None
-ABI_VERSION = 333  # mrisr_version() of the library these struct layouts and signatures belong to
+ABI_VERSION = 334 # mrisr_version() of the library these struct layouts and signatures belong to
 
 
 def load():

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(os.path.dirname(HERE), "build", "mrisr")
 LIB = os.path.join(HERE, "libmrisr.so")
-SOURCES = ["api.cpp", "conv_fwd.hip", "conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_pack.hip", "conv_ring.hip", "conv_pc.hip", "conv1x1.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_upadj.hip", "norm.hip", "norm_bwd.hip", "norm_bwd_onepass.hip", "norm_bwd_shuffle.hip", "head_stem.hip", "loss.hip", "optim.hip", "vgg.hip", "image.hip", "evalops.hip", "lowfield.hip", "percentile.hip", "resample.hip", "volume_blend.hip", "volume_eval.hip", "volume_label.hip", "volume_mask.hip", "volume_metrics.hip", "volume_reslice.hip", "volume_register.hip", "volume_intensity.hip", "volume_bias.hip", "volume_denoise.hip", "volume_deform.hip", "volume_lcc.hip", "volume_tissue.hip", "volume_surface.hip", "volume_edge.hip", "volume_stacks.hip", "volume_slices.hip", "volume_kspace.hip", "volume_unring.hip"]
+SOURCES = ["api.cpp", "conv_fwd.hip", "conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_pack.hip", "conv_ring.hip", "conv_pc.hip", "conv1x1.hip", "conv_wgrad.hip", "conv_wgrad_rows.hip", "conv_upadj.hip", "norm.hip", "norm_bwd.hip", "norm_bwd_onepass.hip", "norm_bwd_shuffle.hip", "head_stem.hip", "loss.hip", "optim.hip", "vgg.hip", "image.hip", "evalops.hip", "lowfield.hip", "percentile.hip", "resample.hip", "volume_blend.hip", "volume_eval.hip", "volume_label.hip", "volume_mask.hip", "volume_metrics.hip", "volume_reslice.hip", "volume_register.hip", "volume_intensity.hip", "volume_bias.hip", "volume_denoise.hip", "volume_deform.hip", "volume_lcc.hip", "volume_tissue.hip", "volume_surface.hip", "volume_edge.hip", "volume_stacks.hip", "volume_slices.hip", "volume_kspace.hip", "volume_unring.hip", "volume_noise.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # conv_igemm_*.hip (the classic forward kernel) and conv_pack.hip (the packers, once in one file with it): no SLP
@@ -46,6 +46,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # volume_slices.hip: likewise (the same forward model and taps per slice, the through-plane distance and weight in double, the quotient by the slices' weight sum)
 # volume_kspace.hip: likewise (a line's circulant sum: every product of a table entry and a sample rounded, then every sum, over the source index ascending)
 # volume_unring.hip: likewise (the same circulant sum per sub-voxel shift, the differences and their windowed sums, the interpolation back: a difference, a product, a sum)
+# volume_noise.hip: likewise (the table's interpolation - a rounded product, then a rounded sum - sigma times the normal, the sum with the voxel, the two squares, their sum and the square root)
 # volume_stacks.hip: likewise (the sample's coordinate in double, the taps through volume_taps.h, the profile's products and sums, the quotient by the weight sum, the mean of the stacks and the step)
 FILE_FLAGS = {**{f: ["-fno-slp-vectorize"] for f in ("conv_igemm_bf16.hip", "conv_igemm_f16.hip", "conv_igemm_f32.hip", "conv_pack.hip")},
               "image.hip": ["-ffp-contract=off"], "evalops.hip": ["-ffp-contract=off"],
@@ -58,7 +59,8 @@ FILE_FLAGS = {**{f: ["-fno-slp-vectorize"] for f in ("conv_igemm_bf16.hip", "con
               "volume_tissue.hip": ["-ffp-contract=off"],
               "volume_surface.hip": ["-ffp-contract=off"], "volume_edge.hip": ["-ffp-contract=off"],
               "volume_stacks.hip": ["-ffp-contract=off"], "volume_slices.hip": ["-ffp-contract=off"],
-              "volume_kspace.hip": ["-ffp-contract=off"], "volume_unring.hip": ["-ffp-contract=off"]}
+              "volume_kspace.hip": ["-ffp-contract=off"], "volume_unring.hip": ["-ffp-contract=off"],
+              "volume_noise.hip": ["-ffp-contract=off"]}
 
 
 def _deps_mtime():

@@ -1,4 +1,4 @@
-"""What the volume scripts share: the ``--cpu`` flag, the k-space flags, the unring flags, the guarded ``main``, the upload of a frame, the joining
+"""What the volume scripts share: the ``--cpu`` flag, the k-space flags, the degradation's noise flags, the unring flags, the guarded ``main``, the upload of a frame, the joining
 and saving of frames, and the mask loading of ``evaluate_volume.py`` and ``segment_volume.py``.  A script imports it after the
 ``REPO`` path insert.
 """
@@ -38,6 +38,30 @@ def kspace_options(args) -> dict:
     if args.degrade != "mean":
         chosen["degrade"] = args.degrade
     return chosen
+
+
+def add_degrade_noise_flags(parser):
+    """``--degrade_noise`` / ``--degrade_snr`` / ``--degrade_seed`` of ``evaluate_volume.py`` (``volume_lowfield``); absent from the
+    namespace unless given, so the parsed defaults are those of a build without them.  ``degrade_noise_options`` reads them back."""
+    import argparse
+    g = parser.add_mutually_exclusive_group()
+    g.add_argument("--degrade_noise", type=float, default=argparse.SUPPRESS, metavar="SIGMA",
+                   help="(extension) without --input: add Rician noise of this sigma, in intensity units, to the low-resolution volume "
+                        "made from the reference (any --degrade, the default mean included) - a simulated low-field acquisition")
+    g.add_argument("--degrade_snr", type=float, default=argparse.SUPPRESS, metavar="R",
+                   help="(extension) the same with sigma = the median of that volume's Otsu foreground / R")
+    parser.add_argument("--degrade_seed", type=int, default=argparse.SUPPRESS, metavar="N",
+                        help="(extension) the seed of --degrade_noise / --degrade_snr; every scan and frame draws its own noise from it (default: 0)")
+
+
+def degrade_noise_options(args):
+    """-> None without the flags (``--degrade_seed`` alone is an error), else ``{"sigma": s}`` or ``{"snr": r}`` with ``"seed"``."""
+    chosen = {k: getattr(args, flag) for k, flag in (("sigma", "degrade_noise"), ("snr", "degrade_snr")) if hasattr(args, flag)}
+    if not chosen:
+        if hasattr(args, "degrade_seed"):
+            raise ValueError("--degrade_seed goes with --degrade_noise or --degrade_snr")
+        return None
+    return {**chosen, "seed": getattr(args, "degrade_seed", 0)}
 
 
 def add_unring_flags(parser, flag, when):

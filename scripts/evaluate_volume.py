@@ -116,6 +116,15 @@ k-space padded with zeros and transformed back - periodic sinc interpolation of 
 volume of a run without ``--input`` by truncating the reference's k-space to its centre (``volume_kspace.truncate2``), the resolution
 loss of the 2-D training path (``csrc/lowfield.hip``), instead of the mean over pairs; the tables' titles then say so.  With ``--input``
 it is ignored, with a warning.  Without the two flags a run writes the bytes it wrote before.
+
+``--degrade_noise SIGMA`` or ``--degrade_snr R`` (without ``--input``, with any ``--degrade``, the default ``mean`` included; even extents
+on the doubled axes) makes the low-resolution volume a simulated low-field acquisition: it is made first, then Rician noise of
+standard deviation SIGMA - or the median of its Otsu foreground over R - is added (``volume_lowfield.add_noise``;
+``csrc/volume_noise.hip``), seeded by ``--degrade_seed`` (default 0; every scan and frame draws its own noise) and reproducible to the
+bit.  The U-Net is trained on noisy low-resolution slices; this scores it on such input.  The tables' titles say so: ``(degrade
+kspace, noise σ = 20, seed 0)``.  With one of the two, ``--denoise_input nlm`` is accepted without ``--input`` and denoises the volume
+just made, before ``--unring_input``: truncate, noise, denoise, x2, against a real truth.  Without the flags a run writes the bytes it
+wrote before.
 """
 import argparse
 import csv
@@ -141,8 +150,10 @@ from mri_superresolution_amd.volume_register import register_rigid              
 from mri_superresolution_amd.volume_reslice import covered_share, reslice    # noqa: E402
 from mri_superresolution_amd.volume_sharpness import check_bins as check_edge_bins        # noqa: E402
 from mri_superresolution_amd.volume_kspace import truncate2                  # noqa: E402
-from scripts._cli import (add_cpu_flag, add_kspace_flags, add_unring_flags, join_frames, kspace_options, load_mask, log_device,   # noqa: E402
-                          make_parent, require_gpu, start_logging, to_device, unring_frame, unring_options, voxel_sizes)
+from mri_superresolution_amd.volume_lowfield import add_noise, frame_seeds, sigma_for_snr      # noqa: E402
+from scripts._cli import (add_cpu_flag, add_degrade_noise_flags, add_kspace_flags, add_unring_flags, degrade_noise_options, join_frames,   # noqa: E402
+                          kspace_options, load_mask, log_device, make_parent, require_gpu, start_logging, to_device, unring_frame,
+                          unring_options, voxel_sizes)
 
 logger = logging.getLogger("evaluate_volume")
 CSV_COLUMNS = ["scan", "method", "ssim", "psnr", "mse", "rmse", "mae"]      # the column style of scripts/evaluate.py
@@ -168,8 +179,14 @@ def edge_columns(classes):
 def check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias="none", match_bias_sigma_mm=25.0,
                   denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, deform_input="none", deform_exp_steps=2,
                   tissue_dice=0, mask=None, tissue_surface=False, deform_force="ssd", deform_lcc_radius=2, tissue_edges=False,
-                  edge_radius_mm=4.0, edge_bin_mm=0.5):
+                  edge_radius_mm=4.0, edge_bin_mm=0.5, degrade_noise=None):
     """The option rules of one scan, stated once: ``score_scan`` applies them, ``main`` before it loads a model."""
+    if degrade_noise is not None:
+        if input_path:
+            raise ValueError("--degrade_noise and --degrade_snr go without --input: they add noise to the low-resolution volume made here")
+        level = degrade_noise.get("sigma", degrade_noise.get("snr"))
+        if len([k for k in ("sigma", "snr") if k in degrade_noise]) != 1 or not np.isfinite(level) or level < 0 or (level == 0 and "snr" in degrade_noise):
+            raise ValueError(f"--degrade_noise takes a finite sigma that is not negative, --degrade_snr a finite positive ratio, one of the two; got {degrade_noise}")
     if isinstance(tissue_dice, bool) or not isinstance(tissue_dice, int) or not (tissue_dice == 0 or 2 <= tissue_dice <= 6):
         raise ValueError(f"--tissue_dice is 0 (off) or a number of classes in 2..6, got {tissue_dice}")
     if tissue_dice and mask is None:
@@ -194,7 +211,7 @@ def check_options(input_path, align, align_interp, align_init, align_mask, match
         raise ValueError(f"--deform_lcc_radius must be an integer in 1..{MAX_LCC_RADIUS}, got {deform_lcc_radius}")
     if denoise_input not in ("none", "nlm"):
         raise ValueError(f"--denoise_input is none or nlm, got {denoise_input!r}")
-    if denoise_input != "none" and not input_path:
+    if denoise_input != "none" and not input_path and degrade_noise is None:
         raise ValueError("--denoise_input goes with --input")
     if denoise_sigma is not None and not (np.isfinite(denoise_sigma) and denoise_sigma > 0):
         raise ValueError(f"--denoise_sigma must be finite and positive, got {denoise_sigma}")
@@ -228,15 +245,21 @@ def upload_input(frame, device="cuda", denoise_input="none", denoise_sigma=None,
     denoised on its own grid (``volume_denoise.denoise_volume``, sigma estimated from the frame's background unless given), and only
     then, with ``onto = (matrix, shape, interpolation)``, resliced (``--align``).  ``unring`` (the keywords of ``volume_unring.unring``):
     unringed on its own grid after the denoising and before the reslice.  ``"none"``, no ``unring`` and no ``onto``: the upload alone."""
-    lr = torch.from_numpy(np.ascontiguousarray(frame)).to(device)
+    lr = clean_input(torch.from_numpy(np.ascontiguousarray(frame)).to(device), denoise_input, denoise_sigma, denoise_beta, denoise_radius,
+                     what, unring)
+    if onto is not None:
+        lr = reslice(lr, *onto)
+    return lr
+
+
+def clean_input(lr, denoise_input="none", denoise_sigma=None, denoise_beta=1.0, denoise_radius=3, what="input", unring=None):
+    """The first two steps of ``upload_input`` on a CUDA volume, in its order: the denoising, then the unringing."""
     if denoise_input != "none":
         lr, noise = denoise_volume(lr, sigma=denoise_sigma, beta=denoise_beta, radius=denoise_radius, return_noise=True)
         logger.info(f"{what} denoised (nlm, radius {denoise_radius}, beta {denoise_beta:g}): sigma {noise['sigma']:.6g}"
                     + (f" from {noise['count']} background voxels" if denoise_sigma is None else " (given)"))
     if unring is not None:
         lr = unring_frame(lr, unring, logger, f"{what}: ")
-    if onto is not None:
-        lr = reslice(lr, *onto)
     return lr
 
 
@@ -292,7 +315,8 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
                save_mask=None, align=None, align_interp="linear", align_bins=64, align_init="header", align_mask="none",
                match="none", match_bias="none", match_bias_sigma_mm=25.0, denoise_input="none", denoise_sigma=None, denoise_beta=1.0,
                denoise_radius=3, deform_input="none", deform_exp_steps=2, tissue_dice=0, tissue_surface=False, deform_force="ssd",
-               deform_lcc_radius=2, tissue_edges=False, edge_radius_mm=4.0, edge_bin_mm=0.5, zerofill=None, degrade="mean", unring_input=None):
+               deform_lcc_radius=2, tissue_edges=False, edge_radius_mm=4.0, edge_bin_mm=0.5, zerofill=None, degrade="mean", unring_input=None,
+               degrade_noise=None, scan_index=0):
     """-> rows ``{"scan", "method", *METRIC_COLUMNS}``, one per timepoint and method.  ``mask`` (``"otsu"`` or a NIfTI path): two
     rows per timepoint and method, with ``"region"`` (``whole`` / ``foreground``), ``"mask_voxels"``, ``"voxels"`` and, for Otsu,
     ``"threshold"``; with ``mask_largest`` / ``mask_fill_holes`` also ``"cleanup"`` (components, kept size, voxels filled; NaN for a
@@ -315,10 +339,15 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
     ``"kspace_hamming"``): the low-resolution volume is the reference's truncated k-space (``volume_eval.evaluate_volume``).
     ``unring_input`` (the keywords of ``volume_unring.unring``: axes, K, window): every input frame is unringed on its own grid after
     ``denoise_input`` and before ``align`` (``upload_input``); without ``input_path`` the low-resolution volume a k-space ``degrade`` makes
-    is unringed instead (even extents on the doubled axes)."""
+    is unringed instead (even extents on the doubled axes).
+    ``degrade_noise`` (``{"sigma": s}`` or ``{"snr": r}``, with ``"seed"``; without ``input_path``): the low-resolution volume is made
+    here from the reference by ``degrade``, the mean over pairs included, and Rician noise is added to it (``volume_lowfield.add_noise``;
+    ``snr``: sigma is the median of the volume's Otsu foreground over ``r``); frame ``t`` of scan number ``scan_index`` draws with
+    ``volume_lowfield.frame_seeds(seed, scan_index, frames)[t]``.  ``denoise_input="nlm"`` then denoises that volume, before
+    ``unring_input`` (even extents on the doubled axes)."""
     check_options(input_path, align, align_interp, align_init, align_mask, match, match_bias, match_bias_sigma_mm, denoise_input,
                   denoise_sigma, denoise_beta, denoise_radius, deform_input, deform_exp_steps, tissue_dice, mask, tissue_surface,
-                  deform_force, deform_lcc_radius, tissue_edges, edge_radius_mm, edge_bin_mm)
+                  deform_force, deform_lcc_radius, tissue_edges, edge_radius_mm, edge_bin_mm, degrade_noise)
     noise_options = (denoise_input, denoise_sigma, denoise_beta, denoise_radius)
     if unring_input is not None and not input_path and degrade == "mean":
         raise ValueError("--unring_input goes with --input or with --degrade kspace / kspace_hamming")
@@ -372,13 +401,24 @@ def score_scan(model, reference_path, input_path=None, isotropic=False, axis=2, 
             lr = low_frames[t] if align else upload_input(low_frames[t], device, *noise_options,
                                                           what=f"{input_path}{f'[t={t}]' if len(ref_frames) > 1 else ''}",
                                                           unring=unring_input)
-        made = unring_input is not None and lr is None       # the truncated k-space of the reference, made here and unringed
-        if made:
+        made = (unring_input is not None or degrade_noise is not None) and lr is None       # the low-resolution volume is made here
+        if made and degrade_noise is None:                   # the truncated k-space of the reference, unringed
             if any(vol.shape[a] % 2 for a in axes):
                 raise ValueError(f"--unring_input with --degrade {degrade}: the reference {tuple(vol.shape)} has an odd extent on a doubled axis")
             vol = vol.float().contiguous()
             lr = unring_frame(truncate2(vol, axes, "hamming" if degrade == "kspace_hamming" else "none"), unring_input, logger,
                               f"{name}{f'[t={t}]' if len(ref_frames) > 1 else ''} (degrade {degrade}): ")
+        elif made:                                           # degraded, then noise; denoised and unringed on request, in upload_input's order
+            if any(vol.shape[a] % 2 for a in axes):
+                raise ValueError(f"--degrade_noise / --degrade_snr: the reference {tuple(vol.shape)} has an odd extent on a doubled axis")
+            what = f"{name}{f'[t={t}]' if len(ref_frames) > 1 else ''} (degrade {degrade})"
+            vol = vol.float().contiguous()
+            lr = downsample2(vol, axes) if degrade == "mean" else truncate2(vol, axes, "hamming" if degrade == "kspace_hamming" else "none")
+            sigma = degrade_noise["sigma"] if "sigma" in degrade_noise else sigma_for_snr(lr, degrade_noise["snr"])
+            seed = frame_seeds(degrade_noise.get("seed", 0), scan_index, len(ref_frames))[t]
+            lr = add_noise(lr, sigma, seed, out=lr)
+            logger.info(f"{what}: Rician noise added, sigma {sigma:.6g}, seed {seed}")
+            lr = clean_input(lr, *noise_options, what=what, unring=unring_input)
         if masks is not None:
             m = masks[t] if align else torch.from_numpy(masks[t]).to(device)
         if lr is not None and not made:
@@ -481,7 +521,7 @@ def main(args):
         check_options(args.input, args.align, args.align_interp, args.align_init, args.align_mask, args.match_intensity, args.match_bias,
                       args.match_bias_sigma_mm, args.denoise_input, args.denoise_sigma, args.denoise_beta, args.denoise_radius,
                       args.deform_input, args.deform_exp_steps, args.tissue_dice, args.mask, args.tissue_surface, args.deform_force,
-                      args.deform_lcc_radius, args.tissue_edges, args.edge_radius_mm, args.edge_bin_mm)
+                      args.deform_lcc_radius, args.tissue_edges, args.edge_radius_mm, args.edge_bin_mm, degrade_noise_options(args))
         if args.save_mask and len(args.reference) != 1:
             raise ValueError("--save_mask goes with exactly one --reference scan")
         if not 0 <= args.mask_close <= 4:
@@ -501,10 +541,16 @@ def main(args):
         dice += edge_columns(args.tissue_dice) if args.tissue_edges else []
         shown = {"foreground": dice}                     # the tables of the whole volume stay as they are
         degraded = f" (degrade {args.degrade})" if args.degrade != "mean" else ""
+        degrade_noise = degrade_noise_options(args)
+        if degrade_noise is not None:
+            level = f"σ = {degrade_noise['sigma']:g}" if "sigma" in degrade_noise else f"SNR = {degrade_noise['snr']:g}"
+            degraded = f" (degrade {args.degrade}, noise {level}, seed {degrade_noise['seed']})"
+            if args.denoise_input != "none":
+                degraded += " (denoised)"
         unring_input = unring_options(args, "unring_input")
         if unring_input is not None:                     # what it goes with: score_scan's rule
             degraded += f" (input unringed along {' '.join(str(a) for a in sorted(unring_input['axes']))}, K = {unring_input['K']})"
-        for path in args.reference:
+        for index, path in enumerate(args.reference):
             scan_rows = score_scan(model, path, input_path=args.input, isotropic=args.isotropic, axis=args.axis, data_range=args.data_range,
                                    batch_size=args.batch_size, use_amp=args.use_amp, use_graph=not args.no_graph, device=device,
                                    graph_cache=graphs, mask=args.mask, mask_close=args.mask_close, mask_largest=args.mask_largest,
@@ -517,7 +563,8 @@ def main(args):
                                    deform_lcc_radius=args.deform_lcc_radius, tissue_dice=args.tissue_dice,
                                    tissue_surface=args.tissue_surface, tissue_edges=args.tissue_edges,
                                    edge_radius_mm=args.edge_radius_mm, edge_bin_mm=args.edge_bin_mm, **kspace_options(args),
-                                   **(dict(unring_input=unring_input) if unring_input is not None else {}))
+                                   **(dict(unring_input=unring_input) if unring_input is not None else {}),
+                                   **(dict(degrade_noise=degrade_noise, scan_index=index) if degrade_noise is not None else {}))
             for scan in dict.fromkeys(r["scan"] for r in scan_rows):
                 for region in regions:
                     part = [r for r in scan_rows if r["scan"] == scan and r.get("region") == region]
@@ -624,6 +671,7 @@ def parse_args(argv=None):
     p.add_argument("--edge_radius_mm", type=float, default=4.0, help="--tissue_edges: the profile runs this far either side of an interface")
     p.add_argument("--edge_bin_mm", type=float, default=0.5, help="--tissue_edges: the width of a bin of the profile (at most 64 bins)")
     add_kspace_flags(p)
+    add_degrade_noise_flags(p)
     p.add_argument("--output_csv", type=str, default=None, help="write every row and the means to this CSV file")
     return p.parse_args(argv)
 
